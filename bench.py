@@ -19,6 +19,7 @@ fixes the total = strong scaling, e.g. 256 for BASELINE config 4) is sharded by 
 and sits INSIDE the timed region.  `value` is the whole-job audio-seconds per wall-second (max over ranks).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            # N > 1: re-launches itself under torch.distributed.run
+    python bench.py ... --dump-outputs DIR                         # + the last timed step's output as DIR/waveform.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -27,6 +28,7 @@ import ctypes as C
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -38,6 +40,9 @@ REF_CPU_FILE = "r02_reference_cpu_timing.json"
 F32_MFMA_PEAK_TFLOPS = 157.3   # dense f32 MFMA (the exact-f32 DFT GEMMs of the STFT front / back end)
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3, "mixed": 2500.0, "bf16x3": 2500.0 / 3}  # dense peaks, /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_GBPS = 8000.0
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs: budget of all files together, on disk (64 MB, also < 64 MiB)
+DUMP_HEADER_BYTES = 4096       # reserved per file for the .npy header (np.save writes 128 bytes for these shapes)
+DUMP_SAMPLE_SEED = 0
 
 
 def cpu_baseline():
@@ -96,7 +101,8 @@ def free_port():
 
 
 def relaunch(args):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run` with N local ranks (one per GPU)."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run` with N local ranks (one per GPU) as a child
+    process and exit with its status (a child killed by signal N exits 128 + N, as a shell reports it)."""
     if args.backend == "nccl" and not args.share_gpu:
         import torch
         have = torch.cuda.device_count()
@@ -104,7 +110,30 @@ def relaunch(args):
             raise SystemExit(f"bench.py: --gpus {args.gpus} requested but only {have} GPU(s) are visible -- refusing to fall back to fewer ranks")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a fresh child process, never exec: device_count() above may already have initialised the GPU runtime in this one
+    rc = subprocess.call(cmd)
+    sys.exit(128 - rc if rc < 0 else rc)
+
+
+def dump_outputs(outdir, arrays):
+    """Writes each host array as outdir/<name>.npy in float32 (float64 stays float64).  When the files together would exceed
+    DUMP_MAX_BYTES on disk (DUMP_HEADER_BYTES reserved per file for its header), each array is replaced by a fixed, seeded sample
+    of its flattened elements (sorted flat indices, the same for the same shape), so that two builds run with the same arguments
+    can still be compared element for element."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    data_budget = DUMP_MAX_BYTES - DUMP_HEADER_BYTES * len(arrays)
+    for name, a in arrays.items():
+        if total > data_budget:
+            keep = a.size * data_budget // total
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=keep, replace=False))
+            print(f"bench.py: {name} {a.shape} -> seeded sample of {keep} of {a.size} elements (--dump-outputs budget "
+                  f"{DUMP_MAX_BYTES / 1e6:g} MB)", file=sys.stderr)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 # BASELINE.json configurations by name: what `--config` sets (flags given explicitly on the command line win)
@@ -149,7 +178,12 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo + --stub-step: launcher / collective test on CPU")
     ap.add_argument("--stub-step", action="store_true", help="replace enhance() by a trivial CPU function (tests of the launcher only)")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use cuda:0 (with --backend gloo: exercises the N > 1 path on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (waveform: float32 [B, 1, L]; "
+                         f"a seeded sample beyond {DUMP_MAX_BYTES / 1e6:g} MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config:
         given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
         for k, v in CONFIGS[args.config].items():
@@ -191,7 +225,7 @@ def main():
 
         def step(src, k=0):
             t1 = time.perf_counter()
-            out = sharded_apply(lambda yb: yb * 2.0 + 1.0, src)
+            out = sharded_apply(lambda yb: yb * 2.0 + k, src)   # (depends on k: the tests can tell which step's output they see)
             if stats is not None:
                 stats["gather_s"] = stats.get("gather_s", 0.0) + (time.perf_counter() - t1)
             return out
@@ -234,7 +268,10 @@ def main():
 
     def sync_all():
         if dist is not None:
-            dist.barrier()
+            if dev.type == "cuda":
+                dist.barrier()
+            else:   # a CPU collective: dist.barrier() probes for an accelerator, which opens the GPU on a GPU machine
+                dist.all_reduce(torch.zeros(1))
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
 
@@ -278,6 +315,9 @@ def main():
     else:
         out, elapsed, per_rank_ms, gather_ms = timed(y, args.steps)
     assert out.shape[0] == gbatch and out.device == y.device and torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        # the enhanced waveforms of the last timed step (every rank holds the all-gathered batch)
+        dump_outputs(args.dump_outputs, {"waveform": out.detach().cpu().numpy()})
     if nfe is None:
         nfe = model.last_nfe   # adaptive solver: realised number of vector-field evaluations of the last step
 

@@ -165,7 +165,8 @@ assert torch.equal(sharded_enhance(m, y[:1], N=2, generator=g2), r1)
 assert torch.equal(sharded_enhance(m, y, N=2, generator=g2), r2), "generator= after a call with an idle rank"
 one = sharded_enhance(m, y[:1], N=2, seed=1)      # one clip, two ranks: rank 1 idles but still gathers
 assert one.shape == (1, 1, 100) and torch.equal(one, m.enhance(y[:1], N=2, noise=clip_noise(1, 0, (1, 16, 64), "cpu")[None]))
-dist.barrier(); dist.destroy_process_group()
+# a CPU all-reduce as the closing barrier: dist.barrier() probes for an accelerator, which opens the GPU on a GPU machine
+dist.all_reduce(torch.zeros(1)); dist.destroy_process_group()
 print("rank", os.environ["RANK"], "ok")
 '''
 
@@ -229,7 +230,8 @@ for B, per in ((256, 32), (64, 8), (20, None)):
     assert m.calls == [hi - lo] and (per is None or hi - lo == per), (m.calls, lo, hi)
     ref = Stub().enhance(y, N=3, noise=torch.stack([clip_noise(11, i, (1, 16, 64), "cpu") for i in range(B)]))
     assert out.shape == (B, 1, 40) and torch.equal(out, ref), B
-dist.barrier(); dist.destroy_process_group()
+# a CPU all-reduce as the closing barrier: dist.barrier() probes for an accelerator, which opens the GPU on a GPU machine
+dist.all_reduce(torch.zeros(1)); dist.destroy_process_group()
 print("rank", rank, "ok")
 '''
 
@@ -248,7 +250,7 @@ def test_batch_sharding_gloo_world8_cfg4_cfg5(tmp_path):
 
 
 def test_bench_self_launch_gloo_world2():
-    """`python bench.py --gpus 2` WITHOUT a launcher re-executes itself under torch.distributed.run with two ranks, shards the
+    """`python bench.py --gpus 2` WITHOUT a launcher runs torch.distributed.run with two ranks as a child process, shards the
     global batch by clip, all-gathers the results inside the timed region and prints ONE line with n_gpus = the real world size
     (here: gloo + a stub step, the model needs a GPU; the code path -- relaunch, sharded_apply, timing reduction -- is the
     one the multi-GPU bench takes)."""
@@ -299,6 +301,41 @@ def test_bench_config_flag_cfg4_shard_line():
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "unrecognized arguments" in r.stderr
     assert bench.CONFIGS["cfg5"]["precision"] == "fp32" and bench.CONFIGS["cfg5"]["seconds"] == 4.0 and bench.CONFIGS["cfg3"]["preset"] == "flowdec_25s"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes what the LAST timed step returned as DIR/waveform.npy (float32 [B, 1, L]): the stub step
+    returns 2 y + k at step k, so the warm-up and the earlier timed steps are told apart.  The same bytes for the same arguments,
+    the same array under two ranks (gloo + a stub step here); --steps 0 is refused; beyond the budget the files on disk, headers
+    included, stay within DUMP_MAX_BYTES and hold a fixed, seeded sample."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    common = ["--backend", "gloo", "--stub-step", "--steps", "3", "--warmup", "1", "--seconds", "0.01", "--global-batch", "5"]
+    for d, gpus in (("a", "1"), ("b", "1"), ("c", "2")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", gpus, *common, "--dump-outputs", str(tmp_path / d)],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == 3
+    a = np.load(tmp_path / "a" / "waveform.npy")
+    y = 0.1 * torch.randn(5, 1, 480, generator=torch.Generator().manual_seed(0))      # the stub's seeded global batch
+    assert a.dtype == np.float32 and a.shape == (5, 1, 480) and np.array_equal(a, (y * 2.0 + 2).numpy())   # step k = steps - 1 = 2
+    assert (tmp_path / "a" / "waveform.npy").read_bytes() == (tmp_path / "b" / "waveform.npy").read_bytes()
+    assert np.array_equal(np.load(tmp_path / "c" / "waveform.npy"), a)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-step", "--steps", "0"], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+    sys.path.insert(0, ROOT)
+    import bench
+    on_disk = lambda d: sum(os.path.getsize(f) for f in d.iterdir())
+    # BASELINE cfg 4 on 8 GPUs: 256 x 2 s clips = 98.3 MB of float32 -> a sample within the real budget
+    bench.dump_outputs(str(tmp_path / "big"), {"waveform": np.zeros((256, 1, 96000), np.float32)})
+    assert on_disk(tmp_path / "big") <= bench.DUMP_MAX_BYTES <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", bench.DUMP_HEADER_BYTES + 4000)
+    x = np.arange(3 * 1000, dtype=np.float32).reshape(3, 1, 1000)
+    bench.dump_outputs(str(tmp_path / "s1"), {"waveform": x})
+    bench.dump_outputs(str(tmp_path / "s2"), {"waveform": x})
+    s = np.load(tmp_path / "s1" / "waveform.npy")
+    assert on_disk(tmp_path / "s1") <= bench.DUMP_MAX_BYTES and s.dtype == np.float32 and s.size == 1000
+    assert np.all(np.diff(s) > 0) and np.isin(s, x).all() and np.array_equal(s, np.load(tmp_path / "s2" / "waveform.npy"))
 
 
 def test_bench_refuses_missing_gpus():
