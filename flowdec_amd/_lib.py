@@ -25,6 +25,8 @@ FD_NO_SIDE_STREAM = 0x40000  # fd_model_config.act_dtype: side branches stay on 
 FD_EBUSY = -5
 FD_BF16X3_OPERANDS = 0x20000  # with FD_F32: operands as hi + lo bf16 pairs, three bf16 MFMAs per product (precision='bf16x3')
 FD_TILE = {0: 0, 32: 0x1000, 64: 0x2000, 128: 0x3000, "64c": 0x4000, "32c": 0x5000, "duo": 0x6000, "persist": 0x7000}  # fd_conv2d: output channels per workgroup (0 = default)
+# fd_conv_kernel_counts slots (enum FD_CONV_KERNEL_* in include/flowdec_hip.h, in order)
+CONV_KERNELS = ("DIRECT", "DIRECT_MIXED", "DIRECT_SPLIT", "WINO", "WINO4", "WINO4F", "WINO44F", "HEAD", "HEADF")
 SOLVERS = {"euler": 0, "midpoint": 1, "heun2": 2, "heun2_eulerlast": 3}
 ADAPTIVE_SOLVERS = {"dopri5": 0, "tsit5": 1}   # FD_ADAPTIVE_*
 
@@ -78,6 +80,7 @@ SIGNATURES = {
     "fd_conv_stats_tiles": (c_int, [c_int, c_int]),
     "fd_conv2d": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_float, _P, c_int, _P,
                           c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_conv_kernel_counts": (c_int, [C.POINTER(c_ll), c_int]),
     "fd_time_embedding": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
     "fd_temb_bias": (c_int, [_P, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
     "fd_stft_workspace_bytes": (c_size_t, [c_int] * 4),

@@ -43,6 +43,7 @@
 //                     convolution result is bit-identical to the staged epilogue; the statistics differ in summation order only.
 #include <string.h>
 
+#include <atomic>
 #include <mutex>
 #include <type_traits>
 
@@ -1248,6 +1249,17 @@ int fd_conv_init_attributes() {
 
 FD_T2(extern "C" int fd_debug_buffer(void* p) { g_dbg = reinterpret_cast<unsigned long long*>(p); return FD_OK; })
 
+// fd_conv_kernel_counts: host dispatches of fd_conv2d per kernel family (include/flowdec_hip.h)
+static std::atomic<long long> g_kernel_counts[FD_CONV_KERNEL_COUNT];
+static int counted(int kind, int rc) {
+  if (rc == FD_OK) g_kernel_counts[kind].fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
+extern "C" int fd_conv_kernel_counts(long long* counts, int n) {
+  for (int i = 0; counts && i < n && i < FD_CONV_KERNEL_COUNT; ++i) counts[i] = g_kernel_counts[i].load(std::memory_order_relaxed);
+  return FD_CONV_KERNEL_COUNT;
+}
+
 extern "C" int fd_conv_cout_pad(int Cout) { return cout_pad(Cout); }
 extern "C" int fd_conv_stats_tiles(int H, int W) { return fd_cdiv(H, 16) * fd_cdiv(W, 16); }
 
@@ -1371,15 +1383,16 @@ extern "C" int fd_conv2d(const void* in0, int C0, const void* in1, int C1, const
   if (wino44) {
     FD_REQUIRE(fd_wino44f_supported(Cout, C0, C1, S0, S1, ksize) && fd_wino44f_shape_ok(H, W),
                "fd_conv2d: FD_F32 | FD_WINOGRAD44 needs ksize 3, Cout %% 128 == 0, channel counts %% 8 == 0, H %% 16 == W %% 16 == 0");
-    return fd_wino44f_launch(a, fd_stream(stream));
+    return counted(FD_CONV_KERNEL_WINO44F, fd_wino44f_launch(a, fd_stream(stream)));
   }
-  if (wino4f) return fd_wino4f_launch(a, fd_stream(stream));
-  if (wino4) return fd_wino4_launch(a, fd_stream(stream));
-  if (wino) return fd_wino_launch(a, fd_stream(stream));
-  if (mixed) return dispatch_conv_mixed(a, fd_stream(stream));
-  if (split) return dispatch_conv_split(a, fd_stream(stream));
-  if (bn_hint == 0 && fd_head_supported(a, ksize, dtype)) return fd_head_launch(a, fd_stream(stream));
-  if (bn_hint == 0 && tile == 0 && fd_headf_supported(a, ksize, dtype)) return fd_headf_launch(a, fd_stream(stream));
-  if (dtype == FD_BF16) return dispatch_conv<bf16>(a, fd_stream(stream), bn_hint, tile == FD_TILE_BN64_CHUNK || tile == FD_TILE_BN32_CHUNK, tile == FD_TILE_PERSIST);
-  return dispatch_conv<float>(a, fd_stream(stream), bn_hint, false);
+  if (wino4f) return counted(FD_CONV_KERNEL_WINO4F, fd_wino4f_launch(a, fd_stream(stream)));
+  if (wino4) return counted(FD_CONV_KERNEL_WINO4, fd_wino4_launch(a, fd_stream(stream)));
+  if (wino) return counted(FD_CONV_KERNEL_WINO, fd_wino_launch(a, fd_stream(stream)));
+  if (mixed) return counted(FD_CONV_KERNEL_DIRECT_MIXED, dispatch_conv_mixed(a, fd_stream(stream)));
+  if (split) return counted(FD_CONV_KERNEL_DIRECT_SPLIT, dispatch_conv_split(a, fd_stream(stream)));
+  if (bn_hint == 0 && fd_head_supported(a, ksize, dtype)) return counted(FD_CONV_KERNEL_HEAD, fd_head_launch(a, fd_stream(stream)));
+  if (bn_hint == 0 && tile == 0 && fd_headf_supported(a, ksize, dtype)) return counted(FD_CONV_KERNEL_HEADF, fd_headf_launch(a, fd_stream(stream)));
+  if (dtype == FD_BF16)
+    return counted(FD_CONV_KERNEL_DIRECT, dispatch_conv<bf16>(a, fd_stream(stream), bn_hint, tile == FD_TILE_BN64_CHUNK || tile == FD_TILE_BN32_CHUNK, tile == FD_TILE_PERSIST));
+  return counted(FD_CONV_KERNEL_DIRECT, dispatch_conv<float>(a, fd_stream(stream), bn_hint, false));
 }

@@ -121,6 +121,18 @@ def conv2d(x0, packed_w, Cout, ksize, x1=None, affine=None, bias=None, skip=None
     return (out, stats) if want_stats else out
 
 
+def conv_kernel_counts():
+    """Cumulative host dispatches of fd_conv2d per kernel family since the library was loaded, {name: count} (fd_conv_kernel_counts;
+    names = _lib.CONV_KERNELS).  A graph replay is not a dispatch; take differences around the calls of interest."""
+    import ctypes as C
+    n = len(L.CONV_KERNELS)
+    buf = (C.c_longlong * n)()
+    total = L.load().fd_conv_kernel_counts(buf, n)
+    if total != n:
+        raise RuntimeError(f"flowdec_hip: fd_conv_kernel_counts reports {total} kernel families, the binding knows {n}")
+    return dict(zip(L.CONV_KERNELS, buf))
+
+
 def time_embedding(t, gfp_w, w1, b1, w2, b2):
     nt, nf = t.numel(), gfp_w.numel()
     out = torch.empty(nt, 4 * nf, dtype=torch.float32, device=t.device)

@@ -202,6 +202,19 @@ int fd_conv2d(const void* in0, int C0, const void* in1, int C1, const float* aff
               int S1, const void* packed_w, const float* bias, int bias_rows, const void* skip, float scale, void* out,
               int Cout, float* stats, int B, int H, int W, int ksize, int dtype, void* stream);
 
+/* Which kernel fd_conv2d launched: one process-wide cumulative counter per kernel family, incremented (relaxed atomics) when a call
+ * has passed its argument checks and enqueued its launch.  DIRECT = conv_mfma.hip in bf16 or f32 storage (every FD_TILE_* width),
+ * DIRECT_MIXED / DIRECT_SPLIT = the same kernel with FD_BF16_OPERANDS / FD_BF16X3_OPERANDS, WINO = F(2,3), WINO4 = F(4,3) bf16,
+ * WINO4F = F(4,3) f32, WINO44F = F(4x4, 3x3) f32, HEAD / HEADF = the Cout = 4 pyramid-head kernels (conv_head.hip / conv_headf.hip).
+ * The counters count HOST dispatches: a launch recorded into a captured graph is counted once, at capture; replays of the graph are
+ * not counted.  The model's planning walks (workspace sizing) never call fd_conv2d and count nothing.  There is no reset: read the
+ * counters before and after and take the difference.  Writes min(n, FD_CONV_KERNEL_COUNT) counters to `counts` (host memory) and
+ * returns FD_CONV_KERNEL_COUNT. */
+enum { FD_CONV_KERNEL_DIRECT, FD_CONV_KERNEL_DIRECT_MIXED, FD_CONV_KERNEL_DIRECT_SPLIT, FD_CONV_KERNEL_WINO,
+       FD_CONV_KERNEL_WINO4, FD_CONV_KERNEL_WINO4F, FD_CONV_KERNEL_WINO44F, FD_CONV_KERNEL_HEAD,
+       FD_CONV_KERNEL_HEADF, FD_CONV_KERNEL_COUNT };
+int fd_conv_kernel_counts(long long* counts, int n);
+
 /* Time embedding: GaussianFourierProjection -> Linear -> SiLU -> Linear (ncsnpp.py:263-274,
  * layerspp.py:42-51); t [nt] float32 -> temb [nt][4*nf]. */
 int fd_time_embedding(const float* t, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,

@@ -626,18 +626,22 @@ def test_fp32_auto_runs_winograd4_f32_and_matches_direct():
     import flowdec_amd
     g = load_golden("g10_ncsnpp_nf64.npz")
     sd = O.random_state_dict(seed=int(g["seed"]), nf=64)
-    outs = {}
+    from flowdec_amd import ops
+    outs, w44 = {}, {}
     for algo in ("auto", "direct"):
         m = flowdec_amd.from_preset("flowdec_75m", precision="fp32", conv_algo=algo)
         assert m.backbone.conv_algo == algo
         m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=False)
         m = m.cuda()
+        before = ops.conv_kernel_counts()["WINO44F"]
         outs[algo] = m(cu(g["x"]), cu(g["y"]), torch.tensor([0.5], device="cuda")).cpu().numpy()
+        w44[algo] = ops.conv_kernel_counts()["WINO44F"] - before
         check(f"ncsnpp_nf64[fp32,{algo}]", outs[algo], g["out"], TOL_FWD_FULL["fp32"])
         del m
     e = rel_err(outs["auto"], outs["direct"])
     report("fp32_forward[auto (2-D F(4x4,3x3) f32) vs direct]", e, 2e-5)
     assert 0 < e < 2e-5, e            # (0 would mean the F(4,3) kernel did not run: G10's image is 768 x 64 = 192 tiles)
+    assert w44["auto"] > 0 and w44["direct"] == 0, w44   # the dispatch counters say which kernel ran
     with pytest.raises(ValueError):
         flowdec_amd.from_preset("flowdec_75m", precision="fp32", conv_algo="winograd")
 

@@ -63,9 +63,11 @@ CONV_CASES = [
     ("3x3_concat", 1, 16, 16, 64, 32, 128, 3, True, 1, True, 0, 0),
     ("3x3_concat_pad", 2, 16, 16, 32, 16, 128, 3, True, 1, False, 0, 0),     # second segment padded to a chunk
     ("3x3_partial_tiles", 1, 24, 8, 32, 0, 128, 3, True, 1, True, 0, 0),     # W = 8 < tile, H not multiple of 16
+    # the 3x3_head_* rows ask for statistics (want_stats=True below), so fd_conv2d runs them on the direct kernel's BN = 32 configuration,
+    # never on the dedicated head kernels (conv_head.hip / conv_headf.hip: no statistics output) -- those are pinned by test_hip_conv_exact.py
     ("3x3_head_cout4", 2, 16, 16, 128, 0, 4, 3, True, 1, True, 0, 0),
-    ("3x3_head_odd_chunks", 1, 24, 20, 96, 0, 4, 3, True, 1, True, 0, 0),     # 3 chunks: generic BN = 32 configuration
-    ("3x3_head_concat_plain", 2, 20, 36, 64, 64, 4, 3, False, 1, False, 0, 0),  # dedicated head kernel, two segments, ragged tiles
+    ("3x3_head_odd_chunks", 1, 24, 20, 96, 0, 4, 3, True, 1, True, 0, 0),     # 3 bf16 chunks (6 in f32)
+    ("3x3_head_concat_plain", 2, 20, 36, 64, 64, 4, 3, False, 1, False, 0, 0),  # two segments, ragged tiles
     ("3x3_head_256", 2, 32, 16, 256, 0, 4, 3, True, 2, True, 0, 0),
     ("3x3_small_c8", 1, 16, 16, 8, 0, 8, 3, True, 1, False, 0, 0),
     ("3x3_cout16", 1, 32, 16, 16, 8, 16, 3, True, 1, True, 0, 0),
@@ -125,8 +127,12 @@ def test_conv2d(ops, case, prec):
     x0 = nhwc(x[:, :C0], dt)
     x1 = nhwc(x[:, C0:], dt) if C1 else None
     pw = ops.pack_conv_weight(dev(w), C0=C0, dtype=dt, w_sc=w_sc, S0=S0 if S0 else None)
+    before = ops.conv_kernel_counts()
     out, stats = ops.conv2d(x0, pw, Cout, k, x1=x1, affine=aff, bias=bias, skip=skip, scale=scale, sc0=sc0, sc1=sc1, want_stats=True)
     torch.cuda.synchronize()
+    after = ops.conv_kernel_counts()
+    moved = {kn: after[kn] - before[kn] for kn in after if after[kn] != before[kn]}
+    assert moved == {"DIRECT": 1}, f"{name}: a statistics-producing call must run the direct kernel, the counters moved by {moved}"
     got = from_nhwc(out)
     # bf16: output rounding 2^-9 relative + transcendental differences of the fused SiLU; f32: accumulation order
     tol = 6e-3 if prec == "bf16" else 2e-5

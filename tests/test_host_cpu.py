@@ -37,6 +37,14 @@ def test_abi_exports_every_declared_symbol():
     assert lib.fd_upfirdn2d_out_size(768, 1, 2, 1, 1, 4) == 384 and lib.fd_upfirdn2d_out_size(96, 2, 1, 2, 1, 4) == 192
     assert lib.fd_conv_cout_pad(4) == 32 and lib.fd_conv_cout_pad(128) == 128 and lib.fd_conv_cout_pad(256) == 256
     assert lib.fd_conv_stats_tiles(768, 256) == 48 * 16
+    # the kernel-dispatch counters: one per FD_CONV_KERNEL_* slot, written to host memory
+    import ctypes as C
+    assert lib.fd_conv_kernel_counts(None, 0) == len(_lib.CONV_KERNELS) == 9
+    buf = (C.c_longlong * 12)(*([-1] * 12))
+    assert lib.fd_conv_kernel_counts(buf, 12) == 9
+    assert min(buf[:9]) >= 0 and list(buf)[9:] == [-1] * 3          # writes min(n, FD_CONV_KERNEL_COUNT) slots
+    buf = (C.c_longlong * 2)(-1, -1)
+    assert lib.fd_conv_kernel_counts(buf, 1) == 9 and buf[0] >= 0 and buf[1] == -1
 
 
 def test_model_create_validates_arguments():
