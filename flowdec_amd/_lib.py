@@ -49,6 +49,15 @@ class FdResblockDesc(C.Structure):
                 ("w0", c_void_p), ("bias0", c_void_p), ("bias0_rows", c_int), ("w1", c_void_p), ("bias1", c_void_p)]
 
 
+class FdAttnDesc(C.Structure):
+    _fields_ = [("C", c_int), ("gn_gamma", c_void_p), ("gn_beta", c_void_p), ("w_qkv", c_void_p), ("b_qkv", c_void_p),
+                ("w_out", c_void_p), ("b_out", c_void_p)]
+
+
+class FdModelArch(C.Structure):
+    _fields_ = [("bottleneck_attn", c_int), ("output_ksize", c_int)]
+
+
 class FdScoreConfig(C.Structure):
     _fields_ = [("theta", c_float), ("sigma_min", c_float), ("sigma_max", c_float), ("t_eps", c_float), ("snr", c_float),
                 ("N", c_int), ("predictor", c_int), ("corrector", c_int), ("corrector_steps", c_int), ("denoise", c_int)]
@@ -73,6 +82,8 @@ SIGNATURES = {
     "fd_gn_silu_apply": (c_int, [_P, _P, _P, c_int, c_ll, c_int, c_int, _P]),
     "fd_resblock_workspace_bytes": (c_size_t, [C.POINTER(FdResblockDesc), c_int, c_int, c_int, c_int]),
     "fd_resblock": (c_int, [C.POINTER(FdResblockDesc), _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "fd_attn_block_workspace_bytes": (c_size_t, [C.POINTER(FdAttnDesc), c_int, c_int, c_int, c_int]),
+    "fd_attn_block": (c_int, [C.POINTER(FdAttnDesc), _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "fd_gn_finalize": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_ll, c_float, _P]),
     "fd_conv_packed_bytes": (c_ll, [c_int] * 7),
     "fd_conv_pack_weights": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -94,6 +105,7 @@ SIGNATURES = {
     "fd_num_frames": (c_int, [c_int, c_int]),
     "fd_padded_frames": (c_int, [c_int]),
     "fd_model_create": (c_int, [C.POINTER(FdModelConfig), C.POINTER(_P)]),
+    "fd_model_create_ex": (c_int, [C.POINTER(FdModelConfig), C.POINTER(FdModelArch), C.POINTER(_P)]),
     "fd_model_destroy": (None, [_P]),
     "fd_model_num_params": (c_int, [_P]),
     "fd_model_param_info": (c_int, [_P, c_int, C.POINTER(C.c_char_p), C.POINTER(c_int), C.POINTER(c_int * 4)]),

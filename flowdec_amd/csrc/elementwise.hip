@@ -1,7 +1,7 @@
 // elementwise.hip -- the HBM-bound kernels of the NCSN++ vector field (NHWC activations):
 // GroupNorm statistics, FIR x2 resampling (+ fused GroupNorm/SiLU), generic upfirdn2d,
 // fused bias+act, time embedding, the 4-channel convs at the edges of the U-Net, and the
-// ODE state updates fused with the final 1x1 output layer.
+// ODE state updates fused with the final output layer (1x1, or 3x3 for the SGMSE-style backbone).
 #include <type_traits>
 
 #include "common.h"
@@ -752,19 +752,47 @@ __global__ __launch_bounds__(256) void combine_kernel(const T* __restrict__ p4, 
   }
 }
 
-// output_layer (1x1, 4 -> 2, no bias; ncsnpp.py:100,398) + view_as_complex (:407-411) fused with the
-// solver's state update:  dst = base + coef * (v + k_old);  optionally k_save = v.
+// The 3x3 output layer (4 -> 2, zero padding 'same', no bias; the SGMSE-style backbone's output_layer_kwargs) at pixel i of the
+// [B][H][W] image: f32, taps ascending, input channels ascending per tap.
 template <typename T>
+__device__ __forceinline__ float2 output3x3(const T* __restrict__ pyr, const float* __restrict__ wo, long long i, int H, int W) {
+  const int w = (int)(i % W), h = (int)((i / W) % H);
+  float vx = 0.f, vy = 0.f;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+    if (h + dy - 1 < 0 || h + dy - 1 >= H) continue;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      if (w + dx - 1 < 0 || w + dx - 1 >= W) continue;
+      float p[4];
+      fd_load_vec<T, 4>(pyr + 4 * (i + (long long)(dy - 1) * W + (dx - 1)), p);
+#pragma unroll
+      for (int ci = 0; ci < 4; ++ci) {
+        vx = fmaf(wo[ci * 9 + dy * 3 + dx], p[ci], vx);
+        vy = fmaf(wo[36 + ci * 9 + dy * 3 + dx], p[ci], vy);
+      }
+    }
+  }
+  return float2{vx, vy};
+}
+
+// output_layer (1x1, 4 -> 2, no bias; ncsnpp.py:100,398 -- or 3x3, KS = 3) + view_as_complex (:407-411) fused with the
+// solver's state update:  dst = base + coef * (v + k_old);  optionally k_save = v.
+template <typename T, int KS>
 __global__ void output_update_kernel(const T* __restrict__ pyr, const float* __restrict__ wo, const float2* __restrict__ base,
                                      const float2* __restrict__ kold, float coef, float2* __restrict__ dst,
-                                     float2* __restrict__ ksave, long long n) {
+                                     float2* __restrict__ ksave, long long n, int H, int W) {
   const float w0 = wo[0], w1 = wo[1], w2 = wo[2], w3 = wo[3], w4 = wo[4], w5 = wo[5], w6 = wo[6], w7 = wo[7];
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float p[4];
-    fd_load_vec<T, 4>(pyr + 4 * i, p);
     float2 v;
-    v.x = fmaf(w3, p[3], fmaf(w2, p[2], fmaf(w1, p[1], w0 * p[0])));
-    v.y = fmaf(w7, p[3], fmaf(w6, p[2], fmaf(w5, p[1], w4 * p[0])));
+    if constexpr (KS == 3) {
+      v = output3x3<T>(pyr, wo, i, H, W);
+    } else {
+      float p[4];
+      fd_load_vec<T, 4>(pyr + 4 * i, p);
+      v.x = fmaf(w3, p[3], fmaf(w2, p[2], fmaf(w1, p[1], w0 * p[0])));
+      v.y = fmaf(w7, p[3], fmaf(w6, p[2], fmaf(w5, p[1], w4 * p[0])));
+    }
     if (ksave) ksave[i] = v;
     float2 s = v;
     if (kold) { const float2 k = kold[i]; s.x += k.x; s.y += k.y; }
@@ -790,16 +818,22 @@ __global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __
 // Predictor / corrector update of the ScoreDec sampler (sampling/predictors.py:48-71, correctors.py:52-66) fused with the
 // output layer:  dst = cb * base + cy * Y + cn * v + cz * z   (v = output_layer(pyr) as complex; every coefficient is a
 // real scalar that the host derives from the OUVE closed forms, sdes.py:168-192).
-template <typename T>
+template <typename T, int KS>
 __global__ void score_update_kernel(const T* __restrict__ pyr, const float* __restrict__ wo, const float2* __restrict__ base, float cb,
                                     const float2* __restrict__ Y, float cy, float cn, const float2* __restrict__ z, float cz,
-                                    float2* __restrict__ dst, long long n) {
+                                    float2* __restrict__ dst, long long n, int H, int W) {
   const float w0 = wo[0], w1 = wo[1], w2 = wo[2], w3 = wo[3], w4 = wo[4], w5 = wo[5], w6 = wo[6], w7 = wo[7];
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    float p[4];
-    fd_load_vec<T, 4>(pyr + 4 * i, p);
-    const float vx = fmaf(w3, p[3], fmaf(w2, p[2], fmaf(w1, p[1], w0 * p[0])));
-    const float vy = fmaf(w7, p[3], fmaf(w6, p[2], fmaf(w5, p[1], w4 * p[0])));
+    float vx, vy;
+    if constexpr (KS == 3) {
+      const float2 v = output3x3<T>(pyr, wo, i, H, W);
+      vx = v.x; vy = v.y;
+    } else {
+      float p[4];
+      fd_load_vec<T, 4>(pyr + 4 * i, p);
+      vx = fmaf(w3, p[3], fmaf(w2, p[2], fmaf(w1, p[1], w0 * p[0])));
+      vy = fmaf(w7, p[3], fmaf(w6, p[2], fmaf(w5, p[1], w4 * p[0])));
+    }
     const float2 b = base[i];
     float2 o = {fmaf(cn, vx, cb * b.x), fmaf(cn, vy, cb * b.y)};
     if (cy != 0.f) { const float2 yv = Y[i]; o.x = fmaf(cy, yv.x, o.x); o.y = fmaf(cy, yv.y, o.y); }
@@ -1061,13 +1095,20 @@ static int edge_launch(int which, const fd_edge_args& a, hipStream_t st) {
     }
     case 3: {  // output + update
       const long long n = (long long)a.B * a.H * a.W;
-      hipLaunchKernelGGL(output_update_kernel<T>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.kold, a.coef, (float2*)a.out, (float2*)a.ksave, n);
+      if (a.ks == 3)
+        hipLaunchKernelGGL((output_update_kernel<T, 3>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.kold, a.coef, (float2*)a.out, (float2*)a.ksave, n, a.H, a.W);
+      else
+        hipLaunchKernelGGL((output_update_kernel<T, 1>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.kold, a.coef, (float2*)a.out, (float2*)a.ksave, n, a.H, a.W);
       break;
     }
     case 4: {  // output + score-sampler update
       const long long n = (long long)a.B * a.H * a.W;
-      hipLaunchKernelGGL(score_update_kernel<T>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, a.cb,
-                         (const float2*)a.y, a.cy, a.coef, (const float2*)a.z, a.cz, (float2*)a.out, n);
+      if (a.ks == 3)
+        hipLaunchKernelGGL((score_update_kernel<T, 3>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, a.cb,
+                           (const float2*)a.y, a.cy, a.coef, (const float2*)a.z, a.cz, (float2*)a.out, n, a.H, a.W);
+      else
+        hipLaunchKernelGGL((score_update_kernel<T, 1>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, a.cb,
+                           (const float2*)a.y, a.cy, a.coef, (const float2*)a.z, a.cz, (float2*)a.out, n, a.H, a.W);
       break;
     }
     case 5: {  // input convolution 4 -> Cout with GroupNorm partials (16 x 16 tiles)
@@ -1078,7 +1119,8 @@ static int edge_launch(int which, const fd_edge_args& a, hipStream_t st) {
         case 16: FD_CONV_IN(2); break;
         case 32: FD_CONV_IN(4); break;
         case 64: FD_CONV_IN(8); break;
-        default: return fd_set_error(FD_EINVAL, "edge_launch: conv_in needs Cout in {8, 16, 32, 64}");
+        case 128: FD_CONV_IN(16); break;
+        default: return fd_set_error(FD_EINVAL, "edge_launch: conv_in needs Cout in {8, 16, 32, 64, 128}");
       }
 #undef FD_CONV_IN
       break;

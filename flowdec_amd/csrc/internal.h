@@ -24,6 +24,7 @@ struct fd_edge_args {
   const void* z = nullptr;     // score update: dst = cb*base + cy*y + coef*v + cz*z
   float cb = 1.f, cy = 0.f, cz = 0.f;
   int B = 0, H = 0, W = 0, Cout = 0;
+  int ks = 1;                  // output layer (ops 3, 4): 1x1 or 3x3 (zero padding 'same'; w = [2][4][3][3])
 };
 
 // elementwise.hip
@@ -58,3 +59,9 @@ size_t fd_ndac_mfma_packed_bytes(int Ci, int Co, int K, int stride, int transpos
 void fd_ndac_mfma_pack(const float* w_ci_k_co, int Ci, int Co, int K, int stride, int transposed, void* dst);
 int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
                       int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st);
+// attn.hip: the bottleneck attention block (x -> out, GroupNorm affine given); qkv = f32 workspace of fd_attn_qkv_bytes; stats (optional) =
+// GroupNorm partials of out, [B][fd_attn_stats_tiles(H, W)][C][2]
+size_t fd_attn_qkv_bytes(int B, int N, int C);
+int fd_attn_stats_tiles(int H, int W);
+int fd_attn_launch(const void* x, const float* affine, const fd_attn_desc& d, float* qkv, void* out, float* stats, int B, int N, int dtype,
+                   hipStream_t st);

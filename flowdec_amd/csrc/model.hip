@@ -18,7 +18,7 @@
 
 namespace {
 
-enum ModKind { M_GFP, M_LINEAR, M_CONV_IN, M_RB, M_COMBINE, M_GN, M_CONV_HEAD };
+enum ModKind { M_GFP, M_LINEAR, M_CONV_IN, M_RB, M_COMBINE, M_GN, M_CONV_HEAD, M_ATTN };
 
 struct Mod {
   ModKind kind;
@@ -36,7 +36,8 @@ struct Mod {
   float *gn0_g = nullptr, *gn0_b = nullptr, *gn1_g = nullptr, *gn1_b = nullptr;
   float* b1 = nullptr;                     // Conv_1 bias (+ Conv_2 bias when the shortcut conv is folded in)
   float* bias0_eff = nullptr;              // [nt][cout] Conv_0 bias + Dense_0(silu(temb)), model-owned scratch
-  float *w_f32 = nullptr, *b_f32 = nullptr;  // small f32 weights (conv_in, combine, head bias, gn affine)
+  float *w_f32 = nullptr, *b_f32 = nullptr;  // small f32 weights (conv_in, combine, head bias, gn affine; attention: NIN_3)
+  float *w_qkv = nullptr, *b_qkv = nullptr;  // attention: NIN_0 | NIN_1 | NIN_2 packed side by side ([C][3C], [3C])
 };
 
 struct ParamInfo {
@@ -109,6 +110,7 @@ struct GraphKey {
 
 struct fd_model {
   fd_model_config cfg;
+  fd_model_arch arch{0, 1};
   int dt = FD_BF16;                 // storage type (cfg.act_dtype without the algorithm flags)
   int n_freq = 0, temb_dim = 0;
   std::vector<Mod> mods;
@@ -123,7 +125,7 @@ struct fd_model {
   float* temb = nullptr;            // [MAX_NT][temb_dim]
   fd_temb_job* jobs_dev = nullptr;
   int njobs = 0;
-  float* wo = nullptr;              // output_layer weight [2][4]
+  float* wo = nullptr;              // output_layer weight [2][4][ks][ks]
   fd_stft_plan* stft = nullptr;
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::set<GraphKey> seen;          // keys that ran once eagerly: a solve is captured at its SECOND sighting
@@ -168,7 +170,7 @@ namespace {
 int gn_groups(int C) { return (C / 4 < 32) ? C / 4 : 32; }
 
 // mirrors NCSNpp.__init__ (ncsnpp.py:102-251) for progressive='output_skip', progressive_input='input_skip',
-// combine 'sum', biggan blocks, no attention
+// combine 'sum', biggan blocks, no attention at the resolution levels, optionally one AttnBlockpp at the bottleneck (:196-199)
 void build_structure(fd_model* m) {
   const fd_model_config& c = m->cfg;
   const int nf = c.nf, R = c.num_levels, nrb = c.num_res_blocks, nch = 4;
@@ -177,7 +179,8 @@ void build_structure(fd_model* m) {
   mods.clear(); P.clear();
   auto add_param = [&](const std::string& n, std::vector<int> s) { P.push_back(ParamInfo{n, s}); };
   auto pref = [](int i) { return "backbone.all_modules." + std::to_string(i) + "."; };
-  add_param("backbone.output_layer.weight", {2, nch, 1, 1});
+  const int ks = m->arch.output_ksize;
+  add_param("backbone.output_layer.weight", {2, nch, ks, ks});
   int idx = 0;
   auto push = [&](Mod md) { md.idx = idx++; mods.push_back(md); return (int)mods.size() - 1; };
   auto add_rb = [&](int c0, int c1, int cout, bool up, bool down, int level) {
@@ -214,6 +217,15 @@ void build_structure(fd_model* m) {
   }
   in_ch = hs_c.back();
   add_rb(in_ch, 0, in_ch, false, false, R - 1);
+  if (m->arch.bottleneck_attn) {   // layerspp.py:72-89: GroupNorm_0, then NIN_0..3 (W [in][out], b)
+    Mod md{}; md.kind = M_ATTN; md.cin = md.cout = in_ch; md.level = R - 1;
+    const int i = mods[push(md)].idx;
+    add_param(pref(i) + "GroupNorm_0.weight", {in_ch}); add_param(pref(i) + "GroupNorm_0.bias", {in_ch});
+    for (int k = 0; k < 4; ++k) {
+      add_param(pref(i) + "NIN_" + std::to_string(k) + ".W", {in_ch, in_ch});
+      add_param(pref(i) + "NIN_" + std::to_string(k) + ".b", {in_ch});
+    }
+  }
   add_rb(in_ch, 0, in_ch, false, false, R - 1);
   for (int lvl = R - 1; lvl >= 0; --lvl) {
     for (int b = 0; b < nrb + 1; ++b) {
@@ -470,6 +482,25 @@ struct Fwd {
     return FD_OK;
   }
 
+  // AttnBlockpp at the bottleneck (ncsnpp.py:326-327): GroupNorm_0 from the partials x's producer emitted, q|k|v in f32 scratch, out with
+  // the partials the next ResBlock's GroupNorm_0 consumes
+  int attn(const Mod& md, Tens& x, Tens& out) {
+    size_t aff;
+    FD_TRY(gn_affine(x, nullptr, md.gn0_g, md.gn0_b, &aff));
+    const int N = x.H * x.W;
+    const size_t qkv = arena.alloc(fd_attn_qkv_bytes(B, N, x.C));
+    out = talloc(x.C, x.H, x.W);
+    out.tiles = fd_attn_stats_tiles(x.H, x.W); out.stride = x.C;
+    out.sums = arena.alloc(sizeof(float) * 2 * (size_t)B * out.tiles * out.stride);
+    if (!dry) {
+      fd_attn_desc d{}; d.C = x.C; d.gn_gamma = md.gn0_g; d.gn_beta = md.gn0_b; d.w_qkv = md.w_qkv; d.b_qkv = md.b_qkv; d.w_out = md.w_f32; d.b_out = md.b_f32;
+      FD_TRY(fd_attn_launch(ptr(x.off), (const float*)ptr(aff), d, (float*)ptr(qkv), ptr(out.off), (float*)ptr(out.sums), B, N, dt, st));
+    }
+    arena.release(qkv);
+    arena.release(aff);
+    return FD_OK;
+  }
+
   // ncsnpp.py:254-399
   int run(const float* x, const float* y, const float* t, float t_imm, int nt, const OutSpec& os) {
     const fd_model_config& c = m->cfg;
@@ -494,7 +525,7 @@ struct Fwd {
       // all_modules.3 (3x3, 4 -> nf), emitting the GroupNorm partials of its output.  bf16 mode, whole tiles: a vector-FMA kernel next to
       // its stores (conv_in_kernel: the layer is all prologue and epilogue on the matrix cores, 237 -> 60 us at 8 x 768 x 256); otherwise
       // the MFMA kernel on the zero-padded 8-channel input
-      const bool vec_in = dt == FD_BF16 && md.w_f32 && F % 16 == 0 && T % 16 == 0 && (md.cout == 8 || md.cout == 16 || md.cout == 32 || md.cout == 64);
+      const bool vec_in = dt == FD_BF16 && md.w_f32 && F % 16 == 0 && T % 16 == 0 && (md.cout == 8 || md.cout == 16 || md.cout == 32 || md.cout == 64 || md.cout == 128);
       if (vec_in) {
         h0.tiles = (F / 16) * (T / 16); h0.stride = md.cout;
         h0.sums = arena.alloc(sizeof(float) * 2 * (size_t)B * h0.tiles * h0.stride);
@@ -538,6 +569,12 @@ struct Fwd {
     {
       Tens a1, a2;
       FD_TRY(resblock(mods[mi++], hs.back(), nullptr, nt, a1));
+      if (mods[mi].kind == M_ATTN) {
+        Tens at;
+        FD_TRY(attn(mods[mi++], a1, at));
+        tfree(a1);
+        a1 = at;
+      }
       FD_TRY(resblock(mods[mi++], a1, nullptr, nt, a2));
       tfree(a1);
       h = a2;
@@ -585,7 +622,7 @@ struct Fwd {
     if (!hs.empty() || mi != mods.size()) return fd_set_error(FD_ESTATE, "internal: module walk mismatch");
     if (!dry) {
       fd_edge_args a; a.x = ptr(pyramid.off); a.w = m->wo; a.base = os.base; a.kold = os.kold; a.coef = os.coef; a.out = os.dst; a.ksave = os.ksave;
-      a.B = B; a.H = F; a.W = T;
+      a.B = B; a.H = F; a.W = T; a.ks = m->arch.output_ksize;
       if (os.score) { a.y = os.yv; a.z = os.z; a.cb = os.cb; a.cy = os.cy; a.cz = os.cz; }
       FD_TRY(fd_edge_op(os.score ? 4 : 3, a, dt, st));
     }
@@ -783,9 +820,11 @@ int run_maybe_graph(fd_model* m, const GraphKey& key, bool use_graph, hipStream_
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-extern "C" int fd_model_create(const fd_model_config* cfg, fd_model** out) {
-  FD_REQUIRE(cfg && out, "fd_model_create: null pointer");
-  FD_REQUIRE(cfg->nf >= 8 && cfg->nf % 8 == 0 && cfg->nf <= 64, "fd_model_create: nf must be a multiple of 8 in [8, 64] (got %d)", cfg->nf);
+extern "C" int fd_model_create_ex(const fd_model_config* cfg, const fd_model_arch* arch, fd_model** out) {
+  FD_REQUIRE(cfg && arch && out, "fd_model_create: null pointer");
+  FD_REQUIRE(cfg->nf >= 8 && cfg->nf % 8 == 0 && cfg->nf <= 128, "fd_model_create: nf must be a multiple of 8 in [8, 128] (got %d)", cfg->nf);
+  FD_REQUIRE(arch->bottleneck_attn == 0 || arch->bottleneck_attn == 1, "fd_model_create_ex: bottleneck_attn must be 0 or 1");
+  FD_REQUIRE(arch->output_ksize == 1 || arch->output_ksize == 3, "fd_model_create_ex: output_ksize must be 1 or 3 (got %d)", arch->output_ksize);
   FD_REQUIRE(cfg->num_levels >= 1 && cfg->num_levels <= 8 && cfg->num_res_blocks >= 1, "fd_model_create: bad level / block counts");
   const int act_nos = cfg->act_dtype & ~FD_NO_SIDE_STREAM;
   FD_REQUIRE(((act_nos & 0xff) == FD_BF16 && !(act_nos & (FD_BF16_OPERANDS | FD_BF16X3_OPERANDS))) || act_nos == FD_F32 || act_nos == (FD_F32 | FD_WINOGRAD_AUTO) ||
@@ -806,14 +845,24 @@ extern "C" int fd_model_create(const fd_model_config* cfg, fd_model** out) {
     const int ch = cfg->nf * cfg->ch_mult[i];
     FD_REQUIRE(ch >= 8 && ch <= 256 && (ch & (ch - 1)) == 0, "fd_model_create: level width nf*ch_mult=%d must be a power of two in [8, 256]", ch);
   }
+  if (arch->bottleneck_attn) {
+    const int C = cfg->nf * cfg->ch_mult[cfg->num_levels - 1];
+    FD_REQUIRE(C >= 16, "fd_model_create_ex: the bottleneck attention block needs >= 16 channels (got %d)", C);
+  }
   fd_model* m = new fd_model();
   m->cfg = *cfg;
+  m->arch = *arch;
   m->dt = cfg->act_dtype & 0xff;
   m->n_freq = cfg->n_fft / 2 + 1;
   m->temb_dim = 4 * cfg->nf;
   build_structure(m);
   *out = m;
   return FD_OK;
+}
+
+extern "C" int fd_model_create(const fd_model_config* cfg, fd_model** out) {
+  const fd_model_arch arch{0, 1};
+  return fd_model_create_ex(cfg, &arch, out);
 }
 
 extern "C" void fd_model_destroy(fd_model* m) {
@@ -913,6 +962,23 @@ extern "C" int fd_model_finalize(fd_model* m, void* stream) {
         const std::string q = md.kind == M_COMBINE ? p + "Conv_0." : p;
         FD_TRY(upload_f32(m, q + "weight", &md.w_f32));
         FD_TRY(upload_f32(m, q + "bias", &md.b_f32));
+        break;
+      }
+      case M_ATTN: {
+        FD_TRY(upload_f32(m, p + "GroupNorm_0.weight", &md.gn0_g)); FD_TRY(upload_f32(m, p + "GroupNorm_0.bias", &md.gn0_b));
+        const int Cc = md.cout;
+        std::vector<float>& wq = m->host[p + "qkv.W"];
+        std::vector<float>& bq = m->host[p + "qkv.b"];
+        wq.assign((size_t)Cc * 3 * Cc, 0.f); bq.assign((size_t)3 * Cc, 0.f);
+        for (int k = 0; k < 3; ++k) {
+          const std::vector<float>& w = m->host[p + "NIN_" + std::to_string(k) + ".W"];
+          const std::vector<float>& bb = m->host[p + "NIN_" + std::to_string(k) + ".b"];
+          for (int r = 0; r < Cc; ++r)
+            for (int c = 0; c < Cc; ++c) wq[(size_t)r * 3 * Cc + k * Cc + c] = w[(size_t)r * Cc + c];
+          for (int c = 0; c < Cc; ++c) bq[(size_t)k * Cc + c] = bb[c];
+        }
+        FD_TRY(upload_f32(m, p + "qkv.W", &md.w_qkv)); FD_TRY(upload_f32(m, p + "qkv.b", &md.b_qkv));
+        FD_TRY(upload_f32(m, p + "NIN_3.W", &md.w_f32)); FD_TRY(upload_f32(m, p + "NIN_3.b", &md.b_f32));
         break;
       }
       case M_GN:

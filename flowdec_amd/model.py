@@ -52,6 +52,24 @@ class ResnetBlockBigGANpp(nn.Module):
         self.up, self.down, self.in_ch, self.out_ch = up, down, in_ch, out_ch
 
 
+class NIN(nn.Module):
+    """layers.py:566-575 (parameter container): y = x W + b over the channel axis, W is [in, out]."""
+
+    def __init__(self, in_dim, num_units):
+        super().__init__()
+        self.W = nn.Parameter(torch.zeros(in_dim, num_units))
+        self.b = nn.Parameter(torch.zeros(num_units))
+
+
+class AttnBlockpp(nn.Module):
+    """layerspp.py:72-101 (parameter container; skip_rescale=True): the bottleneck attention block of the SGMSE-style backbone."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.GroupNorm_0 = nn.GroupNorm(num_groups=min(channels // 4, 32), num_channels=channels, eps=1e-6)
+        self.NIN_0, self.NIN_1, self.NIN_2, self.NIN_3 = (NIN(channels, channels) for _ in range(4))
+
+
 class Combine(nn.Module):
     """layerspp.py:54-69 (parameter container, method 'sum')."""
 
@@ -76,10 +94,11 @@ CONV_ALGOS = {"direct": 0, "winograd": L.FD_WINOGRAD, "winograd_lowres": L.FD_WI
 class NCSNpp(nn.Module):
     """NCSN++ vector field v(x_t, y, t) -- constructor signature of ncsnpp.py:52-75.
 
-    Supported (= every shipped FlowDec config, config/model/backbone/ncsnpp_final_no_attn.yaml):
-    swish, BigGAN blocks, FIR [1,3,3,1], skip_rescale, progressive 'output_skip', progressive_input
-    'input_skip' combined by 'sum', Fourier embedding, no attention, 1x1 bias-free output layer.
-    Anything else raises NotImplementedError.
+    Supported (every shipped FlowDec config, config/model/backbone/ncsnpp_final_no_attn.yaml, and the SGMSE-style
+    ncsnpp_default_ycond.yaml): swish, BigGAN blocks, FIR [1,3,3,1], skip_rescale, progressive 'output_skip', progressive_input
+    'input_skip' combined by 'sum', Fourier embedding, optionally one attention block at the bottleneck (bottleneck_attn), a
+    bias-free output layer of 1x1 or 3x3 ('same' zero padding).  Attention at the resolution levels (attn_resolutions) and
+    anything else raises NotImplementedError.
     """
 
     def __init__(self, nonlinearity="swish", nf=128, ch_mult=(1, 1, 2, 2, 2, 2, 2), num_res_blocks=2,
@@ -95,7 +114,7 @@ class NCSNpp(nn.Module):
         all_res = [image_size // (2 ** i) for i in range(len(ch_mult))]
         unsupported = []
         if nonlinearity != "swish": unsupported.append("nonlinearity != swish")
-        if any(r in tuple(attn_resolutions) for r in all_res) or bottleneck_attn: unsupported.append("attention blocks")
+        if any(r in tuple(attn_resolutions) for r in all_res): unsupported.append("attention blocks at the resolution levels (attn_resolutions)")
         if not (conditional and fir and skip_rescale and resamp_with_conv): unsupported.append("conditional/fir/skip_rescale/resamp_with_conv must be True")
         if tuple(fir_kernel) != (1, 3, 3, 1): unsupported.append("fir_kernel != [1,3,3,1]")
         if resblock_type.lower() != "biggan": unsupported.append("resblock_type != biggan")
@@ -104,8 +123,14 @@ class NCSNpp(nn.Module):
         if embedding_type.lower() != "fourier": unsupported.append("embedding_type != fourier")
         if dropout != 0.0: unsupported.append("dropout != 0 (inference only)")
         if num_channels != 4: unsupported.append("num_channels != 4")
-        if dict(output_layer_kwargs).get("kernel_size", 3) != 1 or dict(output_layer_kwargs).get("bias", False):
-            unsupported.append("output layer other than 1x1 without bias")
+        olk = dict(output_layer_kwargs)
+        out_ks = olk.get("kernel_size", 3)
+        out_ks = out_ks[0] if isinstance(out_ks, (tuple, list)) and len(set(out_ks)) == 1 else out_ks
+        pad = olk.get("padding", 0)
+        pad_ok = out_ks == 1 or pad == "same" or pad == 1 or (isinstance(pad, (tuple, list)) and tuple(pad) == (1, 1))
+        if out_ks not in (1, 3) or olk.get("bias", True) or not pad_ok or olk.get("padding_mode", "zeros") != "zeros" or \
+                any(k not in ("kernel_size", "bias", "padding", "padding_mode") for k in olk):
+            unsupported.append("output layer other than a bias-free 1x1 or 3x3 ('same' zero padding) convolution")
         if unsupported:
             raise NotImplementedError("flowdec_amd.NCSNpp: unsupported configuration: " + "; ".join(unsupported))
         if precision not in ("bf16", "fp32", "mixed", "bf16x3"):
@@ -119,7 +144,8 @@ class NCSNpp(nn.Module):
         # channels on whole 16 x 16 tiles
         self.nf, self.ch_mult, self.num_res_blocks, self.precision, self.conv_algo = nf, ch_mult, num_res_blocks, precision, conv_algo
         self.num_resolutions = len(ch_mult)
-        self.output_layer = nn.Conv2d(num_channels, 2, kernel_size=1, bias=False)
+        self.bottleneck_attn, self.output_ksize = bool(bottleneck_attn), int(out_ks)
+        self.output_layer = nn.Conv2d(num_channels, 2, kernel_size=self.output_ksize, padding=self.output_ksize // 2, bias=False)
         temb_dim = nf * 4
         mods = [GaussianFourierProjection(embedding_size=nf, scale=fourier_scale), nn.Linear(2 * nf, temb_dim),
                 nn.Linear(temb_dim, temb_dim), nn.Conv2d(num_channels, nf, 3, padding=1)]
@@ -133,7 +159,10 @@ class NCSNpp(nn.Module):
                 mods.append(ResnetBlockBigGANpp(in_ch, temb_dim=temb_dim, down=True))
                 mods.append(Combine(num_channels, in_ch)); hs_c.append(in_ch)
         in_ch = hs_c[-1]
-        mods += [ResnetBlockBigGANpp(in_ch, temb_dim=temb_dim), ResnetBlockBigGANpp(in_ch, temb_dim=temb_dim)]
+        mods.append(ResnetBlockBigGANpp(in_ch, temb_dim=temb_dim))
+        if self.bottleneck_attn:
+            mods.append(AttnBlockpp(in_ch))
+        mods.append(ResnetBlockBigGANpp(in_ch, temb_dim=temb_dim))
         for lvl in reversed(range(R)):
             for _ in range(num_res_blocks + 1):
                 out_ch = nf * ch_mult[lvl]
@@ -171,6 +200,9 @@ class NCSNpp(nn.Module):
         if not self.side_stream:
             cfg.act_dtype |= L.FD_NO_SIDE_STREAM
         return cfg
+
+    def _arch_struct(self):
+        return L.FdModelArch(int(self.bottleneck_attn), self.output_ksize)
 
     def invalidate(self):
         """Drop the packed device copy (called after parameters change)."""
@@ -218,7 +250,7 @@ class NCSNpp(nn.Module):
         with torch.cuda.device(dev):
             h = C.c_void_p()
             cfg = self._config_struct()
-            L.check(lib.fd_model_create(C.byref(cfg), C.byref(h)))
+            L.check(lib.fd_model_create_ex(C.byref(cfg), C.byref(self._arch_struct()), C.byref(h)))
             sd = {"backbone." + k: v for k, v in self.state_dict().items()}
             n = lib.fd_model_num_params(h)
             for i in range(n):
@@ -991,6 +1023,16 @@ BACKBONE_FINAL_NO_ATTN = dict(image_size=768, nonlinearity="swish", nf=64, ch_mu
                               fourier_scale=16, dropout=0.0, num_channels=4,
                               output_layer_kwargs=dict(kernel_size=1, bias=False, padding="same", padding_mode="zeros"))
 
+# config/model/backbone/ncsnpp_default_ycond.yaml: the SGMSE+ backbone (flow_model_sgmse / score_model_sgmse)
+BACKBONE_SGMSE = dict(image_size=768, nonlinearity="swish", nf=128, ch_mult=(1, 1, 2, 2, 2, 2, 2), num_res_blocks=2,
+                      attn_resolutions=(), bottleneck_attn=True, resamp_with_conv=True, conditional=True, fir=True,
+                      fir_kernel=(1, 3, 3, 1), skip_rescale=True, resblock_type="biggan", progressive="output_skip",
+                      progressive_input="input_skip", progressive_combine="sum", init_scale=0.0, embedding_type="fourier",
+                      fourier_scale=16, dropout=0.0, num_channels=4,
+                      output_layer_kwargs=dict(kernel_size=3, bias=False, padding="same", padding_mode="zeros"))
+# feature_extractor/compressed_complex_stft_sgmse1534.yaml
+STFT_SGMSE = dict(alpha=0.5, beta=0.15)
+
 PRESETS = {
     "flowdec_75m": dict(sigma_file="flowdec_autoparams_75m.npy"),
     "flowdec_25s": dict(sigma_file="flowdec_autoparams_25s.npy"),
@@ -999,6 +1041,10 @@ PRESETS = {
     # baselines (config/baseline_scoredec_75s.yaml -> model/score_model_final.yaml + sde/ouve_final.yaml; baseline_regression_75s.yaml)
     "baseline_scoredec_75s": dict(kind="score", sde=dict(theta=1.5, sigma_min=0.05, sigma_max=0.82, N=30), t_eps=3e-2),
     "baseline_regression_75s": dict(kind="regression"),
+    # config/model/flow_model_sgmse.yaml, score_model_sgmse.yaml (+ sde/ouve_sgmse.yaml): the SGMSE-style backbone and features
+    "flow_model_sgmse": dict(sigma_file=None, sigma_y=0.5, backbone=BACKBONE_SGMSE, stft=STFT_SGMSE),
+    "score_model_sgmse": dict(kind="score", sde=dict(theta=1.5, sigma_min=0.05, sigma_max=0.5, N=30), t_eps=3e-2, backbone=BACKBONE_SGMSE,
+                              stft=STFT_SGMSE),
 }
 
 
@@ -1006,9 +1052,10 @@ def from_preset(name: str = "flowdec_75m", precision: str = "bf16", **backbone_o
     """Instantiate the model a reference user gets from `instantiate(compose(config_name=name)['model'])`."""
     if name not in PRESETS:
         raise KeyError(f"unknown preset {name!r}; available: {sorted(PRESETS)}")
-    bb = dict(BACKBONE_FINAL_NO_ATTN); bb.update(backbone_overrides)
+    bb = dict(PRESETS[name].get("backbone", BACKBONE_FINAL_NO_ATTN)); bb.update(backbone_overrides)
     backbone = NCSNpp(precision=precision, **bb)
-    fe = AmplitudeCompressedComplexSTFT(window_fn="hann", n_fft=1534, n_hops=4, sampling_rate=48000, alpha=0.3, beta=0.33)
+    stft = dict(alpha=0.3, beta=0.33); stft.update(PRESETS[name].get("stft", {}))
+    fe = AmplitudeCompressedComplexSTFT(window_fn="hann", n_fft=1534, n_hops=4, sampling_rate=48000, **stft)
     kind = PRESETS[name].get("kind", "flow")
     if kind == "score":
         return ScoreModel(sde=OUVESDE(**PRESETS[name]["sde"]), t_eps=PRESETS[name]["t_eps"], backbone=backbone, feature_extractor=fe,
@@ -1016,5 +1063,5 @@ def from_preset(name: str = "flowdec_75m", precision: str = "bf16", **backbone_o
     if kind == "regression":
         return RegressionModel(backbone=backbone, feature_extractor=fe, sampling_rate=48000).eval()
     sf = PRESETS[name]["sigma_file"]
-    sigma_y = sigma_y_from_file(sf, factor=1, kernel_bandwidth=3) if sf else 0.66
+    sigma_y = sigma_y_from_file(sf, factor=1, kernel_bandwidth=3) if sf else PRESETS[name].get("sigma_y", 0.66)
     return FlowModel(backbone=backbone, feature_extractor=fe, sampling_rate=48000, sigma_x=0.0, sigma_y=sigma_y).eval()

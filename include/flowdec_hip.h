@@ -159,7 +159,7 @@ int fd_fir_resample(const void* x, const float* affine, void* out_raw, void* out
 /* The input convolution of NCSN++ (all_modules.3 = conv3x3(4, nf), ncsnpp.py:291 via layers.py:128-134) on the packed NHWC input
  * [B][H][W][8] (channels 0..3 = x.re, x.im, y.re, y.im; 4..7 ignored), zero padding, as f32 vector FMAs (taps ascending, input channels
  * ascending, one fma each), with the GroupNorm partial sums of the output: stats[B][(H / 16) * (W / 16)][Cout][2] = per 16 x 16 pixel
- * tile (sum x, sum x^2) of the f32 values.  w = [Cout][4][3][3] float32 (the checkpoint's layout), Cout in {8, 16, 32, 64},
+ * tile (sum x, sum x^2) of the f32 values.  w = [Cout][4][3][3] float32 (the checkpoint's layout), Cout in {8, 16, 32, 64, 128},
  * H % 16 == W % 16 == 0.  dtype = storage type of `in8` and `out`. */
 int fd_conv_in(const void* in8, const float* w, const float* bias, void* out, float* stats, int B, int H, int W, int Cout, int dtype,
                void* stream);
@@ -283,6 +283,23 @@ int fd_decompress_istft_ragged(const fd_stft_plan* plan, const float* X, const i
  * values (feature_extractors.py:118-139) as a stand-alone pass; X == Y allowed. */
 int fd_compress_spec(const float* X, float* Y, long long n, float alpha, float beta, int inverse, void* stream);
 int fd_num_frames(int L, int hop);     /* 1 + L / hop */
+/* One AttnBlockpp.forward with skip_rescale (layerspp.py:72-101; the bottleneck block of the SGMSE-style backbone):
+ * out = (x + NIN_3(softmax(q k^T C^-0.5) v)) / sqrt(2), q | k | v = NIN_0..2(GroupNorm_0(x)), GroupNorm_0 = min(C/4, 32) groups,
+ * eps 1e-6, affine, no SiLU; the softmax runs over all H*W positions of an image.  x / out = NHWC [B][H][W][C] in `dtype`
+ * (FD_BF16 or FD_F32); every product, sum and exponential is float32 in both.  C = 16, 32, 64, 128 or 256.
+ *   w_qkv = [C][3C]: NIN_0.W | NIN_1.W | NIN_2.W side by side (NIN.W is [in][out]),  b_qkv = [3C] likewise
+ *   w_out = NIN_3.W [C][C],  b_out = NIN_3.b [C]
+ * stats (optional, may be NULL): the GroupNorm partial sums of out, [B][ceil(H*W / 16)][C][2] (sum, sum of squares). */
+typedef struct fd_attn_desc {
+  int C;
+  const float *gn_gamma, *gn_beta;
+  const float *w_qkv, *b_qkv;
+  const float *w_out, *b_out;
+} fd_attn_desc;
+size_t fd_attn_block_workspace_bytes(const fd_attn_desc* d, int B, int H, int W, int dtype);
+int fd_attn_block(const fd_attn_desc* d, const void* x, void* out, float* stats, int B, int H, int W, int dtype, void* ws, size_t ws_bytes,
+                  void* stream);
+
 int fd_padded_frames(int T);           /* next multiple of 64 */
 
 /* ------------------------------------------------------------------------------------------------
@@ -302,6 +319,15 @@ typedef struct fd_model_config {
 } fd_model_config;
 
 int fd_model_create(const fd_model_config* cfg, fd_model** out);
+/* Architecture switches beyond the shipped backbone (fd_model_create = fd_model_create_ex with {0, 1}):
+ *   bottleneck_attn  1 = an AttnBlockpp between the two middle ResBlocks (ncsnpp.py:196-199, 325-330; one more all_modules slot)
+ *   output_ksize     1 = output_layer 1x1 [2][4][1][1]; 3 = 3x3 with zero padding 'same' [2][4][3][3]; never a bias
+ * The SGMSE-style backbone (config/model/backbone/ncsnpp_default_ycond.yaml) is {1, 3} with nf = 128. */
+typedef struct fd_model_arch {
+  int bottleneck_attn;
+  int output_ksize;
+} fd_model_arch;
+int fd_model_create_ex(const fd_model_config* cfg, const fd_model_arch* arch, fd_model** out);
 void fd_model_destroy(fd_model* m);
 /* Number of parameter tensors the model expects, and the i-th name / shape (reference state_dict
  * layout `backbone.all_modules.<i>.<...>`). */
