@@ -135,6 +135,10 @@ SIGNATURES = {
     "fd_profile_read_stft": (c_int, [_P, C.POINTER(C.c_double * 6), C.POINTER(c_int * 2)]),
     "fd_conv1d": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
     "fd_conv_transpose1d": (c_int, [_P, _P, _P, _P, _P] + [c_int] * 7 + [_P]),
+    "fd_ndac_mfma_packed_bytes": (c_size_t, [c_int] * 5),
+    "fd_ndac_mfma_pack_weights": (c_int, [_P] + [c_int] * 5 + [_P]),
+    "fd_ndac_mfma_variant": (c_int, [c_int] * 9 + [C.POINTER(c_int * 5)]),
+    "fd_ndac_mfma_conv1d": (c_int, [_P] * 7 + [c_int] * 9 + [_P]),
     "fd_ndac_create": (c_int, [C.POINTER(FdNdacConfig), C.POINTER(_P)]),
     "fd_ndac_destroy": (None, [_P]),
     "fd_ndac_hop_length": (c_int, [_P]),

@@ -55,10 +55,12 @@ int fd_stft_inverse(fd_stft_plan* p, const float* X, const int* lens, int B, int
 size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop);
 // ndac_mfma.hip: the codec's wide convolutions on the matrix cores (split-bf16 operands, f32 tolerance)
 bool fd_ndac_mfma_supported(int Ci, int Co, int K, int stride, int dil, int transposed);
-size_t fd_ndac_mfma_packed_bytes(int Ci, int Co, int K, int stride, int transposed);
+// (fd_ndac_mfma_packed_bytes: public, include/flowdec_hip.h)
 void fd_ndac_mfma_pack(const float* w_ci_k_co, int Ci, int Co, int K, int stride, int transposed, void* dst);
 int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
                       int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st);
+// ndac.hip: PyTorch weight layout ([Co][Ci][K] conv, [Ci][Co][K] transposed) -> the codec's own [Ci][K][Co] (host memory)
+void fd_ndac_weight_ci_k_co(const float* w, int Ci, int Co, int K, int transposed, float* dst);
 // attn.hip: the bottleneck attention block (x -> out, GroupNorm affine given); qkv = f32 workspace of fd_attn_qkv_bytes; stats (optional) =
 // GroupNorm partials of out, [B][fd_attn_stats_tiles(H, W)][C][2]
 size_t fd_attn_qkv_bytes(int B, int N, int C);

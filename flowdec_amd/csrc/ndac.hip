@@ -741,6 +741,13 @@ extern "C" int fd_ndac_set_param(fd_ndac* m, const char* name, const float* host
   return fd_set_error(FD_EINVAL, "fd_ndac_set_param: unknown parameter '%s'", name);
 }
 
+void fd_ndac_weight_ci_k_co(const float* w, int Ci, int Co, int K, int transposed, float* dst) {
+  for (int ci = 0; ci < Ci; ++ci)
+    for (int k = 0; k < K; ++k)
+      for (int co = 0; co < Co; ++co)
+        dst[((size_t)ci * K + k) * Co + co] = transposed ? w[((size_t)ci * Co + co) * K + k] : w[((size_t)co * Ci + ci) * K + k];
+}
+
 extern "C" int fd_ndac_finalize(fd_ndac* m, void* stream) {
   FD_REQUIRE(m, "fd_ndac_finalize: null codec");
   if (m->finalized) return FD_OK;
@@ -767,10 +774,7 @@ extern "C" int fd_ndac_finalize(fd_ndac* m, void* stream) {
       const int d0 = p.shape[0], d1 = p.shape[1], K = p.shape[2];
       const int Ci = tr ? d0 : d1, Co = tr ? d1 : d0;
       std::vector<float> t((size_t)Ci * K * Co);
-      for (int ci = 0; ci < Ci; ++ci)
-        for (int k = 0; k < K; ++k)
-          for (int co = 0; co < Co; ++co)
-            t[((size_t)ci * K + k) * Co + co] = tr ? it->second[((size_t)ci * Co + co) * K + k] : it->second[((size_t)co * Ci + ci) * K + k];
+      fd_ndac_weight_ci_k_co(it->second.data(), Ci, Co, K, tr, t.data());
       it->second.swap(t);
       const bool down = p.name.rfind("encoder.", 0) == 0 && nblk == 2 && p.name.size() > 15 &&
                         p.name.compare(p.name.size() - 15, 15, ".block.4.weight") == 0;   // encoder.block.<i>.block.4 = the strided WNConv1d (K = 2 s)

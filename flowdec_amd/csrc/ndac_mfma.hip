@@ -311,7 +311,8 @@ bool fd_ndac_mfma_supported(int Ci, int Co, int K, int stride, int dil, int tran
   return (size_t)(TN + span) * ROWB * 2 <= 64 * 1024;
 }
 
-size_t fd_ndac_mfma_packed_bytes(int Ci, int Co, int K, int stride, int transposed) {   // + one step of prefetch padding
+extern "C" size_t fd_ndac_mfma_packed_bytes(int Ci, int Co, int K, int stride, int transposed) {   // + one step of prefetch padding
+  if (!fd_ndac_mfma_supported(Ci, Co, K, stride, 1, transposed)) return 0;
   const int ntaps = stride > 1 ? K / stride : K, nphase = transposed ? stride : 1;
   const size_t steps = (size_t)nphase * chunks_of(Ci, stride, transposed) * ntaps * 2;
   return (steps * Co * 16 * 2 + 3 * 2 * 64 * 8) * sizeof(unsigned short);
@@ -354,13 +355,18 @@ void fd_ndac_mfma_pack(const float* w, int Ci, int Co, int K, int stride, int tr
                 }
 }
 
-int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
-                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st) {
+namespace {
+
+// The launch geometry of one call: the kernel variant (MT, S, NT), grid and LDS size.  fd_ndac_mfma_conv launches what this returns and
+// fd_ndac_mfma_variant reports it, so the two cannot disagree.
+struct Plan { MArgs a; int S, mt, nt; dim3 grid; size_t lds; };
+
+int plan_conv(int B, int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, Plan* p) {
+  FD_REQUIRE(B > 0 && T > 0 && pad >= 0, "ndac mfma conv: bad shape B %d T %d pad %d", B, T, pad);
   FD_REQUIRE(fd_ndac_mfma_supported(Ci, Co, K, stride, dil, transposed), "ndac mfma conv: unsupported shape Ci %d Co %d K %d stride %d dilation %d", Ci, Co, K,
              stride, dil);
-  FD_REQUIRE(x && wp && bias && (out || out_act) && (!out_act || alpha_out), "ndac mfma conv: null argument");
-  MArgs a{};
-  a.x = x; a.wp = static_cast<const uint4*>(wp); a.bias = bias; a.res = res; a.out = out; a.out_act = out_act; a.alpha_out = alpha_out;
+  MArgs& a = p->a;
+  a = MArgs{};
   a.Ci = Ci; a.T = T; a.Co = Co; a.pad = pad;
   a.nchunk = chunks_of(Ci, stride, transposed);
   long long To;
@@ -374,6 +380,7 @@ int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const f
   } else if (stride > 1) {
     S = stride;
     a.ntaps = K / stride; a.nphase = 1;
+    FD_REQUIRE((long long)T + 2 * pad >= K, "ndac mfma conv: empty output");   // (C division truncates: -1 / S + 1 would be 1)
     To = ((long long)T + 2 * pad - K) / stride + 1;
     a.N = (int)To;
     a.xlo = 0; a.rbase = 0; a.rstep = 1; span = a.ntaps - 1;
@@ -392,8 +399,47 @@ int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const f
   const long long wgs256 = (long long)fd_cdiv(a.N, TN) * (Co / (32 * mt)) * a.nphase * B;
   const int nt = wgs256 >= 512 ? 2 : 1, tn = 128 * nt;
   a.rows = tn + span;
-  const dim3 grid(fd_cdiv(a.N, tn), Co / (32 * mt) * a.nphase, B);
-  const size_t lds = (size_t)a.rows * ROWB * 2;
-  if (nt == 2) return mt == 3 ? launch<3, 2>(a, S, grid, lds, st) : launch<2, 2>(a, S, grid, lds, st);
-  return mt == 3 ? launch<3, 1>(a, S, grid, lds, st) : launch<2, 1>(a, S, grid, lds, st);
+  p->S = S; p->mt = mt; p->nt = nt;
+  p->grid = dim3(fd_cdiv(a.N, tn), Co / (32 * mt) * a.nphase, B);
+  p->lds = (size_t)a.rows * ROWB * 2;
+  return FD_OK;
+}
+
+}  // namespace
+
+int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
+                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st) {
+  Plan p;
+  FD_TRY(plan_conv(B, Ci, T, Co, K, stride, pad, dil, transposed, &p));
+  FD_REQUIRE(x && wp && bias && (out || out_act) && (!out_act || alpha_out), "ndac mfma conv: null argument");
+  // every epilogue with a residual also writes the activated output (epilogue_dispatch has no <RES, OUT, !ACT> instance)
+  FD_REQUIRE(!res || out_act, "ndac mfma conv: a residual needs the activated output out_act");
+  MArgs& a = p.a;
+  a.x = x; a.wp = static_cast<const uint4*>(wp); a.bias = bias; a.res = res; a.out = out; a.out_act = out_act; a.alpha_out = alpha_out;
+  if (p.nt == 2) return p.mt == 3 ? launch<3, 2>(a, p.S, p.grid, p.lds, st) : launch<2, 2>(a, p.S, p.grid, p.lds, st);
+  return p.mt == 3 ? launch<3, 1>(a, p.S, p.grid, p.lds, st) : launch<2, 1>(a, p.S, p.grid, p.lds, st);
+}
+
+// ---- test-level C ABI (include/flowdec_hip.h) -----------------------------------------------------------------------------------------
+extern "C" int fd_ndac_mfma_pack_weights(const float* w, int Ci, int Co, int K, int stride, int transposed, void* packed) {
+  FD_REQUIRE(w && packed, "fd_ndac_mfma_pack_weights: null pointer");
+  FD_REQUIRE(fd_ndac_mfma_supported(Ci, Co, K, stride, 1, transposed), "fd_ndac_mfma_pack_weights: unsupported shape Ci %d Co %d K %d stride %d transposed %d",
+             Ci, Co, K, stride, transposed);
+  std::vector<float> t((size_t)Ci * K * Co);
+  fd_ndac_weight_ci_k_co(w, Ci, Co, K, transposed, t.data());
+  fd_ndac_mfma_pack(t.data(), Ci, Co, K, stride, transposed, packed);
+  return FD_OK;
+}
+
+extern "C" int fd_ndac_mfma_variant(int B, int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, int* variant) {
+  FD_REQUIRE(variant, "fd_ndac_mfma_variant: null pointer");
+  Plan p;
+  FD_TRY(plan_conv(B, Ci, T, Co, K, stride, pad, dil, transposed, &p));
+  variant[0] = p.mt; variant[1] = p.S; variant[2] = p.nt; variant[3] = (int)p.grid.x; variant[4] = (int)p.grid.y;
+  return FD_OK;
+}
+
+extern "C" int fd_ndac_mfma_conv1d(const float* x, const void* packed, const float* bias, const float* residual, float* out, float* out_act,
+                                   const float* alpha_out, int B, int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, void* stream) {
+  return fd_ndac_mfma_conv(x, packed, bias, residual, out, out_act, alpha_out, B, Ci, T, Co, K, stride, pad, dil, transposed, fd_stream(stream));
 }

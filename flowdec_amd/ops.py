@@ -133,6 +133,36 @@ def conv_kernel_counts():
     return dict(zip(L.CONV_KERNELS, buf))
 
 
+def ndac_mfma_pack_weights(w, stride=1, transposed=False):
+    """PyTorch-layout conv weights (numpy float32 [Co][Ci][K], or [Ci][Co][K] if transposed) -> the packed A operand of
+    ndac_mfma.hip as a numpy uint16 array (fd_ndac_mfma_pack_weights, host only)."""
+    import numpy as np
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    Ci, Co = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+    K = w.shape[2]
+    nb = L.load().fd_ndac_mfma_packed_bytes(Ci, Co, K, stride, int(transposed))
+    out = np.zeros(max(nb, 2) // 2, np.uint16)
+    L.check(L.load().fd_ndac_mfma_pack_weights(w.ctypes.data, Ci, Co, K, stride, int(transposed), out.ctypes.data))
+    return out
+
+
+def ndac_mfma_variant(B, Ci, T, Co, K, stride=1, pad=0, dil=1, transposed=False):
+    """The launch fd_ndac_mfma_conv1d makes for this shape: dict(MT, S, NT, grid=(x, y)) (fd_ndac_mfma_variant, host only)."""
+    import ctypes as C
+    v = (C.c_int * 5)()
+    L.check(L.load().fd_ndac_mfma_variant(B, Ci, T, Co, K, stride, pad, dil, int(transposed), C.byref(v)))
+    return dict(MT=v[0], S=v[1], NT=v[2], grid=(v[3], v[4]))
+
+
+def ndac_mfma_conv1d(x, packed, bias, Co, K, stride=1, pad=0, dil=1, transposed=False, residual=None, out=None, out_act=None, alpha_out=None):
+    """fd_ndac_mfma_conv1d on x [B, Ci, T] float32 (GPU) with `packed` = ndac_mfma_pack_weights(...) on the GPU.  Writes into the
+    caller's `out` / `out_act` tensors [B, Co, To] (either may be None, not both)."""
+    L.require_cuda(x, packed, bias, residual, out, out_act, alpha_out)
+    B, Ci, T = x.shape
+    L.check(L.load().fd_ndac_mfma_conv1d(L.ptr(x), L.ptr(packed), L.ptr(bias), L.ptr(residual), L.ptr(out), L.ptr(out_act), L.ptr(alpha_out),
+                                         B, Ci, T, Co, K, stride, pad, dil, int(transposed), L.stream()))
+
+
 def time_embedding(t, gfp_w, w1, b1, w2, b2):
     nt, nf = t.numel(), gfp_w.numel()
     out = torch.empty(nt, 4 * nf, dtype=torch.float32, device=t.device)

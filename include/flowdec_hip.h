@@ -454,6 +454,21 @@ int fd_conv1d(const float* x, const float* w, const float* bias, const float* al
               int T, int Co, int K, int stride, int padding, int dilation, int tanh_out, void* stream);
 int fd_conv_transpose1d(const float* x, const float* w, const float* bias, const float* alpha_in, float* out, int B, int Ci, int T, int Co,
                         int K, int stride, int padding, void* stream);
+/* The matrix-core convolution of FD_NDAC_MFMA_DECODER / _ENCODER (split-bf16 operands, f32 accumulation) on its own, for tests.
+ * Shapes it supports: Co a multiple of 64 or 96; stride 1 (any dilation) or transposed (K % stride == 0, dilation 1) with Ci % 32 == 0;
+ * strided (stride 2 / 4 / 5 / 8 / 10, K % stride == 0, dilation 1) with any Ci; the staged tile (256 + span) x 160 B within 64 KiB.
+ *   fd_ndac_mfma_packed_bytes / _pack_weights (host memory): PyTorch weights w ([Co][Ci][K] conv, [Ci][Co][K] transposed) -> the
+ *     kernel's pre-split A-operand layout (hi and lo bf16 terms); bytes 0 / FD_EINVAL for an unsupported shape.
+ *   fd_ndac_mfma_variant (host only): the launch fd_ndac_mfma_conv1d would make, variant[5] = {MT (32-channel tiles per workgroup:
+ *     2 or 3), S (0: stride 1 or transposed; else the polyphase stride), NT (32-position tiles per wave: 1 or 2), grid.x, grid.y}.
+ *   fd_ndac_mfma_conv1d: device x [B][Ci][T] (already activated), packed weights, bias [Co]; outputs [B][Co][To]: out = conv + bias
+ *     (+ residual), out_act = Snake of it with alpha_out [Co] (hardware sine).  Any of out / out_act may be NULL but not both; a
+ *     residual needs out_act. */
+size_t fd_ndac_mfma_packed_bytes(int Ci, int Co, int K, int stride, int transposed);
+int fd_ndac_mfma_pack_weights(const float* w, int Ci, int Co, int K, int stride, int transposed, void* packed);
+int fd_ndac_mfma_variant(int B, int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, int* variant);
+int fd_ndac_mfma_conv1d(const float* x, const void* packed, const float* bias, const float* residual, float* out, float* out_act,
+                        const float* alpha_out, int B, int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, void* stream);
 
 typedef struct fd_ndac fd_ndac;
 typedef struct fd_ndac_config {   /* dac.DAC.__init__ keyword arguments (the `metadata["kwargs"]` of a weights.pth) */

@@ -29,6 +29,7 @@ CONV1D_CASES = [
     # name, B, Ci, T, Co, K, stride, pad, dil, alpha, residual, tanh
     ("first_conv", 2, 1, 300, 8, 7, 1, 3, 1, False, False, False),
     ("res7_dil1", 2, 16, 257, 16, 7, 1, 3, 1, True, False, False),
+    ("res7_dil3", 2, 16, 257, 16, 7, 1, 9, 3, True, False, False),
     ("res7_dil9", 1, 24, 200, 24, 7, 1, 27, 9, True, False, False),
     ("res1x1_residual", 2, 16, 130, 16, 1, 1, 0, 1, True, True, False),
     ("down_s2", 2, 8, 256, 16, 4, 2, 1, 1, True, False, False),
@@ -60,6 +61,34 @@ def test_conv1d(case):
     dx, dw, db, da, dr = dev(x), dev(w), dev(b), dev(alpha) if use_alpha else None, dev(res) if use_res else None   # (kept alive across the launch)
     lib_call("fd_conv1d", L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(da), L.ptr(dr), L.ptr(out), B, Ci, T, Co, K, s, p, d, int(use_tanh), L.stream())
     check(f"ndac_conv1d[{name}]", out.cpu().numpy(), ref, 1e-5)
+
+
+@pytest.mark.parametrize("K,d", [(7, 1), (7, 3), (7, 9), (1, 1), (3, 1)])
+def test_conv1d_s1_kernel_bits_equal_generic(K, d):
+    """ndac.hip: conv1d_s1_kernel<K, D> (Co >= 4) and the generic conv1d_kernel (Co = 2, 3) accumulate every output in the same fma
+    order, so the same weight rows give the same bits -- with the input Snake, a residual, a partial input-channel chunk and a ragged end."""
+    from flowdec_amd import _lib as L
+    rng = np.random.default_rng(100 * K + d)
+    B, Ci, T, Co = 2, 20, 301, 8
+    p = (K - 1) * d // 2
+    x = rng.standard_normal((B, Ci, T)).astype(np.float32)
+    w = (rng.standard_normal((Co, Ci, K)) / np.sqrt(Ci * K)).astype(np.float32)
+    b = rng.standard_normal(Co).astype(np.float32)
+    alpha = (1 + 0.3 * rng.standard_normal(Ci)).astype(np.float32)
+    res = rng.standard_normal((B, Co, T)).astype(np.float32)
+    dx, da = dev(x), dev(alpha)
+
+    def conv(rows):
+        n = len(rows)
+        out = torch.full((B, n, T), float("nan"), device="cuda")
+        dw, db, dr = dev(w[rows]), dev(b[rows]), dev(res[:, rows])
+        lib_call("fd_conv1d", L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(da), L.ptr(dr), L.ptr(out), B, Ci, T, n, K, 1, p, d, 0, L.stream())
+        return out.cpu().numpy()
+
+    full = conv(list(range(Co)))                                           # conv1d_s1_kernel<K, d>
+    check(f"ndac_conv1d_s1_k{K}_d{d}", full, N.conv1d(N.snake(x, alpha), w, b, padding=p, dilation=d) + res, 1e-5)
+    for rows in ([0, 1, 2], [3, 4, 5], [6, 7]):                            # conv1d_kernel (Co < 4)
+        assert np.array_equal(conv(rows), full[:, rows]), f"K {K} dilation {d}: rows {rows} differ between the two kernels"
 
 
 @pytest.mark.parametrize("s,Ci,Co,T", [(2, 16, 8, 100), (4, 24, 12, 77), (8, 48, 24, 40), (10, 20, 10, 33), (5, 9, 7, 50)])
