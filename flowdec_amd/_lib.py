@@ -102,6 +102,10 @@ SIGNATURES = {
     "fd_stft_compress_ragged": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, c_int, _P, _P, c_int, _P, c_size_t, _P]),
     "fd_decompress_istft_ragged": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, c_int, _P, c_size_t, _P]),
     "fd_compress_spec": (c_int, [_P, _P, c_ll, c_float, c_float, c_int, _P]),
+    "fd_stft_tables": (c_int, [c_int, c_int, _P, _P, _P]),
+    "fd_stft_gemm_variant": (c_int, [c_int] * 3),
+    "fd_stft_gemm_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "fd_istft_envelope_ok": (c_int, [c_int] * 4),
     "fd_num_frames": (c_int, [c_int, c_int]),
     "fd_padded_frames": (c_int, [c_int]),
     "fd_model_create": (c_int, [C.POINTER(FdModelConfig), C.POINTER(_P)]),

@@ -12,6 +12,7 @@
 //   spec'[B*T][1536]  x E[1536][1536]    ->  windowed time frames, then a gather overlap-add.
 #include <math.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -22,6 +23,7 @@ struct fd_stft_plan {
   float* Dt = nullptr;   // [kpad][kpad]   forward: rows = sample k (window folded), cols = 2f (re), 2f+1 (im)
   float* E = nullptr;    // [kpad][kpad]   inverse: rows = 2f / 2f+1, cols = sample n (window and 1/N folded)
   float* w2 = nullptr;   // [n_fft]        window^2 (overlap-add envelope)
+  std::vector<float> w2_host;   // the same on the host: the inverse checks the envelope before it launches
   // optional per-kernel timing (fd_stft_plan_profile): events 0..3 bracket {absmax + framing | DFT GEMM | compression} of the LAST
   // forward call, 4..7 {decompression | inverse DFT GEMM | overlap-add} of the last inverse call
   bool prof = false;
@@ -163,11 +165,20 @@ __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const float* __restrict
       }
 }
 
-// narrow tiles while the wide ones would leave compute units idle
-static void launch_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, hipStream_t st) {
-  const int rows = fd_cdiv(M, 128);
-  if ((long long)rows * (N / 128) >= 512) hipLaunchKernelGGL(sgemm_mfma_kernel<128>, dim3(N / 128, rows), dim3(256), 0, st, A, Bm, C, M, N, K);
-  else hipLaunchKernelGGL(sgemm_mfma_kernel<32>, dim3(N / 32, rows), dim3(256), 0, st, A, Bm, C, M, N, K);
+// The tile width BN of one GEMM (128 or 32; FD_EINVAL for a shape the kernel cannot take): narrow tiles while the wide ones would leave
+// compute units idle.  launch_sgemm launches what this returns and fd_stft_gemm_variant reports it, so the two cannot disagree.
+int sgemm_bn(int M, int N, int K) {
+  FD_REQUIRE(M >= 1 && N >= 128 && N % 128 == 0 && K >= 16 && K % 16 == 0, "stft gemm: unsupported shape M %d N %d K %d (M >= 1, N a multiple "
+             "of 128, K of 16)", M, N, K);
+  return (long long)fd_cdiv(M, 128) * (N / 128) >= 512 ? 128 : 32;
+}
+
+int launch_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, hipStream_t st) {
+  const int bn = sgemm_bn(M, N, K);
+  if (bn < 0) return bn;
+  if (bn == 128) hipLaunchKernelGGL(sgemm_mfma_kernel<128>, dim3(N / 128, fd_cdiv(M, 128)), dim3(256), 0, st, A, Bm, C, M, N, K);
+  else hipLaunchKernelGGL(sgemm_mfma_kernel<32>, dim3(N / 32, fd_cdiv(M, 128)), dim3(256), 0, st, A, Bm, C, M, N, K);
+  return FD_OK;
 }
 
 // spec[b*T+t][2f,2f+1] -> Y[b][f][t] = beta * |X|^alpha * exp(j angle X); frames t >= T are zero padding
@@ -251,25 +262,53 @@ __global__ void overlap_add_kernel(const float* __restrict__ FR, const int* __re
 
 inline int grid_cap(long long n) { long long g = (n + 255) / 256; return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g)); }
 
+// torch.signal.windows.hann(n_fft, sym=True) as the float32 tensor of the reference (feature_extractors.py:73-75); zero at both ends
+inline float hann_f32(int k, int n_fft) { return (float)(0.5 - 0.5 * cos(2.0 * M_PI * k / (n_fft - 1))); }
+
+// the GEMM width of one (n_fft): the 2 (n_fft/2 + 1) interleaved spectrum columns (>= n_fft samples) rounded up to a multiple of 128
+inline int stft_kpad(int n_fft) { return (n_fft + 2 + 127) / 128 * 128; }
+
+// torch.istft(center = True, length = L) raises where the overlap-add envelope env(p) = sum_t w^2[p - hop t] (frames t < T) is below
+// 1e-11 on a kept position p in [n_fft/2, min(n_fft/2 + L, n_fft + hop (T - 1))); there overlap_add_kernel would divide 0 by 0.  Away from
+// both ends every frame that can cover p is present, so env is periodic in p with period hop: the first and the last n_fft + hop kept
+// positions take every value it has.  Prefix sums of w^2 along each residue class mod hop give each env(p) in O(1): O(n_fft + hop) in all.
+bool envelope_ok(const float* w2, int n_fft, int hop, int T, int L) {
+  std::vector<double> S(n_fft);
+  for (int n = 0; n < n_fft; ++n) S[n] = (double)w2[n] + (n >= hop ? S[n - hop] : 0.0);
+  auto env = [&](long long p) {
+    const long long t_hi = std::min<long long>(p / hop, T - 1), t_lo = p >= n_fft ? (p - n_fft + hop) / hop : 0;
+    if (t_lo > t_hi) return 0.0;
+    const long long n_hi = p - hop * t_lo, n_lo = p - hop * t_hi;   // the terms n_lo, n_lo + hop, ..., n_hi
+    return S[n_hi] - (n_lo >= hop ? S[n_lo - hop] : 0.0);
+  };
+  const long long start = n_fft / 2, end = std::min<long long>(start + L, n_fft + (long long)hop * (T - 1)), span = (long long)n_fft + hop;
+  for (long long p = start; p < end && p < start + span; ++p)
+    if (!(env(p) >= 1e-11)) return false;
+  for (long long p = std::max(start + span, end - span); p < end; ++p)
+    if (!(env(p) >= 1e-11)) return false;
+  return true;
+}
+
 }  // namespace
 
-extern "C" int fd_stft_plan_create(int n_fft, int hop, fd_stft_plan** out) {
+// The plan's tables (host memory, zero beyond n_fft / the 2 (n_fft/2 + 1) spectrum columns): Dt / E [kpad][kpad], w2 [n_fft].
+extern "C" int fd_stft_tables(int n_fft, int hop, float* Dt_out, float* E_out, float* w2_out) {
   FD_REQUIRE(n_fft > 0 && n_fft % 2 == 0 && hop > 0, "stft plan: n_fft must be even and positive");
-  fd_stft_plan* p = new fd_stft_plan();
-  p->n_fft = n_fft; p->hop = hop; p->n_freq = n_fft / 2 + 1;
-  p->kpad = (2 * p->n_freq + 127) / 128 * 128;  // 1536 for n_fft 1534
-  if (p->kpad < n_fft) p->kpad = (n_fft + 127) / 128 * 128;
-  const int K = p->kpad;
-  std::vector<float> Dt((size_t)K * K, 0.f), E((size_t)K * K, 0.f), w2(n_fft);
+  const int K = stft_kpad(n_fft), n_freq = n_fft / 2 + 1;
+  if (!Dt_out && !E_out && !w2_out) return K;
+  FD_REQUIRE(Dt_out && E_out && w2_out, "fd_stft_tables: null pointer");
+  float* Dt = Dt_out;
+  float* E = E_out;
+  std::fill(Dt, Dt + (size_t)K * K, 0.f);
+  std::fill(E, E + (size_t)K * K, 0.f);
   std::vector<double> w(n_fft);
   for (int k = 0; k < n_fft; ++k) {
-    w[k] = 0.5 - 0.5 * cos(2.0 * M_PI * k / (n_fft - 1));  // torch.signal.windows.hann(sym=True), feature_extractors.py:73-75
-    const float wf = (float)w[k];                           // the reference window is a float32 tensor
+    const float wf = hann_f32(k, n_fft);
     w[k] = (double)wf;
-    w2[k] = wf * wf;
+    w2_out[k] = wf * wf;
   }
   for (int k = 0; k < n_fft; ++k)
-    for (int f = 0; f < p->n_freq; ++f) {
+    for (int f = 0; f < n_freq; ++f) {
       const long long ph = ((long long)k * f) % n_fft;  // exact phase reduction
       const double ang = 2.0 * M_PI * (double)ph / n_fft;
       Dt[(size_t)k * K + 2 * f] = (float)(w[k] * cos(ang));
@@ -278,12 +317,24 @@ extern "C" int fd_stft_plan_create(int n_fft, int hop, fd_stft_plan** out) {
       E[(size_t)(2 * f) * K + k] = (float)(w[k] * cf * cos(ang) / n_fft);
       E[(size_t)(2 * f + 1) * K + k] = (float)(-w[k] * cf * sin(ang) / n_fft);
     }
+  return K;
+}
+
+extern "C" int fd_stft_plan_create(int n_fft, int hop, fd_stft_plan** out) {
+  const int K = fd_stft_tables(n_fft, hop, nullptr, nullptr, nullptr);
+  if (K < 0) return K;
+  std::vector<float> Dt((size_t)K * K), E((size_t)K * K), w2(n_fft);
+  fd_stft_tables(n_fft, hop, Dt.data(), E.data(), w2.data());
+  fd_stft_plan* p = new fd_stft_plan();
+  p->n_fft = n_fft; p->hop = hop; p->n_freq = n_fft / 2 + 1;
+  p->kpad = K;  // 1536 for n_fft 1534
   FD_HIP(hipMalloc(&p->Dt, sizeof(float) * K * K));
   FD_HIP(hipMalloc(&p->E, sizeof(float) * K * K));
   FD_HIP(hipMalloc(&p->w2, sizeof(float) * n_fft));
   FD_HIP(hipMemcpy(p->Dt, Dt.data(), sizeof(float) * K * K, hipMemcpyHostToDevice));
   FD_HIP(hipMemcpy(p->E, E.data(), sizeof(float) * K * K, hipMemcpyHostToDevice));
   FD_HIP(hipMemcpy(p->w2, w2.data(), sizeof(float) * n_fft, hipMemcpyHostToDevice));
+  p->w2_host = std::move(w2);
   *out = p;
   return FD_OK;
 }
@@ -322,7 +373,7 @@ extern "C" int fd_stft_plan_profile_read(fd_stft_plan* p, double* ms6, int* call
 
 size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop) {
   const int T = 1 + L / hop;
-  const size_t kpad = ((size_t)(n_fft + 2) + 127) / 128 * 128;
+  const size_t kpad = stft_kpad(n_fft);
   return 2 * fd_align(sizeof(float) * (size_t)B * T * kpad) + 256;
 }
 
@@ -340,7 +391,7 @@ int fd_stft_forward(fd_stft_plan* p, const float* y, const int* lens, int B, int
   hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(1024), 0, st, y, lens, L, p->n_fft, normalize, normfac);
   hipLaunchKernelGGL(frame_kernel, dim3(grid_cap((long long)M * K)), dim3(256), 0, st, y, lens, normfac, frames, B, L, T, p->n_fft, p->hop, K);
   mark(1);
-  launch_sgemm(frames, p->Dt, spec, M, K, K, st);
+  FD_TRY(launch_sgemm(frames, p->Dt, spec, M, K, K, st));
   mark(2);
   hipLaunchKernelGGL(compress_kernel, dim3(grid_cap((long long)B * p->n_freq * T_pad)), dim3(256), 0, st, spec, lens, (float2*)Y, B, p->n_freq, T,
                      T_pad, K, L, p->n_fft, p->hop, alpha, beta);
@@ -354,6 +405,14 @@ int fd_stft_inverse(fd_stft_plan* p, const float* X, const int* lens, int B, int
                     int L, void* ws, size_t ws_bytes, hipStream_t st) {
   const int K = p->kpad;
   FD_REQUIRE(T >= 1 && T_pad >= T, "istft: bad frame counts");
+  // a ragged batch's clip lengths live on the device: refuse every geometry in which some clip length could meet a zero envelope (the
+  // symmetric Hann window is zero at both ends; with hop <= n_fft / 2 and T = 1 + length / hop no kept sample is covered by those alone)
+  if (lens)
+    FD_REQUIRE(2 * p->hop <= p->n_fft && p->n_fft >= 4, "istft (ragged): hop %d > n_fft / 2 = %d: some clip lengths would meet a zero window "
+               "envelope (torch.istft raises there); the ragged form needs hop <= n_fft / 2", p->hop, p->n_fft / 2);
+  else
+    FD_REQUIRE(envelope_ok(p->w2_host.data(), p->n_fft, p->hop, T, L), "istft: zero window envelope: %d frames of hop %d and n_fft %d do not "
+               "cover all %d samples with a window sum >= 1e-11 (torch.istft raises here)", T, p->hop, p->n_fft, L);
   const size_t need = 2 * fd_align(sizeof(float) * (size_t)B * T * K);
   if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "istft: workspace too small (%zu < %zu)", ws_bytes, need);
   float* Z = reinterpret_cast<float*>(ws);
@@ -364,7 +423,7 @@ int fd_stft_inverse(fd_stft_plan* p, const float* X, const int* lens, int B, int
   hipLaunchKernelGGL(decompress_kernel, dim3(grid_cap((long long)M * (K / 2))), dim3(256), 0, st, (const float2*)X, lens, Z, B, p->n_freq, T, T_pad, K,
                      L, p->n_fft, p->hop, alpha, beta);
   mark(5);
-  launch_sgemm(Z, p->E, FR, M, K, K, st);
+  FD_TRY(launch_sgemm(Z, p->E, FR, M, K, K, st));
   mark(6);
   hipLaunchKernelGGL(overlap_add_kernel, dim3(grid_cap((long long)B * L)), dim3(256), 0, st, FR, lens, p->w2, normfac, y, B, T, L, p->n_fft, p->hop, K);
   mark(7);
@@ -431,4 +490,25 @@ extern "C" int fd_decompress_istft_ragged(const fd_stft_plan* plan, const float*
   FD_REQUIRE(plan && X && lengths && y && ws && B > 0 && L > 0, "fd_decompress_istft_ragged: bad arguments");
   FD_REQUIRE(T == 1 + L / plan->hop, "fd_decompress_istft_ragged: T must be the frame count of the row length L (1 + L / hop = %d, got %d)", 1 + L / plan->hop, T);
   return fd_stft_inverse(const_cast<fd_stft_plan*>(plan), X, lengths, B, T, T_pad, alpha, beta, normfac, y, L, ws, ws_bytes, fd_stream(stream));
+}
+
+// ---- test-level C ABI (include/flowdec_hip.h) -----------------------------------------------------------------------------------------
+extern "C" int fd_stft_gemm_variant(int M, int N, int K) { return sgemm_bn(M, N, K); }
+
+extern "C" int fd_stft_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, void* stream) {
+  const int bn = sgemm_bn(M, N, K);
+  if (bn < 0) return bn;
+  FD_REQUIRE(A && B && C, "fd_stft_gemm_f32: null pointer");
+  FD_REQUIRE(((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) % 16 == 0, "fd_stft_gemm_f32: A, B and C must be 16-byte aligned");
+  FD_TRY(launch_sgemm(A, B, C, M, N, K, fd_stream(stream)));
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+extern "C" int fd_istft_envelope_ok(int n_fft, int hop, int T, int L) {
+  FD_REQUIRE(n_fft > 0 && n_fft % 2 == 0 && hop > 0 && T >= 1 && L > 0, "fd_istft_envelope_ok: bad arguments n_fft %d hop %d T %d L %d", n_fft, hop,
+             T, L);
+  std::vector<float> w2(n_fft);
+  for (int k = 0; k < n_fft; ++k) w2[k] = hann_f32(k, n_fft) * hann_f32(k, n_fft);
+  return envelope_ok(w2.data(), n_fft, hop, T, L) ? 1 : 0;
 }

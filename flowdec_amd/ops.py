@@ -267,6 +267,40 @@ def decompress_istft(X, T, length, normfac=None, n_fft=1534, hop=384, alpha=0.3,
     return y
 
 
+def stft_tables(n_fft, hop=384):
+    """The plan's tables for (n_fft, hop) as numpy float32 arrays (Dt [kpad][kpad], E [kpad][kpad], w2 [n_fft]) (fd_stft_tables, host only)."""
+    import numpy as np
+    lib = L.load()
+    K = lib.fd_stft_tables(n_fft, hop, None, None, None)
+    L.check(min(K, 0))
+    Dt, E, w2 = np.empty((K, K), np.float32), np.empty((K, K), np.float32), np.empty(n_fft, np.float32)
+    L.check(min(lib.fd_stft_tables(n_fft, hop, Dt.ctypes.data, E.ctypes.data, w2.ctypes.data), 0))
+    return Dt, E, w2
+
+
+def stft_gemm_variant(M, N, K):
+    """The tile width BN (128 or 32) of the DFT GEMM for this shape (fd_stft_gemm_variant, host only)."""
+    bn = L.load().fd_stft_gemm_variant(M, N, K)
+    L.check(min(bn, 0))
+    return bn
+
+
+def stft_gemm(A, B):
+    """fd_stft_gemm_f32: A [M, K] @ B [K, N], float32 GPU tensors -> C [M, N]."""
+    L.require_cuda(A, B)
+    A, B = A.contiguous(), B.contiguous()
+    C = torch.empty(A.shape[0], B.shape[1], dtype=torch.float32, device=A.device)
+    L.check(L.load().fd_stft_gemm_f32(L.ptr(A), L.ptr(B), L.ptr(C), A.shape[0], B.shape[1], A.shape[1], L.stream()))
+    return C
+
+
+def istft_envelope_ok(n_fft, hop, T, length):
+    """False where decompress_istft refuses (T frames leave a zero window envelope on a kept sample; torch.istft raises there)."""
+    r = L.load().fd_istft_envelope_ok(n_fft, hop, T, length)
+    L.check(min(r, 0))
+    return bool(r)
+
+
 def upfirdn2d_raw(x, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
     """x: [major, in_h, in_w, minor] (the reference binding's view, op/upfirdn2d.py:123)."""
     L.require_cuda(x, kernel)

@@ -282,6 +282,23 @@ int fd_decompress_istft_ragged(const fd_stft_plan* plan, const float* X, const i
 /* CompressAmplitudesAndScale.forward (inverse = 0: beta |x|^alpha e^{j angle x}) / .invert (inverse = 1) on n complex64
  * values (feature_extractors.py:118-139) as a stand-alone pass; X == Y allowed. */
 int fd_compress_spec(const float* X, float* Y, long long n, float alpha, float beta, int inverse, void* stream);
+/* The pieces of the transforms on their own, for tests.
+ *   fd_stft_tables (host memory): the plan's tables for (n_fft, hop), validated as fd_stft_plan_create does.  Returns kpad (the GEMM
+ *     width: 2 (n_fft/2 + 1) rounded up to a multiple of 128) or FD_EINVAL; with Dt, E and w2 all NULL it only returns kpad.
+ *     Dt [kpad][kpad]: row k, columns 2f / 2f+1 = w[k] cos / -w[k] sin (2 pi k f / n_fft); E [kpad][kpad]: rows 2f / 2f+1, column n =
+ *     c_f w[n] cos / -c_f w[n] sin (2 pi n f / n_fft) / n_fft, c_f = 1 at DC and Nyquist, else 2; zero beyond n_fft / the 2 (n_fft/2 + 1)
+ *     spectrum columns.  w2 [n_fft] = w^2, w the float32 symmetric Hann window.
+ *   fd_stft_gemm_variant (host only): the tile width BN (128 or 32) fd_stft_gemm_f32 would launch for M x N x K, FD_EINVAL if it refuses.
+ *   fd_stft_gemm_f32: the transforms' DFT GEMM, device C[M][N] = A[M][K] B[K][N] (row-major float32; M >= 1, N a multiple of 128, K of
+ *     16, A / B / C 16-byte aligned -- anything else is refused on the host).
+ *   fd_istft_envelope_ok (host only): 1 if fd_decompress_istft takes (n_fft, hop, T, L), 0 if it refuses because the overlap-add window
+ *     envelope falls below 1e-11 on a kept sample (exactly where torch.istft(center=True, length=L) raises); FD_EINVAL for bad
+ *     arguments.  Always 1 for FlowModel.enhance's own T = 1 + L / hop with hop <= n_fft / 2.  The ragged form cannot see its lengths
+ *     on the host and refuses hop > n_fft / 2 (and n_fft < 4) altogether. */
+int fd_stft_tables(int n_fft, int hop, float* Dt, float* E, float* w2);
+int fd_stft_gemm_variant(int M, int N, int K);
+int fd_stft_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, void* stream);
+int fd_istft_envelope_ok(int n_fft, int hop, int T, int L);
 int fd_num_frames(int L, int hop);     /* 1 + L / hop */
 /* One AttnBlockpp.forward with skip_rescale (layerspp.py:72-101; the bottleneck block of the SGMSE-style backbone):
  * out = (x + NIN_3(softmax(q k^T C^-0.5) v)) / sqrt(2), q | k | v = NIN_0..2(GroupNorm_0(x)), GroupNorm_0 = min(C/4, 32) groups,
