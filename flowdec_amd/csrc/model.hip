@@ -20,6 +20,14 @@ namespace {
 
 enum ModKind { M_GFP, M_LINEAR, M_CONV_IN, M_RB, M_COMBINE, M_GN, M_CONV_HEAD, M_ATTN };
 
+// How a model picks the kernel of each convolution (pick_conv): the algorithm flag of its act_dtype, resolved by fd_model_create.  The
+// operand modes (FD_BF16_OPERANDS / FD_BF16X3_OPERANDS) and fd_resblock are CS_DIRECT; CS_AUTO_F32 is pure FD_F32 | FD_WINOGRAD_AUTO.
+enum ConvSchedule { CS_DIRECT, CS_WINOGRAD, CS_WINOGRAD_LOWRES, CS_AUTO, CS_LATENCY, CS_AUTO_F32 };
+
+// Packed weights of one convolution, one per kernel it may run (null where the schedule or that kernel's shape rules leave it out):
+// direct (conv_mfma.hip), Winograd F(2,3) bf16 (conv_wino.hip), F(4,3) bf16 (conv_wino4.hip), 2-D F(4x4, 3x3) float32 (conv_wino44f.hip)
+struct ConvW { const void *direct = nullptr, *f23 = nullptr, *f43 = nullptr, *f44 = nullptr; };
+
 struct Mod {
   ModKind kind;
   int idx;              // index in all_modules
@@ -27,12 +35,8 @@ struct Mod {
   int c0 = 0, c1 = 0;   // virtual-concat split of cin (RB)
   bool up = false, down = false, has_c2 = false;
   int level = 0;                 // resolution level the block's convolutions run at (0 = full resolution)
-  bool wino0 = false, wino1 = false;   // Conv_0 / Conv_1 (+ folded Conv_2) packed for the Winograd kernel
-  void* w0w = nullptr; void* w1w = nullptr;   // FD_WINOGRAD_AUTO: second (Winograd) packing next to the direct one in w0 / w1
-  void* w0w4 = nullptr; void* w1w4 = nullptr; // FD_WINOGRAD_AUTO: third packing, for the F(4,3) kernel (conv_wino4.hip), where its shape rules allow
-  void* w0w44 = nullptr; void* w1w44 = nullptr; // FD_F32 | FD_WINOGRAD_AUTO: packing for the 2-D F(4x4, 3x3) float32 kernel (conv_wino44f.hip)
   // device pointers (filled by finalize)
-  void* w0 = nullptr; void* w1 = nullptr; void* w2 = nullptr;   // packed conv weights
+  ConvW conv0, conv1;   // RB: Conv_0 and Conv_1 (+ the folded 1x1 shortcut Conv_2); conv_in / pyramid head: conv0 (direct)
   float *gn0_g = nullptr, *gn0_b = nullptr, *gn1_g = nullptr, *gn1_b = nullptr;
   float* b1 = nullptr;                     // Conv_1 bias (+ Conv_2 bias when the shortcut conv is folded in)
   float* bias0_eff = nullptr;              // [nt][cout] Conv_0 bias + Dense_0(silu(temb)), model-owned scratch
@@ -112,6 +116,8 @@ struct fd_model {
   fd_model_config cfg;
   fd_model_arch arch{0, 1};
   int dt = FD_BF16;                 // storage type (cfg.act_dtype without the algorithm flags)
+  ConvSchedule sched = CS_DIRECT;   // kernel choice per convolution (cfg.act_dtype's algorithm flags)
+  int opflag = 0;                   // FD_BF16_OPERANDS / FD_BF16X3_OPERANDS of cfg.act_dtype: or'ed into every packing and launch
   int n_freq = 0, temb_dim = 0;
   std::vector<Mod> mods;
   std::vector<ParamInfo> params;
@@ -254,20 +260,36 @@ int upload_f32(fd_model* m, const std::string& name, float** out) {
   return FD_OK;
 }
 
-int pack_conv(fd_model* m, const std::string& name, int Cout, int C0, int C1, int ks, const std::string& sc_name, int S0, int S1,
-              void** out, hipStream_t st, int algo = 0) {
+// 3x3 convolution `name` (+ the 1x1 shortcut `sc_name` folded into its K loop, if named) packed for the kernel of `algo`
+int pack_conv(fd_model* m, const std::string& name, int Cout, int C0, int C1, const std::string& sc_name, int S0, int S1, int algo,
+              const void** out, hipStream_t st) {
   float *src = nullptr, *sc = nullptr;
   FD_TRY(upload_f32(m, name, &src));
   if (!sc_name.empty()) FD_TRY(upload_f32(m, sc_name, &sc));
   void* dst = nullptr;
-  algo |= m->cfg.act_dtype & (FD_BF16_OPERANDS | FD_BF16X3_OPERANDS);   // mixed / split modes: bf16 weights for f32 activations
-  const long long bytes = fd_conv_packed_bytes(Cout, C0, C1, ks, S0, S1, m->dt | algo);
+  const int wdtype = m->dt | algo | m->opflag;   // mixed / split modes: bf16 weights for f32 activations
+  const long long bytes = fd_conv_packed_bytes(Cout, C0, C1, 3, S0, S1, wdtype);
   FD_REQUIRE(bytes > 0, "internal: no packing for conv '%s'", name.c_str());
   FD_HIP(hipMalloc(&dst, (size_t)bytes));
   m->dev_allocs.push_back(dst);
-  FD_TRY(fd_conv_pack_weights(src, sc, dst, Cout, C0, C1, ks, S0, S1, m->dt | algo, st));
+  FD_TRY(fd_conv_pack_weights(src, sc, dst, Cout, C0, C1, 3, S0, S1, wdtype, st));
   *out = dst;
   return FD_OK;
+}
+
+// One ResBlock convolution packed for every kernel that the model's schedule may pick for it (pick_conv) and whose shape rules it
+// meets.  FD_WINOGRAD / FD_WINOGRAD_LOWRES keep one packing: F(2,3) where it applies, else direct.
+int pack_rb_conv(fd_model* m, int level, const std::string& name, int Cout, int C0, int C1, const std::string& sc_name, int S0, int S1,
+                 ConvW* w, hipStream_t st) {
+  auto fits = [&](int algo) { return fd_conv_packed_bytes(Cout, C0, C1, 3, S0, S1, m->dt | algo) > 0; };
+  auto pack = [&](int algo, const void** out) { return pack_conv(m, name, Cout, C0, C1, sc_name, S0, S1, algo, out, st); };
+  const bool f23_only = m->sched == CS_WINOGRAD || (m->sched == CS_WINOGRAD_LOWRES && level >= 2);
+  if (f23_only && fits(FD_WINOGRAD)) return pack(FD_WINOGRAD, &w->f23);
+  const bool by_size = m->sched == CS_AUTO || m->sched == CS_LATENCY;
+  if (by_size && fits(FD_WINOGRAD)) FD_TRY(pack(FD_WINOGRAD, &w->f23));
+  if (by_size && fits(FD_WINOGRAD4)) FD_TRY(pack(FD_WINOGRAD4, &w->f43));
+  if (m->sched == CS_AUTO_F32 && fits(FD_WINOGRAD44)) FD_TRY(pack(FD_WINOGRAD44, &w->f44));
+  return pack(0, &w->direct);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -285,6 +307,38 @@ struct OutSpec {           // what to do with v = NCSNpp(x, y, t):  dst = base +
   const float* z = nullptr;
   float cb = 1.f, cy = 0.f, cz = 0.f;
 };
+
+// The kernel one model convolution runs: packed weights and the fd_conv2d algorithm / workgroup flags.  First match wins.  Every rule
+// looks at the IMAGE (px_tiles: 16 x 16-pixel tiles of one output image), never at the batch: a clip must give the same bits alone, in
+// a batch, or in a shard of a batch (section 8(e)).
+struct ConvPick { const void* w; int flags; };
+ConvPick pick_conv(ConvSchedule s, const ConvW& w, int px_tiles, bool whole_tiles, int cin, int cout, bool shortcut) {
+  const bool autosel = s == CS_AUTO, latency = s == CS_LATENCY;
+  // fp32 `auto`: 2-D F(4x4, 3x3) in float32, a quarter of the direct kernel's MFMAs: 1.8-2.2 x the direct kernel per launch at 128 couts,
+  // and at 256 couts 1.1-1.4 x the F(4,3) float32 kernel (profiles/r06_wino44f.txt); the matrix pipe bounds the launch at any grid size
+  if (s == CS_AUTO_F32 && w.f44 && whole_tiles) return {w.f44, FD_WINOGRAD44};
+  // `latency` (one short clip on the whole chip; profiles/r02_latency_tiles.txt): images of at most 24 tiles run the direct kernel with
+  // 32-channel workgroups and chunk-resident weights (8 x the workgroups, one barrier per chunk)
+  if (latency && px_tiles <= 24 && cout >= 64) return {w.direct, FD_TILE_BN32_CHUNK};
+  // the 96 x 32 level: 18.5 us vs 22.6 (Winograd) at 8 clips, 17.1 vs 21.9 at one
+  if (autosel && px_tiles <= 16 && cout >= 64) return {w.direct, FD_TILE_BN64_CHUNK};
+  // F(2,3): its 128-cout workgroups are half the size of the direct kernel's, so a small grid fills the chip better with them (measured:
+  // 1.12-1.14x at 48 tiles per image x 8 clips, 0.93-0.97x at 192+ per image); `latency` takes it up to 128 tiles.  Never with a folded
+  // 1x1 shortcut: its input is the UN-NORMALISED residual stream, which the F(2,3) kernel would narrow to the fp16 range (GroupNorm+SiLU
+  // outputs and their FIR-resampled versions are bounded)
+  if ((autosel || latency) && w.f23 && !shortcut && px_tiles <= (latency ? 128 : 96)) return {w.f23, FD_WINOGRAD};
+  // F(4,3) with 256-cout workgroups: half the MFMAs of the direct kernel, 1.09-1.19x per launch on images of more than 96 tiles
+  // (profiles/r04_wino4_vs_direct.txt), 1.07x on the 64-channel input of the first block.  In `auto` it ALSO takes the folded-shortcut
+  // Conv_1 launches of images of 17..96 tiles: 1.17-1.20x over the direct kernel at 192 x 64 x 8 clips (MEASUREMENTS R4.2, "L2" row);
+  // the shortcut runs as a bf16 GEMM on the raw residual stream in its epilogue (no fp16 range issue).  `latency`, above 128 tiles: one
+  // 1 s clip 60.0 -> 63.4x, one 2 s clip 79 -> 88.8x real time
+  if ((autosel || (latency && px_tiles > 128)) && w.f43 && whole_tiles && cin >= 64) return {w.f43, FD_WINOGRAD4};
+  // `latency`, folded-shortcut convolutions of the 384 x 64 level (96 tiles): 96 workgroups of 256 channels leave 160 CUs idle; 128-channel
+  // workgroups are 1.28-1.39x per launch there (scripts/ab_conv_b1.py with AB_H=384 AB_W=64), same bits
+  if (latency && px_tiles <= 128 && cout >= 256 && cout % 128 == 0) return {w.direct, FD_TILE_BN128};
+  // `winograd` / `winograd_lowres` packed an F(2,3)-capable convolution for that kernel alone
+  return w.direct ? ConvPick{w.direct, 0} : ConvPick{w.f23, FD_WINOGRAD};
+}
 
 struct Fwd {
   fd_model* m;
@@ -346,56 +400,17 @@ struct Fwd {
     return fd_gn_finalize((const float*)ptr(a.sums), a.tiles, a.stride, a.C, b ? (const float*)ptr(b->sums) : nullptr, b ? b->tiles : 0,
                           b ? b->stride : 0, b ? b->C : 0, gamma, beta, (float*)ptr(*aff_off), B, gn_groups(C), (long long)a.H * a.W, 1e-6f, st);
   }
-  // out = scale * (conv_k(act([a|b])) + conv_1x1([s0|s1]) + bias + skip); optionally emits the GroupNorm partials of out
-  // FD_WINOGRAD_AUTO: the Winograd kernel's 128-cout workgroups are half the size of the direct kernel's, so a small grid fills the
-  // chip better with them (measured: 1.12-1.14x at 48 tiles per image x 8 clips, 0.93-0.97x at 192+ per image).  The choice looks at
-  // the IMAGE only, never at the batch: a clip must give the same bits alone, in a batch, or in a shard of a batch (section 8(e)).
-  bool auto_wino(const Tens& out) const { return fd_cdiv(out.H, 16) * fd_cdiv(out.W, 16) <= 96; }
-  // FD_LOW_LATENCY (one short clip on the whole chip; profiles/r02_latency_tiles.txt): images of at most 24 tiles run the direct
-  // kernel with 32-channel workgroups and chunk-resident weights (8 x the workgroups, one barrier per chunk); the F(2,3) kernel
-  // (128-channel workgroups) takes everything else up to 128 tiles unless a 1x1 shortcut is folded in; those run the direct kernel with
-  // 128-channel workgroups up to 128 tiles; above 128 tiles everything runs the F(4,3) kernel.  By image size only.
-  int conv(const Tens& a, const Tens* b, size_t aff, const Tens* s0, const Tens* s1, const void* w, const float* bias, int bias_rows,
-           const Tens* skip, float scale, Tens& out, int ks, bool want_stats, bool wino = false, const void* w_wino = nullptr,
-           const void* w_wino4 = nullptr, const void* w_wino44 = nullptr) {
-    int tile = 0;
-    bool wino4 = false, wino44 = false;
-    int order = 0;
-    const int opflag = m ? (m->cfg.act_dtype & (FD_BF16_OPERANDS | FD_BF16X3_OPERANDS)) : 0;
-    const int px_tiles = fd_cdiv(out.H, 16) * fd_cdiv(out.W, 16);
-    const bool latency = m && (m->cfg.act_dtype & FD_LOW_LATENCY) && dt == FD_BF16;
-    const bool autosel = m && (m->cfg.act_dtype & FD_WINOGRAD_AUTO) && dt == FD_BF16;
-    // fp32 mode (pure f32: storage, operands, exact f32 MFMA): F(4,3) in float32 (conv_wino4f.hip) wherever its shape rules hold (Cout = 256,
-    // whole 16 x 16 tiles, >= 64 input channels) -- the f32 matrix instruction is 16 x slower than the fp16 one, the launch is MFMA-bound at
-    // any grid size, and both kernels use one 256-cout workgroup per tile: halving the MFMAs is worth 1.6-1.9 x per launch.  By shape only.
-    const bool autosel_f32 = m && (m->cfg.act_dtype & FD_WINOGRAD_AUTO) && dt == FD_F32 && opflag == 0;
-    // fp32 mode: 2-D Winograd F(4x4, 3x3) in float32 (conv_wino44f.hip: a quarter of the direct kernel's MFMAs) wherever its shape rules hold
-    // (Cout % 128 == 0, whole 16 x 16 tiles, channel counts % 8 == 0): 1.1-1.4 x the F(4,3) float32 kernel per launch at 256 couts and
-    // 1.8-2.2 x the direct kernel at 128 (profiles/r06_wino44f.txt); the matrix pipe bounds the launch at any grid size.  By shape only.
-    if (m && (m->cfg.act_dtype & FD_WINOGRAD_AUTO) && dt == FD_F32 && opflag == 0 && w_wino44 && out.H % 16 == 0 && out.W % 16 == 0) { w = w_wino44; wino44 = true; }
-    else if (latency && px_tiles <= 24 && out.C >= 64) tile = FD_TILE_BN32_CHUNK;
-    else if (autosel && px_tiles <= 16 && out.C >= 64) tile = FD_TILE_BN64_CHUNK;   // the 96 x 32 level: 18.5 us vs 22.6 (Winograd) at 8 clips, 17.1 vs 21.9 at one
-    // (never with a folded 1x1 shortcut: its input is the UN-NORMALISED residual stream, which the Winograd kernel would narrow to
-    // the fp16 range; GroupNorm+SiLU outputs and their FIR-resampled versions are bounded)
-    else if (w_wino && !s0 && (auto_wino(out) || (latency && px_tiles <= 128))) { w = w_wino; wino = true; }
-    // images of more than 96 tiles (the two upper resolution levels of a 2 s clip): Winograd F(4,3) with 256-cout workgroups -- half the
-    // MFMAs of the direct kernel, 1.09-1.19x per launch (profiles/r04_wino4_vs_direct.txt); whole 16 x 16 tiles only.  In `auto` mode this
-    // branch ALSO takes the folded-shortcut Conv_1 launches of images of 17..96 tiles (the F(2,3) branch above excludes them): 1.17-1.20x
-    // over the direct kernel at 192 x 64 x 8 clips (MEASUREMENTS R4.2, "L2" row).  One clip alone gives those launches 96 workgroups of
-    // 512 threads on 256 CUs -- that case is what conv_algo = 'latency' (FD_TILE_BN128 below) is for; the choice must not look at B.
-    // (the 64-channel input of the first block included: 1.07x with the halo of a chunk pair per request)
-    // (a folded 1x1 shortcut runs as a bf16 GEMM on the raw residual stream in that kernel's epilogue: no fp16 range issue)
-    // (FD_LOW_LATENCY: everything above 128 tiles: one 1 s clip 60.0 -> 63.4x, one 2 s clip 79 -> 88.8x real time)
-    else if ((autosel || (latency && px_tiles > 128) || autosel_f32) && w_wino4 && !(s0 && skip) && out.H % 16 == 0 &&
-             out.W % 16 == 0 && a.C + (b ? b->C : 0) >= 64) {
-      w = w_wino4; wino4 = true;
-      // every other F(4,3) launch of a forward walks its tiles backwards: a consumer then starts on the lines its producer wrote last,
-      // which the memory-side cache still holds (the position in the launch sequence decides, so every forward has the same schedule)
-      if (!dry && (w4_launches++ & 1) != 0) order = FD_TILE_REVERSED;   // (counted in launching walks only: a planning walk cannot shift the schedule)
-    }
-    // one clip, folded-shortcut convolutions of the 384 x 64 level (96 tiles): 96 workgroups of 256 channels leave 160 CUs idle; 128-channel
-    // workgroups are 1.28-1.39x per launch there (scripts/ab_conv_b1.py with AB_H=384 AB_W=64), same bits
-    else if (latency && px_tiles <= 128 && out.C >= 256 && out.C % 128 == 0) tile = FD_TILE_BN128;
+  // out = scale * (conv_3x3(act([a|b])) + conv_1x1([s0|s1]) + bias + skip); optionally emits the GroupNorm partials of out
+  int conv(const Tens& a, const Tens* b, size_t aff, const Tens* s0, const Tens* s1, const ConvW& w, const float* bias, int bias_rows,
+           const Tens* skip, float scale, Tens& out, bool want_stats) {
+    constexpr int ks = 3;
+    const int cin = a.C + (b ? b->C : 0);
+    const ConvPick pick = pick_conv(m ? m->sched : CS_DIRECT, w, fd_cdiv(out.H, 16) * fd_cdiv(out.W, 16), out.H % 16 == 0 && out.W % 16 == 0,
+                                    cin, out.C, s0 != nullptr);
+    int flags = pick.flags;
+    // every other F(4,3) launch of a forward walks its tiles backwards: a consumer then starts on the lines its producer wrote last,
+    // which the memory-side cache still holds (the position in the launch sequence decides, so every forward has the same schedule)
+    if (flags == FD_WINOGRAD4 && !dry && (w4_launches++ & 1) != 0) flags |= FD_TILE_REVERSED;   // (counted in launching walks only: a planning walk cannot shift the schedule)
     if (want_stats) {
       out.tiles = fd_conv_stats_tiles(out.H, out.W);
       out.stride = fd_conv_cout_pad(out.C);
@@ -411,18 +426,18 @@ struct Fwd {
       FD_HIP(hipEventRecord(m->ev[m->ev_used].first, st));
     }
     const int rc = fd_conv2d(ptr(a.off), a.C, b ? ptr(b->off) : nullptr, b ? b->C : 0, aff == (size_t)-1 ? nullptr : (const float*)ptr(aff),
-                             s0 ? ptr(s0->off) : nullptr, s0 ? s0->C : 0, s1 ? ptr(s1->off) : nullptr, s1 ? s1->C : 0, w, bias, bias_rows,
+                             s0 ? ptr(s0->off) : nullptr, s0 ? s0->C : 0, s1 ? ptr(s1->off) : nullptr, s1 ? s1->C : 0, pick.w, bias, bias_rows,
                              skip ? ptr(skip->off) : nullptr, scale, ptr(out.off), out.C, want_stats ? (float*)ptr(out.sums) : nullptr, B,
-                             out.H, out.W, ks, dt | (wino ? FD_WINOGRAD : 0) | (wino4 ? FD_WINOGRAD4 : 0) | (wino44 ? FD_WINOGRAD44 : 0) | order | tile | opflag, st);
+                             out.H, out.W, ks, dt | flags | (m ? m->opflag : 0), st);
     if (m && m->profiling) {
       FD_HIP(hipEventRecord(m->ev[m->ev_used].second, st));
       ++m->ev_used;
-      m->prof_flops += 2.0 * B * out.H * out.W * (double)out.C *
-                       ((a.C + (b ? b->C : 0)) * ks * ks + (s0 ? s0->C : 0) + (s1 ? s1->C : 0));
-      const double cin = a.C + (b ? b->C : 0), csc = (s0 ? s0->C : 0) + (s1 ? s1->C : 0);
+      const double csc = (s0 ? s0->C : 0) + (s1 ? s1->C : 0);
+      m->prof_flops += 2.0 * B * out.H * out.W * (double)out.C * (cin * ks * ks + csc);
       // F(4,3): 6 products per 4 outputs and kernel row instead of 12 (the folded shortcut runs as a plain GEMM); F(2,3): 4 instead of 6
       // F(4x4, 3x3): 36 products per 16 outputs instead of 144
-      m->prof_flops_exec += 2.0 * B * out.H * out.W * (double)out.C * (cin * ks * ks * (wino44 ? 0.25 : wino4 ? 0.5 : wino ? 2.0 / 3.0 : 1.0) + csc);
+      const double exec = (flags & FD_WINOGRAD44) ? 0.25 : (flags & FD_WINOGRAD4) ? 0.5 : (flags & FD_WINOGRAD) ? 2.0 / 3.0 : 1.0;
+      m->prof_flops_exec += 2.0 * B * out.H * out.W * (double)out.C * (cin * ks * ks * exec + csc);
       m->prof_bytes += (double)B * out.H * out.W * esz * (cin + csc + (skip ? out.C : 0) + out.C) + (double)esz * out.C * (cin * ks * ks + csc);
     }
     return rc;
@@ -460,10 +475,10 @@ struct Fwd {
     if (md.up || md.down) {
       xr = talloc(md.cin, OH, OW); hr = talloc(md.cin, OH, OW);
       if (!dry) FD_TRY(fir(ptr(x0.off), (const float*)ptr(aff0), ptr(xr.off), ptr(hr.off), H, W, md.cin, md.up ? 1 : -1));
-      FD_TRY(conv(hr, nullptr, (size_t)-1, nullptr, nullptr, md.w0, md.bias0_eff, nt, nullptr, 1.f, h1, 3, true, md.wino0, md.w0w, md.w0w4, md.w0w44));
+      FD_TRY(conv(hr, nullptr, (size_t)-1, nullptr, nullptr, md.conv0, md.bias0_eff, nt, nullptr, 1.f, h1, true));
       tfree(hr);
     } else {
-      FD_TRY(conv(x0, x1, aff0, nullptr, nullptr, md.w0, md.bias0_eff, nt, nullptr, 1.f, h1, 3, true, md.wino0, md.w0w, md.w0w4, md.w0w44));
+      FD_TRY(conv(x0, x1, aff0, nullptr, nullptr, md.conv0, md.bias0_eff, nt, nullptr, 1.f, h1, true));
     }
     arena.release(aff0);
     size_t aff1;
@@ -471,10 +486,10 @@ struct Fwd {
     if (!out_given) out = talloc(md.cout, OH, OW);
     else { out.C = md.cout; out.H = OH; out.W = OW; out.sums = (size_t)-1; }   // fd_resblock: the caller's output tensor
     if (md.has_c2) {  // Conv_1(act(GN1(h))) + Conv_2(x) in one launch (shortcut conv folded in as extra K steps)
-      if (md.up || md.down) FD_TRY(conv(h1, nullptr, aff1, &xr, nullptr, md.w1, md.b1, 1, nullptr, rs2, out, 3, true, md.wino1, md.w1w, md.w1w4, md.w1w44));
-      else FD_TRY(conv(h1, nullptr, aff1, &x0, x1, md.w1, md.b1, 1, nullptr, rs2, out, 3, true, md.wino1, md.w1w, md.w1w4, md.w1w44));
+      if (md.up || md.down) FD_TRY(conv(h1, nullptr, aff1, &xr, nullptr, md.conv1, md.b1, 1, nullptr, rs2, out, true));
+      else FD_TRY(conv(h1, nullptr, aff1, &x0, x1, md.conv1, md.b1, 1, nullptr, rs2, out, true));
     } else {
-      FD_TRY(conv(h1, nullptr, aff1, nullptr, nullptr, md.w1, md.b1, 1, &x0, rs2, out, 3, true, md.wino1, md.w1w, md.w1w4, md.w1w44));
+      FD_TRY(conv(h1, nullptr, aff1, nullptr, nullptr, md.conv1, md.b1, 1, &x0, rs2, out, true));
     }
     if (md.up || md.down) tfree(xr);
     arena.release(aff1);
@@ -532,7 +547,7 @@ struct Fwd {
         if (!dry) { fd_edge_args a; a.x = ptr(in4.off); a.w = md.w_f32; a.bias = md.b_f32; a.out = ptr(h0.off); a.stats = (float*)ptr(h0.sums);
                     a.B = B; a.H = F; a.W = T; a.Cout = md.cout; FD_TRY(fd_edge_op(5, a, dt, st)); }
       } else {
-        FD_TRY(conv(in4, nullptr, (size_t)-1, nullptr, nullptr, md.w0, md.b_f32, 1, nullptr, 1.f, h0, 3, true));
+        FD_TRY(conv(in4, nullptr, (size_t)-1, nullptr, nullptr, md.conv0, md.b_f32, 1, nullptr, 1.f, h0, true));
         if (!dry && m->profiling) {   // the 4 padding channels are not algorithmic work
           m->prof_flops -= 2.0 * B * F * T * (double)md.cout * 4 * 9;
           m->prof_flops_exec -= 2.0 * B * F * T * (double)md.cout * 4 * 9;
@@ -599,11 +614,11 @@ struct Fwd {
       if (have_pyr) {
         Tens pu = talloc(4, h.H, h.W);
         if (!dry) FD_TRY(fir(ptr(pyramid.off), nullptr, ptr(pu.off), nullptr, pyramid.H, pyramid.W, 4, +1));
-        FD_TRY(conv(h, nullptr, aff, nullptr, nullptr, head.w0, head.b_f32, 1, &pu, 1.f, pnew, 3, false));
+        FD_TRY(conv(h, nullptr, aff, nullptr, nullptr, head.conv0, head.b_f32, 1, &pu, 1.f, pnew, false));
         release_later(pu.off, side); release_later(pyramid.off, side);
         pu.off = pyramid.off = (size_t)-1;
       } else {
-        FD_TRY(conv(h, nullptr, aff, nullptr, nullptr, head.w0, head.b_f32, 1, nullptr, 1.f, pnew, 3, false));
+        FD_TRY(conv(h, nullptr, aff, nullptr, nullptr, head.conv0, head.b_f32, 1, nullptr, 1.f, pnew, false));
       }
       release_later(aff, side);
       pyramid = pnew; have_pyr = true;
@@ -835,7 +850,7 @@ extern "C" int fd_model_create_ex(const fd_model_config* cfg, const fd_model_arc
     const int algo = cfg->act_dtype & (FD_WINOGRAD | FD_WINOGRAD_LOWRES | FD_WINOGRAD_AUTO | FD_LOW_LATENCY);
     FD_REQUIRE((algo & (algo - 1)) == 0, "fd_model_create: at most one of FD_WINOGRAD / FD_WINOGRAD_LOWRES / FD_WINOGRAD_AUTO / FD_LOW_LATENCY (got 0x%x)", algo);
     FD_REQUIRE(algo == 0 || (cfg->act_dtype & 0xff) == FD_BF16 || (algo == FD_WINOGRAD_AUTO && act_nos == (FD_F32 | FD_WINOGRAD_AUTO)),
-               "fd_model_create: the convolution-algorithm flags go with FD_BF16 storage (FD_WINOGRAD_AUTO also with pure FD_F32: F(4,3) in float32)");
+               "fd_model_create: the convolution-algorithm flags go with FD_BF16 storage (FD_WINOGRAD_AUTO also with pure FD_F32: 2-D F(4x4, 3x3) in float32)");
     FD_REQUIRE((cfg->act_dtype & FD_TILE_MASK) == 0, "fd_model_create: FD_TILE_* selects the workgroup width of ONE fd_conv2d launch, not of a model");
     FD_REQUIRE((cfg->act_dtype & ~(0xff | FD_WINOGRAD | FD_WINOGRAD_LOWRES | FD_WINOGRAD_AUTO | FD_LOW_LATENCY | FD_BF16_OPERANDS | FD_BF16X3_OPERANDS |
                                   FD_NO_SIDE_STREAM)) == 0, "fd_model_create: unknown bits in act_dtype (0x%x)", cfg->act_dtype);
@@ -853,6 +868,10 @@ extern "C" int fd_model_create_ex(const fd_model_config* cfg, const fd_model_arc
   m->cfg = *cfg;
   m->arch = *arch;
   m->dt = cfg->act_dtype & 0xff;
+  m->opflag = cfg->act_dtype & (FD_BF16_OPERANDS | FD_BF16X3_OPERANDS);
+  const int algo = cfg->act_dtype & (FD_WINOGRAD | FD_WINOGRAD_LOWRES | FD_WINOGRAD_AUTO | FD_LOW_LATENCY);   // (at most one, checked above)
+  m->sched = algo == FD_WINOGRAD ? CS_WINOGRAD : algo == FD_WINOGRAD_LOWRES ? CS_WINOGRAD_LOWRES : algo == FD_LOW_LATENCY ? CS_LATENCY :
+             algo != FD_WINOGRAD_AUTO ? CS_DIRECT : m->dt == FD_F32 ? CS_AUTO_F32 : CS_AUTO;
   m->n_freq = cfg->n_fft / 2 + 1;
   m->temb_dim = 4 * cfg->nf;
   build_structure(m);
@@ -953,7 +972,7 @@ extern "C" int fd_model_finalize(fd_model* m, void* stream) {
         for (int o = 0; o < md.cout; ++o)
           for (int c = 0; c < 4; ++c)
             for (int k = 0; k < 9; ++k) w8[((size_t)o * 8 + c) * 9 + k] = w4[((size_t)o * 4 + c) * 9 + k];
-        FD_TRY(pack_conv(m, p + "weight.pad8", md.cout, 8, 0, 3, "", 0, 0, &md.w0, st));
+        FD_TRY(pack_conv(m, p + "weight.pad8", md.cout, 8, 0, "", 0, 0, 0, &md.conv0.direct, st));
         FD_TRY(upload_f32(m, p + "bias", &md.b_f32));
         FD_TRY(upload_f32(m, p + "weight", &md.w_f32));   // [Cout][4][3][3] for the vector-FMA kernel of the bf16 mode
         break;
@@ -986,46 +1005,21 @@ extern "C" int fd_model_finalize(fd_model* m, void* stream) {
         FD_TRY(upload_f32(m, p + "bias", &md.gn0_b));
         break;
       case M_CONV_HEAD:
-        FD_TRY(pack_conv(m, p + "weight", md.cout, md.cin, 0, 3, "", 0, 0, &md.w0, st));
+        FD_TRY(pack_conv(m, p + "weight", md.cout, md.cin, 0, "", 0, 0, 0, &md.conv0.direct, st));
         FD_TRY(upload_f32(m, p + "bias", &md.b_f32));
         break;
       case M_RB: {
         FD_TRY(upload_f32(m, p + "GroupNorm_0.weight", &md.gn0_g)); FD_TRY(upload_f32(m, p + "GroupNorm_0.bias", &md.gn0_b));
         FD_TRY(upload_f32(m, p + "GroupNorm_1.weight", &md.gn1_g)); FD_TRY(upload_f32(m, p + "GroupNorm_1.bias", &md.gn1_b));
         // up/down blocks resample the (single) input first, so Conv_0 / Conv_2 see one tensor of cin channels
-        // algorithm per convolution: Winograd F(2,3) where the configuration asks for it and the shape is supported
-        const bool want_wino = (m->cfg.act_dtype & FD_WINOGRAD) || ((m->cfg.act_dtype & FD_WINOGRAD_LOWRES) && md.level >= 2);
-        md.wino0 = want_wino && fd_conv_packed_bytes(md.cout, md.c0, md.c1, 3, 0, 0, m->dt | FD_WINOGRAD) > 0;
-        md.wino1 = want_wino && fd_conv_packed_bytes(md.cout, md.cout, 0, 3, md.has_c2 ? md.c0 : 0, md.has_c2 ? md.c1 : 0, m->dt | FD_WINOGRAD) > 0;
-        const bool both = (m->cfg.act_dtype & (FD_WINOGRAD_AUTO | FD_LOW_LATENCY)) != 0;   // both packings; the kernel is chosen per launch by its grid
-        if (both && fd_conv_packed_bytes(md.cout, md.c0, md.c1, 3, 0, 0, m->dt | FD_WINOGRAD) > 0)
-          FD_TRY(pack_conv(m, p + "Conv_0.weight", md.cout, md.c0, md.c1, 3, "", 0, 0, &md.w0w, st, FD_WINOGRAD));
-        if (both && fd_conv_packed_bytes(md.cout, md.cout, 0, 3, md.has_c2 ? md.c0 : 0, md.has_c2 ? md.c1 : 0, m->dt | FD_WINOGRAD) > 0)
-          FD_TRY(pack_conv(m, p + "Conv_1.weight", md.cout, md.cout, 0, 3, md.has_c2 ? p + "Conv_2.weight" : std::string(), md.has_c2 ? md.c0 : 0,
-                           md.has_c2 ? md.c1 : 0, &md.w1w, st, FD_WINOGRAD));
-        const bool both4 = (m->cfg.act_dtype & (FD_WINOGRAD_AUTO | FD_LOW_LATENCY)) != 0;
-        // fp32 mode: the 2-D float32 kernel's packing wherever its shape rules hold; the F(4,3) float32 packing (whose rules are a subset:
-        // Cout = 256, channels % 16) only where they do not -- Fwd::conv prefers the 2-D kernel, a second copy would be dead memory
-        if (both4 && m->dt == FD_F32 && !(m->cfg.act_dtype & (FD_BF16_OPERANDS | FD_BF16X3_OPERANDS))) {
-          if (fd_conv_packed_bytes(md.cout, md.c0, md.c1, 3, 0, 0, FD_F32 | FD_WINOGRAD44) > 0)
-            FD_TRY(pack_conv(m, p + "Conv_0.weight", md.cout, md.c0, md.c1, 3, "", 0, 0, &md.w0w44, st, FD_WINOGRAD44));
-          if (fd_conv_packed_bytes(md.cout, md.cout, 0, 3, md.has_c2 ? md.c0 : 0, md.has_c2 ? md.c1 : 0, FD_F32 | FD_WINOGRAD44) > 0)
-            FD_TRY(pack_conv(m, p + "Conv_1.weight", md.cout, md.cout, 0, 3, md.has_c2 ? p + "Conv_2.weight" : std::string(), md.has_c2 ? md.c0 : 0,
-                             md.has_c2 ? md.c1 : 0, &md.w1w44, st, FD_WINOGRAD44));
-        }
-        if (both4 && !md.w0w44 && fd_conv_packed_bytes(md.cout, md.c0, md.c1, 3, 0, 0, m->dt | FD_WINOGRAD4) > 0)
-          FD_TRY(pack_conv(m, p + "Conv_0.weight", md.cout, md.c0, md.c1, 3, "", 0, 0, &md.w0w4, st, FD_WINOGRAD4));
-        if (both4 && !md.w1w44 && fd_conv_packed_bytes(md.cout, md.cout, 0, 3, md.has_c2 ? md.c0 : 0, md.has_c2 ? md.c1 : 0, m->dt | FD_WINOGRAD4) > 0)
-          FD_TRY(pack_conv(m, p + "Conv_1.weight", md.cout, md.cout, 0, 3, md.has_c2 ? p + "Conv_2.weight" : std::string(), md.has_c2 ? md.c0 : 0,
-                           md.has_c2 ? md.c1 : 0, &md.w1w4, st, FD_WINOGRAD4));
-        FD_TRY(pack_conv(m, p + "Conv_0.weight", md.cout, md.c0, md.c1, 3, "", 0, 0, &md.w0, st, md.wino0 ? FD_WINOGRAD : 0));
-        if (md.has_c2) {  // fold the 1x1 shortcut into Conv_1's K loop; biases add
-          FD_TRY(pack_conv(m, p + "Conv_1.weight", md.cout, md.cout, 0, 3, p + "Conv_2.weight", md.c0, md.c1, &md.w1, st, md.wino1 ? FD_WINOGRAD : 0));
+        FD_TRY(pack_rb_conv(m, md.level, p + "Conv_0.weight", md.cout, md.c0, md.c1, "", 0, 0, &md.conv0, st));
+        // Conv_1 with the 1x1 shortcut Conv_2 folded into its K loop; biases add
+        FD_TRY(pack_rb_conv(m, md.level, p + "Conv_1.weight", md.cout, md.cout, 0, md.has_c2 ? p + "Conv_2.weight" : std::string(),
+                            md.has_c2 ? md.c0 : 0, md.has_c2 ? md.c1 : 0, &md.conv1, st));
+        if (md.has_c2) {
           std::vector<float>& b1 = m->host[p + "Conv_1.bias"];
           const std::vector<float>& b2 = m->host[p + "Conv_2.bias"];
           for (size_t i = 0; i < b1.size(); ++i) b1[i] += b2[i];
-        } else {
-          FD_TRY(pack_conv(m, p + "Conv_1.weight", md.cout, md.cout, 0, 3, "", 0, 0, &md.w1, st, md.wino1 ? FD_WINOGRAD : 0));
         }
         FD_TRY(upload_f32(m, p + "Conv_1.bias", &md.b1));
         fd_temb_job j{};
@@ -1396,7 +1390,7 @@ int resblock_run(const fd_resblock_desc& d, const void* x0, const void* x1, void
                  hipStream_t st, size_t* peak) {
   Mod md; md.kind = M_RB; md.cin = d.cin0 + d.cin1; md.c0 = d.cin0; md.c1 = d.cin1; md.cout = d.cout;
   md.up = d.up != 0; md.down = d.down != 0; md.has_c2 = d.has_conv2 != 0;
-  md.w0 = const_cast<void*>(d.w0); md.w1 = const_cast<void*>(d.w1);
+  md.conv0 = ConvW{d.w0}; md.conv1 = ConvW{d.w1};
   md.gn0_g = const_cast<float*>(d.gn0_gamma); md.gn0_b = const_cast<float*>(d.gn0_beta);
   md.gn1_g = const_cast<float*>(d.gn1_gamma); md.gn1_b = const_cast<float*>(d.gn1_beta);
   md.bias0_eff = const_cast<float*>(d.bias0); md.b1 = const_cast<float*>(d.bias1);

@@ -332,7 +332,7 @@ typedef struct fd_model_config {
   int n_fft;             /* 1534 */
   int hop;               /* 384 */
   float alpha, beta;     /* 0.3, 0.33 */
-  int act_dtype;         /* FD_BF16 (bf16 storage + bf16 MFMA) [| FD_WINOGRAD | FD_WINOGRAD_LOWRES | FD_WINOGRAD_AUTO | FD_LOW_LATENCY], FD_F32 (f32 storage + exact f32 MFMA), FD_F32 | FD_BF16_OPERANDS or FD_F32 | FD_BF16X3_OPERANDS */
+  int act_dtype;         /* FD_BF16 (bf16 storage + bf16 MFMA) [| FD_WINOGRAD | FD_WINOGRAD_LOWRES | FD_WINOGRAD_AUTO | FD_LOW_LATENCY], FD_F32 (f32 storage + exact f32 MFMA) [| FD_WINOGRAD_AUTO], FD_F32 | FD_BF16_OPERANDS or FD_F32 | FD_BF16X3_OPERANDS */
 } fd_model_config;
 
 int fd_model_create(const fd_model_config* cfg, fd_model** out);

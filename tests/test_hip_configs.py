@@ -646,6 +646,49 @@ def test_fp32_auto_runs_winograd4_f32_and_matches_direct():
         flowdec_amd.from_preset("flowdec_75m", precision="fp32", conv_algo="winograd")
 
 
+# (precision, conv_algo) -> T_pad -> fd_conv2d dispatches per kernel family (ops.conv_kernel_counts, non-zero slots) of ONE forward of
+# flowdec_75m at B = 1 on a 768 x T_pad image.  The levels of T_pad = 128 and 256 span 6 .. 768 tiles of 16 x 16 pixels, which reaches
+# every rule of the model's convolution schedule (Fwd::conv).
+CONV_SCHEDULE = {('bf16', 'auto'): {128: {'DIRECT': 13, 'HEAD': 4, 'WINO': 12, 'WINO4': 15}, 256: {'DIRECT': 13, 'HEAD': 4, 'WINO': 6, 'WINO4': 21}},
+               ('bf16', 'direct'): {128: {'DIRECT': 40, 'HEAD': 4}, 256: {'DIRECT': 40, 'HEAD': 4}},
+               ('bf16', 'latency'): {128: {'DIRECT': 26, 'HEAD': 4, 'WINO': 6, 'WINO4': 8}, 256: {'DIRECT': 16, 'HEAD': 4, 'WINO': 6, 'WINO4': 18}},
+               ('bf16', 'winograd'): {128: {'HEAD': 4, 'WINO': 40}, 256: {'HEAD': 4, 'WINO': 40}},
+               ('bf16', 'winograd_lowres'): {128: {'DIRECT': 18, 'HEAD': 4, 'WINO': 22}, 256: {'DIRECT': 18, 'HEAD': 4, 'WINO': 22}},
+               ('bf16x3', 'auto'): {128: {'DIRECT_SPLIT': 45}, 256: {'DIRECT_SPLIT': 45}},
+               ('fp32', 'auto'): {128: {'DIRECT': 1, 'HEADF': 4, 'WINO44F': 40}, 256: {'DIRECT': 1, 'HEADF': 4, 'WINO44F': 40}},
+               ('fp32', 'direct'): {128: {'DIRECT': 41, 'HEADF': 4}, 256: {'DIRECT': 41, 'HEADF': 4}},
+               ('mixed', 'auto'): {128: {'DIRECT_MIXED': 45}, 256: {'DIRECT_MIXED': 45}}}
+
+
+def conv_schedule_counts():
+    import flowdec_amd
+    from flowdec_amd import ops
+    sd = {k: torch.from_numpy(v) for k, v in O.random_state_dict(seed=11, nf=64).items()}
+    rng = np.random.default_rng(11)
+    got = {}
+    for prec, algo in (("bf16", "direct"), ("bf16", "winograd"), ("bf16", "winograd_lowres"), ("bf16", "auto"), ("bf16", "latency"),
+                       ("fp32", "direct"), ("fp32", "auto"), ("mixed", "auto"), ("bf16x3", "auto")):
+        m = flowdec_amd.from_preset("flowdec_75m", precision=prec, conv_algo=algo)
+        m.load_state_dict(sd, strict=False)
+        m = m.cuda()
+        for T in (128, 256):
+            x, y = (cu((rng.standard_normal((1, 1, 768, T)) + 1j * rng.standard_normal((1, 1, 768, T))).astype(np.complex64)) for _ in range(2))
+            before = ops.conv_kernel_counts()
+            out = m(x, y, torch.tensor([0.5], device="cuda"))
+            after = ops.conv_kernel_counts()
+            assert torch.isfinite(torch.view_as_real(out)).all()
+            got.setdefault((prec, algo), {})[T] = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+        del m
+    return got
+
+
+def test_conv_schedule_is_pinned():
+    """Which kernel each convolution of a model forward runs, for all nine (precision, conv_algo) configurations.  The model tests
+    are tolerance-based and would pass with another kernel choice; this one fails on any change of the schedule."""
+    got = conv_schedule_counts()
+    assert got == CONV_SCHEDULE, got
+
+
 def test_conv2d_winograd4_rejects_unsupported():
     from flowdec_amd import ops
     bad = [(torch.randn(128, 32, 3, 3), torch.bfloat16),    # Cout != 256
