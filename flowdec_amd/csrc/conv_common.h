@@ -49,6 +49,15 @@ struct ConvArgs {
 };
 
 
+// Buffer resource over the `bytes` bytes at `base` (a halo band: a 32-bit range cannot hold a whole large image).  Every input is
+// read-first-laned, so the descriptor is provably wave-uniform and no buffer operation on it gets a waterfall loop.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t band_rsrc(const void* base, unsigned bytes) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
+                                           (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
 constexpr int AFF_BYTES = 512 * 8;  // per-(b,c) (a,d) pairs of up to 512 activated input channels, staged in LDS
 
 }  // namespace fdconv

@@ -72,7 +72,9 @@ __global__ __launch_bounds__(NTH, 2) void conv_head_kernel(ConvArgs p) {
   const int H = p.H, W = p.W;
   const int t = threadIdx.x, q = t & 3, prow = t >> 2;
 
-  // ---- halo loader (duplicate-slot trick: no divergent branch in the conversion) ------------------------------------------
+  // ---- halo loader (duplicate-slot trick: no divergent branch in the conversion).  Addressed from the tile's halo BAND (rows hb ..
+  // hb + band_rows - 1 of image b): the buffer resource covers the band, the per-lane 32-bit offsets count from its first pixel. ------
+  const int hb = h0 > 0 ? h0 - 1 : 0, band_rows = (h0 + TH + 1 < H ? h0 + TH + 1 : H) - hb;
   int pixl[HITER], hlds[HITER];
   unsigned pvalid = 0;
 #pragma unroll
@@ -82,11 +84,11 @@ __global__ __launch_bounds__(NTH, 2) void conv_head_kernel(ConvArgs p) {
     const int hr = hp / HW, hc = hp - hr * HW;
     const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
     const bool ok = gh >= 0 && gh < H && gw >= 0 && gw < W;
-    pixl[i] = ok ? gh * W + gw : 0;
+    pixl[i] = ok ? (gh - hb) * W + gw : 0;   // (outside the image: pixel 0 of the band, masked by the conversion)
     hlds[i] = (hr * PITCH + hc) * ROWB + q * 16;
     if (ok) pvalid |= 1u << i;
   }
-  const size_t img_elems = (size_t)H * W;
+  const size_t img_elems = (size_t)H * W, band_pix = (size_t)b * img_elems + (size_t)hb * W;
   int nchunks = 0;
   for (int s = 0; s < p.nseg; ++s) nchunks += (p.seg[s].C + CK - 1) / CK;
   const int nsteps = nchunks * 9;
@@ -101,8 +103,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_head_kernel(ConvArgs p) {
       if (cs >= p.nseg) { cur_end = true; cs = p.nseg - 1; }
     }
     const Seg sg = p.seg[cs];
-    const bf16* src = reinterpret_cast<const bf16*>(sg.src) + (size_t)b * img_elems * sg.C;
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(src), 0, (int)(img_elems * sg.C * sizeof(bf16)), 0x00020000);
+    const bf16* src = reinterpret_cast<const bf16*>(sg.src) + band_pix * sg.C;
+    const __amdgpu_buffer_rsrc_t srd = band_rsrc(src, (unsigned)band_rows * W * sg.C * (unsigned)sizeof(bf16));
     const int c = cch * CK + q * EPS;
     const bool ok = c < sg.C && !cur_end;
     const int nc = ok ? c : 0;

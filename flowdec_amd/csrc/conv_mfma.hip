@@ -261,11 +261,18 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_kernel(ConvArgs p) 
 
   // ---- loader bookkeeping.  Loads are unconditional (clamped addresses); validity is applied when the
   // registers are written to LDS. ----------------------------------------------------------------------------
-  int pixl[G::HITER];   // clamped pixel index inside the loader's image
+  // The loader addresses its tile's halo BAND (rows lhb .. lhb + band rows - 1 of image lb): a 64-bit wave-uniform base, a buffer
+  // resource over the band, per-lane 32-bit offsets from the band's first pixel -- bounded by the band, not by the image.
+  int pixl[G::HITER];   // clamped pixel index inside the loader's band (0 outside the image: the band's first pixel, masked on conversion)
   int hlds[G::HITER];   // LDS byte offset of the slot
   unsigned pvalid = 0, hexist = 0;
   int lb = b, lth = th_i, ltw = tw_i;   // tile the LOADER works on (RE: one chunk ahead of the MFMAs, i.e. possibly already the next tile)
+  size_t lband = 0;                     // first pixel of the loader's band (image-major pixel index)
+  unsigned lband_pix = 0;               // pixels in the band
   auto set_loader_tile = [&](int lh0, int lw0, int H, int W) {
+    const int lhb = lh0 > 0 ? lh0 - 1 : 0;
+    lband = (size_t)lb * ((size_t)H * W) + (size_t)lhb * W;
+    lband_pix = (unsigned)(((lh0 + G::TH + 1 < H ? lh0 + G::TH + 1 : H) - lhb) * W);
     pvalid = 0; hexist = 0;
 #pragma unroll
     for (int i = 0; i < G::HITER; ++i) {
@@ -274,14 +281,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_kernel(ConvArgs p) 
       const int hr = hpc / G::HW, hc = hpc - hr * G::HW;
       const int gh = lh0 - 1 + hr, gw = lw0 - 1 + hc;
       const bool ok = gh >= 0 && gh < H && gw >= 0 && gw < W;
-      pixl[i] = ok ? gh * W + gw : 0;
+      pixl[i] = ok ? (gh - lhb) * W + gw : 0;
       hlds[i] = (hr * PITCH + hc) * ROWB + q * 16;
       if (hp < G::HH * G::HW) { hexist |= 1u << i; if (ok) pvalid |= 1u << i; }
     }
   };
   set_loader_tile(h0, w0, H, W);
   const __amdgpu_buffer_rsrc_t wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, (int)p.w_bytes, 0x00020000);
-  const size_t img_elems = (size_t)H * W;
 
   u32x4 hreg[G::HITER];
   u32x4 hreg_hi[MIXED ? G::HITER : 1];   // MIXED: channels 4..7 of the slot (f32 in memory)
@@ -292,17 +298,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_kernel(ConvArgs p) 
   bool nchan_ok = false;
   auto next_chunk = [&](int s, int ch) {
     const Seg sg = p.seg[s];
-    const TS* src = reinterpret_cast<const TS*>(sg.src) + (size_t)lb * img_elems * sg.C;
-    nsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<TS*>(src), 0, (int)(unsigned)(img_elems * sg.C * sizeof(TS)), 0x00020000);   // num_records: unsigned 32 bits
+    nsrd = band_rsrc(reinterpret_cast<const TS*>(sg.src) + lband * sg.C, lband_pix * (unsigned)sg.C * (unsigned)sizeof(TS));   // (fd_conv2d: < 2^31 bytes)
     nC = sg.C;
     const int c = SPLIT ? ch * CK + (q & 1) * 8 : ch * CK + q * EPS;   // SPLIT: slots 0,1 = hi, 2,3 = lo of the same 16 channels
     nchan_ok = c < sg.C;
     nc = nchan_ok ? c : 0;
     naff = sg.aff_off >= 0 ? (sg.aff_off + nc) * 8 + (RE ? (lb & 1) * AFF_BYTES : 0) : -1;  // byte offset of this slot's (a,d) pairs in the LDS table (RE: one table per image parity)
   };
-  int npix_on = 1;   // 0: the prefetch target is unused (last chunk of the K loop) -> every lane re-reads pixel 0 (one cache line, no HBM traffic)
+  int npix_on = 1;   // 0: the prefetch target is unused (last chunk of the K loop) -> every lane re-reads band pixel 0 (one cache line, no HBM traffic)
   auto load_halo_slot = [&](int i) {
-    // byte offset inside ONE image, unsigned 32 bits: an f32 image of a 30 s clip is 2.97 GB (the buffer resource's range is 4 GiB)
+    // byte offset inside the loader's band: unsigned 32 bits
     const unsigned off = ((unsigned)(pixl[i] * npix_on) * (unsigned)nC + (unsigned)nc) * (unsigned)sizeof(TS);
     hreg[i] = __builtin_amdgcn_raw_buffer_load_b128(nsrd, (int)off, 0, 0);
     if constexpr (MIXED) hreg_hi[i] = __builtin_amdgcn_raw_buffer_load_b128(nsrd, (int)(off + 16u), 0, 0);
@@ -1360,10 +1365,12 @@ extern "C" int fd_conv2d(const void* in0, int C0, const void* in1, int C1, const
   FD_REQUIRE(B > 0 && H > 0 && W > 0, "fd_conv2d: bad shape");
   FD_REQUIRE(bias == nullptr || bias_rows == 1 || bias_rows == B, "fd_conv2d: bias_rows must be 1 or B");
   int cm = C0; if (C1 > cm) cm = C1; if (S0 > cm) cm = S0; if (S1 > cm) cm = S1; if (Cout > cm) cm = Cout;
-  // 32-bit byte offsets inside one image: unsigned in the direct kernel (4 GiB: ~43 s of audio with f32 storage), the bf16-only kernels
-  // (Winograd, heads) keep the signed range (2 GiB: ~43 s in bf16 as well)
-  FD_REQUIRE((long long)H * W * cm * (dtype == FD_BF16 ? 2 : 4) < (dtype == FD_BF16 ? (1ll << 31) : (1ll << 32)),
-             "fd_conv2d: one image of %d x %d x %d elements exceeds %d GiB (32-bit buffer offsets; ~43 s of audio)", H, W, cm, dtype == FD_BF16 ? 2 : 4);
+  // The kernels address a workgroup's input from a 64-bit base at the first row of its halo band (at most 18 rows: 16-row tiles + halo)
+  // and its output from the tile's first row, with 32-bit per-lane offsets: what has to fit 31 bits is a band, not an image.
+  FD_REQUIRE((long long)H * W < (1ll << 31), "fd_conv2d: an image of %d x %d pixels exceeds 2^31 pixels (32-bit pixel indices)", H, W);
+  FD_REQUIRE(18ll * W * cm * (dtype == FD_BF16 ? 2 : 4) < (1ll << 31),
+             "fd_conv2d: a halo band of 18 rows x %d pixels x %d channels exceeds 2 GiB (32-bit per-lane byte offsets)", W, cm);
+  FD_REQUIRE(W < (1 << 19), "fd_conv2d: W = %d exceeds 2^19 pixels (per-tile pixel index of the folded-shortcut loader)", W);
   FD_TRY(fd_conv_init_attributes());
   const int taps = ksize * ksize;
   ConvArgs a{};

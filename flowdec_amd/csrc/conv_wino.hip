@@ -184,7 +184,10 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino_kernel(ConvArgs p) {
 
   // ---- halo loader.  Loads are unconditional (clamped addresses); validity is applied when the converted registers are
   // written to LDS.  Threads whose third slot lies past the 18 x 18 halo redo their second one (same load, same value, same
-  // LDS address) so that the conversion code has no divergent branch and can be interleaved with the MFMAs. -----------------
+  // LDS address) so that the conversion code has no divergent branch and can be interleaved with the MFMAs.  Addressed from the
+  // tile's halo BAND (rows hb .. hb + band_rows - 1 of image b): the buffer resource covers the band, the per-lane 32-bit offsets
+  // count from its first pixel (outside the image: that pixel, masked by the conversion). -----------------------------------------
+  const int hb = h0 > 0 ? h0 - 1 : 0, band_rows = (h0 + TH + 1 < H ? h0 + TH + 1 : H) - hb;
   int pixl[HITER], hlds[HITER];
   unsigned pvalid = 0;
 #pragma unroll
@@ -194,11 +197,11 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino_kernel(ConvArgs p) {
     const int hr = hp / HW, hc = hp - hr * HW;
     const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
     const bool ok = gh >= 0 && gh < H && gw >= 0 && gw < W;
-    pixl[i] = ok ? gh * W + gw : 0;
+    pixl[i] = ok ? (gh - hb) * W + gw : 0;
     hlds[i] = (hr * WP + hc) * ROWB + q * 16;
     if (ok) pvalid |= 1u << i;
   }
-  const size_t img_elems = (size_t)H * W;
+  const size_t band_pix = (size_t)b * ((size_t)H * W) + (size_t)hb * W;
   u32x4 hreg[HITER];
   __amdgpu_buffer_rsrc_t nsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, 16, 0x00020000);
   int nC = 0, nc = 0, naff = 0;
@@ -214,8 +217,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino_kernel(ConvArgs p) {
     }
     if (cur_end) return;
     const Seg sg = p.seg[cs];
-    const bf16* src = reinterpret_cast<const bf16*>(sg.src) + (size_t)b * img_elems * sg.C;
-    nsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(src), 0, (int)(img_elems * sg.C * sizeof(bf16)), 0x00020000);
+    nsrd = band_rsrc(reinterpret_cast<const bf16*>(sg.src) + band_pix * sg.C, (unsigned)band_rows * W * sg.C * (unsigned)sizeof(bf16));
     nC = sg.C;
     const int c = cch * CK + q * EPS;
     const bool nchan_ok = c < sg.C;
@@ -224,7 +226,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino_kernel(ConvArgs p) {
 #pragma unroll
     for (int i = 0; i < HITER; ++i) vmask[i] = (nchan_ok && ((pvalid >> i) & 1u)) ? 0xffffffffu : 0u;
   };
-  // past the end of the K loop every lane re-reads element 0 of the last tensor (one cache line; the data is never used)
+  // past the end of the K loop every lane re-reads element 0 of the last tensor's band (one cache line; the data is never used)
   auto load_halo = [&]() {
     const int on = cur_end ? 0 : 1;
 #pragma unroll

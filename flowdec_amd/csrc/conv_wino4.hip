@@ -147,10 +147,14 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   // per wave (SQ counters, profiles/r04_wino4_*): everything a lane needs per chunk is computed ONCE here and kept in registers. -----
   auto opaque = [&](int v) { asm volatile("" : "+v"(v)); return v; };
   const size_t img_elems = (size_t)H * W;
+  // The halo is addressed from its BAND: the first halo row of this tile (row hb of image b, a 64-bit wave-uniform base), so the
+  // per-lane 32-bit byte offsets stay below (TH + 2) x W x C x 2 bytes whatever the image size (fd_conv2d checks the band bytes).
+  const int hb = h0 > 0 ? h0 - 1 : 0;
+  const size_t band_pix = (size_t)b * img_elems + (size_t)hb * W;
   // the (at most two) concat segments in scalar registers: no kernel-argument loads inside the K loop
-  const bf16* const sb0 = reinterpret_cast<const bf16*>(p.seg[0].src) + (size_t)b * img_elems * p.seg[0].C;
+  const bf16* const sb0 = reinterpret_cast<const bf16*>(p.seg[0].src) + band_pix * p.seg[0].C;
   const bool two3 = p.nseg > 1 && p.seg[1].taps == 9;   // (segments with taps == 1 are the folded shortcut: epilogue phase E2)
-  const bf16* const sb1 = two3 ? reinterpret_cast<const bf16*>(p.seg[1].src) + (size_t)b * img_elems * p.seg[1].C : sb0;
+  const bf16* const sb1 = two3 ? reinterpret_cast<const bf16*>(p.seg[1].src) + band_pix * p.seg[1].C : sb0;
   const int sC0 = p.seg[0].C, sC1 = two3 ? p.seg[1].C : 0;
   const int nch0 = sC0 / CK, n3 = nch0 + sC1 / CK;
   const int hq = wave & 1;
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   // per-lane halo constants.  Ordering between the request side (lane t, piece t + 512 i) and the conversion side (piece (hp * 4 + 2 e +
   // hq), written by another lane): "request after the barrier of step 3 of an even chunk (every conversion of the previous pair is done),
   // landed before the barrier of step 8 (every wave waits for its own requests first), converted after it".  Pixels outside the image:
-  // the request reads pixel 0 (harmless), the conversion masks the value.  Lanes without a pixel in pass 1 redo pass 0.
+  // the request reads pixel 0 of the band (inside the image; harmless), the conversion masks the value.  Lanes without a pixel in pass 1 redo pass 0.
   int hpix[RAW_PASSES], zadr[2];
   unsigned hvalid = 0;
 #pragma unroll
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
     const int hp = sl < NPIECE ? sl >> 2 : 0;
     const int hr = hp / HW, hc = hp - hr * HW;
     const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
-    hpix[i] = (gh >= 0 && gh < H && gw >= 0 && gw < W) ? gh * W + gw : 0;
+    hpix[i] = (gh >= 0 && gh < H && gw >= 0 && gw < W) ? (gh - hb) * W + gw : 0;
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {            // conversion side
@@ -418,8 +422,10 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   //       W[cout][k] x[k][pixel], v_mfma_f32_32x32x16_bf16 on the RAW residual stream (no fp16 conversion: the direct kernel's numerics).
   //   E3  per (ct, nt): stage the round's 128 pixels x 128 couts as [pixel plane j][tile][cout] f32, sweep with 8 couts (16 B of bf16)
   //       per lane: bias / residual / scale / statistics / store.
-  bf16* const out = reinterpret_cast<bf16*>(p.out) + (size_t)b * img_elems * p.Cout;
-  const bf16* const skip = SKIP ? reinterpret_cast<const bf16*>(p.skip) + (size_t)b * img_elems * p.Cout : nullptr;
+  // output and residual from the tile's first row (row h0 of image b): the per-lane offsets of out_off stay 32-bit
+  const size_t row0_pix = (size_t)b * img_elems + (size_t)h0 * W;
+  bf16* const out = reinterpret_cast<bf16*>(p.out) + row0_pix * p.Cout;
+  const bf16* const skip = SKIP ? reinterpret_cast<const bf16*>(p.skip) + row0_pix * p.Cout : nullptr;
   float* const biast = reinterpret_cast<float*>(smem + BIAS_OFF);      // [256] f32 (zeros without a bias)
   float* const statt = reinterpret_cast<float*>(smem + STAT_OFF);      // [ct][wave][oct 16][16] f32 partial sums
   float* const isct = reinterpret_cast<float*>(smem + ISC_OFF);        // [256] f32: 1 / (the cout's weight scale)
@@ -435,8 +441,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   // element offset of pass ps of round (ct, nt) for this thread: staged pixel pp + 32 ps = plane ps of tile pp, cout octet oct
   auto out_off = [&](int tt, int ct, int nt, int ps) {
     const int oct = tt & 15, pp = tt >> 4;
-    const int gh = h0 + nt * 8 + (pp >> 2), gw = w0 + 4 * (pp & 3) + ps;
-    return (gh * W + gw) * p.Cout + ct * 128 + oct * 8;
+    const int rh = nt * 8 + (pp >> 2), gw = w0 + 4 * (pp & 3) + ps;   // (row relative to h0)
+    return (rh * W + gw) * p.Cout + ct * 128 + oct * 8;
   };
   // residual of round r -> SK[r & 1] by DMA: thread t requests exactly the 16 bytes it adds in the sweep (pass ps at (ps * 512 + t) * 16),
   // so the only synchronisation is this wave's own counted vmcnt
@@ -618,21 +624,21 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
       const Seg q0 = p.seg[p.nseg - nsc], q1 = p.seg[p.nseg - 1];
       const int S0 = q0.C, Stot = S0 + (nsc > 1 ? q1.C : 0);
       const int nstage = Stot / (16 * SCK);
-      const bf16* const xb0 = reinterpret_cast<const bf16*>(q0.src) + (size_t)b * img_elems * q0.C;
-      const bf16* const xb1 = reinterpret_cast<const bf16*>(q1.src) + (size_t)b * img_elems * q1.C;
+      const bf16* const xb0 = reinterpret_cast<const bf16*>(q0.src) + row0_pix * q0.C;   // (from the tile's first row, as the output)
+      const bf16* const xb1 = reinterpret_cast<const bf16*>(q1.src) + row0_pix * q1.C;
       const char* const wsc = reinterpret_cast<const char*>(p.w) + (size_t)(n3 + 1) * 18 * SLAB + cq * 2048;
       // per-lane source of the stage DMA.  A stage row is one pixel's 64 bytes (SCK = 2 K steps x 2 channel halves): FOUR adjacent
       // lanes fetch one pixel's contiguous 64 B (one memory request), lane l of DMA instruction i of wave w fills the 16 bytes at
       // ((i * 8 + w) * 64 + l) * 16: row r = that >> 2, 16-byte position q = l & 3, which holds piece (kk * 2 + half) = q ^ ((r >> 2) & 3)
       // (the XOR keeps the 64-byte-stride fragment reads free of bank conflicts)
       static_assert(SCK == 2, "a stage row = 2 K steps x 2 halves x 16 B; K step kk of the weights is loaded by wave group xt = kk");
-      int xsrc[2];   // per DMA instruction: (pixel index) << 8 | byte offset of the piece inside the pixel's 64 B
+      int xsrc[2];   // per DMA instruction: (pixel index from row h0) << 8 | byte offset of the piece inside the pixel's 64 B
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int r = ((i * 8 + wave) * 64 + lane) >> 2;
         const int xtile = r & 63, xj = r >> 6;
         const int piece = (lane & 3) ^ ((r >> 2) & 3);
-        xsrc[i] = (((h0 + (xtile >> 2)) * W + w0 + 4 * (xtile & 3) + xj) << 8) | (piece * 16);
+        xsrc[i] = (((xtile >> 2) * W + w0 + 4 * (xtile & 3) + xj) << 8) | (piece * 16);
       }
       const unsigned lane16e = (unsigned)(lane * 16);
       // x of stage st -> x buffer `slot`, weights of stage st -> this wave's buffer `slot`; past the last stage: a harmless re-read of

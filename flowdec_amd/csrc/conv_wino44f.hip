@@ -133,6 +133,10 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino44f_kernel(ConvArgs p) {
   const int h0 = th_i * TH, w0 = tw_i * TW;
   const int H = p.H, W = p.W;
   const size_t img_elems = (size_t)H * W;
+  // The halo is addressed from its BAND: the first halo row of this tile (row hb of image b, a 64-bit wave-uniform base), so the
+  // per-lane 32-bit byte offsets stay below (TH + 2) x W x C x 4 bytes whatever the image size (fd_conv2d checks the band bytes).
+  const int hb = h0 > 0 ? h0 - 1 : 0;
+  const size_t band_pix = (size_t)b * img_elems + (size_t)hb * W;
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -147,7 +151,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino44f_kernel(ConvArgs p) {
   struct Cursor { int s, left; const float* src; int C, c0, aoff; };
   auto cur_enter = [&](Cursor& q, int sidx) {
     q.s = sidx; q.C = p.seg[sidx].C; q.aoff = p.seg[sidx].aff_off; q.c0 = 0; q.left = q.C / CK - 1;
-    q.src = reinterpret_cast<const float*>(p.seg[sidx].src) + (size_t)b * img_elems * q.C;
+    q.src = reinterpret_cast<const float*>(p.seg[sidx].src) + band_pix * q.C;
   };
   auto cur_next = [&](Cursor& q) {
     if (q.left > 0) { --q.left; q.c0 += CK; }
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino44f_kernel(ConvArgs p) {
     const int hr = hreal ? lane / WC : 0, hc = hreal ? lane - hr * WC : 0;
     const int gh = h0 - 1 + 4 * ty_w + hr, gw = w0 - 1 + 8 * tp_w + hc;
     hok = hreal && gh >= 0 && gh < H && gw >= 0 && gw < W;
-    hpix = hok ? gh * W + gw : 0;
+    hpix = hok ? (gh - hb) * W + gw : 0;   // (outside the image: pixel 0 of the band, masked by the conversion)
   }
   const unsigned zlds = (unsigned)(Z_OFF + wave * 2 * ZWAVE * 4);
   auto dma_halo = [&]() {              // the next chunk -> z window kd & 1 (always 2 operations: the counted waits rely on it)

@@ -21,10 +21,11 @@ the GPU sees a batch.  With `--seed S` file i of the work list draws its noise f
 of a file does not depend on the batching (`--batch-files 1` = the reference's loop).  Under `--rtf` a batch is timed as a whole and
 its time is split over its files in proportion to their duration (every file of a batch gets the batch's rtf).
 
-Length limit: the reference skips files longer than 30 s; so does this driver, in every precision (one image of the conv kernels
-must stay below 2 GiB in bf16 and below 4 GiB with f32 storage -- 32-bit byte offsets inside an image -- both ~43 s of audio).
-`PRECISION_MAX_SECONDS` is where a precision with a shorter reach would say so: such files are then skipped WITH a message and
-the exit status is 3 (the reference would have processed them).
+Length limit: the reference skips files longer than 30 s; so does this driver by default, in every precision.  `--max-seconds S`
+moves that limit: the kernels address images of any length that fits in device memory (a 180 s clip in bf16 is one call), and
+what remains is the device memory itself.  A file whose workspace (`fd_enhance_workspace_bytes`) does not fit in the free device
+memory is skipped WITH a message, like a file over a precision's limit (`PRECISION_MAX_SECONDS`, where a precision with a shorter
+reach would say so): the exit status is then 3.
 """
 import argparse
 import contextlib
@@ -39,10 +40,10 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .model import BACKBONE_FINAL_NO_ATTN, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, from_preset
+from .model import BACKBONE_FINAL_NO_ATTN, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, WorkspaceTooLarge, from_preset
 
 MAX_SECONDS = 30.0  # enhance.py:115
-PRECISION_MAX_SECONDS = {}   # precision -> clip length it can take, if shorter than MAX_SECONDS (none since round 4: every mode reaches ~43 s)
+PRECISION_MAX_SECONDS = {}   # precision -> clip length it can take, if shorter than --max-seconds (none: every mode takes any length that fits in memory)
 PRECISION_NOTE = {   # printed at start-up so that a log says which arithmetic produced the files
     "bf16": "bf16 storage and MFMA operands, f32 accumulation; ~2e-2 relative waveform error vs the fp32 reference on random weights",
     "mixed": "f32 residual stream, bf16 MFMA operands; ~1.3e-2",
@@ -278,6 +279,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
     p.add_argument("--seed", type=int, default=None, help="file i of the work list draws its initial noise from a generator seeded SEED + i "
                                                           "(default: nondeterministic like the reference)")
+    p.add_argument("--max-seconds", type=float, default=MAX_SECONDS,
+                   help="files longer than this are skipped (default: the reference's %g s); longer clips are limited by device memory only" % MAX_SECONDS)
     p.add_argument("--batch-files", type=int, default=8, help="files of one T_pad bucket per native call (1 = one file per call, the reference's loop)")
     return p
 
@@ -294,8 +297,8 @@ def collect_files(files: str, single_file: bool) -> Tuple[List[str], Optional[Li
 
 @dataclass
 class RunResult:
-    """What a CLI run did: files enhanced, files skipped because they exceed the length limit of the chosen precision (but not the
-    reference's 30 s), files skipped as too long for the reference as well."""
+    """What a CLI run did: files enhanced, files skipped because they exceed the length limit of the chosen precision (but not
+    --max-seconds) or because their workspace does not fit in device memory, files skipped as longer than --max-seconds."""
     n_done: int = 0
     n_over_precision_limit: int = 0
     n_too_long: int = 0
@@ -393,18 +396,19 @@ def file_generator(model: FlowModel, seed: Optional[int], index: int):
     return None if seed is None else torch.Generator(device=model.device).manual_seed(int(seed) + int(index))
 
 
-def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str):
-    """Load -> the reference's length rule (enhance.py:115,139) -> resample to the model rate.  -> waveform [C, L] or None (skipped)."""
+def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS):
+    """Load -> the reference's length rule (enhance.py:115,139; `length_limit` = --max-seconds) -> resample to the model rate.
+    -> waveform [C, L] or None (skipped)."""
     y, sr = load_wav(job.src)
     seconds = y.shape[-1] / sr
-    if seconds > MAX_SECONDS:
+    if seconds > length_limit:
         res.n_too_long += 1
         print("Skipping file due to length:", job.src)
         return None
     if seconds > max_seconds:
         res.n_over_precision_limit += 1
         print(f"Skipping file: {seconds:.1f} s exceeds the {max_seconds:g} s limit of precision={precision} "
-              f"(the reference's limit is {MAX_SECONDS:g} s; use --precision bf16 for files up to it):", job.src)
+              f"(the length limit is {length_limit:g} s; use --precision bf16 for files up to it):", job.src)
         return None
     if sr != model.sampling_rate:
         print("RESAMPLING from", sr, "to", model.sampling_rate)
@@ -412,23 +416,34 @@ def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: 
     return y
 
 
-def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResult, max_seconds: float) -> None:
-    """One file per native call (the reference's loop): load -> enhance (timed under --rtf) -> save.  Updates `res`."""
-    y = load_for_model(model, job, res, max_seconds, args.precision)
+def skip_over_memory(job: FileJob, res: RunResult, err: Exception) -> None:
+    res.n_over_precision_limit += 1
+    print(f"Skipping file: {err}:", job.src)
+
+
+def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResult, max_seconds: float, y=None) -> None:
+    """One file per native call (the reference's loop): load -> enhance (timed under --rtf) -> save.  Updates `res`.  `y`: the file's
+    waveform when the caller has already loaded (and resampled) it."""
+    if y is None:
+        y = load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds)
     if y is None:
         return
     sr = model.sampling_rate
     # use_graph=False: every file has its own length, and a replay would not be faster anyway -- a one-clip solve is bound by the GPU,
     # not by the host's launches (profiles/r02_graph_cost.txt: eager 18.06 ms, replay 18.10 ms; capture + instantiate 2.4 ms)
-    with GpuTimer(args.rtf) as timer:
-        x_hat = model.enhance(y, N=args.N, solver=args.solver, generator=file_generator(model, args.seed, job.index), use_graph=False)
+    try:
+        with GpuTimer(args.rtf) as timer:
+            x_hat = model.enhance(y, N=args.N, solver=args.solver, generator=file_generator(model, args.seed, job.index), use_graph=False)
+    except WorkspaceTooLarge as err:
+        skip_over_memory(job, res, err)
+        return
     if timer.seconds is not None:
         log.rtf(job.dst, timer.seconds, y.shape[-1] / sr)
     save_wav(job.dst, x_hat.cpu(), sr)
     res.n_done += 1
 
 
-def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int):
+def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length_limit: float = MAX_SECONDS):
     """Buckets the pending jobs by the frame count their spectrogram pads to (from the wav HEADERS: nothing is decoded here) and cuts
     every bucket into batches of at most `batch_files` files, in work-list order.  Multi-channel files, unreadable headers and files
     the length rule will skip go through the one-file path (their own messages).  -> list of lists of FileJob."""
@@ -440,7 +455,7 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int):
             n, sr, channels = wav_info(job.src)
         except Exception:   # an unreadable file fails in its own one-file call, with the reference's behaviour (an exception)
             singles.append([job]); continue
-        if channels != 1 or n / sr > MAX_SECONDS or batch_files <= 1:
+        if channels != 1 or n / sr > length_limit or batch_files <= 1:
             singles.append([job]); continue
         buckets.setdefault(padded_frames_of(resampled_length(n, sr, model.sampling_rate), hop), []).append(job)
     batches = []
@@ -452,14 +467,19 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int):
 
 def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLog, res: RunResult, max_seconds: float) -> None:
     """One ragged native call for the files of `batch` (same T_pad bucket).  Every output equals the one-file call bit for bit."""
-    loaded = [(job, load_for_model(model, job, res, max_seconds, args.precision)) for job in batch]
+    loaded = [(job, load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds)) for job in batch]
     loaded = [(job, y) for job, y in loaded if y is not None]
     if not loaded:
         return
     sr = model.sampling_rate
     gens = [file_generator(model, args.seed, job.index) for job, _ in loaded]
-    with GpuTimer(args.rtf) as timer:
-        outs = model.enhance_batch([y for _, y in loaded], N=args.N, solver=args.solver, generator=gens)
+    try:
+        with GpuTimer(args.rtf) as timer:
+            outs = model.enhance_batch([y for _, y in loaded], N=args.N, solver=args.solver, generator=gens)
+    except WorkspaceTooLarge:   # the batch does not fit: one call per file (each result is the same, bit for bit)
+        for job, y in loaded:
+            enhance_file(model, job, args, log, res, max_seconds, y=y)
+        return
     total = sum(y.shape[-1] for _, y in loaded) / sr
     for (job, y), x_hat in zip(loaded, outs):
         if timer.seconds is not None:   # the batch's time, split in proportion to the files' durations
@@ -486,7 +506,7 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision)
         print("Done loading model.")
     noisy, clean = collect_files(args.files, args.single_file)
-    max_seconds = min(MAX_SECONDS, PRECISION_MAX_SECONDS.get(args.precision, MAX_SECONDS))
+    max_seconds = min(args.max_seconds, PRECISION_MAX_SECONDS.get(args.precision, args.max_seconds))
     print(f"flowdec_amd: precision={args.precision} ({PRECISION_NOTE[args.precision]}), solver={args.solver}, N={args.N}, "
           f"files per native call <= {max(args.batch_files, 1)}")
     res = RunResult()
@@ -494,7 +514,7 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
     jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
     batchable = args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast")   # (the adaptive solvers step clip by clip)
     with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None) as log:
-        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable else 1):
+        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable else 1, args.max_seconds):
             if len(batch) == 1:
                 enhance_file(model, batch[0], args, log, res, max_seconds)
             else:

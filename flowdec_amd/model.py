@@ -280,6 +280,8 @@ class NCSNpp(nn.Module):
         buf = self._ws.get(kind)
         if buf is None or buf.numel() < nbytes or buf.device != torch.device(device):
             self._ws.pop(kind, None)
+            del buf
+            check_workspace_fits(nbytes, device)
             buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
             self._ws[kind] = buf
         return buf
@@ -308,6 +310,26 @@ class NCSNpp(nn.Module):
             L.check(lib.fd_ncsnpp_forward(h, L.ptr(torch.view_as_real(x)), L.ptr(torch.view_as_real(y)), L.ptr(t), t.numel(),
                                           L.ptr(torch.view_as_real(out)), B, T, L.ptr(ws), ws.numel(), L.stream()))
         return out
+
+
+class WorkspaceTooLarge(RuntimeError):
+    """The workspace of a call (fd_*_workspace_bytes) exceeds the device memory that is free for it: the clip is too long for one call on
+    this device."""
+
+
+def check_workspace_fits(nbytes, device):
+    """Raise WorkspaceTooLarge unless `nbytes` fit in the device memory free right now: free on the device plus what the caching
+    allocator holds unused.  (Checked before the allocation, so that a clip that cannot fit fails with both numbers instead of an
+    out-of-memory error from inside a graph capture.)"""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return
+    free, _ = torch.cuda.mem_get_info(dev)
+    avail = free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if nbytes > avail:
+        raise WorkspaceTooLarge(f"flowdec_hip: the call needs a workspace of {int(nbytes)} bytes ({nbytes / 2**30:.2f} GiB), but only "
+                                f"{int(avail)} bytes ({avail / 2**30:.2f} GiB) of device memory are free on {dev}: the clip is too long "
+                                f"for one call on this device")
 
 
 class _NativeCall:
