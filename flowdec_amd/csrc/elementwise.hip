@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "noise.h"
 
 namespace {
 
@@ -802,13 +803,30 @@ __global__ void output_update_kernel(const T* __restrict__ pyr, const float* __r
   }
 }
 
+// Element i of a [B][F][T] plane of Gaussian noise: read from the caller's buffer, or (SEEDED) generated in registers from the clip's
+// seed (noise.h).  A thread recomputes the Philox call it shares with the neighbouring frame instead of handling a frame pair: the
+// consumers below stay one element per thread like their unseeded forms (one grid, one index map), and the ~150 integer / float
+// operations per element hide behind the 24-40 bytes each of them moves (they replace an 8-byte load).
+template <bool SEEDED>
+__device__ __forceinline__ float2 noise_elem(const float2* __restrict__ z, const unsigned long long* __restrict__ seeds, int draw, long long i,
+                                             int F, int T) {
+  if constexpr (SEEDED) {
+    const long long row = i / T;
+    return fd_noise_at(seeds[row / F], draw, (int)(row % F), (int)(i - row * T));
+  } else {
+    return z[i];
+  }
+}
+
 // x0 = Y + sigma_fac * (sigma_y[f] * noise).type(complex64)   (model.py:512, :530-536); sigma is float64
-__global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __restrict__ noise, const double* __restrict__ sigma,
-                                  int sigma_n, float sigma_fac, float2* __restrict__ x0, int F, int T, long long n) {
+template <bool SEEDED>
+__global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __restrict__ noise, const unsigned long long* __restrict__ seeds,
+                                  int draw, const double* __restrict__ sigma, int sigma_n, float sigma_fac, float2* __restrict__ x0, int F,
+                                  int T, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int f = (int)((i / T) % F);
     const double s = sigma[sigma_n == 1 ? 0 : f];
-    const float2 nz = noise[i], yv = Y[i];
+    const float2 nz = noise_elem<SEEDED>(noise, seeds, draw, i, F, T), yv = Y[i];
     const float nx = (float)(s * (double)nz.x), ny = (float)(s * (double)nz.y);
     float2 o = {yv.x + sigma_fac * nx, yv.y + sigma_fac * ny};
     x0[i] = o;
@@ -817,11 +835,13 @@ __global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __
 
 // Predictor / corrector update of the ScoreDec sampler (sampling/predictors.py:48-71, correctors.py:52-66) fused with the
 // output layer:  dst = cb * base + cy * Y + cn * v + cz * z   (v = output_layer(pyr) as complex; every coefficient is a
-// real scalar that the host derives from the OUVE closed forms, sdes.py:168-192).
-template <typename T, int KS>
+// real scalar that the host derives from the OUVE closed forms, sdes.py:168-192).  SEEDED: z comes from the clips' seeds (draw index
+// `draw`) instead of a buffer, and is not generated at all when cz == 0.
+template <typename T, int KS, bool SEEDED>
 __global__ void score_update_kernel(const T* __restrict__ pyr, const float* __restrict__ wo, const float2* __restrict__ base, float cb,
-                                    const float2* __restrict__ Y, float cy, float cn, const float2* __restrict__ z, float cz,
-                                    float2* __restrict__ dst, long long n, int H, int W) {
+                                    const float2* __restrict__ Y, float cy, float cn, const float2* __restrict__ z,
+                                    const unsigned long long* __restrict__ seeds, int draw, float cz, float2* __restrict__ dst, long long n,
+                                    int H, int W) {
   const float w0 = wo[0], w1 = wo[1], w2 = wo[2], w3 = wo[3], w4 = wo[4], w5 = wo[5], w6 = wo[6], w7 = wo[7];
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float vx, vy;
@@ -837,17 +857,51 @@ __global__ void score_update_kernel(const T* __restrict__ pyr, const float* __re
     const float2 b = base[i];
     float2 o = {fmaf(cn, vx, cb * b.x), fmaf(cn, vy, cb * b.y)};
     if (cy != 0.f) { const float2 yv = Y[i]; o.x = fmaf(cy, yv.x, o.x); o.y = fmaf(cy, yv.y, o.y); }
-    if (cz != 0.f) { const float2 zv = z[i]; o.x = fmaf(cz, zv.x, o.x); o.y = fmaf(cz, zv.y, o.y); }
+    if (cz != 0.f) { const float2 zv = noise_elem<SEEDED>(z, seeds, draw, i, H, W); o.x = fmaf(cz, zv.x, o.x); o.y = fmaf(cz, zv.y, o.y); }
     dst[i] = o;
   }
 }
 
-// dst = a + cq * q  (prior sample x_T = Y + std(T) * z, sdes.py:197-202)
-__global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restrict__ q, float cq, float2* __restrict__ dst, long long n) {
+// dst = a + cq * q  (prior sample x_T = Y + std(T) * z, sdes.py:197-202); q = a [B][F][T] plane of noise (buffer or seeds)
+template <bool SEEDED>
+__global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restrict__ q, const unsigned long long* __restrict__ seeds, int draw,
+                             float cq, float2* __restrict__ dst, int F, int T, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float2 av = a[i], qv = q[i];
+    const float2 av = a[i], qv = noise_elem<SEEDED>(q, seeds, draw, i, F, T);
     float2 o = {fmaf(cq, qv.x, av.x), fmaf(cq, qv.y, av.y)};
     dst[i] = o;
+  }
+}
+
+// The planes draw0 .. draw0 + n_draws - 1 of the seeded noise as a buffer: out[d][b][f][t] (complex64; BITS: the two raw words of
+// every element as uint32 instead).  One thread = one frame pair = one Philox call; with an even T the pair is one 16-byte store.
+template <bool BITS>
+__global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ out, const unsigned long long* __restrict__ seeds, int B, int F,
+                                                         int T, int draw0, long long npairs) {
+  const int tp = (T + 1) >> 1;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npairs; i += (long long)gridDim.x * 256) {
+    const int t = 2 * (int)(i % tp);
+    long long q = i / tp;
+    const int f = (int)(q % F); q /= F;
+    const int b = (int)(q % B), d = (int)(q / B);
+    unsigned r[4];
+    const unsigned long long seed = seeds[b];
+    philox4x32_10((unsigned)t >> 1, (unsigned)f, (unsigned)(draw0 + d), 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
+    float2 z0, z1;
+    if constexpr (BITS) {
+      z0 = float2{__uint_as_float(r[0]), __uint_as_float(r[1])};
+      z1 = float2{__uint_as_float(r[2]), __uint_as_float(r[3])};
+    } else {
+      z0 = fd_noise_from_bits(uint2{r[0], r[1]});
+      z1 = fd_noise_from_bits(uint2{r[2], r[3]});
+    }
+    float2* o = out + (((long long)d * B + b) * F + f) * T + t;
+    if ((T & 1) == 0) {
+      *reinterpret_cast<float4*>(o) = float4{z0.x, z0.y, z1.x, z1.y};
+    } else {
+      o[0] = z0;
+      if (t + 1 < T) o[1] = z1;
+    }
   }
 }
 
@@ -1103,12 +1157,12 @@ static int edge_launch(int which, const fd_edge_args& a, hipStream_t st) {
     }
     case 4: {  // output + score-sampler update
       const long long n = (long long)a.B * a.H * a.W;
-      if (a.ks == 3)
-        hipLaunchKernelGGL((score_update_kernel<T, 3>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, a.cb,
-                           (const float2*)a.y, a.cy, a.coef, (const float2*)a.z, a.cz, (float2*)a.out, n, a.H, a.W);
-      else
-        hipLaunchKernelGGL((score_update_kernel<T, 1>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, a.cb,
-                           (const float2*)a.y, a.cy, a.coef, (const float2*)a.z, a.cz, (float2*)a.out, n, a.H, a.W);
+#define FD_SCORE_UPDATE(KS_, SEEDED_)                                                                                                          \
+  hipLaunchKernelGGL((score_update_kernel<T, KS_, SEEDED_>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, \
+                     a.cb, (const float2*)a.y, a.cy, a.coef, (const float2*)a.z.ptr, a.z.seeds, a.z.draw, a.cz, (float2*)a.out, n, a.H, a.W)
+      if (a.z.seeds) { if (a.ks == 3) FD_SCORE_UPDATE(3, true); else FD_SCORE_UPDATE(1, true); }
+      else { if (a.ks == 3) FD_SCORE_UPDATE(3, false); else FD_SCORE_UPDATE(1, false); }
+#undef FD_SCORE_UPDATE
       break;
     }
     case 5: {  // input convolution 4 -> Cout with GroupNorm partials (16 x 16 tiles)
@@ -1146,17 +1200,42 @@ extern "C" int fd_conv_in(const void* in8, const float* w, const float* bias, vo
   return fd_edge_op(5, a, dtype, fd_stream(stream));
 }
 
-int fd_init_state(const float* Y, const float* noise, const double* sigma_dev, int sigma_n, float sigma_fac, float* x0, int B,
+int fd_init_state(const float* Y, const fd_noise_src& noise, const double* sigma_dev, int sigma_n, float sigma_fac, float* x0, int B,
                   int F, int T, hipStream_t st) {
   const long long n = (long long)B * F * T;
-  hipLaunchKernelGGL(init_state_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)Y, (const float2*)noise, sigma_dev, sigma_n,
-                     sigma_fac, (float2*)x0, F, T, n);
+  if (noise.seeds)
+    hipLaunchKernelGGL(init_state_kernel<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)Y, (const float2*)nullptr, noise.seeds,
+                       noise.draw, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
+  else
+    hipLaunchKernelGGL(init_state_kernel<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)Y, (const float2*)noise.ptr,
+                       (const unsigned long long*)nullptr, 0, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }
 
-int fd_caxpy(const float* a, const float* q, float cq, float* dst, long long n, hipStream_t st) {
-  hipLaunchKernelGGL(caxpy_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)q, cq, (float2*)dst, n);
+int fd_caxpy(const float* a, const fd_noise_src& q, float cq, float* dst, int B, int F, int T, hipStream_t st) {
+  const long long n = (long long)B * F * T;
+  if (q.seeds)
+    hipLaunchKernelGGL(caxpy_kernel<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)nullptr, q.seeds, q.draw, cq,
+                       (float2*)dst, F, T, n);
+  else
+    hipLaunchKernelGGL(caxpy_kernel<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)q.ptr,
+                       (const unsigned long long*)nullptr, 0, cq, (float2*)dst, F, T, n);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+extern "C" int fd_noise_fill(void* out, const unsigned long long* seeds, int B, int F, int T_pad, int draw0, int n_draws, int mode, void* stream) {
+  FD_REQUIRE(out && seeds, "fd_noise_fill: null pointer");
+  FD_REQUIRE(B > 0 && F > 0 && T_pad > 0 && draw0 >= 0 && n_draws > 0, "fd_noise_fill: bad shape (B=%d F=%d T_pad=%d draw0=%d n_draws=%d)", B, F, T_pad, draw0, n_draws);
+  FD_REQUIRE(mode == FD_NOISE_GAUSSIAN || mode == FD_NOISE_BITS, "fd_noise_fill: unknown mode %d", mode);
+  FD_REQUIRE((uintptr_t)out % 16 == 0, "fd_noise_fill: out must be 16-byte aligned");
+  const long long npairs = (long long)n_draws * B * F * ((T_pad + 1) / 2);
+  const dim3 grid(grid_for(npairs, 256, 1 << 16));
+  if (mode == FD_NOISE_BITS)
+    hipLaunchKernelGGL(noise_fill_kernel<true>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, B, F, T_pad, draw0, npairs);
+  else
+    hipLaunchKernelGGL(noise_fill_kernel<false>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, B, F, T_pad, draw0, npairs);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

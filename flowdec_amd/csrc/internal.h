@@ -10,6 +10,14 @@ struct fd_temb_job {
   int Cout;
 };
 
+// Where a [B][F][T] plane of sampler noise comes from: a caller-filled buffer (`ptr`), or the clips' seeds (DEVICE uint64 [B]) and the
+// index of the draw -- then the consuming kernel generates the plane in registers (noise.h)
+struct fd_noise_src {
+  const float* ptr = nullptr;
+  const unsigned long long* seeds = nullptr;
+  int draw = 0;
+};
+
 struct fd_edge_args {
   const void* x = nullptr;   // main input (4-channel NHWC tensor, or complex x for pack)
   const void* y = nullptr;   // second input (complex y for pack; h for combine)
@@ -21,7 +29,7 @@ struct fd_edge_args {
   void* ksave = nullptr;
   float* stats = nullptr;      // combine: [B][fd_combine_tiles][Cout][2] GroupNorm partials of the output
   float coef = 1.f;
-  const void* z = nullptr;     // score update: dst = cb*base + cy*y + coef*v + cz*z
+  fd_noise_src z;              // score update: dst = cb*base + cy*y + coef*v + cz*z
   float cb = 1.f, cy = 0.f, cz = 0.f;
   int B = 0, H = 0, W = 0, Cout = 0;
   int ks = 1;                  // output layer (ops 3, 4): 1x1 or 3x3 (zero padding 'same'; w = [2][4][3][3])
@@ -35,14 +43,15 @@ int fd_temb_bias_batched(const fd_temb_job* jobs_dev, int njobs, const float* te
 //        4 = output layer + score-sampler update, 5 = input convolution 3x3 4 -> Cout (x = packed input, w = [Cout][4][3][3] f32) with
 //        the GroupNorm partials of its output in `stats` ([B][(H / 16) * (W / 16)][Cout][2])
 int fd_edge_op(int which, const fd_edge_args& a, int dtype, hipStream_t st);
-int fd_init_state(const float* Y, const float* noise, const double* sigma_dev, int sigma_n, float sigma_fac, float* x0, int B,
+int fd_init_state(const float* Y, const fd_noise_src& noise, const double* sigma_dev, int sigma_n, float sigma_fac, float* x0, int B,
                   int F, int T, hipStream_t st);
 int fd_combine_tiles(int H, int W);
 // adaptive solver helpers: dst = cx * x + dt * sum c[i] k[i];  partial[b] = sum |p - q|^2 / (atol + rtol max(|r|, |s|))^2
 int fd_ode_lincomb(const float* x, float cx, float dt, const float* const* k, const float* c, int nk, float* dst, long long n, hipStream_t st);
 int fd_ode_scaled_sq(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks,
                      long long n, hipStream_t st);
-int fd_caxpy(const float* a, const float* q, float cq, float* dst, long long n, hipStream_t st);
+// dst = a + cq * q, q = a [B][F][T] plane of noise
+int fd_caxpy(const float* a, const fd_noise_src& q, float cq, float* dst, int B, int F, int T, hipStream_t st);
 // conv_mfma.hip
 int fd_conv_init_attributes();
 // stft.hip

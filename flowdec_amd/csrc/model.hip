@@ -99,12 +99,12 @@ struct Tens {
 // Everything a captured solve bakes into its kernel arguments.  Compared field by field (a memcmp over the struct would read
 // its padding bytes).
 struct GraphKey {
-  const void *Y = nullptr, *noise = nullptr, *X = nullptr, *traj = nullptr, *ws = nullptr, *y = nullptr, *xhat = nullptr, *lens = nullptr;
+  const void *Y = nullptr, *noise = nullptr, *X = nullptr, *traj = nullptr, *ws = nullptr, *y = nullptr, *xhat = nullptr, *lens = nullptr, *seeds = nullptr;
   int B = 0, T = 0, N = 0, solver = 0, L = 0, kind = 0, normalize = 1;
   float sigma_fac = 0.f;
   fd_score_config score{};   // kind 3 only (zero otherwise)
   auto tie() const {
-    return std::tie(Y, noise, X, traj, ws, y, xhat, lens, B, T, N, solver, L, kind, normalize, sigma_fac, score.theta, score.sigma_min, score.sigma_max,
+    return std::tie(Y, noise, X, traj, ws, y, xhat, lens, seeds, B, T, N, solver, L, kind, normalize, sigma_fac, score.theta, score.sigma_min, score.sigma_max,
                     score.t_eps, score.snr, score.N, score.predictor, score.corrector, score.corrector_steps, score.denoise);
   }
   bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
@@ -304,7 +304,7 @@ struct OutSpec {           // what to do with v = NCSNpp(x, y, t):  dst = base +
   // score-sampler form (score = true):  dst = cb * base + cy * yv + coef * v + cz * z
   bool score = false;
   const float* yv = nullptr;
-  const float* z = nullptr;
+  fd_noise_src z;
   float cb = 1.f, cy = 0.f, cz = 0.f;
 };
 
@@ -698,7 +698,7 @@ size_t ode_ws_bytes(const fd_model* m, int B, int T) {
 }
 
 // the solver loop; everything is enqueued on `st` (eagerly or inside a capture)
-int ode_enqueue(fd_model* m, const float* Y, const float* noise, float sigma_fac, int N, int solver, float* X, float* traj, int B, int T, void* ws,
+int ode_enqueue(fd_model* m, const float* Y, const fd_noise_src& noise, float sigma_fac, int N, int solver, float* X, float* traj, int B, int T, void* ws,
                 size_t ws_bytes, hipStream_t st) {
   const size_t nstate = (size_t)B * m->n_freq * T;
   const size_t state = fd_align(sizeof(float) * 2 * nstate);
@@ -765,13 +765,14 @@ int score_draws(const fd_score_config& c) {
   return 1 + c.N * ((c.corrector == FD_CORRECTOR_ALD ? c.corrector_steps : 0) + (c.predictor != FD_PREDICTOR_NONE ? 1 : 0));
 }
 
-// sampling/__init__.py:57-70.  noise = [draws][B][F][T] complex64, consumed in the reference's order of randn_like calls.
-int score_enqueue(fd_model* m, const float* Y, const float* noise, const fd_score_config& c, float* X, int B, int T, void* ws, size_t ws_bytes,
+// sampling/__init__.py:57-70.  noise = [draws][B][F][T] complex64 (or the clips' seeds: draw indices 0, 1, ...), consumed in the reference's
+// order of randn_like calls -- a draw whose coefficient is zero (the last predictor step under `denoise`) still takes its index.
+int score_enqueue(fd_model* m, const float* Y, const fd_noise_src& noise, const fd_score_config& c, float* X, int B, int T, void* ws, size_t ws_bytes,
                   hipStream_t st) {
   const size_t nstate = (size_t)B * m->n_freq * T;
-  const float* z = noise;
-  auto next_z = [&]() { const float* r = z; z += 2 * nstate; return r; };
-  FD_TRY(fd_caxpy(Y, next_z(), ouve_std(c, 1.0f), X, (long long)nstate, st));                 // prior, sdes.py:197-202
+  fd_noise_src z = noise;
+  auto next_z = [&]() { const fd_noise_src r = z; if (z.seeds) ++z.draw; else z.ptr += 2 * nstate; return r; };
+  FD_TRY(fd_caxpy(Y, next_z(), ouve_std(c, 1.0f), X, B, m->n_freq, T, st));                 // prior, sdes.py:197-202
   const std::vector<float> ts = linspace_f32(1.0f, c.t_eps, c.N);
   for (int i = 0; i < c.N; ++i) {
     const float t = ts[i], std_t = ouve_std(c, t);
@@ -1075,20 +1076,35 @@ extern "C" int fd_ncsnpp_forward(fd_model* m, const float* x, const float* y, co
   return forward_call(m, x, y, t, 0.f, nt, os, B, T_pad, ws, ws_bytes, fd_stream(stream));
 }
 
+namespace {
+int ode_solve_impl(fd_model* m, const char* who, const float* Y, const fd_noise_src& noise, float sigma_fac, int N, int solver, float* X_out, float* traj,
+                   int B, int T_pad, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(Y && (noise.ptr || noise.seeds) && X_out && ws, "%s: null pointer", who);
+  FD_REQUIRE(N >= 1, "%s: N must be >= 1", who);
+  FD_REQUIRE(solver_nfe(solver, N) > 0, "%s: unknown solver id %d", who, solver);
+  FD_TRY(check_shape(m, B, T_pad));
+  const size_t need = ode_ws_bytes(m, B, T_pad);
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
+  hipStream_t st = fd_stream(stream);
+  GraphKey key; key.Y = Y; key.noise = noise.ptr; key.seeds = noise.seeds; key.X = X_out; key.traj = traj; key.ws = ws; key.B = B; key.T = T_pad; key.N = N;
+  key.solver = solver; key.kind = 1; key.sigma_fac = sigma_fac;
+  return run_maybe_graph(m, key, use_graph != 0, st, [&]() { return ode_enqueue(m, Y, noise, sigma_fac, N, solver, X_out, traj, B, T_pad, ws, ws_bytes, st); });
+}
+}  // namespace
+
 extern "C" int fd_ode_solve(fd_model* m, const float* Y, const float* noise, float sigma_fac, int N, int solver, float* X_out, float* traj, int B,
                             int T_pad, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_ode_solve");
-  FD_TRY(check_ready(m));
-  FD_REQUIRE(Y && noise && X_out && ws, "fd_ode_solve: null pointer");
-  FD_REQUIRE(N >= 1, "fd_ode_solve: N must be >= 1");
-  FD_REQUIRE(solver_nfe(solver, N) > 0, "fd_ode_solve: unknown solver id %d", solver);
-  FD_TRY(check_shape(m, B, T_pad));
-  const size_t need = ode_ws_bytes(m, B, T_pad);
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_ode_solve: workspace %zu < required %zu bytes", ws_bytes, need);
-  hipStream_t st = fd_stream(stream);
-  GraphKey key; key.Y = Y; key.noise = noise; key.X = X_out; key.traj = traj; key.ws = ws; key.B = B; key.T = T_pad; key.N = N; key.solver = solver;
-  key.kind = 1; key.sigma_fac = sigma_fac;
-  return run_maybe_graph(m, key, use_graph != 0, st, [&]() { return ode_enqueue(m, Y, noise, sigma_fac, N, solver, X_out, traj, B, T_pad, ws, ws_bytes, st); });
+  return ode_solve_impl(m, "fd_ode_solve", Y, fd_noise_src{noise}, sigma_fac, N, solver, X_out, traj, B, T_pad, ws, ws_bytes, use_graph, stream);
+}
+
+// fd_ode_solve with the initial noise generated from the clips' seeds (draw index 0) inside the kernel that forms x0
+extern "C" int fd_ode_solve_seeded(fd_model* m, const float* Y, const unsigned long long* seeds, float sigma_fac, int N, int solver, float* X_out,
+                                   float* traj, int B, int T_pad, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_ode_solve_seeded");
+  return ode_solve_impl(m, "fd_ode_solve_seeded", Y, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, X_out, traj, B, T_pad, ws, ws_bytes, use_graph,
+                        stream);
 }
 
 // ---- adaptive Dormand-Prince 5(4) (torchdyn 'dopri5' semantics restated, see oracle odeint_dopri5; host-driven: one
@@ -1170,7 +1186,7 @@ extern "C" int fd_ode_solve_adaptive_method(fd_model* m, const float* Y, const f
     *out = sqrt(acc / (double)nstate);
     return FD_OK;
   };
-  FD_TRY(fd_init_state(Y, noise, m->sigma_dev, m->sigma_n, sigma_fac, x, B, m->n_freq, T_pad, st));
+  FD_TRY(fd_init_state(Y, fd_noise_src{noise}, m->sigma_dev, m->sigma_n, sigma_fac, x, B, m->n_freq, T_pad, st));
   if (traj) FD_HIP(hipMemcpyAsync(traj, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
   const std::vector<float> ts = t_span_linspace(N);
   float t = ts[0];
@@ -1250,10 +1266,10 @@ extern "C" size_t fd_enhance_normfac_offset(const fd_model* m, int B, int L) {
 }
 
 namespace {
-int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const float* noise, float sigma_fac, int N, int solver, float* x_hat, int B,
+int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, float sigma_fac, int N, int solver, float* x_hat, int B,
                  int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_TRY(check_ready(m));
-  FD_REQUIRE(y && noise && x_hat && ws, "%s: null pointer", who);
+  FD_REQUIRE(y && (noise.ptr || noise.seeds) && x_hat && ws, "%s: null pointer", who);
   FD_REQUIRE(N >= 1 && solver_nfe(solver, N) > 0, "%s: bad N / solver", who);
   FD_REQUIRE(B > 0 && L > m->cfg.n_fft / 2, "%s: clips must be longer than %d samples", who, m->cfg.n_fft / 2);
   const int T = 1 + L / m->cfg.hop, Tp = fd_padded_frames(T);
@@ -1267,7 +1283,7 @@ int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, 
   float* normfac = (float*)((char*)ws + 2 * state);
   char* rest = (char*)ws + 2 * state + fd_align(sizeof(float) * B);
   const size_t rest_bytes = ws_bytes - (2 * state + fd_align(sizeof(float) * B));
-  GraphKey key; key.y = y; key.noise = noise; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.N = N; key.solver = solver; key.kind = 2;
+  GraphKey key; key.y = y; key.noise = noise.ptr; key.seeds = noise.seeds; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.N = N; key.solver = solver; key.kind = 2;
   key.sigma_fac = sigma_fac; key.normalize = m->normalize;
   return run_maybe_graph(m, key, use_graph != 0, st, [&]() {
     FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st));
@@ -1281,7 +1297,7 @@ int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, 
 extern "C" int fd_enhance(fd_model* m, const float* y, const float* noise, float sigma_fac, int N, int solver, float* x_hat, int B, int L, void* ws,
                           size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance");
-  return enhance_impl(m, "fd_enhance", y, nullptr, noise, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return enhance_impl(m, "fd_enhance", y, nullptr, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // FlowModel.enhance on a RAGGED batch: the reference's driver enhances a directory file by file (enhance.py:96-137), every file its
@@ -1295,7 +1311,15 @@ extern "C" int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths
                                  float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance_ragged");
   FD_REQUIRE(lengths, "fd_enhance_ragged: null lengths");
-  return enhance_impl(m, "fd_enhance_ragged", y, lengths, noise, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return enhance_impl(m, "fd_enhance_ragged", y, lengths, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// fd_enhance (lengths == NULL) / fd_enhance_ragged with the initial noise generated from the clips' seeds (DEVICE uint64 [B], draw index 0):
+// no noise buffer exists.  A captured graph is keyed on the POINTERS `seeds` and `lengths`; their contents may change between replays.
+extern "C" int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, float sigma_fac, int N, int solver,
+                                 float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_enhance_seeded");
+  return enhance_impl(m, "fd_enhance_seeded", y, lengths, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT
@@ -1330,22 +1354,35 @@ extern "C" int fd_score_num_draws(const fd_score_config* c) {
   return score_draws(*c);
 }
 
-extern "C" int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_score_config* c, float* x_hat, int B, int L, void* ws,
-                                size_t ws_bytes, int use_graph, void* stream) {
-  FD_MODEL_ENTER(m, "fd_score_enhance");
-  FD_REQUIRE(c && noise, "fd_score_enhance: null pointer");
-  FD_REQUIRE(c->N >= 1, "fd_score_enhance: N must be >= 1");
-  FD_REQUIRE(c->predictor >= FD_PREDICTOR_REVERSE_DIFFUSION && c->predictor <= FD_PREDICTOR_NONE, "fd_score_enhance: unknown predictor id %d", c->predictor);
-  FD_REQUIRE(c->corrector == FD_CORRECTOR_ALD || c->corrector == FD_CORRECTOR_NONE, "fd_score_enhance: unknown corrector id %d", c->corrector);
-  FD_REQUIRE(c->corrector_steps >= 0 && c->corrector_steps <= 64, "fd_score_enhance: corrector_steps out of range");
-  FD_REQUIRE(c->sigma_min > 0.f && c->sigma_max > c->sigma_min && c->theta > 0.f, "fd_score_enhance: bad OUVE parameters");
-  FD_REQUIRE(c->t_eps > 0.f && c->t_eps < 1.f, "fd_score_enhance: t_eps must be in (0, 1)");
-  GraphKey key; key.noise = noise; key.kind = 3; key.score = *c;
+static int score_enhance_impl(fd_model* m, const char* who, const float* y, const fd_noise_src& noise, const fd_score_config* c, float* x_hat, int B,
+                              int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_REQUIRE(c && (noise.ptr || noise.seeds), "%s: null pointer", who);
+  FD_REQUIRE(c->N >= 1, "%s: N must be >= 1", who);
+  FD_REQUIRE(c->predictor >= FD_PREDICTOR_REVERSE_DIFFUSION && c->predictor <= FD_PREDICTOR_NONE, "%s: unknown predictor id %d", who, c->predictor);
+  FD_REQUIRE(c->corrector == FD_CORRECTOR_ALD || c->corrector == FD_CORRECTOR_NONE, "%s: unknown corrector id %d", who, c->corrector);
+  FD_REQUIRE(c->corrector_steps >= 0 && c->corrector_steps <= 64, "%s: corrector_steps out of range", who);
+  FD_REQUIRE(c->sigma_min > 0.f && c->sigma_max > c->sigma_min && c->theta > 0.f, "%s: bad OUVE parameters", who);
+  FD_REQUIRE(c->t_eps > 0.f && c->t_eps < 1.f, "%s: t_eps must be in (0, 1)", who);
+  GraphKey key; key.noise = noise.ptr; key.seeds = noise.seeds; key.kind = 3; key.score = *c;
   const fd_score_config cfg = *c;
-  return enhance_common(m, "fd_score_enhance", y, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
+  return enhance_common(m, who, y, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
                         [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
                           return score_enqueue(m, Y, noise, cfg, X, B, Tp, rest, rest_bytes, st);
                         });
+}
+
+extern "C" int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_score_config* c, float* x_hat, int B, int L, void* ws,
+                                size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_enhance");
+  return score_enhance_impl(m, "fd_score_enhance", y, fd_noise_src{noise}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// fd_score_enhance with every Gaussian plane generated from the clips' seeds inside the kernel that consumes it: draw index k = the k-th plane
+// fd_score_enhance would read
+extern "C" int fd_score_enhance_seeded(fd_model* m, const float* y, const unsigned long long* seeds, const fd_score_config* c, float* x_hat, int B,
+                                       int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_enhance_seeded");
+  return score_enhance_impl(m, "fd_score_enhance_seeded", y, fd_noise_src{nullptr, seeds, 0}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // One evaluation of the score network combined into what the black-box ODE sampler of the reference needs

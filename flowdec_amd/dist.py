@@ -99,14 +99,15 @@ def clip_noise(seed: int, index: int, shape, device) -> torch.Tensor:
 
 def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", noise: Optional[torch.Tensor] = None,
                     seed: Optional[int] = None, generator: Optional[torch.Generator] = None, group=None, always_gather: bool = False,
-                    stats: Optional[dict] = None, **enhance_kwargs) -> torch.Tensor:
+                    stats: Optional[dict] = None, rng: str = "torch", **enhance_kwargs) -> torch.Tensor:
     """`model.enhance(y, N=N, solver=solver)` for a global batch y [B, 1, L] sharded by clip over the ranks of `group`;
     every rank returns all B enhanced waveforms [B, 1, L] on y's device.  Result == the single-process call, bit for bit:
 
       noise=      global initial noise [B, 1, F, T_pad] complex64 (every rank passes the same tensor or at least its own
                   rows): rank r uses rows [lo, hi);
       seed=       clip i draws from the stream (seed, i) (`clip_noise`); the default when nothing is given: rank 0 draws a
-                  seed and broadcasts it;
+                  seed and broadcasts it.  With rng="native" the noise is the library's own instead (`model.enhance(seed=)`):
+                  global clip i uses `flowdec_amd.noise.clip_seed(seed, i)` and no noise tensor is drawn or copied;
       generator=  one generator seeded IDENTICALLY on every rank: the full [B, ...] noise is drawn and sliced, which equals
                   `model.enhance(y, generator=g)` of a single process (costs B x 1.5 MB per second of audio of device memory).
 
@@ -116,6 +117,10 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
     import time
     if y.ndim != 3 or y.shape[1] != 1:
         raise RuntimeError(f"sharded_enhance expects a batch [B, 1, L] (got {tuple(y.shape)})")
+    if rng not in ("torch", "native"):
+        raise ValueError(f"rng must be 'torch' or 'native' (got {rng!r})")
+    if rng == "native" and (noise is not None or generator is not None):
+        raise ValueError("rng='native' draws from seed=: it takes neither noise= nor generator=")
     world, rank = _world(group)
     B, Lw = y.shape[0], y.shape[-1]
     lo, hi = shard_range(B, rank, world)
@@ -123,7 +128,14 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
     out_device = y.device
     t0 = time.perf_counter() if stats is not None else 0.0
     local = None
-    if hi > lo:
+    if rng == "native":
+        if seed is None:
+            seed = _shared_seed(dev, group)   # (every rank, idle ones included, takes part in the broadcast)
+        if hi > lo:
+            from .noise import clip_seed
+            local = model.enhance(y[lo:hi].to(dev, non_blocking=True), N=N, solver=solver, seed=[clip_seed(seed, i) for i in range(lo, hi)],
+                                  **enhance_kwargs)
+    elif hi > lo:
         yl = y[lo:hi].to(dev, non_blocking=True)
         if noise is not None:
             nz = noise[lo:hi]

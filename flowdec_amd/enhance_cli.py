@@ -18,7 +18,8 @@ Batching (round 6): the reference enhances one file per call (enhance.py:96-137)
 files by the frame count their spectrogram pads to (T_pad, util/other.py:25-52) and runs up to `--batch-files` files of a bucket as
 ONE ragged native call (FlowModel.enhance_batch -> fd_enhance_ragged): every file's waveform is bit-identical to the one-file call,
 the GPU sees a batch.  With `--seed S` file i of the work list draws its noise from its own generator seeded S + i, so the result
-of a file does not depend on the batching (`--batch-files 1` = the reference's loop).  Under `--rtf` a batch is timed as a whole and
+of a file does not depend on the batching (`--batch-files 1` = the reference's loop); with `--rng native` the noise is the library's
+own, generated on the GPU from `flowdec_amd.noise.clip_seed(S, i)` (no collisions between (S, i + 1) and (S + 1, i)).  Under `--rtf` a batch is timed as a whole and
 its time is split over its files in proportion to their duration (every file of a batch gets the batch's rtf).
 
 Length limit: the reference skips files longer than 30 s; so does this driver by default, in every precision.  `--max-seconds S`
@@ -40,6 +41,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from .noise import clip_seed
 from .model import BACKBONE_FINAL_NO_ATTN, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, WorkspaceTooLarge, from_preset
 
 MAX_SECONDS = 30.0  # enhance.py:115
@@ -279,6 +281,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
     p.add_argument("--seed", type=int, default=None, help="file i of the work list draws its initial noise from a generator seeded SEED + i "
                                                           "(default: nondeterministic like the reference)")
+    p.add_argument("--rng", type=str, default="torch", choices=["torch", "native"],
+                   help="torch: the noise comes from torch generators (see --seed); native: the library draws it on the GPU, file i of the work "
+                        "list from flowdec_amd.noise.clip_seed(SEED, i) (without --seed one seed is drawn from the OS and printed)")
     p.add_argument("--max-seconds", type=float, default=MAX_SECONDS,
                    help="files longer than this are skipped (default: the reference's %g s); longer clips are limited by device memory only" % MAX_SECONDS)
     p.add_argument("--batch-files", type=int, default=8, help="files of one T_pad bucket per native call (1 = one file per call, the reference's loop)")
@@ -396,6 +401,15 @@ def file_generator(model: FlowModel, seed: Optional[int], index: int):
     return None if seed is None else torch.Generator(device=model.device).manual_seed(int(seed) + int(index))
 
 
+def noise_kwargs(model: FlowModel, args, indices: List[int], batch: bool) -> dict:
+    """The noise arguments of enhance (batch=False, one index) / enhance_batch for the files `indices` of the work list."""
+    if args.rng == "native":
+        seeds = [clip_seed(args.seed, i) for i in indices]
+        return dict(seeds=seeds) if batch else dict(seed=seeds)
+    gens = [file_generator(model, args.seed, i) for i in indices]
+    return dict(generator=gens) if batch else dict(generator=gens[0])
+
+
 def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS):
     """Load -> the reference's length rule (enhance.py:115,139; `length_limit` = --max-seconds) -> resample to the model rate.
     -> waveform [C, L] or None (skipped)."""
@@ -433,7 +447,7 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
     # not by the host's launches (profiles/r02_graph_cost.txt: eager 18.06 ms, replay 18.10 ms; capture + instantiate 2.4 ms)
     try:
         with GpuTimer(args.rtf) as timer:
-            x_hat = model.enhance(y, N=args.N, solver=args.solver, generator=file_generator(model, args.seed, job.index), use_graph=False)
+            x_hat = model.enhance(y, N=args.N, solver=args.solver, use_graph=False, **noise_kwargs(model, args, [job.index], batch=False))
     except WorkspaceTooLarge as err:
         skip_over_memory(job, res, err)
         return
@@ -472,10 +486,10 @@ def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLo
     if not loaded:
         return
     sr = model.sampling_rate
-    gens = [file_generator(model, args.seed, job.index) for job, _ in loaded]
+    noise = noise_kwargs(model, args, [job.index for job, _ in loaded], batch=True)
     try:
         with GpuTimer(args.rtf) as timer:
-            outs = model.enhance_batch([y for _, y in loaded], N=args.N, solver=args.solver, generator=gens)
+            outs = model.enhance_batch([y for _, y in loaded], N=args.N, solver=args.solver, **noise)
     except WorkspaceTooLarge:   # the batch does not fit: one call per file (each result is the same, bit for bit)
         for job, y in loaded:
             enhance_file(model, job, args, log, res, max_seconds, y=y)
@@ -501,6 +515,9 @@ def cli(argv=None) -> int:
 def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
     args = build_parser().parse_args(argv)
     os.makedirs(args.outdir, exist_ok=True)
+    if args.rng == "native" and args.seed is None:
+        args.seed = int.from_bytes(os.urandom(8), "little")
+        print(f"flowdec_amd: --rng native without --seed: using --seed {args.seed}")
     if model is None:
         print("Loading model from checkpoint...")
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision)

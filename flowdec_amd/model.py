@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import noise as fd_noise
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -557,6 +558,8 @@ class FlowModel(nn.Module):
 
     Extensions over the reference signature: ``enhance(..., noise=None, generator=None)`` to inject /
     seed the initial Gaussian noise (the reference draws it from the global device RNG, model.py:512),
+    ``seed=`` (the library's own counter-based noise, generated on the GPU from one 64-bit seed per clip: an int -- clip b
+    uses ``flowdec_amd.noise.clip_seed(seed, b)`` --, B ints or an int64 / uint64 tensor [B]; no noise tensor is filled),
     and ``use_graph`` (hipGraph replay of the whole solve).  ``with_grad=True`` is not supported.
     """
     strict_loading = False
@@ -610,6 +613,13 @@ class FlowModel(nn.Module):
         self._sync_native()
         return self.backbone(xt, y, t)
 
+    def _set_seeds(self, io, seed, B, dev):
+        """The clips' seeds in a buffer that lives as long as `io`: a captured graph is keyed on its address."""
+        if "seeds" not in io:
+            io["seeds"] = torch.empty(B, dtype=torch.int64, device=dev)
+        io["seeds"].copy_(fd_noise.seeds_to_tensor(seed, B, dev))
+        return io["seeds"]
+
     def _get_noise_tensor(self, shape, dev, noise, generator):
         if noise is not None:
             return noise.to(dev, torch.complex64).reshape(shape)
@@ -618,8 +628,9 @@ class FlowModel(nn.Module):
     @torch.no_grad()
     @_serialized
     def enhance(self, y, return_preprocess_info: bool = False, N: int = 50, solver: str = "euler", with_grad: bool = False,
-                sigma_fac: float = 1.0, return_traj: bool = False, noise=None, generator=None, use_graph: bool = True, **kwargs):
+                sigma_fac: float = 1.0, return_traj: bool = False, noise=None, generator=None, use_graph: bool = True, seed=None, **kwargs):
         """Enhances a coded/noisy waveform y (model.py:476-528).  y: [L], [1, L] or [B, 1, L]."""
+        fd_noise.exclusive(seed=seed, noise=noise, generator=generator)
         if with_grad:
             raise NotImplementedError("flowdec_amd.FlowModel.enhance: with_grad=True (backprop through the solver) is out of scope")
         adaptive = solver in L.ADAPTIVE_SOLVERS
@@ -644,7 +655,13 @@ class FlowModel(nn.Module):
         with torch.cuda.device(dev):
             io = self._io_buffers(B, Lw, Tp, F, dev)
             io["y"].copy_(y3.reshape(B, Lw))
-            io["noise"].copy_(self._get_noise_tensor((B, 1, F, Tp), dev, noise, generator))
+            seeds = None
+            if seed is None:
+                io["noise"].copy_(self._get_noise_tensor((B, 1, F, Tp), dev, noise, generator))
+            elif adaptive:   # the host-driven solvers only need the initial plane: filled by the library, then the unseeded call
+                io["noise"].copy_(fd_noise.noise_fill(fd_noise.seeds_to_tensor(seed, B, dev), F, Tp)[0])
+            else:
+                seeds = self._set_seeds(io, seed, B, dev)
             # stream capture is illegal on the legacy default stream: run the solve on a side stream that is
             # ordered after / before the caller's current stream
             cur = torch.cuda.current_stream(dev)
@@ -658,7 +675,7 @@ class FlowModel(nn.Module):
                                                  float(kwargs.get("atol", ADAPTIVE_DEFAULT_TOL)), float(kwargs.get("rtol", ADAPTIVE_DEFAULT_TOL)), L.ADAPTIVE_SOLVERS[solver])
                 else:
                     res = self._enhance_native(lib, h, cfg, io, B, Lw, F, T, Tp, N, solver, sigma_fac, return_traj,
-                                               return_preprocess_info, squeeze_dims, use_graph, dev)
+                                               return_preprocess_info, squeeze_dims, use_graph, dev, seeds)
             cur.wait_stream(side)
         if return_traj:
             res[0].record_stream(cur)
@@ -675,7 +692,7 @@ class FlowModel(nn.Module):
     @torch.no_grad()
     @_serialized
     def enhance_batch(self, clips, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, noise=None, generator=None,
-                      use_graph: bool = True):
+                      use_graph: bool = True, seeds=None):
         """`[self.enhance(c, N=N, solver=solver) for c in clips]` as ONE native call (fd_enhance_ragged) for clips of DIFFERENT
         lengths whose spectrograms pad to the same T_pad -- what the reference's driver does file by file (enhance.py:96-137).
 
@@ -683,7 +700,10 @@ class FlowModel(nn.Module):
         device of its input.  Every clip's result is BIT-IDENTICAL to `self.enhance(clip)` with the same noise: per-clip
         normalisation, reflect padding, frame count, zero padding of the frame axis, iSTFT length (model.py:129-190); the network
         itself never mixes batch items.  Initial noise: `noise` = one [1, 1, F, T_pad] complex tensor per clip, or `generator` =
-        one torch.Generator (drawn clip by clip, i.e. the stream a one-by-one loop would consume) or a list of one per clip."""
+        one torch.Generator (drawn clip by clip, i.e. the stream a one-by-one loop would consume) or a list of one per clip, or
+        `seeds` = one 64-bit seed per clip (a sequence or an int64 / uint64 tensor) for the library's own noise: clip i then equals
+        `self.enhance(clip_i, seed=[seeds[i]])`."""
+        fd_noise.exclusive(seeds=seeds, noise=noise, generator=generator)
         if solver not in L.SOLVERS:
             raise ValueError(f"enhance_batch: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
         dev = self.device
@@ -722,8 +742,10 @@ class FlowModel(nn.Module):
             io["y"].zero_()
             for b, c in enumerate(flat):
                 io["y"][b, :lens[b]].copy_(c)
-                io["noise"][b:b + 1].copy_(self._get_noise_tensor((1, 1, F, Tp), dev, None if noise is None else noise[b], gens[b]))
+                if seeds is None:
+                    io["noise"][b:b + 1].copy_(self._get_noise_tensor((1, 1, F, Tp), dev, None if noise is None else noise[b], gens[b]))
             io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
+            seeds_dev = None if seeds is None else self._set_seeds(io, list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev)
             cur = torch.cuda.current_stream(dev)
             if self._side_stream is None:
                 self._side_stream = torch.cuda.Stream(dev)
@@ -734,8 +756,12 @@ class FlowModel(nn.Module):
                 if need == 0:
                     raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
                 ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
-                L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                                              L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                if seeds_dev is not None:
+                    L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(seeds_dev), float(sigma_fac), int(N),
+                                                  L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                else:
+                    L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
+                                                  L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
                 outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
             cur.wait_stream(side)
         res = []
@@ -771,7 +797,8 @@ class FlowModel(nn.Module):
         return x_hat, info
 
     def _enhance_native(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, solver, sigma_fac, return_traj, return_preprocess_info,
-                        squeeze_dims, use_graph, dev):
+                        squeeze_dims, use_graph, dev, seeds=None):
+        """Fixed-step solve; `seeds` (device int64 [B]) selects the seeded entry points, which never read io["noise"]."""
         if return_traj:   # every solver state is needed: front end, solver and back end as separate native calls
             from . import ops
             Y, normfac, _ = ops.stft_compress(io["y"], normalize=self.normalize_mode == "noisy", **cfg)
@@ -779,9 +806,10 @@ class FlowModel(nn.Module):
             X = torch.empty_like(Y)
             need = lib.fd_model_workspace_bytes(h, B, Tp)
             ws = self.backbone.workspace(("ode", B, Tp), need, dev)
-            L.check(lib.fd_ode_solve(h, L.ptr(torch.view_as_real(Y)), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                                     L.SOLVERS[solver], L.ptr(torch.view_as_real(X)), L.ptr(torch.view_as_real(traj)), B, Tp,
-                                     L.ptr(ws), ws.numel(), 0, L.stream()))
+            solve, src = (lib.fd_ode_solve, torch.view_as_real(io["noise"])) if seeds is None else (lib.fd_ode_solve_seeded, seeds)
+            L.check(solve(h, L.ptr(torch.view_as_real(Y)), L.ptr(src), float(sigma_fac), int(N),
+                          L.SOLVERS[solver], L.ptr(torch.view_as_real(X)), L.ptr(torch.view_as_real(traj)), B, Tp,
+                          L.ptr(ws), ws.numel(), 0, L.stream()))
             x_hats = []
             for i in range(N + 1):
                 xh = ops.decompress_istft(traj[i], T, Lw, normfac, **cfg).reshape(B, 1, Lw)
@@ -793,8 +821,12 @@ class FlowModel(nn.Module):
         if need == 0:
             raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
         ws = self.backbone.workspace(("enh", B, Lw), need, dev)
-        L.check(lib.fd_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                               L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        if seeds is not None:
+            L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), None, L.ptr(seeds), float(sigma_fac), int(N),
+                                          L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        else:
+            L.check(lib.fd_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
+                                   L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
         x_hat = io["out"].reshape(B, 1, Lw).clone()
         info = None
         if return_preprocess_info:
@@ -863,8 +895,9 @@ class _WaveModel(nn.Module):
         return self.backbone.handle()
 
     @_serialized
-    def _wave_call(self, y, n_draws, noise, generator, launch, return_preprocess_info=False):
-        """launch(lib, h, y_dev [B, L], noise_dev [n_draws, B, 1, F, Tp] | None, out [B, L], ws) on a capture-safe side stream."""
+    def _wave_call(self, y, n_draws, noise, generator, launch, return_preprocess_info=False, seed=None):
+        """launch(lib, h, io, B, L, ws) on a capture-safe side stream; io = dict(y [B, L], out [B, L], noise [n_draws, B, 1, F, Tp] | None,
+        seeds int64 [B] | None).  With `seed` no noise tensor exists (io["noise"] is None): the kernels generate it."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
@@ -880,13 +913,18 @@ class _WaveModel(nn.Module):
         F = cfg["n_fft"] // 2 + 1
         Tp = lib.fd_padded_frames(lib.fd_num_frames(Lw, cfg["hop"]))
         with torch.cuda.device(dev):
-            key = (B, Lw, n_draws, str(dev))
+            if seed is not None:
+                n_draws = 0
+            key = (B, Lw, n_draws, seed is not None, str(dev))
             io = self._io.get(key)
             if io is None:
                 io = dict(y=torch.empty(B, Lw, dtype=torch.float32, device=dev), out=torch.empty(B, Lw, dtype=torch.float32, device=dev),
-                          noise=torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev) if n_draws else None)
+                          noise=torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev) if n_draws else None,
+                          seeds=torch.empty(B, dtype=torch.int64, device=dev) if seed is not None else None)
                 self._io = {key: io}
             io["y"].copy_(y3.reshape(B, Lw))
+            if seed is not None:
+                io["seeds"].copy_(fd_noise.seeds_to_tensor(seed, B, dev))
             if n_draws:
                 if noise is not None:
                     io["noise"].copy_(noise.to(dev, torch.complex64).reshape(io["noise"].shape))
@@ -915,7 +953,8 @@ class _WaveModel(nn.Module):
 
 class ScoreModel(_WaveModel):
     """Drop-in for flowdec.model.ScoreModel on the inference path (model.py:581-690): `forward` = score estimate,
-    `enhance` = predictor-corrector sampling (sampler_type='pc').  Extensions: noise= / generator= / use_graph=."""
+    `enhance` = predictor-corrector sampling (sampler_type='pc').  Extensions: noise= / generator= / seed= / use_graph=; with `seed=`
+    (see FlowModel) the sampler's Gaussian planes are generated inside its update kernels and no noise tensor is allocated."""
 
     def __init__(self, sde: OUVESDE, t_eps: float, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -938,9 +977,10 @@ class ScoreModel(_WaveModel):
 
     @torch.no_grad()
     def enhance(self, y, sampler_type="pc", predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5,
-                return_preprocess_info=False, denoise=True, noise=None, generator=None, use_graph: bool = True, **kwargs):
+                return_preprocess_info=False, denoise=True, noise=None, generator=None, use_graph: bool = True, seed=None, **kwargs):
+        fd_noise.exclusive(seed=seed, noise=noise, generator=generator)
         if sampler_type == "ode":
-            return self._enhance_ode(y, N=N, denoise=denoise, noise=noise, generator=generator, return_preprocess_info=return_preprocess_info, **kwargs)
+            return self._enhance_ode(y, N=N, denoise=denoise, noise=noise, generator=generator, seed=seed, return_preprocess_info=return_preprocess_info, **kwargs)
         if sampler_type != "pc":
             raise ValueError(f"{sampler_type} is not a valid sampler type!")
         if predictor not in L.PREDICTORS:
@@ -954,13 +994,17 @@ class ScoreModel(_WaveModel):
 
         def launch(lib, h, io, B, Lw, ws):
             assert lib.fd_score_num_draws(C.byref(cfg)) == n_draws
-            L.check(lib.fd_score_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(io["noise"])), C.byref(cfg), L.ptr(io["out"]), B, Lw,
-                                         L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-        return self._wave_call(y, n_draws, noise, generator, launch, return_preprocess_info)
+            if seed is not None:
+                L.check(lib.fd_score_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["seeds"]), C.byref(cfg), L.ptr(io["out"]), B, Lw,
+                                                    L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+            else:
+                L.check(lib.fd_score_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(io["noise"])), C.byref(cfg), L.ptr(io["out"]), B, Lw,
+                                             L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        return self._wave_call(y, n_draws, noise, generator, launch, return_preprocess_info, seed=seed)
 
 
     @_serialized
-    def _enhance_ode(self, y, N=None, denoise=True, noise=None, generator=None, rtol=1e-5, atol=1e-5, method="RK45", eps=None,
+    def _enhance_ode(self, y, N=None, denoise=True, noise=None, generator=None, seed=None, rtol=1e-5, atol=1e-5, method="RK45", eps=None,
                      return_nfe: bool = False, return_preprocess_info: bool = False, **ignored):
         """sampler_type='ode' (sampling/__init__.py:75-146): the probability-flow ODE integrated by scipy.integrate.solve_ivp
         on the host, exactly like the reference; every drift evaluation is one fd_score_eval (backbone + fused update) on
@@ -986,7 +1030,9 @@ class ScoreModel(_WaveModel):
         with torch.cuda.device(dev):
             Y, normfac, T = ops.stft_compress(y3.reshape(B, Lw).to(dev, torch.float32), normalize=self.normalize_mode == "noisy", **cfg)
             Tp = Y.shape[-1]
-            if noise is None:
+            if seed is not None:   # the prior draw (index 0) of the seeded noise; the ODE itself is noise-free
+                noise = fd_noise.noise_fill(fd_noise.seeds_to_tensor(seed, B, dev), Y.shape[-2], Tp)[0]
+            elif noise is None:
                 noise = torch.randn(Y.shape, dtype=torch.complex64, device=dev, generator=generator)
             std1 = float(self.sde._std(torch.ones(1))[0])
             # prior sample x_T = Y + std(1) * z (sdes.py:197-202), formed on the host where scipy keeps the state anyway

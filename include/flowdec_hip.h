@@ -395,6 +395,32 @@ int fd_enhance(fd_model* m, const float* y, const float* noise, float sigma_fac,
  * (its contents may change between replays). */
 int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths, const float* noise, float sigma_fac, int N, int solver,
                       float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* ---- Seeded noise: the library draws the sampler's Gaussian noise itself, from one 64-bit seed per clip ----------------------
+ * The reference draws from the global device RNG (model.py:512,530-536; correctors.py:61); the entry points above take the noise
+ * as a buffer.  The *_seeded forms take `seeds` (DEVICE uint64 [B]) instead and generate every value in registers, in the kernel
+ * that consumes it -- no noise buffer exists.  The value at (clip seed s, draw index d >= 0, frequency row f, frame t) is a pure
+ * function (NORMATIVE):
+ *   - Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
+ *     (s & 0xffffffff, s >> 32) and counter (t >> 1, f, d, 0) gives r0..r3.  Counter word 3 is reserved and stays 0.
+ *   - an even t uses (ra, rb) = (r0, r1), an odd t (r2, r3).
+ *   - u1 = ((ra >> 9) + 0.5) * 2^-23 in (0, 1), u2 = (rb >> 8) * 2^-24 in [0, 1): both exact in float32.
+ *   - z = sqrt(-ln u1) * (cos 2 pi u2 + i sin 2 pi u2) in float32 (logf, sqrtf, sincospif(2 u2)): complex normal with
+ *     E|z|^2 = 1 (variance 1/2 per component, like torch.randn(complex64)); |z| <= sqrt(24 ln 2) ~ 4.08.
+ *   - draw index: 0 for the flow models' initial state; for the score sampler the k-th randn_like of the reference's order,
+ *     i.e. the index of the plane fd_score_enhance reads (a plane whose coefficient is zero still takes its index).
+ * So a clip's noise does not depend on B, its position in the batch, T_pad, the rank, or how many draws precede it, and a
+ * seeded call equals, bit for bit, the buffer call on fd_noise_fill's output.  A captured graph is keyed on the POINTER `seeds`
+ * (like `lengths`): its contents may change between replays.  Workspaces: the unseeded calls' fd_*_workspace_bytes. */
+#define FD_NOISE_GAUSSIAN 0 /* out = complex64 [n_draws][B][F][T_pad]: the layout fd_score_enhance consumes; n_draws = 1: fd_enhance's */
+#define FD_NOISE_BITS 1     /* out = uint32 [n_draws][B][F][T_pad][2]: the raw words (ra, rb) of every element (for tests) */
+/* The planes draw0 .. draw0 + n_draws - 1 written to `out` (16-byte aligned device memory). */
+int fd_noise_fill(void* out, const unsigned long long* seeds, int B, int F, int T_pad, int draw0, int n_draws, int mode, void* stream);
+/* fd_ode_solve with x0 = Y + sigma_fac * (sigma_y * z(seeds[b], 0, f, t)). */
+int fd_ode_solve_seeded(fd_model* m, const float* Y, const unsigned long long* seeds, float sigma_fac, int N, int solver, float* X_out,
+                        float* traj, int B, int T_pad, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* fd_enhance (lengths == NULL: every clip is L samples long) or fd_enhance_ragged (lengths = DEVICE int32 [B]) on seeded noise. */
+int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, float sigma_fac, int N, int solver,
+                      float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
 /* normalize_mode of the model's front end: 1 = 'noisy' (default), 0 = 'none' (model.py:52, util/other.py:70). */
 int fd_model_set_normalize(fd_model* m, int normalize);
 
@@ -421,6 +447,9 @@ int fd_score_num_draws(const fd_score_config* cfg);
  * the order of the reference's randn_like calls.  Workspace: fd_enhance_workspace_bytes(m, B, L). */
 int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_score_config* cfg, float* x_hat, int B, int L,
                      void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* The same sampler on seeded noise ("Seeded noise" above): no [fd_score_num_draws][B][n_freq][T_pad] buffer is needed. */
+int fd_score_enhance_seeded(fd_model* m, const float* y, const unsigned long long* seeds, const fd_score_config* cfg, float* x_hat, int B,
+                            int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
 /* One score-network evaluation in the form the black-box ODE sampler needs (sampling/__init__.py:75-146, which drives
  * scipy.integrate.solve_ivp on the host): x, Y, out = complex64 [B][1][n_freq][T_pad]; workspace fd_model_workspace_bytes.
  *   FD_SCORE_DRIFT_PF : out = theta (Y - x) - 0.5 g(t)^2 score(x, Y, t)     (probability-flow drift, sdes.py:93-109)
