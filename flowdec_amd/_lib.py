@@ -27,6 +27,7 @@ FD_BF16X3_OPERANDS = 0x20000  # with FD_F32: operands as hi + lo bf16 pairs, thr
 FD_TILE = {0: 0, 32: 0x1000, 64: 0x2000, 128: 0x3000, "64c": 0x4000, "32c": 0x5000, "duo": 0x6000, "persist": 0x7000}  # fd_conv2d: output channels per workgroup (0 = default)
 # fd_conv_kernel_counts slots (enum FD_CONV_KERNEL_* in include/flowdec_hip.h, in order)
 CONV_KERNELS = ("DIRECT", "DIRECT_MIXED", "DIRECT_SPLIT", "WINO", "WINO4", "WINO4F", "WINO44F", "HEAD", "HEADF")
+FIR_FAMILIES = ("UP", "DOWN", "DOWN_MARCH")   # FD_FIR_* of fd_fir_variant, in order
 SOLVERS = {"euler": 0, "midpoint": 1, "heun2": 2, "heun2_eulerlast": 3}
 ADAPTIVE_SOLVERS = {"dopri5": 0, "tsit5": 1}   # FD_ADAPTIVE_*
 
@@ -76,6 +77,7 @@ SIGNATURES = {
     "fd_upfirdn2d_out_size": (c_int, [c_int] * 6),
     "fd_fused_bias_act": (c_int, [_P, _P, _P, c_ll, c_int, c_int, c_int, c_float, c_float, _P]),
     "fd_fir_resample": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_fir_variant": (c_int, [c_int] * 9),
     "fd_conv_in": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_channel_sums_tiles": (c_int, [c_int, c_int]),
     "fd_channel_sums": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -992,79 +992,128 @@ extern "C" int fd_gn_finalize(const float* part0, int tiles0, int stride0, int C
   return FD_OK;
 }
 
-template <typename T, int VEC>
-static int launch_fir(const void* x, const float* affine, void* out_raw, void* out_act, int B, int H, int W, int C,
-                      int direction, hipStream_t st) {
-  // Rows / output block per thread of the fused (activated) variants: big blocks re-use activated inputs (fewer SiLU evaluations per
-  // output), small ones make more, shorter threads -- a small image is latency-bound (one clip at 384 x 64: 13-25 us with the big
-  // blocks).  Every output is the same fma sequence in every variant, so the choice may depend on the batch size.
-  auto blocks = [&](int rows, int cols, int n, int bx = 1) { return dim3(fd_cdiv((long long)B * fd_cdiv(rows, n) * fd_cdiv(cols, bx) * (C / VEC), 256)); };
-  constexpr unsigned ENOUGH = 512;   // workgroups that keep 256 CUs busy
+// ---- FIR x2 resampling: one rule that picks the kernel (fir_select), one switch that launches what it picked (launch_fir) ----
+// family: FD_FIR_UP = fir_up_kernel (rows = input rows per thread N, cols = BX), FD_FIR_DOWN = fir_down_kernel (rows x cols = the BY x BX
+// output block), FD_FIR_DOWN_MARCH = fir_down_march_kernel (rows = NR output rows of a strip, cols = 4); vec = channels per thread;
+// act = the ACT instantiation (an affine is present); fast = the unconditional-store form; grid = workgroups of 256 threads.
+struct fir_variant { int family, rows, cols, vec, act, fast; long long grid; };
+
+// The choice for one fd_fir_resample call, from the shape and from WHICH of affine / out_raw / out_act are present (FD_EINVAL where the
+// call is refused).  Rows / output block per thread of the fused (activated) variants: big blocks re-use activated inputs (fewer SiLU
+// evaluations per output), small ones make more, shorter threads -- a small image is latency-bound (one clip at 384 x 64: 13-25 us with
+// the big blocks).  Every output is the same fma sequence in every variant, so the choice may depend on the batch size.
+static int fir_select(int B, int H, int W, int C, int direction, int dtype, bool has_affine, bool has_raw, bool has_act, fir_variant* out) {
+  FD_REQUIRE(has_raw || has_act, "fd_fir_resample: null pointer");
+  FD_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "fd_fir_resample: bad shape (B=%d H=%d W=%d C=%d)", B, H, W, C);
+  FD_REQUIRE(direction == 1 || direction == -1, "fd_fir_resample: direction must be +1 (up) or -1 (down)");
+  FD_REQUIRE(C % 4 == 0, "fd_fir_resample: C must be a multiple of 4");
+  FD_REQUIRE(direction > 0 || (H % 2 == 0 && W % 2 == 0), "fd_fir_resample: down needs even H, W");
+  FD_REQUIRE(!has_act || has_affine, "fd_fir_resample: out_act needs affine");
+  FD_REQUIRE(dtype == FD_BF16 || dtype == FD_F32, "fd_fir_resample: bad dtype %d", dtype);
+  const bool half = dtype == FD_BF16;
+  // bf16: 8-channel (16-byte) vectors where C allows, except the fused down direction (strips / 4x2 blocks of 4-channel vectors: round 2,
+  // profiles/r02_fir_down_variants.txt -- the 4x2 block fits the register budget only with 4 channels: 430 us vs 512 us for 8-channel
+  // vectors x 4x1 at 8 x 768 x 256 x 256)
+  const int vec = half && !(direction < 0 && has_affine) && C % 8 == 0 ? 8 : 4;
+  const int R = direction > 0 ? H : H / 2, Q = direction > 0 ? W : W / 2;   // the rows / columns the threads tile: input (up), output (down)
+  auto grid = [&](int rows, int cols) { return ((long long)B * fd_cdiv(R, rows) * fd_cdiv(Q, cols) * (C / vec) + 255) / 256; };
+  auto pick = [&](int family, int rows, int cols, bool fast) {
+    *out = fir_variant{family, rows, cols, vec, has_affine ? 1 : 0, fast ? 1 : 0, grid(rows, cols)};
+    return FD_OK;
+  };
+  constexpr long long ENOUGH = 512;   // workgroups that keep 256 CUs busy
   if (direction > 0) {
-#define FD_FIR_UP(ACT_, N_, BX_) hipLaunchKernelGGL((fir_up_kernel<T, VEC, ACT_, N_, BX_>), blocks(H, W, N_, BX_), dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C)
-    if (!affine) FD_FIR_UP(false, 1, 1);
+    if (!has_affine) return pick(FD_FIR_UP, 1, 1, false);
     // measured at 8 x 384 x 128 x 256 -> 768 x 256 (1.8 GB moved): 8 rows x 1 column, 8-channel vectors 414 us; 16 rows 446; 4 rows 432;
     // 4-channel vectors 409 / 458 / 463; two columns per thread (2.5 instead of 3.75 activations per input) 403 (4 ch x 8 rows): the up
     // direction does not react to the activation count or the vector width (4.4 TB/s, 4.0 of them stores) -- BX stays 1.  What it reacts
     // to is the store accounting (FAST): 357-361 us; FAST variants of the other shapes: 4 rows 404, 16 rows 392, 4-channel vectors 380-448
-    else if (blocks(H, W, 8).x >= ENOUGH && H % 8 == 0 && out_raw && out_act)
-      hipLaunchKernelGGL((fir_up_kernel<T, VEC, true, 8, 1, true>), blocks(H, W, 8, 1), dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C);
-    else if (blocks(H, W, 8).x >= ENOUGH) FD_FIR_UP(true, 8, 1);
-    else if (blocks(H, W, 2).x >= ENOUGH) FD_FIR_UP(true, 2, 1);
-    else FD_FIR_UP(true, 1, 1);
-#undef FD_FIR_UP
-  } else {
-    auto dgrid = [&](int by, int bx) { return dim3(fd_cdiv((long long)B * fd_cdiv(H / 2, by) * fd_cdiv(W / 2, bx) * (C / VEC), 256)); };
-#define FD_FIR_DOWN(ACT_, BY_, BX_) hipLaunchKernelGGL((fir_down_kernel<T, VEC, ACT_, BY_, BX_>), dgrid(BY_, BX_), dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C)
-    // measured on MI355X at 8 x 768 x 256 x 256 (bf16, dual output): 1x1 756 us, 2x2 675, 2x1 614, 8x1 565, 4x2 543, 4x1 467
-    // round 2 (profiles/r02_fir_down_variants.txt): with 4-channel vectors the 4x2 block (6.25 instead of 10 SiLU evaluations per
-    // output) fits the register budget: 430 us vs 512 us for 8-channel vectors x 4x1 at the same shape
-    if (!affine) FD_FIR_DOWN(false, 1, 1);
-    else if (VEC == 4) {
-      // round 3: marching strips of NR output rows x 4 columns (1.33 instead of 1.875 activations per input, packed FIR arithmetic)
-      auto mgrid = [&](int nr) { return dim3(fd_cdiv((long long)B * fd_cdiv(H / 2, nr) * fd_cdiv(W / 2, 4) * (C / VEC), 256)); };
-#define FD_FIR_MARCH(NR_)                                                                                                                             \
-  do {                                                                                                                                             \
-    if (out_raw && (H / 2) % NR_ == 0 && (W / 2) % 4 == 0)                                                                                         \
-      hipLaunchKernelGGL((fir_down_march_kernel<T, 4, NR_, true>), mgrid(NR_), dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C); \
-    else                                                                                                                                           \
-      hipLaunchKernelGGL((fir_down_march_kernel<T, 4, NR_, false>), mgrid(NR_), dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C); \
-  } while (0)
-      // measured at B = 8 x 256 channels (scripts/fir_bench.py): 768 x 256: 4x2 blocks 444 us, strips of 4 / 8 / 16 rows 315 / 302 / 292 us;
-      // 384 x 128: 130 us, 102 / 97 / 120 us (16-row strips leave 1.5 workgroups per CU) -> the tallest strip with >= 3 workgroups per CU
-      constexpr unsigned FILL = 768;
-      if (out_act && mgrid(16).x >= FILL) FD_FIR_MARCH(16);
-      else if (out_act && mgrid(8).x >= FILL) FD_FIR_MARCH(8);
-      else if (out_act && mgrid(4).x >= FILL) FD_FIR_MARCH(4);
-      else if (sizeof(T) == 2 && dgrid(4, 2).x >= ENOUGH) FD_FIR_DOWN(true, 4, 2);
-      else if (sizeof(T) == 2 && dgrid(2, 1).x >= ENOUGH) FD_FIR_DOWN(true, 2, 1);
-      else if (sizeof(T) == 4 && dgrid(4, 1).x >= ENOUGH) FD_FIR_DOWN(true, 4, 1);
-      else FD_FIR_DOWN(true, 1, 1);
-    } else if (dgrid(4, 1).x >= ENOUGH) FD_FIR_DOWN(true, 4, 1);
-    else FD_FIR_DOWN(true, 1, 1);
-#undef FD_FIR_DOWN
-#undef FD_FIR_MARCH
+    if (grid(8, 1) >= ENOUGH) return pick(FD_FIR_UP, 8, 1, H % 8 == 0 && has_raw && has_act);
+    if (grid(2, 1) >= ENOUGH) return pick(FD_FIR_UP, 2, 1, false);
+    return pick(FD_FIR_UP, 1, 1, false);
   }
+  // measured on MI355X at 8 x 768 x 256 x 256 (bf16, dual output): 1x1 756 us, 2x2 675, 2x1 614, 8x1 565, 4x2 543, 4x1 467
+  if (!has_affine) return pick(FD_FIR_DOWN, 1, 1, false);
+  // round 3: marching strips of NR output rows x 4 columns (1.33 instead of 1.875 activations per input, packed FIR arithmetic)
+  // measured at B = 8 x 256 channels (scripts/fir_bench.py): 768 x 256: 4x2 blocks 444 us, strips of 4 / 8 / 16 rows 315 / 302 / 292 us;
+  // 384 x 128: 130 us, 102 / 97 / 120 us (16-row strips leave 1.5 workgroups per CU) -> the tallest strip with >= 3 workgroups per CU
+  constexpr long long FILL = 768;
+  if (has_act)
+    for (int nr = 16; nr >= 4; nr >>= 1)
+      if (grid(nr, 4) >= FILL) return pick(FD_FIR_DOWN_MARCH, nr, 4, has_raw && R % nr == 0 && Q % 4 == 0);
+  if (half && grid(4, 2) >= ENOUGH) return pick(FD_FIR_DOWN, 4, 2, false);
+  if (half && grid(2, 1) >= ENOUGH) return pick(FD_FIR_DOWN, 2, 1, false);
+  if (!half && grid(4, 1) >= ENOUGH) return pick(FD_FIR_DOWN, 4, 1, false);
+  return pick(FD_FIR_DOWN, 1, 1, false);
+}
+
+// Launches exactly the variant `v` that fir_select returned (T / VEC = its storage type and vector width).  The kernels fir_select cannot
+// pick for this <T, VEC> are not instantiated: a variant without a case below is an internal error, never another kernel.
+template <typename T, int VEC>
+static int launch_fir(const fir_variant& v, const void* x, const float* affine, void* out_raw, void* out_act, int B, int H, int W, int C,
+                      hipStream_t st) {
+  [[maybe_unused]] constexpr bool HALF = sizeof(T) == 2;
+  const dim3 grid((unsigned)v.grid);
+  const int key = ((v.family * 100 + v.rows) * 10 + v.cols) * 100 + v.act * 10 + v.fast;
+#define FD_FIR_ARGS grid, dim3(256), 0, st, (const T*)x, affine, (T*)out_raw, (T*)out_act, B, H, W, C
+#define FD_FIR_KEY(FAM_, ROWS_, COLS_, ACT_, FAST_) ((((FAM_) * 100 + (ROWS_)) * 10 + (COLS_)) * 100 + (ACT_) * 10 + (FAST_))
+  bool done = true;
+  switch (key) {
+    case FD_FIR_KEY(FD_FIR_UP, 1, 1, 0, 0): hipLaunchKernelGGL((fir_up_kernel<T, VEC, false, 1, 1>), FD_FIR_ARGS); break;
+    case FD_FIR_KEY(FD_FIR_UP, 8, 1, 1, 1): hipLaunchKernelGGL((fir_up_kernel<T, VEC, true, 8, 1, true>), FD_FIR_ARGS); break;
+    case FD_FIR_KEY(FD_FIR_UP, 8, 1, 1, 0): hipLaunchKernelGGL((fir_up_kernel<T, VEC, true, 8, 1>), FD_FIR_ARGS); break;
+    case FD_FIR_KEY(FD_FIR_UP, 2, 1, 1, 0): hipLaunchKernelGGL((fir_up_kernel<T, VEC, true, 2, 1>), FD_FIR_ARGS); break;
+    case FD_FIR_KEY(FD_FIR_UP, 1, 1, 1, 0): hipLaunchKernelGGL((fir_up_kernel<T, VEC, true, 1, 1>), FD_FIR_ARGS); break;
+    case FD_FIR_KEY(FD_FIR_DOWN, 1, 1, 0, 0): hipLaunchKernelGGL((fir_down_kernel<T, VEC, false, 1, 1>), FD_FIR_ARGS); break;
+    default: done = false;
+  }
+  if constexpr (VEC == 4) {   // the fused down direction always runs on 4-channel vectors (fir_select)
+    if (!done) {
+      done = true;
+      switch (key) {
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 16, 4, 1, 1): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 16, true>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 16, 4, 1, 0): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 16, false>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 8, 4, 1, 1): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 8, true>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 8, 4, 1, 0): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 8, false>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 4, 4, 1, 1): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 4, true>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN_MARCH, 4, 4, 1, 0): hipLaunchKernelGGL((fir_down_march_kernel<T, 4, 4, false>), FD_FIR_ARGS); break;
+        case FD_FIR_KEY(FD_FIR_DOWN, 1, 1, 1, 0): hipLaunchKernelGGL((fir_down_kernel<T, VEC, true, 1, 1>), FD_FIR_ARGS); break;
+        default: done = false;
+      }
+    }
+    if constexpr (HALF) {
+      if (!done && key == FD_FIR_KEY(FD_FIR_DOWN, 4, 2, 1, 0)) { hipLaunchKernelGGL((fir_down_kernel<T, VEC, true, 4, 2>), FD_FIR_ARGS); done = true; }
+      if (!done && key == FD_FIR_KEY(FD_FIR_DOWN, 2, 1, 1, 0)) { hipLaunchKernelGGL((fir_down_kernel<T, VEC, true, 2, 1>), FD_FIR_ARGS); done = true; }
+    } else {
+      if (!done && key == FD_FIR_KEY(FD_FIR_DOWN, 4, 1, 1, 0)) { hipLaunchKernelGGL((fir_down_kernel<T, VEC, true, 4, 1>), FD_FIR_ARGS); done = true; }
+    }
+  }
+#undef FD_FIR_KEY
+#undef FD_FIR_ARGS
+  if (!done)
+    return fd_set_error(FD_ESTATE, "internal: fd_fir_resample has no kernel for variant (family %d, %d x %d, vec %d, act %d, fast %d)", v.family,
+                        v.rows, v.cols, v.vec, v.act, v.fast);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }
 
+extern "C" int fd_fir_variant(int B, int H, int W, int C, int direction, int dtype, int has_affine, int want_raw, int want_act) {
+  fir_variant v;
+  const int rc = fir_select(B, H, W, C, direction, dtype, has_affine != 0, want_raw != 0, want_act != 0, &v);
+  if (rc != FD_OK) return rc;
+  return ((((v.family * 100 + v.rows) * 10 + v.cols) * 10 + v.vec) * 10 + v.act) * 10 + v.fast;
+}
+
 extern "C" int fd_fir_resample(const void* x, const float* affine, void* out_raw, void* out_act, int B, int H, int W,
                                int C, int direction, int dtype, void* stream) {
-  FD_REQUIRE(x && (out_raw || out_act), "fd_fir_resample: null pointer");
-  FD_REQUIRE(direction == 1 || direction == -1, "fd_fir_resample: direction must be +1 (up) or -1 (down)");
-  FD_REQUIRE(C % 4 == 0, "fd_fir_resample: C must be a multiple of 4");
-  FD_REQUIRE(direction > 0 || (H % 2 == 0 && W % 2 == 0), "fd_fir_resample: down needs even H, W");
-  FD_REQUIRE(out_act == nullptr || affine != nullptr, "fd_fir_resample: out_act needs affine");
+  FD_REQUIRE(x, "fd_fir_resample: null pointer");
+  fir_variant v;
+  const int rc = fir_select(B, H, W, C, direction, dtype, affine != nullptr, out_raw != nullptr, out_act != nullptr, &v);
+  if (rc != FD_OK) return rc;
   hipStream_t st = fd_stream(stream);
-  if (dtype == FD_BF16) {
-    if (direction < 0 && affine) return launch_fir<bf16, 4>(x, affine, out_raw, out_act, B, H, W, C, direction, st);   // fused down: strips / 4x2 blocks
-    if (C % 8 == 0) return launch_fir<bf16, 8>(x, affine, out_raw, out_act, B, H, W, C, direction, st);
-    return launch_fir<bf16, 4>(x, affine, out_raw, out_act, B, H, W, C, direction, st);
-  } else if (dtype == FD_F32) {
-    return launch_fir<float, 4>(x, affine, out_raw, out_act, B, H, W, C, direction, st);
-  }
-  return fd_set_error(FD_EINVAL, "fd_fir_resample: bad dtype %d", dtype);
+  if (dtype == FD_F32) return launch_fir<float, 4>(v, x, affine, out_raw, out_act, B, H, W, C, st);
+  if (v.vec == 8) return launch_fir<bf16, 8>(v, x, affine, out_raw, out_act, B, H, W, C, st);
+  return launch_fir<bf16, 4>(v, x, affine, out_raw, out_act, B, H, W, C, st);
 }
 
 extern "C" int fd_upfirdn2d_out_size(int in_size, int up, int down, int pad0, int pad1, int ksize) {

@@ -52,15 +52,29 @@ def gn_affine(x0, x1, gamma, beta, eps=1e-6):
     return gn_finalize(s0, C0, s1, C1, gamma, beta, min((C0 + C1) // 4, 32), x0.shape[1] * x0.shape[2], eps)
 
 
-def fir_resample(x, direction, affine=None, want_raw=True):
-    """direction +1 / -1; returns (raw, act) -- act is None without `affine`."""
+def fir_resample(x, direction, affine=None, want_raw=True, want_act=True):
+    """direction +1 / -1; returns (raw, act) -- act is None without `affine` or with want_act=False (the affine is still passed: the
+    ABI allows either output to be NULL), raw is None with want_raw=False."""
     B, H, W, Cc = _nhwc(x)
     oh, ow = (2 * H, 2 * W) if direction > 0 else (H // 2, W // 2)
     raw = torch.empty(B, oh, ow, Cc, dtype=x.dtype, device=x.device) if want_raw else None
-    act = torch.empty(B, oh, ow, Cc, dtype=x.dtype, device=x.device) if affine is not None else None
+    act = torch.empty(B, oh, ow, Cc, dtype=x.dtype, device=x.device) if affine is not None and want_act else None
     L.check(L.load().fd_fir_resample(L.ptr(x), L.ptr(affine), L.ptr(raw), L.ptr(act), B, H, W, Cc, direction,
                                      L.dtype_id(x.dtype), L.stream()))
     return raw, act
+
+
+def fir_variant(B, H, W, C, direction, dtype, affine=False, want_raw=True, want_act=True):
+    """The kernel fd_fir_resample launches for this call (fd_fir_variant, host only): (family, rows, cols, vec, act, fast) with family in
+    _lib.FIR_FAMILIES -- see the header for the fields.  want_act counts only with an affine, as in fir_resample."""
+    code = L.load().fd_fir_variant(B, H, W, C, direction, L.dtype_id(dtype), int(bool(affine)), int(bool(want_raw)), int(bool(affine and want_act)))
+    L.check(min(code, 0))
+    code, fast = divmod(code, 10)
+    code, act = divmod(code, 10)
+    code, vec = divmod(code, 10)
+    code, cols = divmod(code, 10)
+    family, rows = divmod(code, 100)
+    return (L.FIR_FAMILIES[family], rows, cols, vec, act, fast)
 
 
 def conv_in(in8, w, bias):

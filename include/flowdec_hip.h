@@ -155,6 +155,21 @@ int fd_fused_bias_act(const float* x, const float* bias, float* out, long long n
  * direction: +1 = up x2, -1 = down x2.  Either output may be NULL. */
 int fd_fir_resample(const void* x, const float* affine, void* out_raw, void* out_act, int B, int H, int W, int C,
                     int direction, int dtype, void* stream);
+/* Which kernel fd_fir_resample launches for a call (host only, no GPU needed; for tests): the same rule the launch itself goes through.
+ * has_affine / want_raw / want_act = whether `affine` / `out_raw` / `out_act` would be non-NULL.  Returns FD_EINVAL where fd_fir_resample
+ * refuses the call, else the decimal code  F RR C V A S:
+ *   F  = family: FD_FIR_UP (fir_up_kernel: one thread = RR input rows x C input columns), FD_FIR_DOWN (fir_down_kernel: one thread = a
+ *        block of RR x C output pixels), FD_FIR_DOWN_MARCH (fir_down_march_kernel: one thread marches down a strip of RR output rows x C
+ *        columns);
+ *   RR, C = rows (01 .. 16) and columns (1 .. 4) per thread;  V = channels per thread (4 or 8);
+ *   A  = 1 if the kernel evaluates silu(a*x + d) (an affine is present);  S = 1 for the form with unconditional stores (every strip and
+ *        column block whole, both outputs present).
+ * e.g. 2164411 = marching strips of 16 rows x 4 columns, 4 channels, activated, unconditional stores; 11800 = plain 1 x 1 down-sampling
+ * on 8-channel vectors. */
+#define FD_FIR_UP 0
+#define FD_FIR_DOWN 1
+#define FD_FIR_DOWN_MARCH 2
+int fd_fir_variant(int B, int H, int W, int C, int direction, int dtype, int has_affine, int want_raw, int want_act);
 
 /* The input convolution of NCSN++ (all_modules.3 = conv3x3(4, nf), ncsnpp.py:291 via layers.py:128-134) on the packed NHWC input
  * [B][H][W][8] (channels 0..3 = x.re, x.im, y.re, y.im; 4..7 ignored), zero padding, as f32 vector FMAs (taps ascending, input channels
