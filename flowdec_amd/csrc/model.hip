@@ -1322,10 +1322,11 @@ extern "C" int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths
   return enhance_impl(m, "fd_enhance_seeded", y, lengths, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
-// Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT
+// Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT.  lens (device int32 [B]) = a ragged batch
+// (see fd_enhance_ragged), nullptr = every clip is L samples long.
 template <typename Body>
-static int enhance_common(fd_model* m, const char* who, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, GraphKey key,
-                          int use_graph, void* stream, Body&& body) {
+static int enhance_common(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                          GraphKey key, int use_graph, void* stream, Body&& body) {
   FD_TRY(check_ready(m));
   FD_REQUIRE(y && x_hat && ws, "%s: null pointer", who);
   FD_REQUIRE(B > 0 && L > m->cfg.n_fft / 2, "%s: clips must be longer than %d samples", who, m->cfg.n_fft / 2);
@@ -1340,11 +1341,11 @@ static int enhance_common(fd_model* m, const char* who, const float* y, float* x
   float* normfac = (float*)((char*)ws + 2 * state);
   char* rest = (char*)ws + 2 * state + fd_align(sizeof(float) * B);
   const size_t rest_bytes = ws_bytes - (2 * state + fd_align(sizeof(float) * B));
-  key.y = y; key.xhat = x_hat; key.ws = ws; key.B = B; key.L = L; key.normalize = m->normalize;
+  key.y = y; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.normalize = m->normalize;
   return run_maybe_graph(m, key, use_graph != 0, st, [&]() {
-    FD_TRY(fd_stft_forward(m->stft, y, nullptr, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st));
+    FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st));
     FD_TRY(body(Y, X, Tp, (void*)rest, rest_bytes, st));
-    FD_TRY(fd_stft_inverse(m->stft, X, nullptr, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac, x_hat, L, rest, rest_bytes, st));
+    FD_TRY(fd_stft_inverse(m->stft, X, lens, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac, x_hat, L, rest, rest_bytes, st));
     return FD_OK;
   });
 }
@@ -1354,8 +1355,8 @@ extern "C" int fd_score_num_draws(const fd_score_config* c) {
   return score_draws(*c);
 }
 
-static int score_enhance_impl(fd_model* m, const char* who, const float* y, const fd_noise_src& noise, const fd_score_config* c, float* x_hat, int B,
-                              int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+static int score_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, const fd_score_config* c,
+                              float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_REQUIRE(c && (noise.ptr || noise.seeds), "%s: null pointer", who);
   FD_REQUIRE(c->N >= 1, "%s: N must be >= 1", who);
   FD_REQUIRE(c->predictor >= FD_PREDICTOR_REVERSE_DIFFUSION && c->predictor <= FD_PREDICTOR_NONE, "%s: unknown predictor id %d", who, c->predictor);
@@ -1365,7 +1366,7 @@ static int score_enhance_impl(fd_model* m, const char* who, const float* y, cons
   FD_REQUIRE(c->t_eps > 0.f && c->t_eps < 1.f, "%s: t_eps must be in (0, 1)", who);
   GraphKey key; key.noise = noise.ptr; key.seeds = noise.seeds; key.kind = 3; key.score = *c;
   const fd_score_config cfg = *c;
-  return enhance_common(m, who, y, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
+  return enhance_common(m, who, y, lens, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
                         [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
                           return score_enqueue(m, Y, noise, cfg, X, B, Tp, rest, rest_bytes, st);
                         });
@@ -1374,7 +1375,7 @@ static int score_enhance_impl(fd_model* m, const char* who, const float* y, cons
 extern "C" int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_score_config* c, float* x_hat, int B, int L, void* ws,
                                 size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_score_enhance");
-  return score_enhance_impl(m, "fd_score_enhance", y, fd_noise_src{noise}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return score_enhance_impl(m, "fd_score_enhance", y, nullptr, fd_noise_src{noise}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // fd_score_enhance with every Gaussian plane generated from the clips' seeds inside the kernel that consumes it: draw index k = the k-th plane
@@ -1382,7 +1383,23 @@ extern "C" int fd_score_enhance(fd_model* m, const float* y, const float* noise,
 extern "C" int fd_score_enhance_seeded(fd_model* m, const float* y, const unsigned long long* seeds, const fd_score_config* c, float* x_hat, int B,
                                        int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_score_enhance_seeded");
-  return score_enhance_impl(m, "fd_score_enhance_seeded", y, fd_noise_src{nullptr, seeds, 0}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return score_enhance_impl(m, "fd_score_enhance_seeded", y, nullptr, fd_noise_src{nullptr, seeds, 0}, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// ScoreModel.enhance on a RAGGED batch: the contract of fd_enhance_ragged (y / x_hat are [B][L] rows, lengths = device int32 [B], the
+// CALLER guarantees one T_pad bucket, clip b bit-identical to the one-clip call with the same noise or seed, samples [lengths[b], L) of a
+// row of x_hat zero, workspace fd_enhance_workspace_bytes(m, B, L)).  Exactly one of noise ([draws][B][F][T_pad]) and seeds (device uint64
+// [B]) is given.  The sampler's update kernels work per element of [B][F][T_pad] and the network never mixes batch items, so the lengths
+// only reach the STFT / iSTFT.  A captured graph is keyed on the POINTERS lengths / noise / seeds and on the score configuration.
+extern "C" int fd_score_enhance_ragged(fd_model* m, const float* y, const int* lengths, const float* noise, const unsigned long long* seeds,
+                                       const fd_score_config* c, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_enhance_ragged");
+  FD_REQUIRE(lengths, "fd_score_enhance_ragged: null lengths");
+  FD_REQUIRE((noise != nullptr) != (seeds != nullptr), "fd_score_enhance_ragged: exactly one of noise and seeds must be given (got %s)",
+             noise ? "both" : "neither");
+  FD_REQUIRE(B > 0, "fd_score_enhance_ragged: B must be positive (got %d)", B);
+  const fd_noise_src src = noise ? fd_noise_src{noise} : fd_noise_src{nullptr, seeds, 0};
+  return score_enhance_impl(m, "fd_score_enhance_ragged", y, lengths, src, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // One evaluation of the score network combined into what the black-box ODE sampler of the reference needs
@@ -1410,15 +1427,31 @@ extern "C" int fd_score_eval(fd_model* m, const float* x, const float* Y, float 
   return forward_call(m, x, Y, nullptr, t, 1, os, B, T_pad, ws, ws_bytes, fd_stream(stream));
 }
 
-extern "C" int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph,
-                                     void* stream) {
-  FD_MODEL_ENTER(m, "fd_regression_enhance");
+static int regression_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                                   int use_graph, void* stream) {
   GraphKey key; key.kind = 4;
-  return enhance_common(m, "fd_regression_enhance", y, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
+  return enhance_common(m, who, y, lens, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
                         [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
                           OutSpec os; os.dst = X; os.coef = 1.f;                                 // X_hat = backbone(Y, Y, t = 0), model.py:566-578
                           return forward_call(m, Y, Y, nullptr, 0.f, 1, os, B, Tp, rest, rest_bytes, st);
                         });
+}
+
+extern "C" int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph,
+                                     void* stream) {
+  FD_MODEL_ENTER(m, "fd_regression_enhance");
+  return regression_enhance_impl(m, "fd_regression_enhance", y, nullptr, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// RegressionModel.enhance on a RAGGED batch: the contract of fd_enhance_ragged without a noise argument (y / x_hat [B][L] rows, lengths =
+// device int32 [B] of one T_pad bucket, clip b bit-identical to the one-clip call, samples [lengths[b], L) of a row of x_hat zero).  A
+// captured graph is keyed on the POINTER lengths.
+extern "C" int fd_regression_enhance_ragged(fd_model* m, const float* y, const int* lengths, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                                            int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_regression_enhance_ragged");
+  FD_REQUIRE(lengths, "fd_regression_enhance_ragged: null lengths");
+  FD_REQUIRE(B > 0, "fd_regression_enhance_ragged: B must be positive (got %d)", B);
+  return regression_enhance_impl(m, "fd_regression_enhance_ragged", y, lengths, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // ---- one ResnetBlockBigGANpp as a stand-alone call (layerspp.py:252-284; the fusion unit of SURVEY 8(a13)) -----------

@@ -1,11 +1,19 @@
 """Command-line driver equivalent to the reference's `enhance.py`.
 
     python -m flowdec_amd.enhance_cli --ckpt flowdec_75m.ckpt --files noisy_dir/ --outdir out/ --N 3 --solver midpoint [--rtf]
+    python -m flowdec_amd.enhance_cli --ckpt scoredec.ckpt --files noisy_dir/ --outdir out/ --N 30 --predictor reverse_diffusion --corrector ald --snr 0.5
 
 Same arguments and file conventions as the reference (enhance.py:24-49): `--files` is a directory of *.wav, a file list
 (one path per line, or `clean ---> noisy` / `clean,noisy` pair lines, enhance.py:146-164) or, with `--single-file`, one
 wav; files longer than 30 s are skipped (:115,:139); `--rtf` writes `path,runtime,filetime,rtf` rows (:94,:135) with
-rtf = runtime / filetime like the reference.  The score-model-only options are accepted and ignored.
+rtf = runtime / filetime like the reference.
+
+Model class: like `EnhancementModel.load_from_checkpoint` (enhance.py:66) the driver runs the class the checkpoint names in
+`hyper_parameters.model._target_` -- FlowModel, ScoreModel (config/baseline_scoredec_75s.yaml) or RegressionModel
+(config/baseline_regression_75s.yaml); a checkpoint that names none (no hyper_parameters, a bare state_dict) is a FlowModel, and
+`--model {flow,score,regression}` overrides the checkpoint.  `--predictor`, `--corrector`, `--snr` and `--N` reach the score model's
+sampler (a FlowModel ignores the first three); `--solver` is the flow model's (the two baselines ignore it, as in the reference).  All
+three classes run in ragged batches; the regression model draws no noise and ignores `--seed` / `--rng`.
 
 Checkpoints: a Lightning `.ckpt` (dict with `_pl_ema_state_dict` and/or `state_dict`, optionally `hyper_parameters`
 holding the resolved config: callbacks/ema.py:201-215, model.py:100,119) or a bare state_dict.  `--ema` (default)
@@ -16,7 +24,7 @@ Non-48 kHz input is resampled with a restatement of torchaudio.functional.resamp
 
 Batching (round 6): the reference enhances one file per call (enhance.py:96-137).  This driver reads the lengths first, buckets the
 files by the frame count their spectrogram pads to (T_pad, util/other.py:25-52) and runs up to `--batch-files` files of a bucket as
-ONE ragged native call (FlowModel.enhance_batch -> fd_enhance_ragged): every file's waveform is bit-identical to the one-file call,
+ONE ragged native call (`enhance_batch` of the model class -> fd_enhance_ragged / fd_score_enhance_ragged / fd_regression_enhance_ragged): every file's waveform is bit-identical to the one-file call,
 the GPU sees a batch.  With `--seed S` file i of the work list draws its noise from its own generator seeded S + i, so the result
 of a file does not depend on the batching (`--batch-files 1` = the reference's loop); with `--rng native` the noise is the library's
 own, generated on the GPU from `flowdec_amd.noise.clip_seed(S, i)` (no collisions between (S, i + 1) and (S + 1, i)).  Under `--rtf` a batch is timed as a whole and
@@ -42,7 +50,8 @@ import numpy as np
 import torch
 
 from .noise import clip_seed
-from .model import BACKBONE_FINAL_NO_ATTN, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, WorkspaceTooLarge, from_preset
+from .model import (BACKBONE_FINAL_NO_ATTN, OUVESDE, PRESETS, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, RegressionModel, ScoreModel,
+                    WorkspaceTooLarge, from_preset)
 
 MAX_SECONDS = 30.0  # enhance.py:115
 PRECISION_MAX_SECONDS = {}   # precision -> clip length it can take, if shorter than --max-seconds (none: every mode takes any length that fits in memory)
@@ -212,8 +221,42 @@ def _cfg_get(cfg, *path, default=None):
     return cfg
 
 
-def model_from_checkpoint(ckpt, ema: bool = True, precision: str = "bf16", preset: str = "flowdec_75m") -> FlowModel:
-    """Build a FlowModel from a loaded checkpoint object (see module docstring for the accepted layouts)."""
+MODEL_KINDS = {"flow": FlowModel, "score": ScoreModel, "regression": RegressionModel}
+
+
+def model_kind(mcfg: dict, model: str = "auto") -> str:
+    """'flow' / 'score' / 'regression': `model` unless it is 'auto', else the class `hyper_parameters.model._target_` names (the class
+    EnhancementModel.load_from_checkpoint would build, enhance.py:66); a checkpoint without a `_target_` is a FlowModel."""
+    if model != "auto":
+        if model not in MODEL_KINDS:
+            raise ValueError(f"model must be one of {['auto'] + sorted(MODEL_KINDS)} (got {model!r})")
+        return model
+    target = mcfg.get("_target_")
+    if target is None:
+        return "flow"
+    for kind, cls in MODEL_KINDS.items():
+        if str(target).split(".")[-1] == cls.__name__:
+            return kind
+    raise RuntimeError(f"checkpoint names the model class {target!r}: only FlowModel, ScoreModel and RegressionModel are implemented "
+                       f"(--model overrides the checkpoint)")
+
+
+def score_settings(mcfg: dict) -> Tuple[OUVESDE, float]:
+    """(sde, t_eps) of a ScoreModel checkpoint: `model.sde` (theta, sigma_min, sigma_max, N) and `model.t_eps`; what is absent comes from
+    config/model/sde/ouve_final.yaml and score_model_final.yaml's t_eps (the preset baseline_scoredec_75s).  Only the OUVE SDE exists here."""
+    default = PRESETS["baseline_scoredec_75s"]
+    sde_cfg = mcfg.get("sde") or {}
+    target = sde_cfg.get("_target_")
+    if target is not None and str(target).split(".")[-1] != "OUVESDE":
+        raise RuntimeError(f"checkpoint names the SDE {target!r}: only OUVESDE is implemented")
+    par = {k: sde_cfg.get(k, v) for k, v in default["sde"].items()}
+    t_eps = mcfg.get("t_eps")
+    return OUVESDE(**par), float(default["t_eps"] if t_eps is None else t_eps)
+
+
+def model_from_checkpoint(ckpt, ema: bool = True, precision: str = "bf16", preset: str = "flowdec_75m", model: str = "auto"):
+    """Build the FlowModel, ScoreModel or RegressionModel of a loaded checkpoint object (see module docstring for the accepted layouts
+    and `model_kind` for the choice of the class)."""
     if not isinstance(ckpt, dict):
         raise RuntimeError("checkpoint must be a dict")
     if "_pl_ema_state_dict" in ckpt or "state_dict" in ckpt:
@@ -240,38 +283,47 @@ def model_from_checkpoint(ckpt, ema: bool = True, precision: str = "bf16", prese
                                         n_hops=int(fe_cfg.get("n_hops", 4)) if "hop_length" not in fe_cfg else None,
                                         hop_length=fe_cfg.get("hop_length"), sampling_rate=int(_cfg_get(hp, "sampling_rate", default=48000)),
                                         alpha=float(fe_cfg.get("alpha", 0.3)), beta=float(fe_cfg.get("beta", 0.33)))
-    sigma_y = sd["sigma_y"] if "sigma_y" in sd else from_preset(preset, nf=8).sigma_y.data
-    model = FlowModel(backbone=NCSNpp(precision=precision, **bb_cfg), feature_extractor=fe,
-                      sampling_rate=int(_cfg_get(hp, "sampling_rate", default=48000)), sigma_x=0.0, sigma_y=sigma_y.clone())
-    res = model.load_state_dict(sd, strict=False)  # strict_loading = False in the reference (model.py:397)
+    kind = model_kind(mcfg, model)
+    common = dict(backbone=NCSNpp(precision=precision, **bb_cfg), feature_extractor=fe, sampling_rate=int(_cfg_get(hp, "sampling_rate", default=48000)))
+    if kind == "score":
+        sde, t_eps = score_settings(mcfg)
+        net = ScoreModel(sde=sde, t_eps=t_eps, **common)
+    elif kind == "regression":
+        net = RegressionModel(**common)
+    else:
+        sigma_y = sd["sigma_y"] if "sigma_y" in sd else from_preset(preset, nf=8).sigma_y.data
+        net = FlowModel(sigma_x=0.0, sigma_y=sigma_y.clone(), **common)
+    res = net.load_state_dict(sd, strict=False)  # strict_loading = False in the reference (model.py:397)
     missing = [k for k in res.missing_keys if k.startswith("backbone.")]
     if missing:
         raise RuntimeError(f"checkpoint is missing backbone parameters, e.g. {missing[:3]}")
-    return model.eval()
+    return net.eval()
 
 
-def load_from_checkpoint(path: str, map_location="cpu", ema: bool = True, precision: str = "bf16") -> FlowModel:
+def load_from_checkpoint(path: str, map_location="cpu", ema: bool = True, precision: str = "bf16", model: str = "auto"):
     """Replacement for `EnhancementModel.load_from_checkpoint(ckpt, map_location=..., ema=...)` (enhance.py:66)."""
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
-    model = model_from_checkpoint(ckpt, ema=ema, precision=precision)
-    return model.to(map_location) if map_location is not None else model
+    net = model_from_checkpoint(ckpt, ema=ema, precision=precision, model=model)
+    return net.to(map_location) if map_location is not None else net
 
 
 # ------------------------------------------------------------------------------------------------
 # main loop
 # ------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Enhance wav files with a FlowDec postfilter on MI355X")
+    p = argparse.ArgumentParser(description="Enhance wav files with a FlowDec postfilter (or its ScoreDec / regression baselines) on MI355X")
     p.add_argument("--ckpt", type=str, required=True)
     p.add_argument("--files", type=str, required=True)
     p.add_argument("--outdir", type=str, required=True)
     p.add_argument("--N", type=int, required=True)
     p.add_argument("--single-file", action="store_true")
     p.add_argument("--exclude-files-matching", type=str, required=False)
-    p.add_argument("--predictor", type=str, default="reverse_diffusion")   # score model only (ignored)
-    p.add_argument("--corrector", type=str, default="ald")
+    p.add_argument("--predictor", type=str, default="reverse_diffusion", choices=["reverse_diffusion", "euler_maruyama"])   # score model only
+    p.add_argument("--corrector", type=str, default="ald", choices=["ald", "none"])
     p.add_argument("--snr", type=float, default=0.5)
-    p.add_argument("--solver", type=str, default="midpoint")
+    p.add_argument("--solver", type=str, default="midpoint")   # flow model only
+    p.add_argument("--model", type=str, default="auto", choices=["auto", "flow", "score", "regression"],
+                   help="auto: the class the checkpoint names (hyper_parameters.model._target_; none named: flow); the others override it")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--ema", type=lambda s: str(s).lower() not in ("0", "false", "no"), default=True)
     p.add_argument("--skip-existing", type=lambda s: str(s).lower() not in ("0", "false", "no"), default=True)
@@ -402,12 +454,30 @@ def file_generator(model: FlowModel, seed: Optional[int], index: int):
 
 
 def noise_kwargs(model: FlowModel, args, indices: List[int], batch: bool) -> dict:
-    """The noise arguments of enhance (batch=False, one index) / enhance_batch for the files `indices` of the work list."""
+    """The noise arguments of enhance (batch=False, one index) / enhance_batch for the files `indices` of the work list.  The regression
+    model draws no noise: it takes none of them."""
+    if isinstance(model, RegressionModel):
+        return {}
     if args.rng == "native":
         seeds = [clip_seed(args.seed, i) for i in indices]
         return dict(seeds=seeds) if batch else dict(seed=seeds)
     gens = [file_generator(model, args.seed, i) for i in indices]
     return dict(generator=gens) if batch else dict(generator=gens[0])
+
+
+def enhance_kwargs(model, args) -> dict:
+    """The sampler / solver arguments of `enhance` and `enhance_batch` for the model's class: a FlowModel takes --N and --solver, a ScoreModel
+    --N, --predictor, --corrector and --snr, a RegressionModel none (one network evaluation)."""
+    if isinstance(model, ScoreModel):
+        return dict(N=args.N, predictor=args.predictor, corrector=args.corrector, snr=args.snr)
+    if isinstance(model, RegressionModel):
+        return {}
+    return dict(N=args.N, solver=args.solver)
+
+
+def batchable(model, args) -> bool:
+    """Whether the run can use ragged batches: the flow model's adaptive solvers step clip by clip; everything else runs in batches."""
+    return not isinstance(model, FlowModel) or args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast")
 
 
 def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS):
@@ -447,7 +517,7 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
     # not by the host's launches (profiles/r02_graph_cost.txt: eager 18.06 ms, replay 18.10 ms; capture + instantiate 2.4 ms)
     try:
         with GpuTimer(args.rtf) as timer:
-            x_hat = model.enhance(y, N=args.N, solver=args.solver, use_graph=False, **noise_kwargs(model, args, [job.index], batch=False))
+            x_hat = model.enhance(y, use_graph=False, **enhance_kwargs(model, args), **noise_kwargs(model, args, [job.index], batch=False))
     except WorkspaceTooLarge as err:
         skip_over_memory(job, res, err)
         return
@@ -489,7 +559,7 @@ def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLo
     noise = noise_kwargs(model, args, [job.index for job, _ in loaded], batch=True)
     try:
         with GpuTimer(args.rtf) as timer:
-            outs = model.enhance_batch([y for _, y in loaded], N=args.N, solver=args.solver, **noise)
+            outs = model.enhance_batch([y for _, y in loaded], **enhance_kwargs(model, args), **noise)
     except WorkspaceTooLarge:   # the batch does not fit: one call per file (each result is the same, bit for bit)
         for job, y in loaded:
             enhance_file(model, job, args, log, res, max_seconds, y=y)
@@ -520,18 +590,18 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
         print(f"flowdec_amd: --rng native without --seed: using --seed {args.seed}")
     if model is None:
         print("Loading model from checkpoint...")
-        model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision)
+        model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model=args.model)
         print("Done loading model.")
     noisy, clean = collect_files(args.files, args.single_file)
     max_seconds = min(args.max_seconds, PRECISION_MAX_SECONDS.get(args.precision, args.max_seconds))
-    print(f"flowdec_amd: precision={args.precision} ({PRECISION_NOTE[args.precision]}), solver={args.solver}, N={args.N}, "
+    settings = ", ".join(f"{k}={v}" for k, v in enhance_kwargs(model, args).items()) or "one network evaluation"
+    print(f"flowdec_amd: model={type(model).__name__}, precision={args.precision} ({PRECISION_NOTE[args.precision]}), {settings}, "
           f"files per native call <= {max(args.batch_files, 1)}")
     res = RunResult()
     suffix = f"_{args.i_min}-{args.i_max}" if args.i_max else ""
     jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
-    batchable = args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast")   # (the adaptive solvers step clip by clip)
     with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None) as log:
-        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable else 1, args.max_seconds):
+        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable(model, args) else 1, args.max_seconds):
             if len(batch) == 1:
                 enhance_file(model, batch[0], args, log, res, max_seconds)
             else:

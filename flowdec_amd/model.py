@@ -492,6 +492,37 @@ def padded_frames_of(num_samples: int, hop: int = 384) -> int:
     return int(lib.fd_padded_frames(lib.fd_num_frames(int(num_samples), int(hop))))
 
 
+def _ragged_bucket(clips, cfg):
+    """The bucket rule of every `enhance_batch`: clips [L], [1, L] or [1, 1, L] that all pad to ONE frame count.  -> (the clips flattened,
+    their lengths, T_pad, the row length).  The row length is the bucket's LARGEST possible clip (1 + Lrow // hop == T_pad): one
+    workspace / one hipGraph per (B, T_pad)."""
+    from . import ops
+    lib = L.load()
+    hop = cfg["hop"]
+    flat = []
+    for i, c in enumerate(clips):
+        if c.ndim > 3 or any(d != 1 for d in c.shape[:-1]):
+            raise RuntimeError(f"enhance_batch: clip {i} must be [L], [1, L] or [1, 1, L] (got {tuple(c.shape)})")
+        flat.append(c.reshape(-1))
+    lens = [int(c.numel()) for c in flat]
+    Tps = {lib.fd_padded_frames(lib.fd_num_frames(l, hop)) for l in lens}
+    if len(Tps) != 1:
+        raise RuntimeError(f"enhance_batch: the clips pad to different frame counts {sorted(Tps)}; one call takes one T_pad bucket "
+                           f"(bucket with flowdec_amd.model.padded_frames_of)")
+    Tp = Tps.pop()
+    Lrow = hop * Tp - 1
+    ops.check_ragged_lengths(lens, Lrow, cfg["n_fft"], hop)
+    return flat, lens, Tp, Lrow
+
+
+def _per_clip_generators(generator, noise, B):
+    """One generator per clip from `generator` (one for all clips, drawn clip by clip, or a list of one per clip); checks the counts."""
+    gens = generator if isinstance(generator, (list, tuple)) else [generator] * B
+    if noise is not None and len(noise) != B or len(gens) != B:
+        raise RuntimeError("enhance_batch: one noise tensor / generator per clip")
+    return gens
+
+
 def _info_from_ws(lib, h, ws, B, Lw, T, squeeze_dims):
     """preprocess_info of the reference (model.py:161-162); normfac is read where fd_enhance's front end left it."""
     off = lib.fd_enhance_normfac_offset(h, B, Lw)
@@ -715,26 +746,10 @@ class FlowModel(nn.Module):
         lib = L.load()
         h = self._sync_native()
         cfg = self.feature_extractor._cfg()
-        hop, F = cfg["hop"], cfg["n_fft"] // 2 + 1
-        flat = []
-        for i, c in enumerate(clips):
-            if c.ndim > 3 or any(d != 1 for d in c.shape[:-1]):
-                raise RuntimeError(f"enhance_batch: clip {i} must be [L], [1, L] or [1, 1, L] (got {tuple(c.shape)})")
-            flat.append(c.reshape(-1))
-        lens = [int(c.numel()) for c in flat]
-        Tps = {lib.fd_padded_frames(lib.fd_num_frames(l, hop)) for l in lens}
-        if len(Tps) != 1:
-            raise RuntimeError(f"enhance_batch: the clips pad to different frame counts {sorted(Tps)}; one call takes one T_pad bucket "
-                               f"(bucket with flowdec_amd.model.padded_frames_of)")
-        Tp = Tps.pop()
+        F = cfg["n_fft"] // 2 + 1
+        flat, lens, Tp, Lrow = _ragged_bucket(clips, cfg)
         B = len(flat)
-        # the row length is the bucket's LARGEST possible clip (1 + Lrow // hop == T_pad): one workspace / one hipGraph per (B, T_pad)
-        Lrow = hop * Tp - 1
-        from . import ops
-        ops.check_ragged_lengths(lens, Lrow, cfg["n_fft"], hop)
-        gens = generator if isinstance(generator, (list, tuple)) else [generator] * B
-        if noise is not None and len(noise) != B or len(gens) != B:
-            raise RuntimeError("enhance_batch: one noise tensor / generator per clip")
+        gens = _per_clip_generators(generator, noise, B)
         with torch.cuda.device(dev):
             io = self._io_buffers(B, Lrow, Tp, F, dev)
             if "lens" not in io:
@@ -951,6 +966,68 @@ class _WaveModel(nn.Module):
         return (x_hat, info) if return_preprocess_info else x_hat
 
 
+    @_serialized
+    def _ragged_call(self, clips, n_draws, noise, generator, seeds, launch):
+        """The staging of `enhance_batch`: clips of ONE T_pad bucket as zero-padded rows of a [B, hop * T_pad - 1] buffer, then
+        launch(lib, h, io, B, Lrow, ws) on a capture-safe side stream; io = dict(y, out [B, Lrow], lens int32 [B], noise [n_draws, B, 1, F,
+        Tp] | None, seeds int64 [B] | None).  Clip b's planes are noise[b] ([n_draws, 1, 1, F, Tp]) or one draw of that shape from its
+        generator -- what `_wave_call` draws for the clip alone; with `seeds` no noise tensor exists.  -> list of waveforms, each with the
+        shape and on the device of its clip."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
+        clips = list(clips)
+        if not clips:
+            return []
+        lib = L.load()
+        h = self._sync_native()
+        cfg = self.feature_extractor._cfg()
+        F = cfg["n_fft"] // 2 + 1
+        flat, lens, Tp, Lrow = _ragged_bucket(clips, cfg)
+        B = len(flat)
+        gens = _per_clip_generators(generator, noise, B)
+        with torch.cuda.device(dev):
+            if seeds is not None:
+                n_draws = 0
+            key = ("ragged", B, Lrow, n_draws, seeds is not None, str(dev))
+            io = self._io.get(key)
+            if io is None:
+                io = dict(y=torch.empty(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
+                          lens=torch.empty(B, dtype=torch.int32, device=dev),
+                          noise=torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev) if n_draws else None,
+                          seeds=torch.empty(B, dtype=torch.int64, device=dev) if seeds is not None else None)
+                self._io = {key: io}
+            io["y"].zero_()
+            for b, c in enumerate(flat):
+                io["y"][b, :lens[b]].copy_(c)
+                if n_draws:
+                    shape = (n_draws, 1, 1, F, Tp)
+                    z = noise[b].to(dev, torch.complex64).reshape(shape) if noise is not None else \
+                        torch.randn(shape, dtype=torch.complex64, device=dev, generator=gens[b])
+                    io["noise"][:, b:b + 1].copy_(z)
+            io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
+            if seeds is not None:
+                io["seeds"].copy_(fd_noise.seeds_to_tensor(list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev))
+            need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
+            if need == 0:
+                raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
+            ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
+            cur = torch.cuda.current_stream(dev)
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            side = self._side_stream
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                launch(lib, h, io, B, Lrow, ws)
+                outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
+            cur.wait_stream(side)
+        res = []
+        for b, c in enumerate(clips):
+            outs[b].record_stream(cur)
+            res.append(outs[b].reshape(c.shape).to(c.device))
+        return res
+
+
 class ScoreModel(_WaveModel):
     """Drop-in for flowdec.model.ScoreModel on the inference path (model.py:581-690): `forward` = score estimate,
     `enhance` = predictor-corrector sampling (sampler_type='pc').  Extensions: noise= / generator= / seed= / use_graph=; with `seed=`
@@ -971,6 +1048,17 @@ class ScoreModel(_WaveModel):
         std = self.sde_std(t_batch.float())
         return -self.backbone(xt, y, t_batch) / std.reshape(-1, 1, 1, 1)
 
+    def _pc_config(self, predictor, corrector, N, corrector_steps, snr, denoise, eps=None):
+        """-> (fd_score_config of the predictor-corrector sampler, the number of Gaussian planes it consumes)."""
+        if predictor not in L.PREDICTORS:
+            raise ValueError(f"unknown predictor {predictor!r}; supported: {sorted(L.PREDICTORS)}")
+        if corrector not in L.CORRECTORS:
+            raise ValueError(f"unknown corrector {corrector!r}; supported: {sorted(L.CORRECTORS)}")
+        N = self.sde.N if N is None else int(N)
+        cfg = L.FdScoreConfig(self.sde.theta, self.sde.sigma_min, self.sde.sigma_max, float(self.t_eps if eps is None else eps), float(snr), N,
+                              L.PREDICTORS[predictor], L.CORRECTORS[corrector], int(corrector_steps), int(bool(denoise)))
+        return cfg, self.num_draws(N, predictor, corrector, corrector_steps)
+
     def num_draws(self, N=None, predictor="reverse_diffusion", corrector="ald", corrector_steps=1) -> int:
         N = self.sde.N if N is None else N
         return 1 + N * ((corrector_steps if corrector == "ald" else 0) + (1 if predictor != "none" else 0))
@@ -983,14 +1071,7 @@ class ScoreModel(_WaveModel):
             return self._enhance_ode(y, N=N, denoise=denoise, noise=noise, generator=generator, seed=seed, return_preprocess_info=return_preprocess_info, **kwargs)
         if sampler_type != "pc":
             raise ValueError(f"{sampler_type} is not a valid sampler type!")
-        if predictor not in L.PREDICTORS:
-            raise ValueError(f"unknown predictor {predictor!r}; supported: {sorted(L.PREDICTORS)}")
-        if corrector not in L.CORRECTORS:
-            raise ValueError(f"unknown corrector {corrector!r}; supported: {sorted(L.CORRECTORS)}")
-        N = self.sde.N if N is None else int(N)
-        cfg = L.FdScoreConfig(self.sde.theta, self.sde.sigma_min, self.sde.sigma_max, float(kwargs.get("eps", self.t_eps)), float(snr), N,
-                              L.PREDICTORS[predictor], L.CORRECTORS[corrector], int(corrector_steps), int(bool(denoise)))
-        n_draws = self.num_draws(N, predictor, corrector, corrector_steps)
+        cfg, n_draws = self._pc_config(predictor, corrector, N, corrector_steps, snr, denoise, kwargs.get("eps"))
 
         def launch(lib, h, io, B, Lw, ws):
             assert lib.fd_score_num_draws(C.byref(cfg)) == n_draws
@@ -1002,6 +1083,28 @@ class ScoreModel(_WaveModel):
                                              L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
         return self._wave_call(y, n_draws, noise, generator, launch, return_preprocess_info, seed=seed)
 
+    @torch.no_grad()
+    def enhance_batch(self, clips, predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, denoise=True,
+                      noise=None, generator=None, seeds=None, use_graph: bool = True, **kwargs):
+        """`[self.enhance(c, ...) for c in clips]` as ONE native call (fd_score_enhance_ragged) for clips of DIFFERENT lengths whose
+        spectrograms pad to the same T_pad (the bucket rule and the errors of FlowModel.enhance_batch).  Every clip's result is
+        BIT-IDENTICAL to `self.enhance(clip)` with the same noise.  `noise` = one [n_draws, 1, 1, F, T_pad] complex tensor per clip
+        (n_draws = self.num_draws(...)), or `generator` = one torch.Generator (drawn clip by clip) or a list of one per clip -- clip b's
+        planes are then one draw of that shape, exactly what `enhance(clip_b, generator=g_b)` draws --, or `seeds` = one 64-bit seed
+        per clip: clip i equals `self.enhance(clip_i, seed=[seeds[i]])`.  Only the predictor-corrector sampler runs in batches (the ODE
+        sampler is driven from the host, clip by clip)."""
+        fd_noise.exclusive(seeds=seeds, noise=noise, generator=generator)
+        sampler_type = kwargs.get("sampler_type", "pc")
+        if sampler_type != "pc":
+            raise ValueError(f"enhance_batch: sampler_type='pc' only (got {sampler_type!r}); the 'ode' sampler is host-driven: call enhance() per clip")
+        cfg, n_draws = self._pc_config(predictor, corrector, N, corrector_steps, snr, denoise, kwargs.get("eps"))
+
+        def launch(lib, h, io, B, Lrow, ws):
+            assert lib.fd_score_num_draws(C.byref(cfg)) == n_draws
+            L.check(lib.fd_score_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), None if seeds is not None else L.ptr(torch.view_as_real(io["noise"])),
+                                                L.ptr(io["seeds"]) if seeds is not None else None, C.byref(cfg), L.ptr(io["out"]), B, Lrow,
+                                                L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        return self._ragged_call(clips, n_draws, noise, generator, seeds, launch)
 
     @_serialized
     def _enhance_ode(self, y, N=None, denoise=True, noise=None, generator=None, seed=None, rtol=1e-5, atol=1e-5, method="RK45", eps=None,
@@ -1079,6 +1182,15 @@ class RegressionModel(_WaveModel):
         def launch(lib, h, io, B, Lw, ws):
             L.check(lib.fd_regression_enhance(h, L.ptr(io["y"]), L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
         return self._wave_call(y, 0, None, None, launch, return_preprocess_info)
+
+    @torch.no_grad()
+    def enhance_batch(self, clips, use_graph: bool = True):
+        """`[self.enhance(c) for c in clips]` as ONE native call (fd_regression_enhance_ragged) for clips of different lengths in one T_pad
+        bucket (the bucket rule and the errors of FlowModel.enhance_batch); every result is bit-identical to the one-clip call."""
+        def launch(lib, h, io, B, Lrow, ws):
+            L.check(lib.fd_regression_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(),
+                                                     int(use_graph), L.stream()))
+        return self._ragged_call(clips, 0, None, None, None, launch)
 
 
 # ------------------------------------------------------------------------------------------------

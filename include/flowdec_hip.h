@@ -442,7 +442,10 @@ int fd_model_set_normalize(fd_model* m, int normalize);
 /* ---- ScoreDec / regression baselines on the same backbone -------------------------------
  * ScoreModel.enhance (model.py:630-657) with the predictor-corrector sampler of sampling/__init__.py:32-72 on the OUVE
  * SDE (sdes.py:132-206): predictors reverse_diffusion / euler_maruyama / none (sampling/predictors.py:48-83), correctors
- * ald / none (sampling/correctors.py:42-80); the score is -backbone(x, y, t) / std(t) (model.py:613-628). */
+ * ald / none (sampling/correctors.py:42-80); the score is -backbone(x, y, t) / std(t) (model.py:613-628).
+ * Three forms of the sampler: fd_score_enhance (noise planes, clips of one length), fd_score_enhance_seeded (per-clip seeds, one length)
+ * and fd_score_enhance_ragged (either noise source, clips of different lengths in one T_pad bucket); fd_regression_enhance has the
+ * ragged form fd_regression_enhance_ragged.  A clip's result is the same, bit for bit, through every form that can express it. */
 #define FD_PREDICTOR_REVERSE_DIFFUSION 0
 #define FD_PREDICTOR_EULER_MARUYAMA 1
 #define FD_PREDICTOR_NONE 2
@@ -465,6 +468,15 @@ int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_s
 /* The same sampler on seeded noise ("Seeded noise" above): no [fd_score_num_draws][B][n_freq][T_pad] buffer is needed. */
 int fd_score_enhance_seeded(fd_model* m, const float* y, const unsigned long long* seeds, const fd_score_config* cfg, float* x_hat, int B,
                             int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* ScoreModel.enhance on a ragged batch: the contract of fd_enhance_ragged ("Ragged batches" above), restated.  y / x_hat are [B][L]
+ * rows; lengths (DEVICE int32 [B], required) the clips' own sample counts -- the CALLER guarantees that every clip pads to the T_pad of
+ * L (the kernels clamp a length into (n_fft/2, L]).  Exactly one of noise ([fd_score_num_draws][B][n_freq][T_pad] complex64) and seeds
+ * (DEVICE uint64 [B], "Seeded noise" above) is non-NULL; both or neither is FD_EINVAL.  Clip b is bit-identical to fd_score_enhance /
+ * fd_score_enhance_seeded on that clip alone with its noise planes / its seed; samples [lengths[b], L) of a row of x_hat are zero.
+ * Workspace: fd_enhance_workspace_bytes(m, B, L).  A captured graph is keyed on the POINTERS lengths, noise and seeds (their contents
+ * may change between replays) and on the values of *cfg. */
+int fd_score_enhance_ragged(fd_model* m, const float* y, const int* lengths, const float* noise, const unsigned long long* seeds,
+                            const fd_score_config* cfg, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
 /* One score-network evaluation in the form the black-box ODE sampler needs (sampling/__init__.py:75-146, which drives
  * scipy.integrate.solve_ivp on the host): x, Y, out = complex64 [B][1][n_freq][T_pad]; workspace fd_model_workspace_bytes.
  *   FD_SCORE_DRIFT_PF : out = theta (Y - x) - 0.5 g(t)^2 score(x, Y, t)     (probability-flow drift, sdes.py:93-109)
@@ -478,6 +490,11 @@ int fd_score_eval(fd_model* m, const float* x, const float* Y, float t, const fd
 /* RegressionModel.enhance (model.py:566-578): x_hat = iSTFT(backbone(Y, Y, t = 0)). */
 int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph,
                           void* stream);
+/* RegressionModel.enhance on a ragged batch: the same contract as fd_score_enhance_ragged without noise -- [B][L] rows, lengths (DEVICE
+ * int32 [B], required) of ONE T_pad bucket, clip b bit-identical to fd_regression_enhance on that clip alone, samples [lengths[b], L)
+ * of a row of x_hat zero, workspace fd_enhance_workspace_bytes(m, B, L), a captured graph keyed on the POINTER lengths. */
+int fd_regression_enhance_ragged(fd_model* m, const float* y, const int* lengths, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                                 int use_graph, void* stream);
 
 /* Per-launch timing of the dominant kernel (conv MFMA) measured with HIP events on the launch stream;
  * used by bench.py for the roofline object.  enable != 0 starts recording (forces eager launches). */

@@ -2,9 +2,12 @@
 """The reference's use case -- a DIRECTORY of files of different lengths (enhance.py:96-137) -- through enhance_cli with and without
 ragged batching: a synthetic corpus (default 64 files, 1-4 s, 48 kHz), a full-width synthetic Lightning checkpoint, `--rtf`, and the
 aggregate audio-seconds per GPU-second of   --batch-files 1 (one file per call = the reference's loop)   vs   --batch-files 8 / 16.
-Every output file of the batched runs is compared byte for byte with the one-file-per-call run.
+Every output file of the batched runs is compared byte for byte with the one-file-per-call run.  `--model score | regression` runs the
+same corpus, weights and seeds through a ScoreDec / regression checkpoint (the class is named in the checkpoint's hyper_parameters).
 
     python scripts/cli_corpus_rtf.py [--files 64] [--min-s 1] [--max-s 4] [--N 6] [--solver euler] [--out gpurun_out/r06_cli_corpus_rtf.json]
+    python scripts/cli_corpus_rtf.py --model score --N 30 --predictor reverse_diffusion --corrector ald --snr 0.5 --batches 1 8 --out ...
+    python scripts/cli_corpus_rtf.py --model regression --out ...
 """
 import argparse
 import json
@@ -28,18 +31,24 @@ def main():
     ap.add_argument("--max-s", type=float, default=4.0)
     ap.add_argument("--N", type=int, default=6)
     ap.add_argument("--solver", default="euler")
+    ap.add_argument("--model", default="flow", choices=["flow", "score", "regression"])
+    ap.add_argument("--predictor", default="reverse_diffusion")
+    ap.add_argument("--corrector", default="ald")
+    ap.add_argument("--snr", type=float, default=0.5)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 16])
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "bf16x3", "mixed"])
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "r06_cli_corpus_rtf.json"))
     args = ap.parse_args()
     import flowdec_amd
-    from flowdec_amd import enhance_cli
+    from flowdec_amd import boxprobe, enhance_cli
     from flowdec_amd.model import padded_frames_of
 
     tmp = tempfile.mkdtemp(prefix="fd_corpus_")
     try:
         # full-width FlowDec-75m with seeded random weights, saved in the Lightning layout the reference's checkpoints have
-        m = flowdec_amd.from_preset("flowdec_75m", precision=args.precision)
+        # (the baselines: the same backbone and the same seeded weights under config/baseline_scoredec_75s.yaml / baseline_regression_75s.yaml)
+        preset = {"flow": "flowdec_75m", "score": "baseline_scoredec_75s", "regression": "baseline_regression_75s"}[args.model]
+        m = flowdec_amd.from_preset(preset, precision=args.precision)
         g = torch.Generator().manual_seed(1234)
         sd = {}
         for k, v in m.state_dict().items():
@@ -54,8 +63,10 @@ def main():
             else:
                 sd[k] = v.clone()
         ckpt = os.path.join(tmp, "flowdec_75m_synthetic.ckpt")
-        torch.save({"_pl_ema_state_dict": sd, "state_dict": sd}, ckpt)
-        del m
+        obj = {"_pl_ema_state_dict": sd, "state_dict": sd}
+        if args.model != "flow":
+            obj["hyper_parameters"] = {"model": {"_target_": "flowdec.model." + type(m).__name__}}
+        torch.save(obj, ckpt)
         ind = os.path.join(tmp, "in")
         os.makedirs(ind)
         rng = np.random.default_rng(0)
@@ -68,13 +79,18 @@ def main():
         audio = float(lens.sum()) / 48000
         fill = float(sum(lens)) / sum(384.0 * padded_frames_of(int(n)) for n in lens)
         model = enhance_cli.load_from_checkpoint(ckpt, map_location="cuda:0", precision=args.precision)
-        res = {"files": int(args.files), "audio_seconds": audio, "lengths_s": [float(args.min_s), float(args.max_s)], "N": args.N, "solver": args.solver,
+        assert type(model) is type(m)
+        sampler = {"flow": {"N": args.N, "solver": args.solver}, "regression": {},
+                   "score": {"N": args.N, "predictor": args.predictor, "corrector": args.corrector, "snr": args.snr}}[args.model]
+        res = {"files": int(args.files), "audio_seconds": audio, "lengths_s": [float(args.min_s), float(args.max_s)], "model": type(model).__name__, **sampler,
+               "box_calibration": boxprobe.calibrate(),
                "precision": args.precision, "files_per_T_pad_bucket": {str(k): v for k, v in sorted(buckets.items())},
                "samples_over_padded_frames": fill, "runs": {}}
         ref_dir = None
         for bf in args.batches:
             outd = os.path.join(tmp, f"out{bf}")
-            argv = ["--ckpt", ckpt, "--files", ind, "--outdir", outd, "--N", str(args.N), "--solver", args.solver, "--rtf", "--seed", "5", "--batch-files", str(bf)]
+            argv = ["--ckpt", ckpt, "--files", ind, "--outdir", outd, "--N", str(args.N), "--solver", args.solver, "--predictor", args.predictor,
+                    "--corrector", args.corrector, "--snr", str(args.snr), "--rtf", "--seed", "5", "--batch-files", str(bf)]
             enhance_cli.run(argv, model=model)                 # warm-up pass (graph capture of every (B, T_pad) bucket, allocator)
             shutil.rmtree(outd)
             t0 = time.perf_counter()
