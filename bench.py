@@ -4,10 +4,17 @@
 One "step" = one pass of the hot path (FlowModel.enhance: STFT -> 6 x NCSN++ inside the Euler solver -> iSTFT) over one
 batch of synthetic clips.  Workload at N = 1 is BASELINE.json configs[1]: FlowDec-75m, batch = 8 x 2 s clips @ 48 kHz, 6-step
 Euler, bf16.  `value` is timed with the inputs already resident in HBM (the bench contract: "inputs already resident in HBM when
-the timed region starts ... the PCIe-inclusive rate is never `value`"); the same K steps are then timed again from PINNED HOST
-waveforms to host waveforms ("H2D of waveform -> D2H of waveform") and reported next to it as `e2e` -- the two differ
-by the 2 x 6 MB of PCIe copies (< 1 ms of ~120).  The initial noise of every clip is drawn INSIDE the timed call, as the reference
+the timed region starts ... the PCIe-inclusive rate is never `value`").  The initial noise of every clip is drawn INSIDE the timed call, as the reference
 does (flowdec/model.py:512 `_get_noise`): `sharded_enhance(..., seed=)`, one Philox stream per (step, global clip).
+
+A plain run does only what the headline figure needs: set-up, the warm-up steps, the timed steps, `--dump-outputs`, the result line.
+`--full` adds every other measurement to the same line, each with a switch of its own to leave it out:
+  * `box_calibration` / `power` / `value_per_calibration`: a fixed matrix-core loop before the warm-up and clock / power samples
+    around the timed region (`--no-calibration`);
+  * `e2e`: the same K steps timed again from PINNED HOST waveforms to host waveforms ("H2D of waveform -> D2H of
+    waveform") -- it differs from `value` by the 2 x 6 MB of PCIe copies (< 1 ms of ~120) (`--no-e2e`);
+  * `roofline` / `roofline_hbm` / `roofline_stft`: one extra eager step with every launch timed (`--no-roofline`, one GPU only);
+  * `cpu_baseline`: BASELINE config 1 on this host's CPU, the longest of them (`--no-cpu-baseline`, one GPU only).
 
 `--config cfg2|cfg3|cfg4|cfg5|cfg3_nfe6|cfg4_nfe6|cfg5_dopri5` selects a BASELINE.json configuration by name (explicit flags given after
 it still apply): cfg 4 = FlowDec-75m, 32 x 2 s clips PER GPU, midpoint N = 6 (12 evaluations: the reference counts solver steps,
@@ -19,6 +26,7 @@ fixes the total = strong scaling, e.g. 256 for BASELINE config 4) is sharded by 
 and sits INSIDE the timed region.  `value` is the whole-job audio-seconds per wall-second (max over ranks).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            # N > 1: re-launches itself under torch.distributed.run
+    python bench.py ... --full                                     # + calibration / power, e2e, rooflines, CPU baseline
     python bench.py ... --dump-outputs DIR                         # + the last timed step's output as DIR/waveform.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -170,10 +178,12 @@ def main():
     ap.add_argument("--conv-algo", default="auto", choices=["direct", "winograd", "winograd_lowres", "auto", "latency"])
     ap.add_argument("--preset", default="flowdec_75m")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the ~0.3 s box calibration (fd_calibrate_mfma) and the clock / power sampling")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the second timed loop (pinned host waveforms in -> host waveforms out)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: box calibration and clock / "
+                                                        "power, the e2e loop, the rooflines, the CPU baseline (see the --no-* switches)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the extra eager step behind the roofline objects")
+    ap.add_argument("--no-calibration", action="store_true", help="with --full: skip the ~0.3 s box calibration (fd_calibrate_mfma) and the clock / power sampling")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the second timed loop (pinned host waveforms in -> host waveforms out)")
     ap.add_argument("--no-side-stream", action="store_true", help="FD_NO_SIDE_STREAM: keep the side branches on the launch stream")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo + --stub-step: launcher / collective test on CPU")
     ap.add_argument("--stub-step", action="store_true", help="replace enhance() by a trivial CPU function (tests of the launcher only)")
@@ -252,12 +262,12 @@ def main():
                 sd[k] = torch.randn(v.shape, generator=g) / fan_in ** 0.5
         model.load_state_dict(sd, strict=False)
         model = model.to(dev)
-        # the same global batch on every rank (seeded), resident in HBM before the timed region (and once more in pinned host memory
-        # for the e2e loop); each rank enhances its rows.  The initial noise is a GLOBAL tensor indexed by clip, so the result does
+        # the same global batch on every rank (seeded), resident in HBM before the timed region (and, under --full, once more in pinned
+        # host memory for the e2e loop); each rank enhances its rows.  The initial noise is a GLOBAL tensor indexed by clip, so the result does
         # not depend on the number of ranks.
         gen = torch.Generator(device=dev).manual_seed(0)
         y = 0.1 * torch.randn(gbatch, 1, Lw, device=dev, generator=gen)
-        y_host = y.cpu().pin_memory()
+        y_host = y.cpu().pin_memory() if args.full and not args.no_e2e else None
         lib = L.load()
         T = lib.fd_num_frames(Lw, 384); Tp = lib.fd_padded_frames(T)
         nfe = {"euler": args.N, "midpoint": 2 * args.N, "heun2": 2 * args.N, "heun2_eulerlast": 2 * args.N - 1, "dopri5": None}[args.solver]
@@ -299,7 +309,7 @@ def main():
     # carries what THIS box sustains on a fixed matrix-core loop (+ clock / power while it runs) and the clock / power of the timed
     # region itself; `value_per_calibration` = value / mfma_tflops is the figure to compare across boxes and rounds.
     calib = power = None
-    probe = dev.type == "cuda" and not args.no_calibration and not args.stub_step
+    probe = args.full and dev.type == "cuda" and not args.no_calibration and not args.stub_step
     if probe:
         from flowdec_amd import boxprobe
         try:
@@ -355,7 +365,7 @@ def main():
         result["distinct_devices"] = len({(d["uuid"], d["pci"]) for d in devs})
     if args.stub_step:
         result["config"]["workload"] = "STUB step (launcher / collective test, no model)"
-    elif not args.no_e2e:
+    elif args.full and not args.no_e2e:
         # the same K steps from pinned host memory to host memory: H2D of this rank's rows, solve, gather, D2H
         out_h = step(y_host, args.steps - 1)
         assert out_h.device.type == "cpu" and torch.equal(out_h, out.cpu()), "e2e result differs from the HBM-resident one"
@@ -364,7 +374,7 @@ def main():
                          "path": f"pinned host float32 [{gbatch}, 1, {Lw}] -> H2D -> enhance -> all-gather -> D2H host float32 (same K steps, same clock)",
                          "pcie_bytes_per_step": 2 * 4 * (hi - lo) * Lw if world == 1 else 4 * ((hi - lo) + gbatch) * Lw}
 
-    if rank == 0 and world == 1 and not args.no_roofline and not args.stub_step:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and not args.stub_step:
         from flowdec_amd import _lib as L
         # dominant kernel = the MFMA convolution: time every launch of one extra (eager) step with HIP events on the launch
         # stream; algorithmic FLOPs = 2 * pixels * Cout * Cin * k^2 per launch (the DIRECT convolution's count,
@@ -434,7 +444,7 @@ def main():
                     result[key]["traffic"] = t["traffic_per_launch"]
                     result[key]["traffic_source"] = (f"profiles/{TRAFFIC_FILE} (bytes/launch: fetch {t['fetch_corrected_per_launch']:.4g} + "
                                                      f"write {t['write_per_launch']:.4g})")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_step:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub_step:
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(result))

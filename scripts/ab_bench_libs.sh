@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 R=$1; shift
 for i in $(seq $R); do for v in "$@"; do
   L=$GRAFT_REPO_ROOT/flowdec_amd/variants/libflowdec_$v.so; [ $v = hip ] && L=$GRAFT_REPO_ROOT/flowdec_amd/libflowdec_hip.so
-  FLOWDEC_HIP_LIB=$L timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-e2e 2>/dev/null | grep '^{' | python -c "
+  FLOWDEC_HIP_LIB=$L timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-e2e 2>/dev/null | grep '^{' | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline()); p=j.get('power') or {}; c=j.get('box_calibration') or {}
 f=lambda x,n=0: ('%.*f' % (n, x)) if isinstance(x,(int,float)) else 'n/a'

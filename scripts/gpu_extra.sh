@@ -3,7 +3,7 @@
 # conv algorithm choices, cfg5-like.
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
-run() { name=$1; shift; timeout 400 python bench.py "$@" --no-cpu-baseline < /dev/null > $O/bench_$name.json 2> $O/bench_$name.err; python -c "
+run() { name=$1; shift; timeout 400 python bench.py "$@" --full --no-cpu-baseline < /dev/null > $O/bench_$name.json 2> $O/bench_$name.err; python -c "
 import json,sys
 d=json.load(open('$O/bench_$name.json')); r=d.get('roofline',{})
 print('$name', round(d['value'],2), 'x', round(d['ms_per_step'],1), 'ms', round(r.get('achieved',0),1), 'TF', d['config']['workload'][:70])" ; }

@@ -141,3 +141,52 @@ def test_bench_four_ranks_share_gpu(flags, clips):
     assert len(j["per_rank_ms_per_step"]) == 4 and j["ms_per_step"] >= max(j["per_rank_ms_per_step"]) * 0.999
     secs = float(flags[flags.index("--seconds") + 1])
     assert abs(j["value"] - sum(clips) * secs / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+
+
+_BENCH_EXTRA = ("box_calibration", "power", "e2e", "roofline", "roofline_hbm", "roofline_stft", "cpu_baseline")
+
+
+@pytest.fixture(scope="module")
+def bench_line(tmp_path_factory):
+    """name -> (result line, dumped waveform bytes) of one tiny `bench.py` run (1 clip x 1 s, Euler-2), each run once per module."""
+    import json
+    flags = {"plain": [], "full": ["--full", "--no-cpu-baseline"]}      # (the CPU baseline is left out for its length)
+    root, done = tmp_path_factory.mktemp("bench"), {}
+
+    def get(name):
+        if name not in done:
+            env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--seconds", "1",
+                   "--N", "2", "--dump-outputs", str(root / name)] + flags[name]
+            r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+            assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+            out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+            assert len(out) == 1, r.stdout[-2000:]
+            done[name] = (json.loads(out[0]), (root / name / "waveform.npy").read_bytes())
+        return done[name]
+    return get
+
+
+def _check_headline(j):
+    assert j["metric"].startswith("48 kHz audio-seconds/sec") and j["unit"] == "audio-seconds/second" and j["higher_is_better"] is True
+    assert j["dtype"] == "bf16" and j["steps"] == 2 and j["warmup"] == 1 and j["n_gpus"] == 1
+    assert abs(j["value"] - 1.0 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]      # 1 clip x 1 s per step
+
+
+def test_bench_plain_line(bench_line):
+    """A plain `bench.py` run prints the headline line alone: none of the measurements that take runs of their own."""
+    j, wave = bench_line("plain")
+    _check_headline(j)
+    assert not set(_BENCH_EXTRA) & set(j), sorted(j)
+    assert len(wave) > 4 * 48000                                                          # float32 [1, 1, 48000] behind the header
+
+
+def test_bench_full_line(bench_line):
+    """`--full` adds the box calibration / power, the e2e loop and the rooflines to a line whose workload is the plain run's: the
+    same configuration, the same dumped waveforms byte for byte."""
+    j, wave = bench_line("full")
+    _check_headline(j)
+    assert set(_BENCH_EXTRA) - set(j) == {"cpu_baseline"}, sorted(j)
+    assert j["e2e"]["unit"] == "audio-seconds/second" and j["roofline"]["launches"] > 0 and j["box_calibration"].get("mfma_tflops", 0) > 0
+    plain, plain_wave = bench_line("plain")
+    assert plain["config"] == j["config"] and plain_wave == wave

@@ -346,6 +346,19 @@ def test_bench_dump_outputs(tmp_path, monkeypatch):
     assert np.all(np.diff(s) > 0) and np.isin(s, x).all() and np.array_equal(s, np.load(tmp_path / "s2" / "waveform.npy"))
 
 
+def test_bench_full_flag_is_off_by_default():
+    """`--full` (everything the headline figure does not need: calibration / power, e2e, rooflines, CPU baseline) is an option of its
+    own, off by default; none of what it adds applies to the stub step, so the line has the same keys with and without it."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    keys = []
+    for flags in ([], ["--full"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-step", "--steps", "1", "--warmup", "0", "--seconds", "0.01",
+                            *flags], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        keys.append(sorted(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])))
+    assert keys[0] == keys[1] and not {"cpu_baseline", "roofline", "e2e", "box_calibration", "power"} & set(keys[0])
+
+
 def test_bench_refuses_missing_gpus():
     """Never a silent N = 1 line: asking for more GPUs than the box has must fail loudly (this container has none)."""
     import torch
