@@ -131,6 +131,10 @@ SIGNATURES = {
     "fd_enhance": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_enhance_ragged": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_noise_fill": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_noise_fill_at": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_enhance_chunks": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
+    "fd_normfac": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "fd_stitch_chunks": (c_int, [_P, c_ll, _P, _P, c_int, _P, c_int, _P, c_ll, _P]),
     "fd_ode_solve_seeded": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_enhance_seeded": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_enhance_seeded": (c_int, [_P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),

@@ -807,26 +807,30 @@ __global__ void output_update_kernel(const T* __restrict__ pyr, const float* __r
 // seed (noise.h).  A thread recomputes the Philox call it shares with the neighbouring frame instead of handling a frame pair: the
 // consumers below stay one element per thread like their unseeded forms (one grid, one index map), and the ~150 integer / float
 // operations per element hide behind the 24-40 bytes each of them moves (they replace an 8-byte load).
+// frame0 (int32 [B], may be null = zeros): the absolute frame of every row's first column (rows that are chunks of longer recordings).
 template <bool SEEDED>
 __device__ __forceinline__ float2 noise_elem(const float2* __restrict__ z, const unsigned long long* __restrict__ seeds, int draw, long long i,
-                                             int F, int T) {
+                                             int F, int T, const int* __restrict__ frame0 = nullptr) {
   if constexpr (SEEDED) {
     const long long row = i / T;
-    return fd_noise_at(seeds[row / F], draw, (int)(row % F), (int)(i - row * T));
+    const long long b = row / F;
+    return fd_noise_at(seeds[b], draw, (int)(row % F), (frame0 ? frame0[b] : 0) + (int)(i - row * T));
   } else {
     return z[i];
   }
 }
 
 // x0 = Y + sigma_fac * (sigma_y[f] * noise).type(complex64)   (model.py:512, :530-536); sigma is float64
+// SEEDED with frame0 (int32 [B], may be null): row b is a chunk of a longer recording that starts at frame frame0[b] of it, and the
+// noise is the recording's -- z(seed, draw, f, frame0[b] + t): two chunks that overlap start from the same noise where they do
 template <bool SEEDED>
 __global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __restrict__ noise, const unsigned long long* __restrict__ seeds,
-                                  int draw, const double* __restrict__ sigma, int sigma_n, float sigma_fac, float2* __restrict__ x0, int F,
-                                  int T, long long n) {
+                                  const int* __restrict__ frame0, int draw, const double* __restrict__ sigma, int sigma_n, float sigma_fac,
+                                  float2* __restrict__ x0, int F, int T, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const int f = (int)((i / T) % F);
     const double s = sigma[sigma_n == 1 ? 0 : f];
-    const float2 nz = noise_elem<SEEDED>(noise, seeds, draw, i, F, T), yv = Y[i];
+    const float2 nz = noise_elem<SEEDED>(noise, seeds, draw, i, F, T, frame0), yv = Y[i];
     const float nx = (float)(s * (double)nz.x), ny = (float)(s * (double)nz.y);
     float2 o = {yv.x + sigma_fac * nx, yv.y + sigma_fac * ny};
     x0[i] = o;
@@ -875,9 +879,11 @@ __global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restr
 
 // The planes draw0 .. draw0 + n_draws - 1 of the seeded noise as a buffer: out[d][b][f][t] (complex64; BITS: the two raw words of
 // every element as uint32 instead).  One thread = one frame pair = one Philox call; with an even T the pair is one 16-byte store.
+// frame0 (int32 [B], may be null = zeros): column t of row b holds absolute frame frame0[b] + t.  A Philox call serves the ABSOLUTE frames
+// (2k, 2k + 1): with an odd frame0 a thread's pair of columns straddles two calls -- (r2, r3) of the first, (r0, r1) of the next.
 template <bool BITS>
-__global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ out, const unsigned long long* __restrict__ seeds, int B, int F,
-                                                         int T, int draw0, long long npairs) {
+__global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ out, const unsigned long long* __restrict__ seeds,
+                                                         const int* __restrict__ frame0, int B, int F, int T, int draw0, long long npairs) {
   const int tp = (T + 1) >> 1;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < npairs; i += (long long)gridDim.x * 256) {
     const int t = 2 * (int)(i % tp);
@@ -886,7 +892,13 @@ __global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ ou
     const int b = (int)(q % B), d = (int)(q / B);
     unsigned r[4];
     const unsigned long long seed = seeds[b];
-    philox4x32_10((unsigned)t >> 1, (unsigned)f, (unsigned)(draw0 + d), 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
+    const unsigned ta = (unsigned)((frame0 ? frame0[b] : 0) + t);   // absolute frame of the first column
+    philox4x32_10(ta >> 1, (unsigned)f, (unsigned)(draw0 + d), 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
+    if (ta & 1u) {
+      unsigned q[4];
+      philox4x32_10((ta >> 1) + 1u, (unsigned)f, (unsigned)(draw0 + d), 0u, (unsigned)seed, (unsigned)(seed >> 32), q);
+      r[0] = r[2]; r[1] = r[3]; r[2] = q[0]; r[3] = q[1];
+    }
     float2 z0, z1;
     if constexpr (BITS) {
       z0 = float2{__uint_as_float(r[0]), __uint_as_float(r[1])};
@@ -1254,10 +1266,10 @@ int fd_init_state(const float* Y, const fd_noise_src& noise, const double* sigma
   const long long n = (long long)B * F * T;
   if (noise.seeds)
     hipLaunchKernelGGL(init_state_kernel<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)Y, (const float2*)nullptr, noise.seeds,
-                       noise.draw, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
+                       noise.frame0, noise.draw, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
   else
     hipLaunchKernelGGL(init_state_kernel<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)Y, (const float2*)noise.ptr,
-                       (const unsigned long long*)nullptr, 0, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
+                       (const unsigned long long*)nullptr, (const int*)nullptr, 0, sigma_dev, sigma_n, sigma_fac, (float2*)x0, F, T, n);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }
@@ -1274,17 +1286,80 @@ int fd_caxpy(const float* a, const fd_noise_src& q, float cq, float* dst, int B,
   return FD_OK;
 }
 
-extern "C" int fd_noise_fill(void* out, const unsigned long long* seeds, int B, int F, int T_pad, int draw0, int n_draws, int mode, void* stream) {
-  FD_REQUIRE(out && seeds, "fd_noise_fill: null pointer");
-  FD_REQUIRE(B > 0 && F > 0 && T_pad > 0 && draw0 >= 0 && n_draws > 0, "fd_noise_fill: bad shape (B=%d F=%d T_pad=%d draw0=%d n_draws=%d)", B, F, T_pad, draw0, n_draws);
-  FD_REQUIRE(mode == FD_NOISE_GAUSSIAN || mode == FD_NOISE_BITS, "fd_noise_fill: unknown mode %d", mode);
-  FD_REQUIRE((uintptr_t)out % 16 == 0, "fd_noise_fill: out must be 16-byte aligned");
+static int noise_fill_impl(const char* who, void* out, const unsigned long long* seeds, const int* frame0, int B, int F, int T_pad, int draw0, int n_draws,
+                           int mode, void* stream) {
+  FD_REQUIRE(out && seeds, "%s: null pointer", who);
+  FD_REQUIRE(B > 0 && F > 0 && T_pad > 0 && draw0 >= 0 && n_draws > 0, "%s: bad shape (B=%d F=%d T_pad=%d draw0=%d n_draws=%d)", who, B, F, T_pad, draw0, n_draws);
+  FD_REQUIRE(mode == FD_NOISE_GAUSSIAN || mode == FD_NOISE_BITS, "%s: unknown mode %d", who, mode);
+  FD_REQUIRE((uintptr_t)out % 16 == 0, "%s: out must be 16-byte aligned", who);
   const long long npairs = (long long)n_draws * B * F * ((T_pad + 1) / 2);
   const dim3 grid(grid_for(npairs, 256, 1 << 16));
   if (mode == FD_NOISE_BITS)
-    hipLaunchKernelGGL(noise_fill_kernel<true>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, B, F, T_pad, draw0, npairs);
+    hipLaunchKernelGGL(noise_fill_kernel<true>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, frame0, B, F, T_pad, draw0, npairs);
   else
-    hipLaunchKernelGGL(noise_fill_kernel<false>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, B, F, T_pad, draw0, npairs);
+    hipLaunchKernelGGL(noise_fill_kernel<false>, grid, dim3(256), 0, fd_stream(stream), (float2*)out, seeds, frame0, B, F, T_pad, draw0, npairs);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+extern "C" int fd_noise_fill(void* out, const unsigned long long* seeds, int B, int F, int T_pad, int draw0, int n_draws, int mode, void* stream) {
+  return noise_fill_impl("fd_noise_fill", out, seeds, nullptr, B, F, T_pad, draw0, n_draws, mode, stream);
+}
+
+// fd_noise_fill at absolute frames: column t of row b is frame frame0[b] + t (frame0: DEVICE int32 [B], 0 <= frame0[b], frame0[b] + T_pad
+// < 2^31 -- the caller's contract, the values live on the device; NULL = zeros = fd_noise_fill)
+extern "C" int fd_noise_fill_at(void* out, const unsigned long long* seeds, const int* frame0, int B, int F, int T_pad, int draw0, int n_draws, int mode,
+                                void* stream) {
+  return noise_fill_impl("fd_noise_fill_at", out, seeds, frame0, B, F, T_pad, draw0, n_draws, mode, stream);
+}
+
+// ---- long-form stitching: a recording's output [n] from the outputs of its overlapping rows (fd_enhance_chunks) ------------------------
+// Row r holds the recording's samples [starts[r], starts[r] + row_stride) (its tail may be unused); bounds[r - 1] = the boundary between the
+// rows r - 1 and r (ascending).  Sample i belongs to the row whose [bounds[r - 1], bounds[r]) contains it; within xfade / 2 of a boundary
+// between the rows a (earlier) and b it is a + w (b - a) with w = weights[i - (boundary - xfade / 2)], each operation rounded on its own
+// (NumPy float32 gives the same bits).  One output element per thread; an index outside a row is clamped into it (wrong tables give wrong
+// samples, never an out-of-bounds access).
+__global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ rows, long long row_stride, const int* __restrict__ starts,
+                                                     const int* __restrict__ bounds, int n_rows, const float* __restrict__ weights, int xfade,
+                                                     float* __restrict__ out, long long n) {
+#pragma clang fp contract(off)   // three roundings: without this, a + w * d is one fma (also through __fmul_rn / __fadd_rn, which inline to operators)
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n) return;
+  int lo = 0, hi = n_rows - 1;          // r = number of boundaries <= i
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((long long)bounds[mid - 1] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int r = lo, half = xfade >> 1;
+  auto at = [&](int row, long long idx) {
+    long long k = idx - starts[row];
+    k = k < 0 ? 0 : (k >= row_stride ? row_stride - 1 : k);
+    return rows[(long long)row * row_stride + k];
+  };
+  float o;
+  int a = -1;                            // the earlier row of the cross-fade that covers i, if any
+  if (r > 0 && i < (long long)bounds[r - 1] + half) a = r - 1;
+  else if (r + 1 < n_rows && i >= (long long)bounds[r] - half) a = r;
+  if (a >= 0) {
+    long long k = i - ((long long)bounds[a] - half);
+    k = k < 0 ? 0 : (k >= xfade ? xfade - 1 : k);
+    const float va = at(a, i), vb = at(a + 1, i);
+    const float d = vb - va;
+    const float p = weights[k] * d;
+    o = va + p;
+  } else {
+    o = at(r, i);
+  }
+  out[i] = o;
+}
+
+extern "C" int fd_stitch_chunks(const float* rows, long long row_stride, const int* starts, const int* bounds, int n_rows, const float* weights, int xfade,
+                                float* out, long long n, void* stream) {
+  FD_REQUIRE(rows && starts && out && n_rows >= 1 && row_stride >= 1 && n >= 1, "fd_stitch_chunks: bad arguments");
+  FD_REQUIRE(n <= 0x7fffffffll, "fd_stitch_chunks: at most 2^31 - 1 samples per recording (got %lld)", n);
+  FD_REQUIRE(n_rows == 1 || (bounds && xfade >= 0 && xfade % 2 == 0 && (xfade == 0 || weights)), "fd_stitch_chunks: several rows need bounds, an even xfade and its weights");
+  hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fd_stream(stream), rows, row_stride, starts, bounds, n_rows, weights,
+                     n_rows == 1 ? 0 : xfade, out, n);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

@@ -11,11 +11,13 @@ struct fd_temb_job {
 };
 
 // Where a [B][F][T] plane of sampler noise comes from: a caller-filled buffer (`ptr`), or the clips' seeds (DEVICE uint64 [B]) and the
-// index of the draw -- then the consuming kernel generates the plane in registers (noise.h)
+// index of the draw -- then the consuming kernel generates the plane in registers (noise.h).  frame0 (DEVICE int32 [B], seeded initial
+// state only; nullptr = zeros): the absolute frame of every row's first column -- the rows are chunks of longer recordings
 struct fd_noise_src {
   const float* ptr = nullptr;
   const unsigned long long* seeds = nullptr;
   int draw = 0;
+  const int* frame0 = nullptr;
 };
 
 struct fd_edge_args {
@@ -57,8 +59,10 @@ int fd_conv_init_attributes();
 // stft.hip
 // (fd_stft_plan / fd_stft_plan_create / fd_stft_plan_destroy: public, include/flowdec_hip.h)
 // lens: device int32 [B] per-clip sample counts of a ragged batch, or nullptr (every clip is L samples long)
+// normfac_in: device float [B] factors given by the caller (the rows are chunks of files normalised as a whole), or nullptr; when given,
+// no maximum is taken and `normfac` is not written
 int fd_stft_forward(fd_stft_plan* p, const float* y, const int* lens, int B, int L, float alpha, float beta, int normalize, float* normfac,
-                    float* Y, int T_pad, void* ws, size_t ws_bytes, hipStream_t st);
+                    float* Y, int T_pad, void* ws, size_t ws_bytes, hipStream_t st, const float* normfac_in = nullptr);
 int fd_stft_inverse(fd_stft_plan* p, const float* X, const int* lens, int B, int T, int T_pad, float alpha, float beta, const float* normfac,
                     float* y, int L, void* ws, size_t ws_bytes, hipStream_t st);
 size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop);

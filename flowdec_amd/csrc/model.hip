@@ -99,12 +99,13 @@ struct Tens {
 // Everything a captured solve bakes into its kernel arguments.  Compared field by field (a memcmp over the struct would read
 // its padding bytes).
 struct GraphKey {
-  const void *Y = nullptr, *noise = nullptr, *X = nullptr, *traj = nullptr, *ws = nullptr, *y = nullptr, *xhat = nullptr, *lens = nullptr, *seeds = nullptr;
+  const void *Y = nullptr, *noise = nullptr, *X = nullptr, *traj = nullptr, *ws = nullptr, *y = nullptr, *xhat = nullptr, *lens = nullptr, *seeds = nullptr,
+             *frame0 = nullptr, *normfac_in = nullptr;   // fd_enhance_chunks
   int B = 0, T = 0, N = 0, solver = 0, L = 0, kind = 0, normalize = 1;
   float sigma_fac = 0.f;
   fd_score_config score{};   // kind 3 only (zero otherwise)
   auto tie() const {
-    return std::tie(Y, noise, X, traj, ws, y, xhat, lens, seeds, B, T, N, solver, L, kind, normalize, sigma_fac, score.theta, score.sigma_min, score.sigma_max,
+    return std::tie(Y, noise, X, traj, ws, y, xhat, lens, seeds, frame0, normfac_in, B, T, N, solver, L, kind, normalize, sigma_fac, score.theta, score.sigma_min, score.sigma_max,
                     score.t_eps, score.snr, score.N, score.predictor, score.corrector, score.corrector_steps, score.denoise);
   }
   bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
@@ -1267,7 +1268,7 @@ extern "C" size_t fd_enhance_normfac_offset(const fd_model* m, int B, int L) {
 
 namespace {
 int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, float sigma_fac, int N, int solver, float* x_hat, int B,
-                 int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+                 int L, void* ws, size_t ws_bytes, int use_graph, void* stream, const float* normfac_in = nullptr) {
   FD_TRY(check_ready(m));
   FD_REQUIRE(y && (noise.ptr || noise.seeds) && x_hat && ws, "%s: null pointer", who);
   FD_REQUIRE(N >= 1 && solver_nfe(solver, N) > 0, "%s: bad N / solver", who);
@@ -1284,11 +1285,11 @@ int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, 
   char* rest = (char*)ws + 2 * state + fd_align(sizeof(float) * B);
   const size_t rest_bytes = ws_bytes - (2 * state + fd_align(sizeof(float) * B));
   GraphKey key; key.y = y; key.noise = noise.ptr; key.seeds = noise.seeds; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.N = N; key.solver = solver; key.kind = 2;
-  key.sigma_fac = sigma_fac; key.normalize = m->normalize;
+  key.sigma_fac = sigma_fac; key.normalize = m->normalize; key.frame0 = noise.frame0; key.normfac_in = normfac_in;
   return run_maybe_graph(m, key, use_graph != 0, st, [&]() {
-    FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st));
+    FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st, normfac_in));
     FD_TRY(ode_enqueue(m, Y, noise, sigma_fac, N, solver, X, nullptr, B, Tp, rest, rest_bytes, st));
-    FD_TRY(fd_stft_inverse(m->stft, X, lens, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac, x_hat, L, rest, rest_bytes, st));
+    FD_TRY(fd_stft_inverse(m->stft, X, lens, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac_in ? normfac_in : normfac, x_hat, L, rest, rest_bytes, st));
     return FD_OK;
   });
 }
@@ -1320,6 +1321,20 @@ extern "C" int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths
                                  float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance_seeded");
   return enhance_impl(m, "fd_enhance_seeded", y, lengths, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// Long-form: the rows are CHUNKS of longer recordings.  fd_enhance_seeded on ragged rows plus two optional device arrays: frame0 (int32 [B]:
+// the absolute frame of each row's first column -- the seeded noise is then the recording's, z(seed, 0, f, frame0[b] + t)) and normfac_in
+// (float [B]: the recording's normalisation factor from fd_normfac -- no per-row maximum is taken; the front end divides by it, the back
+// end multiplies by it, and the workspace's normfac slot is not written).  Both NULL = fd_enhance_seeded, bit for bit.  A captured graph is
+// additionally keyed on the two POINTERS.
+extern "C" int fd_enhance_chunks(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, const int* frame0,
+                                 const float* normfac_in, float sigma_fac, int N, int solver, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                                 int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_enhance_chunks");
+  FD_REQUIRE(seeds, "fd_enhance_chunks: null seeds");
+  return enhance_impl(m, "fd_enhance_chunks", y, lengths, fd_noise_src{nullptr, seeds, 0, frame0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph,
+                      stream, normfac_in);
 }
 
 // Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT.  lens (device int32 [B]) = a ragged batch

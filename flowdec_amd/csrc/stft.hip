@@ -378,7 +378,7 @@ size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop) {
 }
 
 int fd_stft_forward(fd_stft_plan* p, const float* y, const int* lens, int B, int L, float alpha, float beta, int normalize, float* normfac, float* Y,
-                    int T_pad, void* ws, size_t ws_bytes, hipStream_t st) {
+                    int T_pad, void* ws, size_t ws_bytes, hipStream_t st, const float* normfac_in) {
   const int T = 1 + L / p->hop, K = p->kpad;
   FD_REQUIRE(L > p->n_fft / 2, "stft: clip of %d samples is too short for reflect padding of %d", L, p->n_fft / 2);
   FD_REQUIRE(T_pad >= T, "stft: T_pad %d < T %d", T_pad, T);
@@ -388,8 +388,9 @@ int fd_stft_forward(fd_stft_plan* p, const float* y, const int* lens, int B, int
   const int M = B * T;
   auto mark = [&](int i) { if (p->prof) (void)hipEventRecord(p->ev[i], st); };
   mark(0);
-  hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(1024), 0, st, y, lens, L, p->n_fft, normalize, normfac);
-  hipLaunchKernelGGL(frame_kernel, dim3(grid_cap((long long)M * K)), dim3(256), 0, st, y, lens, normfac, frames, B, L, T, p->n_fft, p->hop, K);
+  if (!normfac_in) hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(1024), 0, st, y, lens, L, p->n_fft, normalize, normfac);
+  hipLaunchKernelGGL(frame_kernel, dim3(grid_cap((long long)M * K)), dim3(256), 0, st, y, lens, normfac_in ? normfac_in : normfac, frames, B, L, T,
+                     p->n_fft, p->hop, K);
   mark(1);
   FD_TRY(launch_sgemm(frames, p->Dt, spec, M, K, K, st));
   mark(2);
@@ -490,6 +491,19 @@ extern "C" int fd_decompress_istft_ragged(const fd_stft_plan* plan, const float*
   FD_REQUIRE(plan && X && lengths && y && ws && B > 0 && L > 0, "fd_decompress_istft_ragged: bad arguments");
   FD_REQUIRE(T == 1 + L / plan->hop, "fd_decompress_istft_ragged: T must be the frame count of the row length L (1 + L / hop = %d, got %d)", 1 + L / plan->hop, T);
   return fd_stft_inverse(const_cast<fd_stft_plan*>(plan), X, lengths, B, T, T_pad, alpha, beta, normfac, y, L, ws, ws_bytes, fd_stream(stream));
+}
+
+// The normalisation factor of the front end on its own (absmax_kernel's rule: max |y| over the clip's own samples, isclose(., 0) -> 1) for
+// rows of ANY length >= 1 -- a whole recording whose chunks are then enhanced with normfac_in (fd_enhance_chunks).  lengths: device int32
+// [B] or NULL (every row is L samples long); a length is clamped into [1, L].  One 1024-thread workgroup per row, as in the front end: a
+// row of an hour (690 MB) is read by ONE compute unit, once per enhance_long call ahead of the solve.  Not measured at that size and not
+// tuned: a multi-workgroup reduction (partial maxima + a second pass) is the step to take if it ever shows next to the solve.
+extern "C" int fd_normfac(const float* y, const int* lengths, int B, int L, float* normfac_out, void* stream) {
+  FD_REQUIRE(y && normfac_out && B > 0 && L > 0 && L <= 0x7fffffff - 1024, "fd_normfac: bad arguments");   // (the kernel's int index steps by 1024)
+  // n_fft = 0 makes clip_len's lower clamp 1 sample: no STFT geometry is involved here
+  hipLaunchKernelGGL(absmax_kernel, dim3(B), dim3(1024), 0, fd_stream(stream), y, lengths, L, 0, 1, normfac_out);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
 }
 
 // ---- test-level C ABI (include/flowdec_hip.h) -----------------------------------------------------------------------------------------

@@ -35,6 +35,14 @@ moves that limit: the kernels address images of any length that fits in device m
 what remains is the device memory itself.  A file whose workspace (`fd_enhance_workspace_bytes`) does not fit in the free device
 memory is skipped WITH a message, like a file over a precision's limit (`PRECISION_MAX_SECONDS`, where a precision with a shorter
 reach would say so): the exit status is then 3.
+
+Long files: `--chunk-seconds S` (default: off) lifts both limits for a FlowModel with `--rng native`.  A file with more samples than a row
+of S seconds holds (S seconds in STFT frames, rounded down to a multiple of 64, at least 64: `longform.chunk_row_frames`) is not
+subject to the length rule; it runs through `FlowModel.enhance_long` -- overlapping rows of that many frames in a workspace that does not
+grow with the file (halos of 256 frames, or a quarter of the row if that is less), seeded with the file's `clip_seed(SEED, i)` -- one file per call, with its own `--rtf` row and a message that
+names the limits it is exempt from.  `--batch-files` rows run per call; if their workspace does not fit, the file is skipped with a message like any other
+file over memory.  Every other file takes
+the paths above and gives the same bytes as without the flag.
 """
 import argparse
 import contextlib
@@ -49,6 +57,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import longform
 from .noise import clip_seed
 from .model import (BACKBONE_FINAL_NO_ATTN, OUVESDE, PRESETS, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, RegressionModel, ScoreModel,
                     WorkspaceTooLarge, from_preset)
@@ -338,6 +347,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "list from flowdec_amd.noise.clip_seed(SEED, i) (without --seed one seed is drawn from the OS and printed)")
     p.add_argument("--max-seconds", type=float, default=MAX_SECONDS,
                    help="files longer than this are skipped (default: the reference's %g s); longer clips are limited by device memory only" % MAX_SECONDS)
+    p.add_argument("--chunk-seconds", type=float, default=None,
+                   help="files longer than a row of this many seconds (in STFT frames, rounded down to a multiple of 64) are enhanced in overlapping "
+                        "rows of that length, in fixed device memory, instead of being skipped by --max-seconds; needs --rng native and a flow "
+                        "model (default: off)")
     p.add_argument("--batch-files", type=int, default=8, help="files of one T_pad bucket per native call (1 = one file per call, the reference's loop)")
     return p
 
@@ -480,16 +493,28 @@ def batchable(model, args) -> bool:
     return not isinstance(model, FlowModel) or args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast")
 
 
-def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS):
+def chunk_samples(model, args) -> Optional[int]:
+    """--chunk-seconds -> the samples of one row at the model's rate (files with more take the long-form path), None when it is off."""
+    if getattr(args, "chunk_seconds", None) is None:
+        return None
+    hop = model.feature_extractor._cfg()["hop"]
+    return longform.row_samples(longform.chunk_row_frames(args.chunk_seconds, model.sampling_rate, hop), hop)
+
+
+def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS,
+                   long_samples: Optional[int] = None):
     """Load -> the reference's length rule (enhance.py:115,139; `length_limit` = --max-seconds) -> resample to the model rate.
-    -> waveform [C, L] or None (skipped)."""
+    -> waveform [C, L] or None (skipped).  A file of more than `long_samples` samples at the model's rate (--chunk-seconds) is exempt
+    from the length rule: it runs in rows."""
     y, sr = load_wav(job.src)
     seconds = y.shape[-1] / sr
-    if seconds > length_limit:
+    if long_samples is not None and resampled_length(y.shape[-1], sr, model.sampling_rate) > long_samples:
+        pass
+    elif seconds > length_limit:
         res.n_too_long += 1
         print("Skipping file due to length:", job.src)
         return None
-    if seconds > max_seconds:
+    elif seconds > max_seconds:
         res.n_over_precision_limit += 1
         print(f"Skipping file: {seconds:.1f} s exceeds the {max_seconds:g} s limit of precision={precision} "
               f"(the length limit is {length_limit:g} s; use --precision bf16 for files up to it):", job.src)
@@ -508,11 +533,29 @@ def skip_over_memory(job: FileJob, res: RunResult, err: Exception) -> None:
 def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResult, max_seconds: float, y=None) -> None:
     """One file per native call (the reference's loop): load -> enhance (timed under --rtf) -> save.  Updates `res`.  `y`: the file's
     waveform when the caller has already loaded (and resampled) it."""
+    long_samples = chunk_samples(model, args)
     if y is None:
-        y = load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds)
+        y = load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds, long_samples)
     if y is None:
         return
     sr = model.sampling_rate
+    if long_samples is not None and y.shape[-1] > long_samples:   # --chunk-seconds: rows of one bucket, a workspace that does not grow with the file
+        row_frames = longform.chunk_row_frames(args.chunk_seconds, sr, model.feature_extractor._cfg()["hop"])
+        rows_per_call = max(args.batch_files, 1)
+        print(f"Long file: {y.shape[-1] / sr:.1f} s in rows of {row_frames} frames, {rows_per_call} per call "
+              f"(--chunk-seconds: exempt from --max-seconds and from the limit of precision={args.precision}):", job.src)
+        try:
+            with GpuTimer(args.rtf) as timer:
+                x_hat = model.enhance_long(y, N=args.N, solver=args.solver, seed=[clip_seed(args.seed, job.index)], row_frames=row_frames,
+                                           halo_frames=longform.chunk_halo_frames(row_frames), rows_per_call=rows_per_call)
+        except WorkspaceTooLarge as err:   # rows_per_call rows of --chunk-seconds do not fit: the file is skipped, the run goes on
+            skip_over_memory(job, res, err)
+            return
+        if timer.seconds is not None:
+            log.rtf(job.dst, timer.seconds, y.shape[-1] / sr)
+        save_wav(job.dst, x_hat.cpu(), sr)
+        res.n_done += 1
+        return
     # use_graph=False: every file has its own length, and a replay would not be faster anyway -- a one-clip solve is bound by the GPU,
     # not by the host's launches (profiles/r02_graph_cost.txt: eager 18.06 ms, replay 18.10 ms; capture + instantiate 2.4 ms)
     try:
@@ -527,10 +570,11 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
     res.n_done += 1
 
 
-def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length_limit: float = MAX_SECONDS):
+def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length_limit: float = MAX_SECONDS, long_samples: Optional[int] = None):
     """Buckets the pending jobs by the frame count their spectrogram pads to (from the wav HEADERS: nothing is decoded here) and cuts
     every bucket into batches of at most `batch_files` files, in work-list order.  Multi-channel files, unreadable headers and files
-    the length rule will skip go through the one-file path (their own messages).  -> list of lists of FileJob."""
+    the length rule will skip go through the one-file path (their own messages), and so do files of more than `long_samples` samples
+    (--chunk-seconds: they run in rows).  -> list of lists of FileJob."""
     from .model import padded_frames_of
     hop = model.feature_extractor._cfg()["hop"]
     buckets, singles = {}, []
@@ -538,6 +582,8 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length
         try:
             n, sr, channels = wav_info(job.src)
         except Exception:   # an unreadable file fails in its own one-file call, with the reference's behaviour (an exception)
+            singles.append([job]); continue
+        if long_samples is not None and resampled_length(n, sr, model.sampling_rate) > long_samples:
             singles.append([job]); continue
         if channels != 1 or n / sr > length_limit or batch_files <= 1:
             singles.append([job]); continue
@@ -583,7 +629,17 @@ def cli(argv=None) -> int:
 
 
 def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.chunk_seconds is not None:
+        if not args.chunk_seconds > 0:
+            parser.error("--chunk-seconds must be positive")
+        if args.rng != "native":
+            parser.error("--chunk-seconds needs --rng native: the rows of a file share the library's noise by absolute frame")
+        if args.model not in ("auto", "flow"):
+            parser.error("--chunk-seconds needs a flow model (got --model %s)" % args.model)
+        if args.solver not in ("euler", "midpoint", "heun2", "heun2_eulerlast"):
+            parser.error("--chunk-seconds needs a fixed-step --solver (euler, midpoint, heun2, heun2_eulerlast)")
     os.makedirs(args.outdir, exist_ok=True)
     if args.rng == "native" and args.seed is None:
         args.seed = int.from_bytes(os.urandom(8), "little")
@@ -592,6 +648,8 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
         print("Loading model from checkpoint...")
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model=args.model)
         print("Done loading model.")
+    if args.chunk_seconds is not None and not isinstance(model, FlowModel):
+        parser.error("--chunk-seconds needs a flow checkpoint (this one is a %s)" % type(model).__name__)
     noisy, clean = collect_files(args.files, args.single_file)
     max_seconds = min(args.max_seconds, PRECISION_MAX_SECONDS.get(args.precision, args.max_seconds))
     settings = ", ".join(f"{k}={v}" for k, v in enhance_kwargs(model, args).items()) or "one network evaluation"
@@ -601,7 +659,8 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
     suffix = f"_{args.i_min}-{args.i_max}" if args.i_max else ""
     jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
     with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None) as log:
-        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable(model, args) else 1, args.max_seconds):
+        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable(model, args) else 1, args.max_seconds,
+                                  chunk_samples(model, args)):
             if len(batch) == 1:
                 enhance_file(model, batch[0], args, log, res, max_seconds)
             else:

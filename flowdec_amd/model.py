@@ -785,6 +785,111 @@ class FlowModel(nn.Module):
             res.append(outs[b].reshape(c.shape).to(c.device))
         return res
 
+    def _long_buffers(self, B, Lrow, dev):
+        """The device arrays of `enhance_long`'s native calls.  They live as long as the shape does: a captured graph is keyed on their
+        addresses, so every group of rows of every file of that shape replays one graph."""
+        key = (B, Lrow, str(dev))
+        if getattr(self, "_io_long_key", None) != key:
+            self._io_long = dict(y=torch.zeros(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
+                                 lens=torch.empty(B, dtype=torch.int32, device=dev), seeds=torch.empty(B, dtype=torch.int64, device=dev),
+                                 frame0=torch.empty(B, dtype=torch.int32, device=dev), normfac=torch.empty(B, dtype=torch.float32, device=dev))
+            self._io_long_key = key
+        return self._io_long
+
+    @torch.no_grad()
+    @_serialized
+    def enhance_long(self, y, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, seed=None, row_frames: int = 3712,
+                     halo_frames: int = 256, xfade: Optional[int] = None, rows_per_call: int = 8, use_graph: bool = True):
+        """`enhance` for a recording of ANY length in fixed device memory (no counterpart in the reference, whose driver skips files over
+        30 s): the recording is cut into overlapping rows of `row_frames` frames (flowdec_amd.longform.plan_rows), the rows run through
+        fd_enhance_chunks in groups of at most `rows_per_call` -- one workspace of (rows_per_call, row_frames) and one hipGraph whatever
+        the length -- and fd_stitch_chunks cross-fades `xfade` samples (default 2 hops) around every boundary.
+
+        y: [L], [1, L] or [C, 1, L]; several channels are independent recordings.  The recording is normalised ONCE, by its own maximum
+        (fd_normfac; normalize_mode='none': not at all).  The noise is the library's own, addressed by the ABSOLUTE frame of the
+        recording: `seed` as in `enhance(seed=)` (an int -> channel c uses clip_seed(seed, c); C ints; an int64 / uint64 tensor [C]),
+        None draws one from torch's default generator.  Rows that overlap start from bit-identical noise in their overlap, so a seam is
+        a cross-fade of two nearly equal signals.  A recording of one row equals `enhance(y, seed=seed)` bit for bit; the result does
+        not depend on `rows_per_call`.  Fixed-step solvers only.  Returns a tensor with the shape and on the device of `y`."""
+        from . import longform, ops
+        if solver not in L.SOLVERS:
+            raise ValueError(f"enhance_long: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
+        if int(rows_per_call) < 1:
+            raise ValueError(f"enhance_long: rows_per_call must be >= 1 (got {rows_per_call})")
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
+        y3 = y
+        while y3.ndim < 3:
+            y3 = y3.unsqueeze(0)
+        if y3.ndim != 3 or y3.shape[1] != 1:
+            raise RuntimeError(f"enhance_long expects [L], [1, L] or [C, 1, L] waveforms (got {tuple(y.shape)})")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        lib = L.load()
+        h = self._sync_native()
+        cfg = self.feature_extractor._cfg()
+        hop = cfg["hop"]
+        C_, n = y3.shape[0], y3.shape[-1]
+        rows = longform.plan_rows(n, hop, row_frames, halo_frames, xfade)
+        xfade = 2 * hop if xfade is None else int(xfade)
+        R = len(rows)
+        Tp = int(lib.fd_padded_frames(lib.fd_num_frames(rows[0].length, hop)))
+        Lrow = hop * Tp - 1
+        ops.check_ragged_lengths([r.length for r in rows], Lrow, cfg["n_fft"], hop)
+        if n // hop + Tp >= 2 ** 31:
+            raise RuntimeError(f"enhance_long: {n} samples exceed the 2^31 absolute frames of the noise contract")
+        jobs = [(c, r) for c in range(C_) for r in rows]          # every channel's rows, one pool: a row's result depends on nothing else
+        n_calls = -(-len(jobs) // int(rows_per_call))
+        B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
+        file_seeds = fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist()
+        normalize = self.normalize_mode == "noisy"
+        with torch.cuda.device(dev):
+            y_dev = y3.reshape(C_, n).to(dev, torch.float32).contiguous()
+            io = self._long_buffers(B, Lrow, dev)
+            cur = torch.cuda.current_stream(dev)
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(dev)
+            side = self._side_stream
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                file_normfac = None
+                if normalize:
+                    file_normfac = torch.empty(C_, dtype=torch.float32, device=dev)
+                    L.check(lib.fd_normfac(L.ptr(y_dev), None, C_, n, L.ptr(file_normfac), L.stream()))
+                need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
+                if need == 0:
+                    raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
+                ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
+                row_out = torch.empty(len(jobs), Lrow, dtype=torch.float32, device=dev)
+                for g0 in range(0, len(jobs), B):
+                    group = jobs[g0:g0 + B]
+                    group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
+                    for b, (c, r) in enumerate(group):
+                        io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
+                        io["y"][b, r.length:].zero_()
+                    chans = torch.tensor([c for c, _ in group], dtype=torch.int64)
+                    io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
+                    io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
+                    io["seeds"].copy_(torch.tensor([file_seeds[c] for c, _ in group], dtype=torch.int64))
+                    if normalize:
+                        io["normfac"].copy_(file_normfac[chans.to(dev)])
+                    L.check(lib.fd_enhance_chunks(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["seeds"]), L.ptr(io["frame0"]),
+                                                  L.ptr(io["normfac"]) if normalize else None, float(sigma_fac), int(N), L.SOLVERS[solver],
+                                                  L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                    k = min(B, len(jobs) - g0)
+                    row_out[g0:g0 + k].copy_(io["out"][:k])
+                x_hat = torch.empty(C_, n, dtype=torch.float32, device=dev)
+                starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
+                bounds = torch.tensor([r.xfade_lo for r in rows[1:]], dtype=torch.int32).to(dev) if R > 1 else None
+                weights = torch.from_numpy(longform.stitch_weights(xfade)).to(dev) if R > 1 and xfade > 0 else None
+                for c in range(C_):
+                    L.check(lib.fd_stitch_chunks(L.ptr(row_out[c * R:(c + 1) * R]), Lrow, L.ptr(starts), L.ptr(bounds), R, L.ptr(weights),
+                                                 xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
+            cur.wait_stream(side)
+        x_hat.record_stream(cur)
+        return x_hat.reshape(y.shape).to(y.device)
+
     def _enhance_adaptive(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev, atol, rtol, method=0):
         """solver='dopri5' / 'tsit5': adaptive 5(4) pair over t_span = linspace(0, 1, N+1) (torchdyn semantics restated, unpinned);
         host-driven (one read-back per attempted step), so no hipGraph.  The realised NFE is left in `self.last_nfe`."""

@@ -417,6 +417,9 @@ int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths, const flo
  * function (NORMATIVE):
  *   - Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
  *     (s & 0xffffffff, s >> 32) and counter (t >> 1, f, d, 0) gives r0..r3.  Counter word 3 is reserved and stays 0.
+ *   - t is the ABSOLUTE frame: frame0[b] + the local frame (column) of row b, where frame0 (DEVICE int32 [B], fd_noise_fill_at /
+ *     fd_enhance_chunks) says where in a longer recording the row starts; 0 <= frame0[b] and frame0[b] + T_pad < 2^31.  Every other
+ *     entry point, and a NULL frame0, has frame0 = 0: t is the local frame.
  *   - an even t uses (ra, rb) = (r0, r1), an odd t (r2, r3).
  *   - u1 = ((ra >> 9) + 0.5) * 2^-23 in (0, 1), u2 = (rb >> 8) * 2^-24 in [0, 1): both exact in float32.
  *   - z = sqrt(-ln u1) * (cos 2 pi u2 + i sin 2 pi u2) in float32 (logf, sqrtf, sincospif(2 u2)): complex normal with
@@ -430,12 +433,42 @@ int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths, const flo
 #define FD_NOISE_BITS 1     /* out = uint32 [n_draws][B][F][T_pad][2]: the raw words (ra, rb) of every element (for tests) */
 /* The planes draw0 .. draw0 + n_draws - 1 written to `out` (16-byte aligned device memory). */
 int fd_noise_fill(void* out, const unsigned long long* seeds, int B, int F, int T_pad, int draw0, int n_draws, int mode, void* stream);
+/* The same planes at absolute frames: column t of row b holds frame frame0[b] + t, i.e. the columns [frame0[b], frame0[b] + T_pad) of an
+ * fd_noise_fill plane with a larger T_pad.  frame0 = NULL is fd_noise_fill, bit for bit. */
+int fd_noise_fill_at(void* out, const unsigned long long* seeds, const int* frame0, int B, int F, int T_pad, int draw0, int n_draws, int mode,
+                     void* stream);
 /* fd_ode_solve with x0 = Y + sigma_fac * (sigma_y * z(seeds[b], 0, f, t)). */
 int fd_ode_solve_seeded(fd_model* m, const float* Y, const unsigned long long* seeds, float sigma_fac, int N, int solver, float* X_out,
                         float* traj, int B, int T_pad, void* ws, size_t ws_bytes, int use_graph, void* stream);
 /* fd_enhance (lengths == NULL: every clip is L samples long) or fd_enhance_ragged (lengths = DEVICE int32 [B]) on seeded noise. */
 int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, float sigma_fac, int N, int solver,
                       float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* ---- Long-form: a recording of any length as overlapping rows of one (B, T_pad) bucket (planner: flowdec_amd/longform.py) ------------
+ * No counterpart in the reference, whose driver skips files over 30 s (enhance.py:115, :139).  Row r of a recording holds its samples
+ * [start_r, start_r + lengths[r]), start_r a multiple of hop, so that the row's frame grid is the recording's and frame0 = start_r / hop.
+ * fd_enhance_chunks = fd_enhance_seeded on ragged rows plus two optional DEVICE arrays:
+ *   frame0     int32 [B]: the initial state uses the recording's noise z(seeds[b], 0, f, frame0[b] + t) ("Seeded noise" above) -- rows that
+ *              overlap start from bit-identical noise in their overlap.
+ *   normfac_in float [B]: the recording's normalisation factor (fd_normfac).  The per-row maximum is not taken: the front end divides
+ *              by normfac_in[b], the back end multiplies by it; the workspace's normfac slot (fd_enhance_normfac_offset) is not written.
+ * Both NULL: fd_enhance_seeded, bit for bit.  Workspace: fd_enhance_workspace_bytes(m, B, L).  A captured graph is keyed on the POINTERS
+ * lengths, seeds, frame0 and normfac_in (their contents may change between replays: one graph serves every group of rows of a file). */
+int fd_enhance_chunks(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, const int* frame0, const float* normfac_in,
+                      float sigma_fac, int N, int solver, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* The front end's normalisation rule on its own: normfac_out[b] = max |y[b][0 .. len_b)|, 1 where that is <= 1e-8 (torch.isclose(., 0));
+ * y [B][L], lengths DEVICE int32 [B] or NULL (len_b = L); rows of ANY length 1 <= len_b <= L <= 2^31 - 1025.  One workgroup per row. */
+int fd_normfac(const float* y, const int* lengths, int B, int L, float* normfac_out, void* stream);
+/* out [n] (n < 2^31) = a recording's output from its rows' outputs.  rows [n_rows][row_stride] float32: row r holds the recording's samples
+ * from starts[r] on; bounds[r - 1] (r = 1 .. n_rows - 1, ascending) = the boundary between the rows r - 1 and r (starts, bounds: DEVICE
+ * int32; bounds may be NULL for one row).  Sample i is copied from the row whose [bounds[r - 1], bounds[r]) holds it, except in the
+ * cross-fades: for i in [bounds[r - 1] - xfade / 2, bounds[r - 1] + xfade / 2), with a / b = the earlier / later row's sample,
+ *   out[i] = a + w * (b - a),  w = weights[i - (bounds[r - 1] - xfade / 2)]
+ * -- subtraction, product and sum each rounded to float32 on its own (no fused multiply-add).  weights: DEVICE float32 [xfade], by
+ * convention w_k = 0.5 - 0.5 cos(pi (k + 0.5) / xfade) evaluated in float64 and rounded once (flowdec_amd.longform.stitch_weights); xfade
+ * even, 0 = no cross-fade.  The caller keeps the cross-fades inside both rows and apart from each other (plan_rows does); an index outside
+ * a row is clamped into it. */
+int fd_stitch_chunks(const float* rows, long long row_stride, const int* starts, const int* bounds, int n_rows, const float* weights, int xfade,
+                     float* out, long long n, void* stream);
 /* normalize_mode of the model's front end: 1 = 'noisy' (default), 0 = 'none' (model.py:52, util/other.py:70). */
 int fd_model_set_normalize(fd_model* m, int normalize);
 
