@@ -124,6 +124,9 @@ SIGNATURES = {
     "fd_ode_adaptive_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
     "fd_ode_solve_adaptive": (c_int, [_P, _P, _P, c_float, c_int, c_float, c_float, _P, _P, C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
     "fd_ode_solve_adaptive_method": (c_int, [_P, _P, _P, c_float, c_int, c_int, c_float, c_float, _P, _P, C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
+    "fd_ode_adaptive_clips_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "fd_ode_solve_adaptive_clips": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, c_float, c_float, _P, _P, C.POINTER(c_int), C.POINTER(c_int),
+                                            C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
     "fd_enhance_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
     "fd_enhance_normfac_offset": (c_size_t, [_P, c_int, c_int]),
     "fd_model_set_normalize": (c_int, [_P, c_int]),

@@ -919,19 +919,30 @@ __global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ ou
 
 // ---- adaptive Dormand-Prince driver helpers (model.hip: fd_ode_solve_adaptive) ------------------------------------
 struct fd_lincomb_args { const float2* k[7]; float c[7]; };
-// dst = cx * x + dt * sum_i c[i] * k[i]   (null k[i] / zero c[i] are skipped by the host)
-__global__ void ode_lincomb_kernel(const float2* __restrict__ x, float cx, float dt, fd_lincomb_args a, int nk, float2* __restrict__ dst, long long n) {
+// dst = cx * x + dt * sum_i c[i] * k[i]   (null k[i] / zero c[i] are skipped by the host).  One body for the batch-global launch (off = 0,
+// n = the whole state) and the per-clip launch (off = the clip's first element, n = one clip): an element's bits depend on its operands only
+__device__ __forceinline__ void ode_lincomb_body(const float2* __restrict__ x, float cx, float dt, const fd_lincomb_args& a, int nk, float2* __restrict__ dst,
+                                                 long long off, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float sx = 0.f, sy = 0.f;
-    for (int j = 0; j < nk; ++j) { const float2 kv = a.k[j][i]; sx = fmaf(a.c[j], kv.x, sx); sy = fmaf(a.c[j], kv.y, sy); }
+    for (int j = 0; j < nk; ++j) { const float2 kv = a.k[j][off + i]; sx = fmaf(a.c[j], kv.x, sx); sy = fmaf(a.c[j], kv.y, sy); }
     float2 o = {dt * sx, dt * sy};
-    if (cx != 0.f) { const float2 xv = x[i]; o.x = fmaf(cx, xv.x, o.x); o.y = fmaf(cx, xv.y, o.y); }
-    dst[i] = o;
+    if (cx != 0.f) { const float2 xv = x[off + i]; o.x = fmaf(cx, xv.x, o.x); o.y = fmaf(cx, xv.y, o.y); }
+    dst[off + i] = o;
   }
 }
-// partial[block] = sum over the block's elements of |p - q|^2 / (atol + rtol * max(|r|, |s|))^2   (complex moduli; q may be null)
-__global__ __launch_bounds__(256) void ode_scaled_sq_kernel(const float2* __restrict__ p, const float2* __restrict__ q, const float2* __restrict__ r,
-                                                            const float2* __restrict__ s, float atol, float rtol, double* __restrict__ partial, long long n) {
+__global__ void ode_lincomb_kernel(const float2* __restrict__ x, float cx, float dt, fd_lincomb_args a, int nk, float2* __restrict__ dst, long long n) {
+  ode_lincomb_body(x, cx, dt, a, nk, dst, 0, n);
+}
+// per-clip step sizes: grid (blocks, B); clip blockIdx.y = elements [b n, (b + 1) n) takes dt[b] from device memory
+__global__ void ode_lincomb_clips_kernel(const float2* __restrict__ x, float cx, const float* __restrict__ dt, fd_lincomb_args a, int nk,
+                                         float2* __restrict__ dst, long long n) {
+  ode_lincomb_body(x, cx, dt[blockIdx.y], a, nk, dst, (long long)blockIdx.y * n, n);
+}
+// *out = sum over the block's elements of |p - q|^2 / (atol + rtol * max(|r|, |s|))^2   (complex moduli; q may be null).  The partition
+// over (gridDim.x, 256 threads), the wave reduction and the red[0..3] order are the same whichever launch calls it
+__device__ __forceinline__ void ode_scaled_sq_body(const float2* __restrict__ p, const float2* __restrict__ q, const float2* __restrict__ r,
+                                                   const float2* __restrict__ s, float atol, float rtol, double* __restrict__ out, long long n) {
   double acc = 0.0;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float2 d = p[i];
@@ -945,7 +956,36 @@ __global__ __launch_bounds__(256) void ode_scaled_sq_kernel(const float2* __rest
   __shared__ double red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if (threadIdx.x == 0) *out = red[0] + red[1] + red[2] + red[3];
+}
+// partial[block]: one sum over the whole [n] state
+__global__ __launch_bounds__(256) void ode_scaled_sq_kernel(const float2* __restrict__ p, const float2* __restrict__ q, const float2* __restrict__ r,
+                                                            const float2* __restrict__ s, float atol, float rtol, double* __restrict__ partial, long long n) {
+  ode_scaled_sq_body(p, q, r, s, atol, rtol, partial + blockIdx.x, n);
+}
+// partial[b][block]: grid (blocks, B); block (j, b) is block j of the one-clip launch on clip b's n elements
+__global__ __launch_bounds__(256) void ode_scaled_sq_clips_kernel(const float2* __restrict__ p, const float2* __restrict__ q, const float2* __restrict__ r,
+                                                                  const float2* __restrict__ s, float atol, float rtol, double* __restrict__ partial,
+                                                                  long long n) {
+  const long long off = (long long)blockIdx.y * n;
+  ode_scaled_sq_body(p + off, q ? q + off : nullptr, r + off, s + off, atol, rtol, partial + (size_t)blockIdx.y * gridDim.x + blockIdx.x, n);
+}
+// masked commit of an attempted step: for every clip b (= blockIdx.y) with accept[b] != 0, x <- x_new and k0 <- k6 (the FSAL stage); a clip
+// that landed on checkpoint ckpt[b] > 0 also writes its plane to traj[ckpt[b]][b] (traj may be null).  Other clips are not touched.
+__global__ void ode_commit_clips_kernel(const int* __restrict__ accept, const int* __restrict__ ckpt, const float2* __restrict__ x_new,
+                                        const float2* __restrict__ k6, float2* __restrict__ x, float2* __restrict__ k0, float2* __restrict__ traj,
+                                        int B, long long n) {
+  const int b = blockIdx.y;
+  if (!accept[b]) return;
+  const long long off = (long long)b * n;
+  const int c = ckpt[b];
+  float2* tr = (traj && c > 0) ? traj + ((long long)c * B + b) * n : nullptr;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float2 v = x_new[off + i];
+    x[off + i] = v;
+    k0[off + i] = k6[off + i];
+    if (tr) tr[i] = v;
+  }
 }
 
 inline int grid_for(long long n, int per_block = 256, int cap = 1 << 20) {
@@ -1379,6 +1419,34 @@ int fd_ode_scaled_sq(const float* p, const float* q, const float* r, const float
                      long long n, hipStream_t st) {
   hipLaunchKernelGGL(ode_scaled_sq_kernel, dim3(nblocks), dim3(256), 0, st, (const float2*)p, (const float2*)q, (const float2*)r, (const float2*)s,
                      atol, rtol, partial, n);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+int fd_ode_lincomb_clips(const float* x, float cx, const float* dt_dev, const float* const* k, const float* c, int nk, float* dst, int B, long long n,
+                         hipStream_t st) {
+  fd_lincomb_args a;
+  int m = 0;
+  for (int j = 0; j < nk && j < 7; ++j)
+    if (k[j] && c[j] != 0.f) { a.k[m] = (const float2*)k[j]; a.c[m] = c[j]; ++m; }
+  for (int j = m; j < 7; ++j) { a.k[j] = nullptr; a.c[j] = 0.f; }
+  hipLaunchKernelGGL(ode_lincomb_clips_kernel, dim3(grid_for(n, 256, 8192), B), dim3(256), 0, st, (const float2*)x, cx, dt_dev, a, m, (float2*)dst, n);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+int fd_ode_scaled_sq_clips(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks, int B,
+                           long long n, hipStream_t st) {
+  hipLaunchKernelGGL(ode_scaled_sq_clips_kernel, dim3(nblocks, B), dim3(256), 0, st, (const float2*)p, (const float2*)q, (const float2*)r,
+                     (const float2*)s, atol, rtol, partial, n);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+int fd_ode_commit_clips(const int* accept, const int* ckpt, const float* x_new, const float* k6, float* x, float* k0, float* traj, int B, long long n,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(ode_commit_clips_kernel, dim3(grid_for(n, 256, 8192), B), dim3(256), 0, st, accept, ckpt, (const float2*)x_new, (const float2*)k6,
+                     (float2*)x, (float2*)k0, (float2*)traj, B, n);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

@@ -52,6 +52,14 @@ int fd_combine_tiles(int H, int W);
 int fd_ode_lincomb(const float* x, float cx, float dt, const float* const* k, const float* c, int nk, float* dst, long long n, hipStream_t st);
 int fd_ode_scaled_sq(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks,
                      long long n, hipStream_t st);
+// the same per clip of a [B][n] state: dt_dev = DEVICE float [B]; partial = [B][nblocks], row b = what fd_ode_scaled_sq gives on clip b alone
+int fd_ode_lincomb_clips(const float* x, float cx, const float* dt_dev, const float* const* k, const float* c, int nk, float* dst, int B, long long n,
+                         hipStream_t st);
+int fd_ode_scaled_sq_clips(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks, int B,
+                           long long n, hipStream_t st);
+// clips with accept[b] != 0 (DEVICE int32 [B]): x <- x_new, k0 <- k6, and traj[ckpt[b]][b] <- x_new where ckpt[b] > 0 and traj is given
+int fd_ode_commit_clips(const int* accept, const int* ckpt, const float* x_new, const float* k6, float* x, float* k0, float* traj, int B, long long n,
+                        hipStream_t st);
 // dst = a + cq * q, q = a [B][F][T] plane of noise
 int fd_caxpy(const float* a, const fd_noise_src& q, float cq, float* dst, int B, int F, int T, hipStream_t st);
 // conv_mfma.hip

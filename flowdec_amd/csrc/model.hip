@@ -153,6 +153,7 @@ struct fd_model {
   size_t ev_fir_used = 0;
   double prof_fir_bytes = 0.0;
   static constexpr int MAX_NT = 256;
+  void* pin_clips = nullptr;        // pinned host memory of fd_ode_solve_adaptive_clips (per-attempt table + error partials), made at its first call
   // One enqueueing call at a time per model: the entry points below share the model's scratch (time-embedding biases, graph cache,
   // side stream, profiling events).  A second thread entering while one is inside gets FD_EBUSY instead of corrupting that state;
   // callers that want concurrency create one fd_model per thread (weights are ~50 MB).  The reference's own native ops are
@@ -893,6 +894,7 @@ extern "C" void fd_model_destroy(fd_model* m) {
   for (auto& e : m->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : m->ev_fir) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   fd_stft_plan_destroy(m->stft);
+  if (m->pin_clips) (void)hipHostFree(m->pin_clips);
   if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
   if (m->ev_join) (void)hipEventDestroy(m->ev_join);
   if (m->side) (void)hipStreamDestroy(m->side);
@@ -1133,6 +1135,65 @@ size_t adaptive_ws_bytes(const fd_model* m, int B, int T) {
   const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * T);
   return 10 * state + fd_align(sizeof(double) * DP_NORM_BLOCKS) + forward_ws_bytes(m, B, T);
 }
+struct Tableau { const double* C; const double (*A)[6]; const double* E; };
+Tableau adaptive_tableau(int method) { return method == FD_ADAPTIVE_TSIT5 ? Tableau{TS_C, TS_A, TS_E} : Tableau{DP_C, DP_A, DP_E}; }
+
+// The step-size controller of ONE solve over t_span `ts` (torchdyn's `_adaptive_odeint` restated, oracle odeint_adaptive): host scalars
+// only.  fd_ode_solve_adaptive_method drives the whole batch with one instance, fd_ode_solve_adaptive_clips every clip with its own --
+// the only implementation of this arithmetic, so that a clip of a per-clip batch takes the decisions of the one-clip call.
+struct StepCtl {
+  float t = 0.f, dt = 0.f, dt_old = 0.f;
+  bool flag = false;
+  int ckpt = 0;
+  // initial step (Hairer): h0 = 0.01 d0 / d1, one explicit Euler probe at t + h0, h1 = (0.01 / max(d1, d2))^(1/6)
+  static double probe_step(double d0, double d1) { return (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1; }
+  float probe_time(double h0) const { return t + (float)h0; }
+  void first_step(double h0, double d1, double d2) {   // d2 = the norm of k(t + h0) - k(t), not yet divided by h0
+    d2 /= h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 6.0);
+    dt = (float)fmin(100.0 * h0, h1);
+  }
+  bool active(const std::vector<float>& ts, int N) const { return t < ts[N]; }
+  // the step to attempt (left in dt): clamped to the end of the span, shortened to land on the next checkpoint
+  void begin(const std::vector<float>& ts, int N) {
+    const float T = ts[N];
+    if (t + dt > T) dt = T - t;
+    flag = false;
+    dt_old = dt;
+    if (ckpt < N && t + dt > ts[ckpt + 1]) { dt_old = dt; flag = true; dt = ts[ckpt + 1] - t; }
+  }
+  float stage_time(double c) const { return t + (float)c * dt; }
+  // after the attempt: accept iff ratio <= 1 (-> true; *landed = the checkpoint the step reached, or 0), then the next step size
+  bool end(double ratio, const std::vector<float>& ts, int N, int* landed) {
+    const bool accept = ratio <= 1.0;
+    *landed = 0;
+    if (accept) {
+      t = t + dt;
+      if (ckpt < N && fabs((double)t - (double)ts[ckpt + 1]) <= 1e-7) {
+        t = ts[ckpt + 1];
+        *landed = ++ckpt;
+      }
+    }
+    if (flag) dt = dt_old - dt;
+    if (ratio == 0.0) dt = dt * 10.f;
+    else {
+      const double minf = ratio < 1.0 ? 1.0 : 0.2;
+      dt = (float)((double)dt * fmin(10.0, fmax(0.9 / pow(ratio, 1.0 / 5.0), minf)));
+    }
+    return accept;
+  }
+};
+constexpr int ADAPTIVE_MAX_ATTEMPTS = 100000;
+
+// per-clip control: the host table of one attempt, copied to the device in one piece.  Rows of B 32-bit words: dt, the six stage times
+// (row 1 doubles as the time of the two initial evaluations), and the commit of the PREVIOUS attempt (accept flag, checkpoint index)
+enum { TAB_DT = 0, TAB_T1 = 1, TAB_ACCEPT = 7, TAB_CKPT = 8, TAB_ROWS = 9 };
+size_t clips_tab_bytes(int B) { return fd_align(sizeof(float) * TAB_ROWS * (size_t)B); }
+size_t clips_partial_bytes(int B) { return fd_align(sizeof(double) * DP_NORM_BLOCKS * (size_t)B); }
+size_t adaptive_clips_ws_bytes(const fd_model* m, int B, int T) {
+  const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * T);
+  return 10 * state + clips_partial_bytes(B) + clips_tab_bytes(B) + forward_ws_bytes(m, B, T);
+}
 }  // namespace
 
 extern "C" size_t fd_ode_adaptive_workspace_bytes(const fd_model* m, int B, int T_pad) {
@@ -1151,9 +1212,7 @@ extern "C" int fd_ode_solve_adaptive_method(fd_model* m, const float* Y, const f
                                             float* X_out, float* traj, int* nfe_out, int B, int T_pad, void* ws, size_t ws_bytes, void* stream) {
   FD_MODEL_ENTER(m, "fd_ode_solve_adaptive");
   FD_REQUIRE(method == FD_ADAPTIVE_DOPRI5 || method == FD_ADAPTIVE_TSIT5, "fd_ode_solve_adaptive: unknown method id %d", method);
-  const double* const TB_C = method == FD_ADAPTIVE_TSIT5 ? TS_C : DP_C;
-  const double (*const TB_A)[6] = method == FD_ADAPTIVE_TSIT5 ? TS_A : DP_A;
-  const double* const TB_E = method == FD_ADAPTIVE_TSIT5 ? TS_E : DP_E;
+  const Tableau tb = adaptive_tableau(method);
   FD_TRY(check_ready(m));
   FD_REQUIRE(Y && noise && X_out && ws, "fd_ode_solve_adaptive: null pointer");
   FD_REQUIRE(N >= 1 && atol > 0.f && rtol >= 0.f, "fd_ode_solve_adaptive: need N >= 1, atol > 0, rtol >= 0");
@@ -1190,64 +1249,192 @@ extern "C" int fd_ode_solve_adaptive_method(fd_model* m, const float* Y, const f
   FD_TRY(fd_init_state(Y, fd_noise_src{noise}, m->sigma_dev, m->sigma_n, sigma_fac, x, B, m->n_freq, T_pad, st));
   if (traj) FD_HIP(hipMemcpyAsync(traj, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
   const std::vector<float> ts = t_span_linspace(N);
-  float t = ts[0];
-  const float T = ts[N];
-  FD_TRY(eval(x, t, k[0]));
-  // initial step (Hairer): h0 = 0.01 d0 / d1, one explicit Euler probe, h1 = (0.01 / max(d1, d2))^(1/6)
+  StepCtl c;
+  c.t = ts[0];
+  FD_TRY(eval(x, c.t, k[0]));
   double d0, d1, d2;
   FD_TRY(norm(x, nullptr, x, x, &d0));
   FD_TRY(norm(k[0], nullptr, x, x, &d1));
-  const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  const double h0 = StepCtl::probe_step(d0, d1);
   {
     const float* kk[1] = {k[0]}; const float cc[1] = {1.f};
     FD_TRY(fd_ode_lincomb(x, 1.f, (float)h0, kk, cc, 1, x_new, (long long)nstate, st));
-    FD_TRY(eval(x_new, t + (float)h0, k[1]));
+    FD_TRY(eval(x_new, c.probe_time(h0), k[1]));
     FD_TRY(norm(k[1], k[0], x, x, &d2));
-    d2 /= h0;
   }
-  const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 6.0);
-  float dt = (float)fmin(100.0 * h0, h1);
-  int ckpt = 0, steps = 0;
-  while (t < T) {
-    if (++steps > 100000) return fd_set_error(FD_ERUNTIME, "fd_ode_solve_adaptive: step limit reached (dt = %g at t = %g)", (double)dt, (double)t);
-    if (t + dt > T) dt = T - t;
-    bool flag = false;
-    float dt_old = dt;
-    if (ckpt < N && t + dt > ts[ckpt + 1]) { dt_old = dt; flag = true; dt = ts[ckpt + 1] - t; }
+  c.first_step(h0, d1, d2);
+  int steps = 0;
+  while (c.active(ts, N)) {
+    if (++steps > ADAPTIVE_MAX_ATTEMPTS)
+      return fd_set_error(FD_ERUNTIME, "fd_ode_solve_adaptive: step limit reached (dt = %g at t = %g)", (double)c.dt, (double)c.t);
+    c.begin(ts, N);
     for (int s = 1; s < 7; ++s) {                                    // stages 2..7; stage 7 is evaluated at the 5th-order solution (FSAL)
       const float* kk[6]; float cc[6];
-      for (int j = 0; j < s; ++j) { kk[j] = k[j]; cc[j] = (float)TB_A[s][j]; }
+      for (int j = 0; j < s; ++j) { kk[j] = k[j]; cc[j] = (float)tb.A[s][j]; }
       float* xs = s == 6 ? x_new : err;                              // `err` doubles as the stage input buffer
-      FD_TRY(fd_ode_lincomb(x, 1.f, dt, kk, cc, s, xs, (long long)nstate, st));
-      FD_TRY(eval(xs, t + (float)TB_C[s] * dt, k[s]));
+      FD_TRY(fd_ode_lincomb(x, 1.f, c.dt, kk, cc, s, xs, (long long)nstate, st));
+      FD_TRY(eval(xs, c.stage_time(tb.C[s]), k[s]));
     }
     {
       const float* kk[7]; float cc[7];
-      for (int j = 0; j < 7; ++j) { kk[j] = k[j]; cc[j] = (float)TB_E[j]; }
-      FD_TRY(fd_ode_lincomb(x, 0.f, dt, kk, cc, 7, err, (long long)nstate, st));
+      for (int j = 0; j < 7; ++j) { kk[j] = k[j]; cc[j] = (float)tb.E[j]; }
+      FD_TRY(fd_ode_lincomb(x, 0.f, c.dt, kk, cc, 7, err, (long long)nstate, st));
     }
     double ratio;
     FD_TRY(norm(err, nullptr, x, x_new, &ratio));
-    if (ratio <= 1.0) {
-      t = t + dt;
+    int landed;
+    if (c.end(ratio, ts, N, &landed)) {
       std::swap(x, x_new);
       std::swap(k[0], k[6]);
-      if (ckpt < N && fabs((double)t - (double)ts[ckpt + 1]) <= 1e-7) {
-        t = ts[ckpt + 1];
-        ++ckpt;
-        if (traj) FD_HIP(hipMemcpyAsync(traj + 2 * nstate * ckpt, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
-      }
-    }
-    if (flag) dt = dt_old - dt;
-    if (ratio == 0.0) dt = dt * 10.f;
-    else {
-      const double minf = ratio < 1.0 ? 1.0 : 0.2;
-      dt = (float)((double)dt * fmin(10.0, fmax(0.9 / pow(ratio, 1.0 / 5.0), minf)));
+      if (landed && traj) FD_HIP(hipMemcpyAsync(traj + 2 * nstate * landed, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
     }
   }
   FD_HIP(hipMemcpyAsync(X_out, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
   FD_HIP(hipStreamSynchronize(st));
   if (nfe_out) *nfe_out = nfe;
+  return FD_OK;
+}
+
+// ---- the same solvers with PER-CLIP step control: clip b of the batch takes the steps, and gives the bits, of the B = 1 call above on
+// that clip.  Every clip has its own controller (StepCtl); the device side reads the clips' step sizes, stage times and commit flags from
+// one small table per attempt.  A clip that has reached t = 1 rides along with dt = 0 until the slowest clip is done.
+extern "C" size_t fd_ode_adaptive_clips_workspace_bytes(const fd_model* m, int B, int T_pad) {
+  if (!m || B > fd_model::MAX_NT || check_shape(m, B, T_pad) != FD_OK) return 0;
+  return adaptive_clips_ws_bytes(m, B, T_pad);
+}
+
+extern "C" int fd_ode_solve_adaptive_clips(fd_model* m, const float* Y, const float* noise, const unsigned long long* seeds, float sigma_fac, int N,
+                                           int method, float atol, float rtol, float* X_out, float* traj, int* nfe_out, int* rejected_out,
+                                           int* evals_out, int B, int T_pad, void* ws, size_t ws_bytes, void* stream) {
+  FD_MODEL_ENTER(m, "fd_ode_solve_adaptive_clips");
+  FD_REQUIRE(method == FD_ADAPTIVE_DOPRI5 || method == FD_ADAPTIVE_TSIT5, "fd_ode_solve_adaptive_clips: unknown method id %d", method);
+  const Tableau tb = adaptive_tableau(method);
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(Y && X_out && ws && nfe_out, "fd_ode_solve_adaptive_clips: null pointer");
+  FD_REQUIRE((noise != nullptr) != (seeds != nullptr), "fd_ode_solve_adaptive_clips: give exactly one of noise and seeds");
+  FD_REQUIRE(N >= 1 && atol > 0.f && rtol >= 0.f, "fd_ode_solve_adaptive_clips: need N >= 1, atol > 0, rtol >= 0");
+  FD_REQUIRE(B <= fd_model::MAX_NT, "fd_ode_solve_adaptive_clips: at most %d clips per call (got %d)", fd_model::MAX_NT, B);
+  FD_TRY(check_shape(m, B, T_pad));
+  const size_t need = adaptive_clips_ws_bytes(m, B, T_pad);
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_ode_solve_adaptive_clips: workspace %zu < required %zu bytes", ws_bytes, need);
+  if (!m->pin_clips) FD_HIP(hipHostMalloc(&m->pin_clips, clips_tab_bytes(fd_model::MAX_NT) + clips_partial_bytes(fd_model::MAX_NT), hipHostMallocDefault));
+  hipStream_t st = fd_stream(stream);
+  const size_t nclip = (size_t)m->n_freq * T_pad, nstate = (size_t)B * nclip;
+  const size_t state = fd_align(sizeof(float) * 2 * nstate);
+  char* base = (char*)ws;
+  float* x = (float*)base; float* x_new = (float*)(base + state); float* err = (float*)(base + 2 * state);
+  float* k[7];
+  for (int i = 0; i < 7; ++i) k[i] = (float*)(base + (3 + i) * state);
+  const size_t head = 10 * state + clips_partial_bytes(B) + clips_tab_bytes(B);
+  double* partial = (double*)(base + 10 * state);
+  float* tab_dev = (float*)(base + 10 * state + clips_partial_bytes(B));
+  void* fws = base + head;
+  const size_t fws_bytes = ws_bytes - head;
+  // pinned host mirrors: free to rewrite after every synchronisation (each copy from / to them is followed by one before the next write)
+  uint32_t* tab = (uint32_t*)m->pin_clips;   // [TAB_ROWS][B] words: floats by bit pattern, flags as integers
+  auto set_f = [&](int row, int b, float v) { memcpy(&tab[(size_t)row * B + b], &v, sizeof v); };
+  auto set_i = [&](int row, int b, int v) { tab[(size_t)row * B + b] = (uint32_t)v; };
+  const double* host_partial = (const double*)((char*)m->pin_clips + clips_tab_bytes(fd_model::MAX_NT));
+  const float* dt_dev = tab_dev + (size_t)TAB_DT * B;
+  const int* accept_dev = (const int*)tab_dev + (size_t)TAB_ACCEPT * B;
+  const int* ckpt_dev = (const int*)tab_dev + (size_t)TAB_CKPT * B;
+  auto upload = [&]() {
+    FD_HIP(hipMemcpyAsync(tab_dev, tab, sizeof(float) * TAB_ROWS * (size_t)B, hipMemcpyHostToDevice, st));
+    return FD_OK;
+  };
+  int evals = 0;
+  auto eval = [&](const float* xin, int row, float* kout) {   // clip b at time tab[row][b]
+    OutSpec os; os.dst = kout; os.coef = 1.f;
+    ++evals;
+    return forward_call(m, xin, Y, tab_dev + (size_t)row * B, 0.f, B, os, B, T_pad, fws, fws_bytes, st);
+  };
+  // the Hairer norm of the one-clip call, clip by clip: the clip's DP_NORM_BLOCKS partials summed in index order
+  std::vector<double> d0(B), d1(B), d2(B), h0(B), ratio(B);
+  auto norm = [&](const float* p_, const float* q_, const float* r_, const float* s_, std::vector<double>& out) {
+    FD_TRY(fd_ode_scaled_sq_clips(p_, q_, r_, s_, atol, rtol, partial, DP_NORM_BLOCKS, B, (long long)nclip, st));
+    FD_HIP(hipMemcpyAsync((void*)host_partial, partial, sizeof(double) * DP_NORM_BLOCKS * (size_t)B, hipMemcpyDeviceToHost, st));
+    FD_HIP(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) {
+      double acc = 0.0;
+      for (int j = 0; j < DP_NORM_BLOCKS; ++j) acc += host_partial[(size_t)b * DP_NORM_BLOCKS + j];
+      out[b] = sqrt(acc / (double)nclip);
+    }
+    return FD_OK;
+  };
+  const fd_noise_src src = seeds ? fd_noise_src{nullptr, seeds, 0} : fd_noise_src{noise};
+  FD_TRY(fd_init_state(Y, src, m->sigma_dev, m->sigma_n, sigma_fac, x, B, m->n_freq, T_pad, st));
+  if (traj) FD_HIP(hipMemcpyAsync(traj, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
+  const std::vector<float> ts = t_span_linspace(N);
+  std::vector<StepCtl> c(B);
+  std::vector<int> nfe(B, 0), rejected(B, 0), accept(B, 0), landed(B, 0);
+  std::vector<char> act(B, 0);
+  for (int i = 0; i < TAB_ROWS * B; ++i) tab[i] = 0u;
+  for (int b = 0; b < B; ++b) { c[b].t = ts[0]; set_f(TAB_T1, b, c[b].t); }
+  FD_TRY(upload());
+  FD_TRY(eval(x, TAB_T1, k[0]));
+  FD_TRY(norm(x, nullptr, x, x, d0));
+  FD_TRY(norm(k[0], nullptr, x, x, d1));
+  for (int b = 0; b < B; ++b) {
+    h0[b] = StepCtl::probe_step(d0[b], d1[b]);
+    set_f(TAB_DT, b, (float)h0[b]);
+    set_f(TAB_T1, b, c[b].probe_time(h0[b]));
+  }
+  FD_TRY(upload());
+  {
+    const float* kk[1] = {k[0]}; const float cc[1] = {1.f};
+    FD_TRY(fd_ode_lincomb_clips(x, 1.f, dt_dev, kk, cc, 1, x_new, B, (long long)nclip, st));
+    FD_TRY(eval(x_new, TAB_T1, k[1]));
+    FD_TRY(norm(k[1], k[0], x, x, d2));
+  }
+  for (int b = 0; b < B; ++b) { c[b].first_step(h0[b], d1[b], d2[b]); nfe[b] = 2; }
+  int steps = 0;
+  bool pending = false;   // the previous attempt's accepted clips still wait for their commit
+  for (;;) {
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+      act[b] = c[b].active(ts, N);
+      any = any || act[b];
+      if (act[b]) c[b].begin(ts, N);
+      set_f(TAB_DT, b, act[b] ? c[b].dt : 0.f);                      // a finished clip: dt = 0, evaluated at its final time, never committed
+      for (int s = 1; s < 7; ++s) set_f(TAB_T1 + s - 1, b, act[b] ? c[b].stage_time(tb.C[s]) : c[b].t);
+      set_i(TAB_ACCEPT, b, accept[b]);
+      set_i(TAB_CKPT, b, landed[b]);
+    }
+    if (!any && !pending) break;
+    FD_TRY(upload());
+    if (pending) FD_TRY(fd_ode_commit_clips(accept_dev, ckpt_dev, x_new, k[6], x, k[0], traj, B, (long long)nclip, st));
+    if (!any) break;
+    if (++steps > ADAPTIVE_MAX_ATTEMPTS) {
+      int b = 0;
+      while (!act[b]) ++b;
+      return fd_set_error(FD_ERUNTIME, "fd_ode_solve_adaptive_clips: step limit reached (clip %d: dt = %g at t = %g)", b, (double)c[b].dt, (double)c[b].t);
+    }
+    for (int s = 1; s < 7; ++s) {
+      const float* kk[6]; float cc[6];
+      for (int j = 0; j < s; ++j) { kk[j] = k[j]; cc[j] = (float)tb.A[s][j]; }
+      float* xs = s == 6 ? x_new : err;
+      FD_TRY(fd_ode_lincomb_clips(x, 1.f, dt_dev, kk, cc, s, xs, B, (long long)nclip, st));
+      FD_TRY(eval(xs, TAB_T1 + s - 1, k[s]));
+    }
+    {
+      const float* kk[7]; float cc[7];
+      for (int j = 0; j < 7; ++j) { kk[j] = k[j]; cc[j] = (float)tb.E[j]; }
+      FD_TRY(fd_ode_lincomb_clips(x, 0.f, dt_dev, kk, cc, 7, err, B, (long long)nclip, st));
+    }
+    FD_TRY(norm(err, nullptr, x, x_new, ratio));
+    pending = false;
+    for (int b = 0; b < B; ++b) {
+      accept[b] = landed[b] = 0;
+      if (!act[b]) continue;                                        // finished before this attempt
+      nfe[b] += 6;
+      accept[b] = c[b].end(ratio[b], ts, N, &landed[b]) ? 1 : 0;
+      if (accept[b]) pending = true; else ++rejected[b];
+    }
+  }
+  FD_HIP(hipMemcpyAsync(X_out, x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
+  FD_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) { nfe_out[b] = nfe[b]; if (rejected_out) rejected_out[b] = rejected[b]; }
+  if (evals_out) *evals_out = evals;
   return FD_OK;
 }
 

@@ -99,7 +99,7 @@ def clip_noise(seed: int, index: int, shape, device) -> torch.Tensor:
 
 def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", noise: Optional[torch.Tensor] = None,
                     seed: Optional[int] = None, generator: Optional[torch.Generator] = None, group=None, always_gather: bool = False,
-                    stats: Optional[dict] = None, rng: str = "torch", **enhance_kwargs) -> torch.Tensor:
+                    stats: Optional[dict] = None, rng: str = "torch", step_control: Optional[str] = None, **enhance_kwargs) -> torch.Tensor:
     """`model.enhance(y, N=N, solver=solver)` for a global batch y [B, 1, L] sharded by clip over the ranks of `group`;
     every rank returns all B enhanced waveforms [B, 1, L] on y's device.  Result == the single-process call, bit for bit:
 
@@ -111,6 +111,10 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
       generator=  one generator seeded IDENTICALLY on every rank: the full [B, ...] noise is drawn and sliced, which equals
                   `model.enhance(y, generator=g)` of a single process (costs B x 1.5 MB per second of audio of device memory).
 
+    The adaptive solvers ('dopri5', 'tsit5') keep that promise with step_control='clip' only (every clip under its own step controller,
+    `FlowModel.enhance`): the default controller takes one error ratio over a rank's whole shard, so its result depends on the sharding.
+    `step_control` is forwarded on every noise path.
+
     y may live on the host (pinned or not): only this rank's rows are copied to the model's device, and the gathered result
     is copied back -- the "H2D of waveform -> D2H of waveform" path of SURVEY 8(d).  `stats`, if given, receives
     {"local_s", "gather_s"} host-clock seconds (it synchronises the device, use it for measurements only)."""
@@ -121,6 +125,8 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
         raise ValueError(f"rng must be 'torch' or 'native' (got {rng!r})")
     if rng == "native" and (noise is not None or generator is not None):
         raise ValueError("rng='native' draws from seed=: it takes neither noise= nor generator=")
+    if step_control is not None:
+        enhance_kwargs = dict(enhance_kwargs, step_control=step_control)
     world, rank = _world(group)
     B, Lw = y.shape[0], y.shape[-1]
     lo, hi = shard_range(B, rank, world)

@@ -30,6 +30,11 @@ of a file does not depend on the batching (`--batch-files 1` = the reference's l
 own, generated on the GPU from `flowdec_amd.noise.clip_seed(S, i)` (no collisions between (S, i + 1) and (S + 1, i)).  Under `--rtf` a batch is timed as a whole and
 its time is split over its files in proportion to their duration (every file of a batch gets the batch's rtf).
 
+Adaptive solvers: `--solver dopri5` / `tsit5` accept or reject a step on one error ratio over the whole native call, so by default
+(`--step-control batch`) a flow model runs them one file per call.  `--step-control clip` gives every file its own step controller
+(`FlowModel.enhance_batch(step_control='clip')` -> fd_ode_solve_adaptive_clips): the files are bucketed and batched like everything
+else, and every file's waveform is still the one-file result, bit for bit.
+
 Length limit: the reference skips files longer than 30 s; so does this driver by default, in every precision.  `--max-seconds S`
 moves that limit: the kernels address images of any length that fits in device memory (a 180 s clip in bf16 is one call), and
 what remains is the device memory itself.  A file whose workspace (`fd_enhance_workspace_bytes`) does not fit in the free device
@@ -331,6 +336,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--corrector", type=str, default="ald", choices=["ald", "none"])
     p.add_argument("--snr", type=float, default=0.5)
     p.add_argument("--solver", type=str, default="midpoint")   # flow model only
+    p.add_argument("--step-control", type=str, default="batch", choices=["batch", "clip"],
+                   help="adaptive --solver (dopri5, tsit5) of a flow model: batch = one step controller per native call, so files run one per "
+                        "call; clip = one controller per file, so files of one T_pad bucket share a call (--batch-files) and every file's "
+                        "waveform is the one-file result, bit for bit")
     p.add_argument("--model", type=str, default="auto", choices=["auto", "flow", "score", "regression"],
                    help="auto: the class the checkpoint names (hyper_parameters.model._target_; none named: flow); the others override it")
     p.add_argument("--device", type=str, default="cuda:0")
@@ -485,12 +494,20 @@ def enhance_kwargs(model, args) -> dict:
         return dict(N=args.N, predictor=args.predictor, corrector=args.corrector, snr=args.snr)
     if isinstance(model, RegressionModel):
         return {}
+    if per_clip_control(args):
+        return dict(N=args.N, solver=args.solver, step_control="clip")
     return dict(N=args.N, solver=args.solver)
 
 
+def per_clip_control(args) -> bool:
+    """--step-control clip with an adaptive --solver: every file steps under its own controller (`FlowModel.enhance(step_control='clip')`)."""
+    return getattr(args, "step_control", "batch") == "clip" and args.solver in ("dopri5", "tsit5")
+
+
 def batchable(model, args) -> bool:
-    """Whether the run can use ragged batches: the flow model's adaptive solvers step clip by clip; everything else runs in batches."""
-    return not isinstance(model, FlowModel) or args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast")
+    """Whether the run can use ragged batches: the flow model's adaptive solvers step clip by clip unless --step-control clip gives
+    every file its own controller; everything else runs in batches."""
+    return not isinstance(model, FlowModel) or args.solver in ("euler", "midpoint", "heun2", "heun2_eulerlast") or per_clip_control(args)
 
 
 def chunk_samples(model, args) -> Optional[int]:

@@ -515,6 +515,16 @@ def _ragged_bucket(clips, cfg):
     return flat, lens, Tp, Lrow
 
 
+def _check_step_control(step_control, solver, who):
+    """`step_control` of the adaptive solvers: None / 'batch' (one controller for the batch) or 'clip' (one per clip) -> per-clip?"""
+    if step_control not in (None, "batch", "clip"):
+        raise ValueError(f"{who}: step_control must be None, 'batch' or 'clip' (got {step_control!r})")
+    if step_control is not None and solver not in L.ADAPTIVE_SOLVERS:
+        raise ValueError(f"{who}: step_control={step_control!r} belongs to the adaptive solvers {sorted(L.ADAPTIVE_SOLVERS)}; "
+                         f"the fixed-step solver {solver!r} has no step size to control")
+    return step_control == "clip"
+
+
 def _per_clip_generators(generator, noise, B):
     """One generator per clip from `generator` (one for all clips, drawn clip by clip, or a list of one per clip); checks the counts."""
     gens = generator if isinstance(generator, (list, tuple)) else [generator] * B
@@ -659,14 +669,23 @@ class FlowModel(nn.Module):
     @torch.no_grad()
     @_serialized
     def enhance(self, y, return_preprocess_info: bool = False, N: int = 50, solver: str = "euler", with_grad: bool = False,
-                sigma_fac: float = 1.0, return_traj: bool = False, noise=None, generator=None, use_graph: bool = True, seed=None, **kwargs):
-        """Enhances a coded/noisy waveform y (model.py:476-528).  y: [L], [1, L] or [B, 1, L]."""
+                sigma_fac: float = 1.0, return_traj: bool = False, noise=None, generator=None, use_graph: bool = True, seed=None,
+                step_control: Optional[str] = None, **kwargs):
+        """Enhances a coded/noisy waveform y (model.py:476-528).  y: [L], [1, L] or [B, 1, L].
+
+        The adaptive solvers ('dopri5', 'tsit5'; `atol=`, `rtol=`) take `step_control`: None / 'batch' accepts or rejects a step on ONE
+        error ratio over the whole batch (torchdyn's behaviour for a batched call), so a clip's result depends on its batch companions;
+        'clip' gives every clip its own controller -- clip b is bit-identical to the one-clip call on it, alone, in any batch and in any
+        shard of a batch, and `seed=` draws the noise inside the solver (no noise tensor).  `last_nfe` is then the largest per-clip
+        NFE; `last_nfe_per_clip`, `last_rejected_per_clip` ([B] int tensors) and `last_evals` (evaluations of the whole batch that ran:
+        clips that are done ride along until the slowest one is) give the detail."""
         fd_noise.exclusive(seed=seed, noise=noise, generator=generator)
         if with_grad:
             raise NotImplementedError("flowdec_amd.FlowModel.enhance: with_grad=True (backprop through the solver) is out of scope")
         adaptive = solver in L.ADAPTIVE_SOLVERS
         if not adaptive and solver not in L.SOLVERS:
             raise ValueError(f"unknown solver {solver!r}; supported: {sorted(L.SOLVERS) + sorted(L.ADAPTIVE_SOLVERS)}")
+        per_clip = _check_step_control(step_control, solver, "enhance")
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
@@ -689,7 +708,7 @@ class FlowModel(nn.Module):
             seeds = None
             if seed is None:
                 io["noise"].copy_(self._get_noise_tensor((B, 1, F, Tp), dev, noise, generator))
-            elif adaptive:   # the host-driven solvers only need the initial plane: filled by the library, then the unseeded call
+            elif adaptive and not per_clip:   # the batch-global driver only needs the initial plane: filled by the library, then the unseeded call
                 io["noise"].copy_(fd_noise.noise_fill(fd_noise.seeds_to_tensor(seed, B, dev), F, Tp)[0])
             else:
                 seeds = self._set_seeds(io, seed, B, dev)
@@ -703,7 +722,8 @@ class FlowModel(nn.Module):
             with torch.cuda.stream(side):
                 if adaptive:
                     res = self._enhance_adaptive(lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev,
-                                                 float(kwargs.get("atol", ADAPTIVE_DEFAULT_TOL)), float(kwargs.get("rtol", ADAPTIVE_DEFAULT_TOL)), L.ADAPTIVE_SOLVERS[solver])
+                                                 float(kwargs.get("atol", ADAPTIVE_DEFAULT_TOL)), float(kwargs.get("rtol", ADAPTIVE_DEFAULT_TOL)), L.ADAPTIVE_SOLVERS[solver],
+                                                 per_clip=per_clip, seeds=seeds)
                 else:
                     res = self._enhance_native(lib, h, cfg, io, B, Lw, F, T, Tp, N, solver, sigma_fac, return_traj,
                                                return_preprocess_info, squeeze_dims, use_graph, dev, seeds)
@@ -723,7 +743,8 @@ class FlowModel(nn.Module):
     @torch.no_grad()
     @_serialized
     def enhance_batch(self, clips, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, noise=None, generator=None,
-                      use_graph: bool = True, seeds=None):
+                      use_graph: bool = True, seeds=None, step_control: Optional[str] = None, atol: float = ADAPTIVE_DEFAULT_TOL,
+                      rtol: float = ADAPTIVE_DEFAULT_TOL):
         """`[self.enhance(c, N=N, solver=solver) for c in clips]` as ONE native call (fd_enhance_ragged) for clips of DIFFERENT
         lengths whose spectrograms pad to the same T_pad -- what the reference's driver does file by file (enhance.py:96-137).
 
@@ -733,10 +754,19 @@ class FlowModel(nn.Module):
         itself never mixes batch items.  Initial noise: `noise` = one [1, 1, F, T_pad] complex tensor per clip, or `generator` =
         one torch.Generator (drawn clip by clip, i.e. the stream a one-by-one loop would consume) or a list of one per clip, or
         `seeds` = one 64-bit seed per clip (a sequence or an int64 / uint64 tensor) for the library's own noise: clip i then equals
-        `self.enhance(clip_i, seed=[seeds[i]])`."""
+        `self.enhance(clip_i, seed=[seeds[i]])`.
+
+        The adaptive solvers ('dopri5', 'tsit5', with `atol`, `rtol`) run here with step_control='clip' only: every clip then steps under
+        its own controller and equals `self.enhance(clip_i, solver=solver, atol=, rtol=)` bit for bit, NFE included (ragged STFT ->
+        fd_ode_solve_adaptive_clips -> ragged iSTFT; `last_nfe_per_clip`, `last_rejected_per_clip`, `last_evals` as in `enhance`).  A
+        batch-global controller would make a clip depend on its companions, so without the keyword they are refused."""
         fd_noise.exclusive(seeds=seeds, noise=noise, generator=generator)
-        if solver not in L.SOLVERS:
-            raise ValueError(f"enhance_batch: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
+        if solver in L.ADAPTIVE_SOLVERS and step_control != "clip":
+            raise ValueError(f"enhance_batch: the adaptive solver {solver!r} runs in a batch with step_control='clip' only (per-clip step "
+                             f"control); without it: fixed-step solvers only ({sorted(L.SOLVERS)})")
+        if solver not in L.SOLVERS and solver not in L.ADAPTIVE_SOLVERS:
+            raise ValueError(f"enhance_batch: unknown solver {solver!r}; supported: {sorted(L.SOLVERS) + sorted(L.ADAPTIVE_SOLVERS)}")
+        per_clip = _check_step_control(step_control, solver, "enhance_batch")
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
@@ -767,17 +797,22 @@ class FlowModel(nn.Module):
             side = self._side_stream
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
-                if need == 0:
-                    raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-                ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
-                if seeds_dev is not None:
-                    L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(seeds_dev), float(sigma_fac), int(N),
-                                                  L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                if per_clip:   # ragged STFT -> per-clip adaptive solve -> ragged iSTFT
+                    x_hat, _ = self._enhance_adaptive(lib, h, cfg, io, B, Lrow, F, lib.fd_num_frames(Lrow, cfg["hop"]), Tp, N, sigma_fac, False, 0, dev,
+                                                      float(atol), float(rtol), L.ADAPTIVE_SOLVERS[solver], per_clip=True, seeds=seeds_dev, lengths=lens)
+                    outs = [x_hat[b, 0, :lens[b]].clone() for b in range(B)]
                 else:
-                    L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                                                  L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-                outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
+                    need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
+                    if need == 0:
+                        raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
+                    ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
+                    if seeds_dev is not None:
+                        L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(seeds_dev), float(sigma_fac), int(N),
+                                                      L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                    else:
+                        L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
+                                                      L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+                    outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
             cur.wait_stream(side)
         res = []
         for b, c in enumerate(clips):
@@ -890,29 +925,46 @@ class FlowModel(nn.Module):
         x_hat.record_stream(cur)
         return x_hat.reshape(y.shape).to(y.device)
 
-    def _enhance_adaptive(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev, atol, rtol, method=0):
+    def _enhance_adaptive(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev, atol, rtol, method=0,
+                          per_clip=False, seeds=None, lengths=None):
         """solver='dopri5' / 'tsit5': adaptive 5(4) pair over t_span = linspace(0, 1, N+1) (torchdyn semantics restated, unpinned);
-        host-driven (one read-back per attempted step), so no hipGraph.  The realised NFE is left in `self.last_nfe`."""
+        host-driven (one read-back per attempted step), so no hipGraph.  The realised NFE is left in `self.last_nfe`.
+        per_clip: every clip under its own controller (fd_ode_solve_adaptive_clips); then `seeds` (device int64 [B]) replaces
+        io["noise"], and `lengths` makes the batch ragged (rows of Lw samples, clip b = the first lengths[b])."""
         from . import ops
-        Y, normfac, _ = ops.stft_compress(io["y"], normalize=self.normalize_mode == "noisy", **cfg)
+        Y, normfac, _ = ops.stft_compress(io["y"], normalize=self.normalize_mode == "noisy", lengths=lengths, **cfg)
         traj = torch.empty(N + 1, B, 1, F, Tp, dtype=torch.complex64, device=dev) if return_traj else None
         X = torch.empty_like(Y)
-        need = lib.fd_ode_adaptive_workspace_bytes(h, B, Tp)
-        ws = self.backbone.workspace(("ode", B, Tp), need, dev)
-        nfe = C.c_int(0)
-        L.check(lib.fd_ode_solve_adaptive_method(h, L.ptr(torch.view_as_real(Y)), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N), int(method),
-                                          atol, rtol, L.ptr(torch.view_as_real(X)), L.ptr(torch.view_as_real(traj)) if return_traj else None,
-                                          C.byref(nfe), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
-        self.last_nfe = int(nfe.value)
+        traj_ptr = L.ptr(torch.view_as_real(traj)) if return_traj else None
+        if per_clip:
+            need = lib.fd_ode_adaptive_clips_workspace_bytes(h, B, Tp)
+            if need == 0:
+                raise RuntimeError(f"flowdec_hip: step_control='clip' takes at most 256 clips of a valid shape per call (got B={B}, T_pad={Tp})")
+            ws = self.backbone.workspace(("ode", B, Tp), need, dev)
+            nfe, rej, evals = (C.c_int * B)(), (C.c_int * B)(), C.c_int(0)
+            L.check(lib.fd_ode_solve_adaptive_clips(h, L.ptr(torch.view_as_real(Y)), None if seeds is not None else L.ptr(torch.view_as_real(io["noise"])),
+                                                    L.ptr(seeds), float(sigma_fac), int(N), int(method), atol, rtol, L.ptr(torch.view_as_real(X)), traj_ptr,
+                                                    nfe, rej, C.byref(evals), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
+            self.last_nfe_per_clip = torch.tensor(list(nfe), dtype=torch.int64)
+            self.last_rejected_per_clip = torch.tensor(list(rej), dtype=torch.int64)
+            self.last_evals = int(evals.value)
+            self.last_nfe = int(self.last_nfe_per_clip.max())
+        else:
+            need = lib.fd_ode_adaptive_workspace_bytes(h, B, Tp)
+            ws = self.backbone.workspace(("ode", B, Tp), need, dev)
+            nfe = C.c_int(0)
+            L.check(lib.fd_ode_solve_adaptive_method(h, L.ptr(torch.view_as_real(Y)), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N), int(method),
+                                                     atol, rtol, L.ptr(torch.view_as_real(X)), traj_ptr, C.byref(nfe), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
+            self.last_nfe = int(nfe.value)
         if return_traj:
             x_hats = []
             for i in range(N + 1):
-                xh = ops.decompress_istft(traj[i], T, Lw, normfac, **cfg).reshape(B, 1, Lw)
+                xh = ops.decompress_istft(traj[i], T, Lw, normfac, lengths=lengths, **cfg).reshape(B, 1, Lw)
                 for _ in range(squeeze_dims):
                     xh = xh.squeeze(0)
                 x_hats.append(xh)
             return traj, x_hats
-        x_hat = ops.decompress_istft(X, T, Lw, normfac, **cfg).reshape(B, 1, Lw)
+        x_hat = ops.decompress_istft(X, T, Lw, normfac, lengths=lengths, **cfg).reshape(B, 1, Lw)
         info = dict(orig_length=Lw, normfac=normfac.reshape(B, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
         return x_hat, info
 

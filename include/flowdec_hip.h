@@ -17,7 +17,7 @@
  *  - Threading.  The operator-level calls (fd_upfirdn2d, fd_fused_bias_act, fd_conv2d, fd_fir_resample, fd_gn_*, fd_stft_*, ...)
  *    keep no state and are re-entrant from any number of threads, like the reference's ops (upfirdn2d_kernel.cu:224-231).  An
  *    fd_model holds scratch that its enqueueing calls share (time-embedding biases, hipGraph cache, side stream, profiling events):
- *    it serves ONE enqueueing call at a time.  A second thread that enters fd_ncsnpp_forward / fd_ode_solve[_adaptive] / fd_enhance /
+ *    it serves ONE enqueueing call at a time.  A second thread that enters fd_ncsnpp_forward / fd_ode_solve[_adaptive[_clips]] / fd_enhance /
  *    fd_score_* / fd_regression_enhance while another is inside gets FD_EBUSY (nothing is enqueued, nothing is corrupted); use one
  *    fd_model per thread for concurrent solves.  "Inside" is the host-side enqueue only -- the GPU work itself is asynchronous:
  *    consecutive calls of one model on DIFFERENT streams must be ordered by the caller (record an event after one call, make the
@@ -398,6 +398,26 @@ int fd_ode_solve_adaptive(fd_model* m, const float* Y, const float* noise, float
 #define FD_ADAPTIVE_TSIT5 1
 int fd_ode_solve_adaptive_method(fd_model* m, const float* Y, const float* noise, float sigma_fac, int N, int method, float atol, float rtol,
                                  float* X_out, float* traj, int* nfe_out, int B, int T_pad, void* ws, size_t ws_bytes, void* stream);
+/* The same solvers with PER-CLIP step control.  The two calls above accept or reject a step on one error ratio taken over the whole
+ * [B][F][T_pad] state (torchdyn's behaviour for a batched call), so a clip's result depends on its batch companions.  Here every clip
+ * carries its own t, dt, checkpoint index and accept / reject decisions: clip b's final state, trajectory planes and nfe_out[b] are
+ * BIT-IDENTICAL to the B = 1 call above on that clip, whatever else is in the batch and however the batch is sharded.
+ *   noise / seeds   exactly one is given: noise = complex64 [B][1][F][T_pad] as above, or seeds = DEVICE uint64 [B] (the library's own
+ *                   noise, draw 0, as in fd_ode_solve_seeded; equals the buffer form on fd_noise_fill's planes).
+ *   B               at most 256 clips (the per-sample time table of the network); more is refused.
+ *   nfe_out         HOST int [B]: the evaluations made while clip b was still integrating = the nfe of its one-clip call.
+ *   rejected_out    HOST int [B] or NULL: clip b's rejected attempts.
+ *   evals_out       HOST int or NULL: the network evaluations (each over the whole batch) the call ran, 2 + 6 x attempts.  A clip that has
+ *                   reached t = 1 rides along with dt = 0, untouched, until the slowest clip is done; B x *evals_out against the sum of
+ *                   nfe_out is that waste.
+ *   traj            optional [N+1][B][1][F][T_pad]: clip b's plane of checkpoint i is written when clip b lands on it.
+ * Host-driven like the calls above: one synchronisation of `stream` per attempted step (one small host-to-device table -- step sizes,
+ * stage times, the previous attempt's commit flags -- and one read-back of B x 512 partial sums), no graph capture.  The workspace is
+ * fd_ode_adaptive_clips_workspace_bytes (0 for a bad shape or B > 256). */
+size_t fd_ode_adaptive_clips_workspace_bytes(const fd_model* m, int B, int T_pad);
+int fd_ode_solve_adaptive_clips(fd_model* m, const float* Y, const float* noise, const unsigned long long* seeds, float sigma_fac, int N, int method,
+                                float atol, float rtol, float* X_out, float* traj, int* nfe_out, int* rejected_out, int* evals_out, int B, int T_pad,
+                                void* ws, size_t ws_bytes, void* stream);
 size_t fd_enhance_workspace_bytes(const fd_model* m, int B, int L);
 /* Byte offset, inside the workspace of fd_enhance / fd_score_enhance / fd_regression_enhance, of the B float32 normalisation
  * factors the front end computed (EnhancementModel._preprocess' `normfac`, model.py:156-162); valid after the call. */
