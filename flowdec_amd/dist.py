@@ -11,8 +11,12 @@ with `gloo` (CPU tensors, or GPU tensors staged through the host) in the tests.
 N-GPU == 1-GPU, bit for bit: the initial noise of clip i (the reference draws it inside enhance from the device RNG,
 flowdec/model.py:512,530-536) depends on the GLOBAL clip index i only -- either sliced from a caller-provided global
 `noise` tensor, or drawn from the per-clip stream (seed, i) -- never on the rank layout.
+
+The corpus path shards by WORK instead of by count: `sharded_enhance_batch` takes clips of any lengths (T_pad buckets cut into ragged
+batches, the batches spread over the ranks by `balance`), `sharded_enhance_long` the (channel, row) jobs of one long recording.  Both
+use the library's seeded noise only, and both return what one process returns, bit for bit, for every world size.
 """
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -201,3 +205,152 @@ def _shared_seed(dev, group=None) -> int:
         s = s if _needs_host_staging(group) else s.to(dev)
         dist.broadcast(s, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
     return int(s.item())
+
+
+# ------------------------------------------------------------------------------------------------
+# the corpus path: clips of any lengths, one long recording
+# ------------------------------------------------------------------------------------------------
+def balance(costs: Sequence[float], world: int) -> List[List[int]]:
+    """Assigns items to ranks: longest cost first, each to the rank with the least load so far.  Equal costs go in item order (lower
+    index first), equal loads to the lower rank; every rank's list comes back in ascending item order.  A pure function of its
+    arguments: every rank computes the same plan from the same costs, nothing is communicated.
+
+    Guarantees: every item appears exactly once; world == 1 gives [list(range(n))]; ranks may be empty (fewer items than ranks, or zero
+    costs elsewhere); max load <= sum(costs) / world + max(costs), the list-scheduling bound (the rank that ends up fullest was the
+    least loaded one, so at most the mean, when it took its last item)."""
+    world = int(world)
+    if world < 1:
+        raise ValueError(f"balance: world must be >= 1 (got {world})")
+    if any(c < 0 for c in costs):
+        raise ValueError("balance: costs must be >= 0")
+    load, plan = [0] * world, [[] for _ in range(world)]
+    for i in sorted(range(len(costs)), key=lambda i: (-costs[i], i)):
+        r = min(range(world), key=lambda r: (load[r], r))
+        load[r] += costs[i]
+        plan[r].append(i)
+    return [sorted(p) for p in plan]
+
+
+def plan_clip_batches(lengths: Sequence[int], hop: int, batch_clips: int) -> List[Tuple[int, List[int]]]:
+    """Clips of `lengths` samples bucketed by the frame count their spectrogram pads to (`padded_frames_of`), buckets in ascending
+    T_pad, every bucket cut in clip order into batches of at most `batch_clips`.  -> [(T_pad, clip indices)], the same on every rank."""
+    from .model import padded_frames_of
+    batch_clips = max(int(batch_clips), 1)
+    buckets = {}
+    for i, n in enumerate(lengths):
+        buckets.setdefault(padded_frames_of(int(n), hop), []).append(i)
+    return [(tp, buckets[tp][k:k + batch_clips]) for tp in sorted(buckets) for k in range(0, len(buckets[tp]), batch_clips)]
+
+
+def sharded_enhance_batch(model, clips, group=None, batch_clips: int = 8, seed: Optional[int] = None, seeds=None, always_gather: bool = False,
+                          stats: Optional[dict] = None, **enhance_kwargs) -> List[torch.Tensor]:
+    """`[model.enhance(c, seed=[s_i], ...) for c in clips]` for a list of clips of ANY lengths ([L], [1, L] or [1, 1, L]), sharded over
+    the ranks of `group`; every rank passes the same list (host tensors are fine) and returns all clips, each with the shape and on the
+    device of its input.  `model` is a FlowModel, a ScoreModel or a RegressionModel (anything with their `enhance_batch`).
+
+    The clips are bucketed by T_pad and cut into ragged batches of at most `batch_clips` (`plan_clip_batches`); a batch costs
+    clips x T_pad, `balance` spreads the batches, and each rank runs its own through `model.enhance_batch` -- where every clip gets the
+    arithmetic of its own one-clip call.  ONE `all_gather_into_tensor` then moves the waveforms, padded to the longest clip (gloo: staged
+    through the host); the result is copied out of the gathered buffer, so it is the one-clip result bit for bit, the sign of a zero
+    included, for every world size.
+
+    Noise is the library's own: `seeds` = one 64-bit seed per clip, or `seed` = an int (clip i uses `noise.clip_seed(seed, i)`); with
+    neither, rank 0 draws a seed and broadcasts it (idle ranks take part).  A RegressionModel draws no noise and takes none of them.
+    `noise=` / `generator=` are refused: a shared generator's stream depends on the order in which the clips are processed, which is
+    what sharding changes.  The adaptive solvers need step_control='clip' (`enhance_batch` enforces it).
+
+    Without a process group (world 1) the clips still run bucketed and batched; there is no collective unless `always_gather`.
+    `stats`, if given, receives {"local_s", "gather_s"} like `sharded_enhance`, plus "plan" (every batch as a list of clip indices) and
+    "mine" (the positions in the plan of the batches this rank ran)."""
+    import time
+    from .model import RegressionModel
+    from .noise import clip_seed
+    for k in ("noise", "generator"):
+        if enhance_kwargs.get(k) is not None:
+            raise ValueError(f"sharded_enhance_batch takes seed= / seeds= only, not {k}=: a generator's stream (and a noise list drawn from one) "
+                             f"depends on the order the clips are processed in, which the sharding changes; the library's seeded noise "
+                             f"belongs to the clip")
+        enhance_kwargs.pop(k, None)
+    clips = list(clips)
+    n = len(clips)
+    world, rank = _world(group)
+    dev = model.device
+    draws_noise = not isinstance(model, RegressionModel)
+    if not draws_noise:
+        seeds = None
+    elif seeds is not None:
+        if seed is not None:
+            raise ValueError("sharded_enhance_batch: pass seed= or seeds=, not both")
+        seeds = [int(s) for s in (seeds.view(torch.int64).tolist() if isinstance(seeds, torch.Tensor) else seeds)]   # (two's complement)
+        if len(seeds) != n:
+            raise ValueError(f"sharded_enhance_batch: {len(seeds)} seeds for {n} clips")
+    else:
+        if seed is None:
+            seed = _shared_seed(dev, group)   # (every rank, idle ones included, takes part in the broadcast)
+        seeds = [clip_seed(seed, i) for i in range(n)]
+    lens = [int(c.numel()) for c in clips]
+    batches = plan_clip_batches(lens, model.feature_extractor._cfg()["hop"], batch_clips)
+    plan, costs = [idx for _, idx in batches], [len(idx) * tp for tp, idx in batches]
+    owner = balance(costs, world)
+    t0 = time.perf_counter() if stats is not None else 0.0
+    local = {}
+    for b in owner[rank]:
+        idx = plan[b]
+        kw = dict(enhance_kwargs, seeds=[seeds[i] for i in idx]) if draws_noise else enhance_kwargs
+        outs = model.enhance_batch([clips[i].to(dev, non_blocking=True) for i in idx], **kw)
+        local.update(zip(idx, outs))
+    if stats is not None:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        stats["local_s"] = stats.get("local_s", 0.0) + (t1 - t0)
+        stats["plan"], stats["mine"] = plan, list(owner[rank])
+    if world == 1 and not always_gather:
+        res = [local[i].reshape(clips[i].shape).to(clips[i].device) for i in range(n)]
+    else:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("sharded_enhance_batch(always_gather=True) needs an initialised process group")
+        # rank r's clips, in the order of its batches, are the slots of row r of a [world, slots, longest clip] buffer
+        slots = [[i for b in owner[r] for i in plan[b]] for r in range(world)]
+        n_slots, l_max = max(max(len(s) for s in slots), 1), max(lens + [1])
+        send = torch.zeros(n_slots, l_max, dtype=torch.float32, device=dev)
+        for k, i in enumerate(slots[rank]):
+            send[k, :lens[i]].copy_(local[i].reshape(-1))
+        if send.is_cuda and _needs_host_staging(group):   # gloo moves host memory: stage device tensors through the host
+            out = torch.empty(world * n_slots, l_max, dtype=torch.float32)
+            dist.all_gather_into_tensor(out, send.cpu(), group=group)
+        else:
+            out = send.new_empty(world * n_slots, l_max)
+            dist.all_gather_into_tensor(out, send, group=group)
+        res = [None] * n
+        for r in range(world):
+            for k, i in enumerate(slots[r]):
+                res[i] = out[r * n_slots + k, :lens[i]].clone().reshape(clips[i].shape).to(clips[i].device)
+    if stats is not None:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        stats["gather_s"] = stats.get("gather_s", 0.0) + (time.perf_counter() - t1)
+    return res
+
+
+def sharded_enhance_long(model, y: torch.Tensor, seed=None, group=None, always_gather: bool = False, row_frames: int = 3712,
+                         halo_frames: int = 256, xfade: Optional[int] = None, **enhance_long_kwargs) -> torch.Tensor:
+    """`model.enhance_long(y, seed=seed, ...)` with the (channel, row) jobs of the ONE recording y ([L], [1, L] or [C, 1, L]) sharded over
+    the ranks of `group`: rank r runs the contiguous jobs `shard_range(jobs, r, world)` (`FlowModel.enhance_long_rows`), the row
+    outputs are all-gathered (`all_gather_shards`, one collective) and every rank stitches the recording (`enhance_long_stitch`).  A row
+    depends on (recording, seed, absolute frame) only, and every rank takes the recording's normalisation from the whole recording (a
+    maximum: order-free, the same bits everywhere), so the result equals the one-process call bit for bit for every world size.
+    Every rank passes the same y.  seed=None: rank 0 draws one and broadcasts it."""
+    world, rank = _world(group)
+    if seed is None:
+        seed = _shared_seed(model.device, group)
+    geometry = dict(row_frames=row_frames, halo_frames=halo_frames, xfade=xfade)
+    if world == 1 and not always_gather:
+        return model.enhance_long(y, seed=seed, **geometry, **enhance_long_kwargs)
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("sharded_enhance_long(always_gather=True) needs an initialised process group")
+    n_jobs = model.enhance_long_jobs(y, **geometry)
+    local = model.enhance_long_rows(y, jobs=shard_range(n_jobs, rank, world), seed=seed, **geometry, **enhance_long_kwargs)
+    return model.enhance_long_stitch(y, all_gather_shards(local, n_jobs, group), **geometry)

@@ -48,14 +48,32 @@ grow with the file (halos of 256 frames, or a quarter of the row if that is less
 names the limits it is exempt from.  `--batch-files` rows run per call; if their workspace does not fit, the file is skipped with a message like any other
 file over memory.  Every other file takes
 the paths above and gives the same bytes as without the flag.
+
+Several GPUs: `--gpus N` runs the corpus on the first N devices of the node.  The launching process never opens a GPU: it plans the work
+list once, writes it as a JSON manifest into --outdir (so that a rank that starts late does not take its siblings' outputs for existing
+ones) and starts N fresh worker processes of this module, all at once.  Worker r loads the checkpoint on cuda:r, makes the SAME batch plan
+as a one-process run (the plan does not depend on N), costs every batch (`batch_cost`), takes `dist.balance(costs, N)[r]` and runs those
+batches with exactly the one-process code, in plan order.  The launcher relays the workers' output prefixed `[rank r]`, merges their
+`rtfs{suffix}.rank{r}.csv` parts into the one `rtfs{suffix}.csv` in plan order -- the rows and the order of a one-process run --, writes
+`triples_list{suffix}.txt`, sums the counts (exit status 3 as before) and removes the parts and the manifest.  File i is seeded from
+(SEED, i) whatever rank and batch it lands in, so every output file has the bytes of the one-process run.  A worker that ends with an
+ordinary error leaves the others to finish; the launcher then exits non-zero, names the rank and keeps the part files (a rerun with
+--skip-existing completes what is missing).  A worker that ends by a signal, an abort or a segmentation fault makes the launcher stop the
+others: nothing more is started on a GPU that may have faulted.  `--share-gpu` puts all ranks on cuda:0 (at most 8): a test aid for
+one-GPU boxes, not a speed-up.  The split is static (no work stealing): that is what makes rtfs.csv reproducible.
 """
 import argparse
+import collections
 import contextlib
 import glob
+import json
 import math
 import os
 import re
+import subprocess
 import sys
+import threading
+import time
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
@@ -68,6 +86,7 @@ from .model import (BACKBONE_FINAL_NO_ATTN, OUVESDE, PRESETS, AmplitudeCompresse
                     WorkspaceTooLarge, from_preset)
 
 MAX_SECONDS = 30.0  # enhance.py:115
+SHARE_GPU_MAX_RANKS = 8   # --share-gpu: worker processes on the one GPU
 PRECISION_MAX_SECONDS = {}   # precision -> clip length it can take, if shorter than --max-seconds (none: every mode takes any length that fits in memory)
 PRECISION_NOTE = {   # printed at start-up so that a log says which arithmetic produced the files
     "bf16": "bf16 storage and MFMA operands, f32 accumulation; ~2e-2 relative waveform error vs the fp32 reference on random weights",
@@ -361,6 +380,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "rows of that length, in fixed device memory, instead of being skipped by --max-seconds; needs --rng native and a flow "
                         "model (default: off)")
     p.add_argument("--batch-files", type=int, default=8, help="files of one T_pad bucket per native call (1 = one file per call, the reference's loop)")
+    p.add_argument("--gpus", type=int, default=1,
+                   help="run the corpus on this many GPUs (cuda:0 .. cuda:N-1), one worker process each, batches spread by frame count; the "
+                        "outputs, rtfs.csv and triples_list.txt are those of a one-process run (default 1: no child process)")
+    p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
+    p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
+    p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
+    p.add_argument("--worker-manifest", type=str, default=None, help=argparse.SUPPRESS)
     return p
 
 
@@ -433,16 +459,34 @@ class GpuTimer:
         return False
 
 
+RTF_HEADER = "path,runtime,filetime,rtf"
+
+
+def rtf_part_name(suffix: str, rank: int) -> str:
+    return f"rtfs{suffix}.rank{rank}.csv"
+
+
+def result_part_name(suffix: str, rank: int) -> str:
+    return f"result{suffix}.rank{rank}.json"
+
+
+def manifest_name(suffix: str) -> str:
+    return f"manifest{suffix}.json"
+
+
 class RunLog:
     """The two side files of a run, in the reference's FORMATS (enhance.py:94,135,143): `rtfs{suffix}.csv` with the header
     path,runtime,filetime,rtf (--rtf) and `triples_list{suffix}.txt` with `clean ---> noisy ---> enhanced` lines (pair lists).
     The files are opened on __enter__ (a failing second open closes the first)."""
 
-    def __init__(self, outdir: str, suffix: str, want_rtf: bool, want_triples: bool):
-        self._paths = (os.path.join(outdir, f"rtfs{suffix}.csv") if want_rtf else None,
-                       os.path.join(outdir, f"triples_list{suffix}.txt") if want_triples else None)
+    def __init__(self, outdir: str, suffix: str, want_rtf: bool, want_triples: bool, part: Optional[int] = None):
+        """part = r: the log of worker r of a --gpus N run -- `rtfs{suffix}.rank{r}.csv` with the plan position (`self.position`, set by
+        the caller before each batch) as an extra first column, and no triples list (the launcher writes that one)."""
+        self._paths = (os.path.join(outdir, f"rtfs{suffix}.csv" if part is None else rtf_part_name(suffix, part)) if want_rtf else None,
+                       os.path.join(outdir, f"triples_list{suffix}.txt") if want_triples and part is None else None)
         self._stack = contextlib.ExitStack()
         self._rtf = self._tri = None
+        self._part, self.position = part, 0
         self.runtime = self.filetime = 0.0
 
     def __enter__(self):
@@ -451,7 +495,7 @@ class RunLog:
             self._tri = guard.enter_context(open(self._paths[1], "w")) if self._paths[1] else None
             self._stack = guard.pop_all()
         if self._rtf:
-            print("path,runtime,filetime,rtf", file=self._rtf)
+            print(RTF_HEADER if self._part is None else "position," + RTF_HEADER, file=self._rtf)
         return self
 
     def __exit__(self, *exc):
@@ -462,7 +506,7 @@ class RunLog:
         self.runtime += runtime
         self.filetime += filetime
         if self._rtf:
-            print(f"{dst},{runtime:.5f},{filetime:.5f},{runtime / filetime:.5f}", file=self._rtf)
+            print(("" if self._part is None else f"{self.position},") + f"{dst},{runtime:.5f},{filetime:.5f},{runtime / filetime:.5f}", file=self._rtf)
 
     def triple(self, job: FileJob):
         if self._tri:
@@ -635,18 +679,198 @@ def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLo
         res.n_done += 1
 
 
+# ------------------------------------------------------------------------------------------------
+# --gpus N: manifest, cost model, launcher, merge
+# ------------------------------------------------------------------------------------------------
+class WorkerFailed(RuntimeError):
+    """A worker of a --gpus N run did not finish; the message names the rank and shows its last lines."""
+
+
+def write_manifest(path: str, jobs: List[FileJob]) -> None:
+    """The work list of a --gpus N run, planned ONCE by the launcher: the workers read it and do not repeat the exists-check."""
+    with open(path, "w") as f:
+        json.dump({"jobs": [dict(index=j.index, src=j.src, dst=j.dst, clean=j.clean, pending=j.pending) for j in jobs]}, f)
+
+
+def read_manifest(path: str) -> List[FileJob]:
+    with open(path, "r") as f:
+        return [FileJob(int(j["index"]), j["src"], j["dst"], j["clean"], bool(j["pending"])) for j in json.load(f)["jobs"]]
+
+
+def batch_cost(model, batch: List[FileJob], args) -> int:
+    """The cost of one batch of the plan in padded STFT frames, from the wav headers: a bucketed batch costs files x T_pad, a single file
+    channels x padded frames, a --chunk-seconds file channels x rows x row frames (`longform.plan_rows`); an unreadable header costs 0 (the
+    file fails in its own call), and so does a file the length rule will skip.  A heuristic -- GPU time taken as proportional to the frames
+    in flight, whatever the batch size and the bucket; how evenly it spreads a real corpus over the ranks has not been measured."""
+    from .model import padded_frames_of
+    hop = model.feature_extractor._cfg()["hop"]
+    long_samples = chunk_samples(model, args)
+    try:
+        n, sr, channels = wav_info(batch[0].src)
+    except Exception:
+        return 0
+    n = resampled_length(n, sr, model.sampling_rate)
+    if len(batch) > 1:
+        return len(batch) * padded_frames_of(n, hop)
+    if long_samples is not None and n > long_samples:
+        row_frames = longform.chunk_row_frames(args.chunk_seconds, model.sampling_rate, hop)
+        return channels * len(longform.plan_rows(n, hop, row_frames, longform.chunk_halo_frames(row_frames))) * row_frames
+    if n / model.sampling_rate > args.max_seconds:
+        return 0
+    return channels * padded_frames_of(n, hop)
+
+
+def visible_gpus() -> int:
+    """torch.cuda.device_count() of a short-lived child process: the launcher itself never opens the GPU."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True, timeout=300)
+    try:
+        return int(r.stdout.strip().splitlines()[-1])
+    except (IndexError, ValueError):
+        raise RuntimeError("could not read the number of visible GPUs: " + (r.stdout + r.stderr)[-500:])
+
+
+def merge_parts(outdir: str, suffix: str, world: int, jobs: List[FileJob], want_rtf: bool, want_triples: bool) -> RunResult:
+    """The launcher's last step: the workers' `rtfs{suffix}.rank{r}.csv` rows sorted by plan position (rows of one position keep their
+    order; the position column is dropped) -> `rtfs{suffix}.csv`, the rows and order of a one-process run; `triples_list{suffix}.txt` from
+    the work list; the workers' RunResults summed.  Removes the part files it read."""
+    res, rows, used = RunResult(), [], []
+    for r in range(world):
+        path = os.path.join(outdir, result_part_name(suffix, r))
+        with open(path, "r") as f:
+            part = json.load(f)
+        used.append(path)
+        res.n_done += int(part["n_done"]); res.n_over_precision_limit += int(part["n_over_precision_limit"]); res.n_too_long += int(part["n_too_long"])
+        res.gpu_seconds += float(part["gpu_seconds"]); res.audio_seconds += float(part["audio_seconds"])
+        if want_rtf:
+            path = os.path.join(outdir, rtf_part_name(suffix, r))
+            with open(path, "r") as f:
+                lines = f.read().splitlines()
+            used.append(path)
+            for k, line in enumerate(lines[1:]):
+                if line.strip():
+                    pos, row = line.split(",", 1)
+                    rows.append((int(pos), r, k, row))
+    if want_rtf:
+        with open(os.path.join(outdir, f"rtfs{suffix}.csv"), "w") as f:
+            print(RTF_HEADER, file=f)
+            for _, _, _, row in sorted(rows):
+                print(row, file=f)
+    if want_triples:
+        with open(os.path.join(outdir, f"triples_list{suffix}.txt"), "w") as f:
+            for job in jobs:
+                print(f"{job.clean} ---> {job.src} ---> {job.dst}", file=f)
+    for path in used:
+        os.remove(path)
+    return res
+
+
+FATAL_STATUS = (134, 139)   # abort / segmentation fault as a shell reports them; a negative status is the signal itself
+
+
+def launch_workers(argv: List[str], world: int, manifest: str, share_gpu: bool):
+    """Starts the `world` workers at once (fresh processes of this module, the environment untouched), relays their output line by line
+    prefixed `[rank r]` and waits for all of them.  -> [(exit status, last lines)].  A worker that ends by a signal, an abort or a
+    segmentation fault ends the run: the others are terminated and WorkerFailed is raised."""
+    procs, tails, threads = [], [], []
+    lock = threading.Lock()
+
+    def relay(r, pipe, tail):
+        for line in pipe:
+            tail.append(line.rstrip("\n"))
+            with lock:
+                print(f"[rank {r}] {line}", end="", flush=True)
+
+    try:
+        for r in range(world):
+            cmd = [sys.executable, "-m", "flowdec_amd.enhance_cli"] + list(argv) + ["--worker-rank", str(r), "--worker-world", str(world),
+                                                                                    "--worker-manifest", manifest]
+            procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, bufsize=1))
+            tails.append(collections.deque(maxlen=20))
+            threads.append(threading.Thread(target=relay, args=(r, procs[-1].stdout, tails[-1]), daemon=True))
+            threads[-1].start()
+        pending = set(range(world))
+        while pending:
+            for r in sorted(pending):
+                rc = procs[r].poll()
+                if rc is None:
+                    continue
+                pending.discard(r)
+                if rc < 0 or rc in FATAL_STATUS:
+                    threads[r].join(timeout=5)
+                    raise WorkerFailed(f"rank {r} ended with status {rc} (signal, abort or segmentation fault): the other workers were stopped, "
+                                       f"nothing more is started on a GPU that may have faulted; the part files stay in --outdir.  Its last lines:\n"
+                                       + "\n".join(tails[r]))
+            if pending:
+                time.sleep(0.05)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.terminate()
+        for p in procs:
+            try:
+                p.wait(timeout=30)
+            except subprocess.TimeoutExpired:
+                p.kill(); p.wait()
+        for t in threads:
+            t.join(timeout=5)
+    return [(p.returncode, list(t)) for p, t in zip(procs, tails)]
+
+
+def run_launcher(args, parser, argv: List[str]) -> RunResult:
+    """The launching process of a --gpus N run (module docstring).  It opens no GPU and loads no checkpoint."""
+    suffix = f"_{args.i_min}-{args.i_max}" if args.i_max else ""
+    if not args.share_gpu:
+        have = visible_gpus()
+        if args.gpus > have:
+            parser.error(f"--gpus {args.gpus} asks for more GPUs than the {have} visible on this node (no worker was started; --share-gpu puts "
+                         f"several workers on one GPU, for tests)")
+    noisy, clean = collect_files(args.files, args.single_file)
+    jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
+    manifest = os.path.join(args.outdir, manifest_name(suffix))
+    for stale in glob.glob(os.path.join(glob.escape(args.outdir), f"*{suffix}.rank*.*")):      # parts a failed earlier run left for diagnosis
+        if re.fullmatch(r"(rtfs|result)%s\.rank\d+\.(csv|json)" % re.escape(suffix), os.path.basename(stale)):
+            os.remove(stale)
+    write_manifest(manifest, jobs)
+    worker_argv = list(argv) + (["--seed", str(args.seed)] if args.seed is not None else [])
+    t0 = time.perf_counter()
+    ended = launch_workers(worker_argv, args.gpus, manifest, args.share_gpu)
+    wall = time.perf_counter() - t0
+    failed = [(r, rc, tail) for r, (rc, tail) in enumerate(ended)
+              if rc not in (0, 3) or not os.path.exists(os.path.join(args.outdir, result_part_name(suffix, r)))]
+    if failed:
+        raise WorkerFailed("\n".join(f"rank {r} ended with status {rc}; its last lines:\n" + "\n".join(tail) for r, rc, tail in failed)
+                           + f"\n{len(failed)} of {args.gpus} workers failed; the others finished.  The part files stay in {args.outdir}; a rerun with "
+                             f"--skip-existing completes what is missing.")
+    res = merge_parts(args.outdir, suffix, args.gpus, jobs, want_rtf=args.rtf, want_triples=clean is not None)
+    os.remove(manifest)
+    if args.rtf and res.gpu_seconds > 0:
+        print(f"total: {res.audio_seconds:.2f} s of audio in {res.gpu_seconds:.3f} s of GPU time -> rtf = {res.gpu_seconds / res.audio_seconds:.5f} "
+              f"({res.audio_seconds / res.gpu_seconds:.1f} x real time)")
+        print(f"{args.gpus} workers: {res.audio_seconds:.2f} s of audio in {wall:.3f} s of wall clock, start-up and checkpoint loading included "
+              f"({res.audio_seconds / wall:.1f} x real time)")
+    else:
+        print(f"{args.gpus} workers: {res.n_done} files in {wall:.3f} s of wall clock, start-up and checkpoint loading included")
+    return res
+
+
 def main(argv=None, model: Optional[FlowModel] = None) -> int:
     """Runs the CLI and returns the number of files enhanced (the detailed result: `run()`)."""
     return run(argv, model).n_done
 
 
 def cli(argv=None) -> int:
-    """Console entry point: exit status 0, or 3 when files were skipped only because of the chosen precision's length limit."""
-    return run(argv).exit_code
+    """Console entry point: exit status 0, or 3 when files were skipped only because of the chosen precision's length limit; 1 when a
+    worker of a --gpus N run failed."""
+    try:
+        return run(argv).exit_code
+    except WorkerFailed as err:
+        print(f"flowdec_amd: {err}", file=sys.stderr)
+        return 1
 
 
 def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
     parser = build_parser()
+    argv = list(sys.argv[1:] if argv is None else argv)
     args = parser.parse_args(argv)
     if args.chunk_seconds is not None:
         if not args.chunk_seconds > 0:
@@ -657,27 +881,54 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
             parser.error("--chunk-seconds needs a flow model (got --model %s)" % args.model)
         if args.solver not in ("euler", "midpoint", "heun2", "heun2_eulerlast"):
             parser.error("--chunk-seconds needs a fixed-step --solver (euler, midpoint, heun2, heun2_eulerlast)")
+    worker = args.worker_rank is not None
+    if args.gpus < 1:
+        parser.error("--gpus must be at least 1")
+    if worker:
+        if args.worker_world is None or args.worker_manifest is None or not 0 <= args.worker_rank < args.worker_world:
+            parser.error("a worker needs its rank, the world size and the manifest (they are set by the launcher of a --gpus N run)")
+        args.device = "cuda:0" if args.share_gpu else f"cuda:{args.worker_rank}"
+    elif args.gpus > 1:
+        if args.device != "cuda:0":
+            parser.error(f"--gpus {args.gpus} places worker r on cuda:r: it does not combine with --device {args.device}")
+        if args.share_gpu and args.gpus > SHARE_GPU_MAX_RANKS:
+            parser.error(f"--share-gpu takes at most {SHARE_GPU_MAX_RANKS} workers (got --gpus {args.gpus})")
+        if model is not None:
+            raise ValueError(f"run(model=...) with --gpus {args.gpus}: the workers are fresh processes and load --ckpt themselves")
     os.makedirs(args.outdir, exist_ok=True)
     if args.rng == "native" and args.seed is None:
         args.seed = int.from_bytes(os.urandom(8), "little")
         print(f"flowdec_amd: --rng native without --seed: using --seed {args.seed}")
+    if args.gpus > 1 and not worker:
+        return run_launcher(args, parser, argv)
     if model is None:
         print("Loading model from checkpoint...")
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model=args.model)
         print("Done loading model.")
     if args.chunk_seconds is not None and not isinstance(model, FlowModel):
         parser.error("--chunk-seconds needs a flow checkpoint (this one is a %s)" % type(model).__name__)
-    noisy, clean = collect_files(args.files, args.single_file)
     max_seconds = min(args.max_seconds, PRECISION_MAX_SECONDS.get(args.precision, args.max_seconds))
     settings = ", ".join(f"{k}={v}" for k, v in enhance_kwargs(model, args).items()) or "one network evaluation"
     print(f"flowdec_amd: model={type(model).__name__}, precision={args.precision} ({PRECISION_NOTE[args.precision]}), {settings}, "
           f"files per native call <= {max(args.batch_files, 1)}")
     res = RunResult()
     suffix = f"_{args.i_min}-{args.i_max}" if args.i_max else ""
-    jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
-    with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None) as log:
-        for batch in plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable(model, args) else 1, args.max_seconds,
-                                  chunk_samples(model, args)):
+    if worker:
+        jobs, clean = read_manifest(args.worker_manifest), None
+    else:
+        noisy, clean = collect_files(args.files, args.single_file)
+        jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
+    plan = plan_batches(model, [j for j in jobs if j.pending], args.batch_files if batchable(model, args) else 1, args.max_seconds,
+                        chunk_samples(model, args))
+    mine = range(len(plan))
+    if worker:      # the plan is the one-process plan; this rank runs its share of it, in plan order
+        from .dist import balance
+        mine = balance([batch_cost(model, batch, args) for batch in plan], args.worker_world)[args.worker_rank]
+        print(f"flowdec_amd: worker {args.worker_rank} of {args.worker_world} on {args.device}: {len(mine)} of {len(plan)} batches")
+    with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None, part=args.worker_rank) as log:
+        for position in mine:
+            batch = plan[position]
+            log.position = position
             if len(batch) == 1:
                 enhance_file(model, batch[0], args, log, res, max_seconds)
             else:
@@ -688,6 +939,10 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
             print(f"total: {log.filetime:.2f} s of audio in {log.runtime:.3f} s of GPU time -> rtf = {log.runtime / log.filetime:.5f} "
                   f"({log.filetime / log.runtime:.1f} x real time)")
     res.gpu_seconds, res.audio_seconds = log.runtime, log.filetime
+    if worker:
+        with open(os.path.join(args.outdir, result_part_name(suffix, args.worker_rank)), "w") as f:
+            json.dump(dict(n_done=res.n_done, n_over_precision_limit=res.n_over_precision_limit, n_too_long=res.n_too_long,
+                           gpu_seconds=res.gpu_seconds, audio_seconds=res.audio_seconds), f)
     return res
 
 

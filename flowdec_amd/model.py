@@ -10,11 +10,12 @@ but every FLOP runs in libflowdec_hip.so (hand-written HIP for gfx950).  The ``n
 holds parameters (so ``load_state_dict(ckpt['_pl_ema_state_dict'])`` works unchanged); there is no
 Lightning / Hydra / torchdyn dependency and no PyTorch compute fallback.
 """
+import contextlib
 import ctypes as C
 import math
 import os
 import threading
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -845,7 +846,61 @@ class FlowModel(nn.Module):
         recording: `seed` as in `enhance(seed=)` (an int -> channel c uses clip_seed(seed, c); C ints; an int64 / uint64 tensor [C]),
         None draws one from torch's default generator.  Rows that overlap start from bit-identical noise in their overlap, so a seam is
         a cross-fade of two nearly equal signals.  A recording of one row equals `enhance(y, seed=seed)` bit for bit; the result does
-        not depend on `rows_per_call`.  Fixed-step solvers only.  Returns a tensor with the shape and on the device of `y`."""
+        not depend on `rows_per_call`.  Fixed-step solvers only.  Returns a tensor with the shape and on the device of `y`.
+
+        The two halves are callable on their own (`enhance_long_rows` -> `enhance_long_stitch`): a row's output depends on (recording,
+        seed, absolute frame) only, so any split of the (channel, row) jobs over calls -- or over processes,
+        `flowdec_amd.dist.sharded_enhance_long` -- stitches to the same bits."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call)
+        with self._long_stream(plan) as (lib, h, y_dev):
+            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs, N, solver, sigma_fac, rows_per_call, use_graph)
+            x_hat = self._long_stitch_rows(lib, plan, row_out)
+        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
+        return x_hat.reshape(y.shape).to(y.device)
+
+    @torch.no_grad()
+    @_serialized
+    def enhance_long_rows(self, y, jobs: Optional[Tuple[int, int]] = None, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0,
+                          seed=None, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None, rows_per_call: int = 8,
+                          use_graph: bool = True):
+        """The first half of `enhance_long`: the outputs of the jobs [lo, hi) = `jobs` (default: all) of the recording's job pool -- job
+        c * R + j is row j of channel c, R rows per channel -- as a float32 device tensor [hi - lo, row samples] (row k holds the samples
+        from its row's start on; what lies beyond the row's length is unspecified).  `seed` must be given: the rows of one recording
+        share it.  The normalisation is the whole recording's whichever jobs run (a maximum: the same bits in every call)."""
+        if seed is None:
+            raise ValueError("enhance_long_rows: pass the recording's seed (the calls that share a recording must share it)")
+        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call)
+        lo, hi = (0, len(plan.jobs)) if jobs is None else (int(jobs[0]), int(jobs[1]))
+        if not 0 <= lo <= hi <= len(plan.jobs):
+            raise ValueError(f"enhance_long_rows: jobs {(lo, hi)} outside the recording's {len(plan.jobs)} (channel, row) jobs")
+        with self._long_stream(plan) as (lib, h, y_dev):
+            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs[lo:hi], N, solver, sigma_fac, rows_per_call, use_graph)
+        row_out.record_stream(torch.cuda.current_stream(plan.dev))
+        return row_out
+
+    @torch.no_grad()
+    @_serialized
+    def enhance_long_stitch(self, y, row_out, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None):
+        """The second half of `enhance_long`: the recording from the outputs of ALL its jobs (`enhance_long_rows`, in job order).  Only the
+        shape, the device and the length of `y` are used."""
+        plan = self._long_plan(y, "euler", 0, row_frames, halo_frames, xfade, 1)
+        if tuple(row_out.shape) != (len(plan.jobs), plan.Lrow) or row_out.dtype != torch.float32:
+            raise ValueError(f"enhance_long_stitch: expected float32 row outputs {(len(plan.jobs), plan.Lrow)} (got {row_out.dtype} {tuple(row_out.shape)})")
+        row_out = row_out.to(plan.dev).contiguous()
+        with self._long_stream(plan, upload=False) as (lib, h, _):
+            x_hat = self._long_stitch_rows(lib, plan, row_out)
+        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
+        return x_hat.reshape(y.shape).to(y.device)
+
+    def enhance_long_jobs(self, y, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None) -> int:
+        """The number of (channel, row) jobs `enhance_long` cuts y into."""
+        return len(self._long_plan(y, "euler", 0, row_frames, halo_frames, xfade, 1).jobs)
+
+    def _long_plan(self, y, solver, seed, row_frames, halo_frames, xfade, rows_per_call):
+        """Argument checks and the host-side geometry of a long-form call: rows, bucket, the (channel, row) job pool, per-channel seeds."""
+        from types import SimpleNamespace
         from . import longform, ops
         if solver not in L.SOLVERS:
             raise ValueError(f"enhance_long: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
@@ -859,71 +914,87 @@ class FlowModel(nn.Module):
             y3 = y3.unsqueeze(0)
         if y3.ndim != 3 or y3.shape[1] != 1:
             raise RuntimeError(f"enhance_long expects [L], [1, L] or [C, 1, L] waveforms (got {tuple(y.shape)})")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
         lib = L.load()
-        h = self._sync_native()
         cfg = self.feature_extractor._cfg()
         hop = cfg["hop"]
         C_, n = y3.shape[0], y3.shape[-1]
         rows = longform.plan_rows(n, hop, row_frames, halo_frames, xfade)
         xfade = 2 * hop if xfade is None else int(xfade)
-        R = len(rows)
         Tp = int(lib.fd_padded_frames(lib.fd_num_frames(rows[0].length, hop)))
         Lrow = hop * Tp - 1
         ops.check_ragged_lengths([r.length for r in rows], Lrow, cfg["n_fft"], hop)
         if n // hop + Tp >= 2 ** 31:
             raise RuntimeError(f"enhance_long: {n} samples exceed the 2^31 absolute frames of the noise contract")
         jobs = [(c, r) for c in range(C_) for r in rows]          # every channel's rows, one pool: a row's result depends on nothing else
-        n_calls = -(-len(jobs) // int(rows_per_call))
-        B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
-        file_seeds = fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist()
-        normalize = self.normalize_mode == "noisy"
+        return SimpleNamespace(dev=dev, y3=y3, C=C_, n=n, rows=rows, R=len(rows), xfade=xfade, Tp=Tp, Lrow=Lrow, jobs=jobs,
+                               file_seeds=fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist(), normalize=self.normalize_mode == "noisy")
+
+    @contextlib.contextmanager
+    def _long_stream(self, plan, upload: bool = True):
+        """The side stream the long-form native calls run on, ordered after / before the caller's current stream.  -> (lib, handle, the
+        recording [C, n] on the device, or None without `upload`)."""
+        lib = L.load()
+        h = self._sync_native()
+        dev = plan.dev
         with torch.cuda.device(dev):
-            y_dev = y3.reshape(C_, n).to(dev, torch.float32).contiguous()
-            io = self._long_buffers(B, Lrow, dev)
+            y_dev = plan.y3.reshape(plan.C, plan.n).to(dev, torch.float32).contiguous() if upload else None
             cur = torch.cuda.current_stream(dev)
             if self._side_stream is None:
                 self._side_stream = torch.cuda.Stream(dev)
             side = self._side_stream
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                file_normfac = None
-                if normalize:
-                    file_normfac = torch.empty(C_, dtype=torch.float32, device=dev)
-                    L.check(lib.fd_normfac(L.ptr(y_dev), None, C_, n, L.ptr(file_normfac), L.stream()))
-                need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
-                if need == 0:
-                    raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-                ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
-                row_out = torch.empty(len(jobs), Lrow, dtype=torch.float32, device=dev)
-                for g0 in range(0, len(jobs), B):
-                    group = jobs[g0:g0 + B]
-                    group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
-                    for b, (c, r) in enumerate(group):
-                        io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
-                        io["y"][b, r.length:].zero_()
-                    chans = torch.tensor([c for c, _ in group], dtype=torch.int64)
-                    io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
-                    io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
-                    io["seeds"].copy_(torch.tensor([file_seeds[c] for c, _ in group], dtype=torch.int64))
-                    if normalize:
-                        io["normfac"].copy_(file_normfac[chans.to(dev)])
-                    L.check(lib.fd_enhance_chunks(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["seeds"]), L.ptr(io["frame0"]),
-                                                  L.ptr(io["normfac"]) if normalize else None, float(sigma_fac), int(N), L.SOLVERS[solver],
-                                                  L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-                    k = min(B, len(jobs) - g0)
-                    row_out[g0:g0 + k].copy_(io["out"][:k])
-                x_hat = torch.empty(C_, n, dtype=torch.float32, device=dev)
-                starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
-                bounds = torch.tensor([r.xfade_lo for r in rows[1:]], dtype=torch.int32).to(dev) if R > 1 else None
-                weights = torch.from_numpy(longform.stitch_weights(xfade)).to(dev) if R > 1 and xfade > 0 else None
-                for c in range(C_):
-                    L.check(lib.fd_stitch_chunks(L.ptr(row_out[c * R:(c + 1) * R]), Lrow, L.ptr(starts), L.ptr(bounds), R, L.ptr(weights),
-                                                 xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
+                yield lib, h, y_dev
             cur.wait_stream(side)
-        x_hat.record_stream(cur)
-        return x_hat.reshape(y.shape).to(y.device)
+
+    def _long_run_jobs(self, lib, h, plan, y_dev, jobs, N, solver, sigma_fac, rows_per_call, use_graph):
+        """`jobs` (a slice of plan.jobs) through fd_enhance_chunks in balanced groups of at most `rows_per_call` -> [len(jobs), Lrow]."""
+        dev, Lrow, normalize = plan.dev, plan.Lrow, plan.normalize
+        row_out = torch.empty(len(jobs), Lrow, dtype=torch.float32, device=dev)
+        if not jobs:
+            return row_out
+        n_calls = -(-len(jobs) // int(rows_per_call))
+        B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
+        io = self._long_buffers(B, Lrow, dev)
+        file_normfac = None
+        if normalize:                                             # the WHOLE recording's factor, whichever of its jobs run here
+            file_normfac = torch.empty(plan.C, dtype=torch.float32, device=dev)
+            L.check(lib.fd_normfac(L.ptr(y_dev), None, plan.C, plan.n, L.ptr(file_normfac), L.stream()))
+        need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
+        if need == 0:
+            raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
+        ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
+        for g0 in range(0, len(jobs), B):
+            group = jobs[g0:g0 + B]
+            group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
+            for b, (c, r) in enumerate(group):
+                io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
+                io["y"][b, r.length:].zero_()
+            chans = torch.tensor([c for c, _ in group], dtype=torch.int64)
+            io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
+            io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
+            io["seeds"].copy_(torch.tensor([plan.file_seeds[c] for c, _ in group], dtype=torch.int64))
+            if normalize:
+                io["normfac"].copy_(file_normfac[chans.to(dev)])
+            L.check(lib.fd_enhance_chunks(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["seeds"]), L.ptr(io["frame0"]),
+                                          L.ptr(io["normfac"]) if normalize else None, float(sigma_fac), int(N), L.SOLVERS[solver],
+                                          L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+            k = min(B, len(jobs) - g0)
+            row_out[g0:g0 + k].copy_(io["out"][:k])
+        return row_out
+
+    def _long_stitch_rows(self, lib, plan, row_out):
+        """fd_stitch_chunks per channel over the outputs of all jobs -> [C, n]."""
+        from . import longform
+        dev, rows, R, n, xfade = plan.dev, plan.rows, plan.R, plan.n, plan.xfade
+        x_hat = torch.empty(plan.C, n, dtype=torch.float32, device=dev)
+        starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
+        bounds = torch.tensor([r.xfade_lo for r in rows[1:]], dtype=torch.int32).to(dev) if R > 1 else None
+        weights = torch.from_numpy(longform.stitch_weights(xfade)).to(dev) if R > 1 and xfade > 0 else None
+        for c in range(plan.C):
+            L.check(lib.fd_stitch_chunks(L.ptr(row_out[c * R:(c + 1) * R]), plan.Lrow, L.ptr(starts), L.ptr(bounds), R, L.ptr(weights),
+                                         xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
+        return x_hat
 
     def _enhance_adaptive(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev, atol, rtol, method=0,
                           per_clip=False, seeds=None, lengths=None):
