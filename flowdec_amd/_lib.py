@@ -64,6 +64,12 @@ class FdScoreConfig(C.Structure):
                 ("N", c_int), ("predictor", c_int), ("corrector", c_int), ("corrector_steps", c_int), ("denoise", c_int)]
 
 
+class FdStreamRow(C.Structure):
+    """fd_stream_row: one entry per row of a streaming step (include/flowdec_hip.h "Streaming"); 64 bytes."""
+    _fields_ = [("ring", c_void_p), ("start", c_ll), ("ring_cap", c_int), ("length", c_int), ("peak_slot", c_int), ("emit_lo", c_int),
+                ("emit_count", c_int), ("tail_lo", c_int), ("tail_in", c_void_p), ("tail_out", c_void_p), ("out", c_void_p)]
+
+
 PREDICTORS = {"reverse_diffusion": 0, "euler_maruyama": 1, "none": 2}
 CORRECTORS = {"ald": 0, "none": 1}
 
@@ -138,6 +144,8 @@ SIGNATURES = {
     "fd_enhance_chunks": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_normfac": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "fd_stitch_chunks": (c_int, [_P, c_ll, _P, _P, c_int, _P, c_int, _P, c_ll, _P]),
+    "fd_stream_gather": (c_int, [_P, c_int, _P, c_int, _P, _P, _P]),
+    "fd_stream_emit": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P]),
     "fd_ode_solve_seeded": (c_int, [_P, _P, _P, c_float, c_int, c_int, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_enhance_seeded": (c_int, [_P, _P, _P, _P, c_float, c_int, c_int, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_enhance_seeded": (c_int, [_P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),

@@ -102,3 +102,91 @@ def chunk_halo_frames(row_frames: int, halo_frames: int = 256) -> int:
     """The halo the command line uses with rows of `row_frames`: the default, but never more than a quarter of the row (rows shorter than
     1024 frames would otherwise be mostly, or entirely, halo)."""
     return min(int(halo_frames), int(row_frames) // 4)
+
+
+class StreamRow(NamedTuple):
+    row: Row                   # the row, field for field what plan_rows gives for the finished recording
+    finished: Tuple[int, int]  # [lo, hi): the samples of the recording that are final once this row has run (consecutive, from 0)
+    index: int                 # the row's number in the recording
+    last: bool
+
+
+class StreamPlanner:
+    """`plan_rows` for a recording whose length is not known yet: fed a running sample count (`push`) and one final `flush`, it yields the
+    rows of `plan_rows(n, ...)` -- the same fields -- as soon as each can run.
+
+    With h = hop, W = row_frames * h - 1, S = (row_frames - 2 * halo_frames - 1) * h, Bo = (row_frames - halo_frames - 1) * h,
+    half = xfade / 2:
+
+      * regular row j = [j * S, j * S + W) is READY as soon as more than j * S + W samples have arrived: plan_rows shifts only the last
+        row, and a row that has a sample beyond its end is not the last;
+      * `flush()` at n samples yields the last row as plan_rows places it: (0, n) if n <= W, else start ceil((n - W) / h) * h;
+      * after regular row j the samples [lo_j - half, hi_j - half) are final (lo_j = (j - 1) * S + Bo, hi_j = j * S + Bo; lo_0 - half
+        reads 0): the cross-fade around hi_j needs the next row.  After the last row they run to n;
+      * RETENTION INVARIANT: with j the next regular row, every row still to come -- regular or last -- starts at or after
+        `retain_from` = (j - 1) * S (0 for j = 0), the start of the previous regular row.  (The last row ends at n with
+        (j - 1) * S + W < n <= j * S + W, so it starts in ((j - 1) * S, j * S]: up to S - h before the next regular start.)  A session
+        therefore keeps its input from `retain_from` on, and `ring_samples` = S + W is enough to hold any row that can come next;
+      * worst-case algorithmic delay: sample hi_{j-1} - half becomes final with row j, i.e. once j * S + W + 1 samples have arrived --
+        `delay_samples` = (row_frames - halo_frames) * h + half samples of FURTHER input (plus the row's compute time);
+      * `push` refuses input once n / h + t_pad would reach 2^31 absolute frames (the noise contract, include/flowdec_hip.h).
+    """
+
+    def __init__(self, hop: int, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None, t_pad: Optional[int] = None):
+        self.hop, self.rf, self.halo = int(hop), int(row_frames), int(halo_frames)
+        self.xfade = 2 * self.hop if xfade is None else int(xfade)
+        self.W = row_samples(self.rf, self.hop)
+        plan_rows(self.W + 1, self.hop, self.rf, self.halo, self.xfade)      # the argument checks of plan_rows, incl. "no room between two halos"
+        self.S = (self.rf - 2 * self.halo - 1) * self.hop
+        self.Bo = (self.rf - self.halo - 1) * self.hop
+        self.half = self.xfade // 2
+        self.t_pad = self.rf if t_pad is None else int(t_pad)
+        self.delay_samples = (self.rf - self.halo) * self.hop + self.half
+        self.ring_samples = self.S + self.W
+        self.n = 0                 # samples arrived
+        self.j = 0                 # the next regular row
+        self.done = 0              # samples final so far: the next finished range starts here
+        self.closed = False
+
+    @property
+    def retain_from(self) -> int:
+        """The first sample a session still needs (the retention invariant of the class docstring)."""
+        return max(self.j - 1, 0) * self.S
+
+    def push(self, count: int) -> None:
+        count = int(count)
+        if self.closed or count < 0:
+            raise ValueError("StreamPlanner.push: the stream is flushed" if self.closed else f"StreamPlanner.push: negative count {count}")
+        if (self.n + count) // self.hop + self.t_pad >= 2 ** 31:
+            raise RuntimeError(f"StreamPlanner.push: {self.n + count} samples exceed the 2^31 absolute frames of the noise contract")
+        self.n += count
+
+    def ready(self) -> bool:
+        return not self.closed and self.n > self.j * self.S + self.W
+
+    def next_row(self) -> Optional[StreamRow]:
+        """The next regular row if it is ready, else None."""
+        if not self.ready():
+            return None
+        j, s = self.j, self.j * self.S
+        lo, hi = (0 if j == 0 else s - self.S + self.Bo), s + self.Bo
+        out = StreamRow(Row(s, self.W, s // self.hop, (lo, hi), None if j == 0 else lo, hi), (self.done, hi - self.half), j, False)
+        assert out.finished[0] == max(lo - self.half, 0) and s >= self.retain_from
+        self.j, self.done = j + 1, hi - self.half
+        return out
+
+    def flush(self) -> StreamRow:
+        """The last row.  Call it once every ready regular row has been taken (`next_row()` is None)."""
+        if self.closed or self.ready() or self.n < 1:
+            raise ValueError("StreamPlanner.flush: " + ("already flushed" if self.closed else "regular rows are still ready" if self.n else "no input"))
+        self.closed = True
+        n, j = self.n, self.j
+        if j == 0:                                                # n <= W: the recording is one row
+            out = StreamRow(Row(0, n, 0, (0, n), None, None), (0, n), 0, True)
+        else:
+            s = -(-(n - self.W) // self.hop) * self.hop           # as plan_rows: n - W rounded UP onto the frame grid
+            lo = (j - 1) * self.S + self.Bo
+            out = StreamRow(Row(s, n - s, s // self.hop, (lo, n), lo, None), (self.done, n), j, True)
+            assert s >= self.retain_from + self.hop and out.finished[0] == lo - self.half
+        self.done = n
+        return out

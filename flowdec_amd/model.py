@@ -379,6 +379,23 @@ def _serialized(fn):
     return wrapper
 
 
+def _normfac_option(fn):
+    """Adds the keyword-only option `normfac` (default None: the recording's maximum) to a long-form entry point; the call reads it as
+    self._long_normfac.  The positional / keyword parameters of the entry points themselves are a pinned surface
+    (tests/test_longform_cpu.py), so the option is additive here rather than one more parameter there.  Goes INSIDE @_serialized: the
+    native lock is held while the value is set."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, normfac=None, **kwargs):
+        self._long_normfac = normfac
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            self._long_normfac = None
+    return wrapper
+
+
 # ------------------------------------------------------------------------------------------------
 # feature extractor mirror
 # ------------------------------------------------------------------------------------------------
@@ -834,6 +851,7 @@ class FlowModel(nn.Module):
 
     @torch.no_grad()
     @_serialized
+    @_normfac_option
     def enhance_long(self, y, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, seed=None, row_frames: int = 3712,
                      halo_frames: int = 256, xfade: Optional[int] = None, rows_per_call: int = 8, use_graph: bool = True):
         """`enhance` for a recording of ANY length in fixed device memory (no counterpart in the reference, whose driver skips files over
@@ -850,10 +868,15 @@ class FlowModel(nn.Module):
 
         The two halves are callable on their own (`enhance_long_rows` -> `enhance_long_stitch`): a row's output depends on (recording,
         seed, absolute frame) only, so any split of the (channel, row) jobs over calls -- or over processes,
-        `flowdec_amd.dist.sharded_enhance_long` -- stitches to the same bits."""
+        `flowdec_amd.dist.sharded_enhance_long` -- stitches to the same bits.
+
+        Keyword `normfac` (normalize_mode='noisy' only; added by @_normfac_option) replaces the recording's maximum: a float, or a tensor of one factor per channel; or
+        "causal": row j is scaled by fd_normfac(y[0 : start_j + len_j)), the peak of everything up to the row's END -- the one
+        normalisation a stream can reproduce (flowdec_amd.stream), as it depends on the samples up to there and on nothing else.
+        Overlapping rows then differ slightly in scale; the cross-fade absorbs the difference.  None: the recording's maximum."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
-        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call)
+        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, self._long_normfac)
         with self._long_stream(plan) as (lib, h, y_dev):
             row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs, N, solver, sigma_fac, rows_per_call, use_graph)
             x_hat = self._long_stitch_rows(lib, plan, row_out)
@@ -862,16 +885,18 @@ class FlowModel(nn.Module):
 
     @torch.no_grad()
     @_serialized
+    @_normfac_option
     def enhance_long_rows(self, y, jobs: Optional[Tuple[int, int]] = None, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0,
                           seed=None, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None, rows_per_call: int = 8,
                           use_graph: bool = True):
         """The first half of `enhance_long`: the outputs of the jobs [lo, hi) = `jobs` (default: all) of the recording's job pool -- job
         c * R + j is row j of channel c, R rows per channel -- as a float32 device tensor [hi - lo, row samples] (row k holds the samples
         from its row's start on; what lies beyond the row's length is unspecified).  `seed` must be given: the rows of one recording
-        share it.  The normalisation is the whole recording's whichever jobs run (a maximum: the same bits in every call)."""
+        share it.  The normalisation is the whole recording's whichever jobs run (a maximum: the same bits in every call); `normfac` as
+        in `enhance_long` (with "causal", overlapping rows differ slightly in scale; the cross-fade of the stitch absorbs it)."""
         if seed is None:
             raise ValueError("enhance_long_rows: pass the recording's seed (the calls that share a recording must share it)")
-        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call)
+        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, self._long_normfac)
         lo, hi = (0, len(plan.jobs)) if jobs is None else (int(jobs[0]), int(jobs[1]))
         if not 0 <= lo <= hi <= len(plan.jobs):
             raise ValueError(f"enhance_long_rows: jobs {(lo, hi)} outside the recording's {len(plan.jobs)} (channel, row) jobs")
@@ -898,7 +923,7 @@ class FlowModel(nn.Module):
         """The number of (channel, row) jobs `enhance_long` cuts y into."""
         return len(self._long_plan(y, "euler", 0, row_frames, halo_frames, xfade, 1).jobs)
 
-    def _long_plan(self, y, solver, seed, row_frames, halo_frames, xfade, rows_per_call):
+    def _long_plan(self, y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, normfac=None):
         """Argument checks and the host-side geometry of a long-form call: rows, bucket, the (channel, row) job pool, per-channel seeds."""
         from types import SimpleNamespace
         from . import longform, ops
@@ -925,9 +950,21 @@ class FlowModel(nn.Module):
         ops.check_ragged_lengths([r.length for r in rows], Lrow, cfg["n_fft"], hop)
         if n // hop + Tp >= 2 ** 31:
             raise RuntimeError(f"enhance_long: {n} samples exceed the 2^31 absolute frames of the noise contract")
+        normalize = self.normalize_mode == "noisy"
+        if normfac is not None:
+            if not normalize:
+                raise ValueError("enhance_long: normfac needs normalize_mode='noisy' (a 'none' model does not normalise)")
+            if isinstance(normfac, str):
+                if normfac != "causal":
+                    raise ValueError(f"enhance_long: normfac is None, a float, a per-channel tensor or 'causal' (got {normfac!r})")
+            else:
+                normfac = torch.as_tensor(normfac, dtype=torch.float32).reshape(-1)
+                if normfac.numel() not in (1, C_) or not bool((torch.isfinite(normfac) & (normfac > 0)).all()):
+                    raise ValueError(f"enhance_long: normfac must be one positive finite factor, or one per channel ({C_})")
+                normfac = normfac.expand(C_)
         jobs = [(c, r) for c in range(C_) for r in rows]          # every channel's rows, one pool: a row's result depends on nothing else
         return SimpleNamespace(dev=dev, y3=y3, C=C_, n=n, rows=rows, R=len(rows), xfade=xfade, Tp=Tp, Lrow=Lrow, jobs=jobs,
-                               file_seeds=fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist(), normalize=self.normalize_mode == "noisy")
+                               file_seeds=fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist(), normalize=normalize, normfac=normfac)
 
     @contextlib.contextmanager
     def _long_stream(self, plan, upload: bool = True):
@@ -956,10 +993,18 @@ class FlowModel(nn.Module):
         n_calls = -(-len(jobs) // int(rows_per_call))
         B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
         io = self._long_buffers(B, Lrow, dev)
-        file_normfac = None
-        if normalize:                                             # the WHOLE recording's factor, whichever of its jobs run here
+        file_normfac = row_index = None                           # [C], or [C, R] with normfac="causal"
+        if normalize and plan.normfac is None:                    # the WHOLE recording's factor, whichever of its jobs run here
             file_normfac = torch.empty(plan.C, dtype=torch.float32, device=dev)
             L.check(lib.fd_normfac(L.ptr(y_dev), None, plan.C, plan.n, L.ptr(file_normfac), L.stream()))
+        elif normalize and isinstance(plan.normfac, str):         # "causal": the peak of [0, row end) -- one prefix pass per row that runs here
+            file_normfac = torch.ones(plan.C, plan.R, dtype=torch.float32, device=dev)
+            row_index = {r.start: j for j, r in enumerate(plan.rows)}
+            for c, r in sorted(set((c, r) for c, r in jobs)):
+                L.check(lib.fd_normfac(L.ptr(y_dev[c]), None, 1, r.start + r.length, L.ptr(file_normfac[c, row_index[r.start]:]), L.stream()))
+            file_normfac = file_normfac.reshape(-1)
+        elif normalize:
+            file_normfac = plan.normfac.to(dev)
         need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
         if need == 0:
             raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
@@ -970,7 +1015,7 @@ class FlowModel(nn.Module):
             for b, (c, r) in enumerate(group):
                 io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
                 io["y"][b, r.length:].zero_()
-            chans = torch.tensor([c for c, _ in group], dtype=torch.int64)
+            chans = torch.tensor([c if row_index is None else c * plan.R + row_index[r.start] for c, r in group], dtype=torch.int64)
             io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
             io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
             io["seeds"].copy_(torch.tensor([plan.file_seeds[c] for c, _ in group], dtype=torch.int64))

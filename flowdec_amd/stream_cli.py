@@ -1,0 +1,119 @@
+"""Pipe front end of the streaming enhancer: raw PCM in, raw PCM out, written as it becomes final.
+
+    python -m flowdec_amd.stream_cli --ckpt C --N 6 --solver euler --seed 7 [--row-frames 256 --halo-frames 64] \\
+        --normfac causal|FLOAT --format s16le|f32le [--in - --out -] [--block-samples 4800]
+
+The input is mono PCM at the model's sampling rate (no resampling), little endian, without a header.  The output -- same format -- is,
+as float32, `model.enhance_long(input, seed=SEED, normfac=..., row_frames=..., halo_frames=...)` bit for bit (flowdec_amd.stream);
+s16le output is that rounded to 16 bits with clipping.  A sample leaves once (row_frames - halo_frames) * hop + xfade / 2 further
+samples have arrived, plus one row's compute time."""
+import argparse
+import sys
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+FORMATS = {"s16le": np.dtype("<i2"), "f32le": np.dtype("<f4")}
+
+
+def _normfac(s: str):
+    if s == "causal":
+        return s
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--normfac is 'causal' or a positive number (got {s!r})")
+    if not (np.isfinite(v) and v > 0):
+        raise argparse.ArgumentTypeError(f"--normfac is 'causal' or a positive number (got {s!r})")
+    return v
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Enhance a raw PCM stream with a FlowDec postfilter on MI355X (stdin -> stdout by default)")
+    p.add_argument("--ckpt", type=str, required=True)
+    p.add_argument("--N", type=int, required=True)
+    p.add_argument("--solver", type=str, default="euler", choices=["euler", "midpoint", "heun2", "heun2_eulerlast"], help="fixed-step solvers only")
+    p.add_argument("--seed", type=int, required=True, help="the stream's noise seed, as enhance_long(seed=SEED)")
+    p.add_argument("--row-frames", type=int, default=256, help="STFT frames per row (a multiple of 64)")
+    p.add_argument("--halo-frames", type=int, default=64)
+    p.add_argument("--normfac", type=_normfac, required=True,
+                   help="causal: every row is scaled by the peak of the stream up to its end; FLOAT: a fixed factor (full scale: 1.0)")
+    p.add_argument("--format", type=str, required=True, choices=sorted(FORMATS))
+    p.add_argument("--in", dest="inp", type=str, default="-", help="input file (default -: stdin)")
+    p.add_argument("--out", type=str, default="-", help="output file (default -: stdout)")
+    p.add_argument("--block-samples", type=int, default=4800, help="samples read per push")
+    p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--ema", type=lambda s: str(s).lower() not in ("0", "false", "no"), default=True)
+    p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.block_samples < 1:
+        p.error("--block-samples must be >= 1")
+    if args.N < 1:
+        p.error("--N must be >= 1")
+    return args
+
+
+def encode(x: torch.Tensor, fmt: str) -> bytes:
+    """float32 samples -> the bytes of `fmt` (s16le: round(x * 32768) clipped to [-32768, 32767])."""
+    a = x.detach().to("cpu", torch.float32).numpy()
+    if fmt == "s16le":
+        a = np.clip(np.rint(a.astype(np.float64) * 32768.0), -32768, 32767)
+    return a.astype(FORMATS[fmt]).tobytes()
+
+
+def run(argv: Optional[List[str]] = None, model=None) -> int:
+    """-> the number of samples written.  `model`: an already loaded FlowModel (tests)."""
+    from .enhance_cli import load_from_checkpoint
+    from .stream import EnhanceStream
+    args = parse_args(argv)
+    if model is None:
+        model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model="flow")
+    st = EnhanceStream(model, seed=args.seed, N=args.N, solver=args.solver, row_frames=args.row_frames, halo_frames=args.halo_frames,
+                       normfac=args.normfac)
+    dt = FORMATS[args.format]
+    fin = sys.stdin.buffer if args.inp == "-" else open(args.inp, "rb")
+    fout = sys.stdout.buffer if args.out == "-" else open(args.out, "wb")
+    written = 0
+    try:
+        want = args.block_samples * dt.itemsize
+        rest = b""
+        while True:
+            buf = fin.read(want)
+            if not buf:
+                break
+            buf = rest + buf
+            k = len(buf) // dt.itemsize * dt.itemsize            # a pipe may cut a sample in two
+            buf, rest = buf[:k], buf[k:]
+            if not buf:
+                continue
+            y = st.push(torch.from_numpy(np.frombuffer(buf, dtype=dt).astype(dt.newbyteorder("=")).copy()))
+            if y.numel():
+                fout.write(encode(y, args.format))
+                fout.flush()
+                written += y.numel()
+        y = st.flush()
+        fout.write(encode(y, args.format))
+        fout.flush()
+        written += y.numel()
+    finally:
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+    print(f"stream_cli: {written} samples written (delay {st.delay_samples} samples)", file=sys.stderr)
+    return written
+
+
+def main(argv=None) -> int:
+    run(argv)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -489,6 +489,44 @@ int fd_normfac(const float* y, const int* lengths, int B, int L, float* normfac_
  * a row is clamped into it. */
 int fd_stitch_chunks(const float* rows, long long row_stride, const int* starts, const int* bounds, int n_rows, const float* weights, int xfade,
                      float* out, long long n, void* stream);
+/* ---- Streaming: the same rows, run as the input arrives (session layer: flowdec_amd/stream.py; planner: longform.StreamPlanner) -------
+ * A stream's output is, bit for bit, enhance_long's on the concatenated input, however the input was cut into pushes and whichever other
+ * streams shared its native calls.  With h = hop, rf = row_frames, halo = halo_frames, X = xfade (even), half = X / 2:
+ *   W = rf * h - 1 (row samples), S = (rf - 2 * halo - 1) * h (stride), Bo = (rf - halo - 1) * h (boundary after a row's start).
+ * Regular row j = [j * S, j * S + W) can run as soon as MORE than j * S + W samples have arrived (it is then known not to be the last
+ * row); the end of the stream (n samples) adds the last row exactly as plan_rows places it.  After regular row j the samples
+ * [lo_j - half, hi_j - half) are final (lo_j = (j - 1) * S + Bo, hi_j = j * S + Bo; lo_0 - half reads 0), after the last row everything
+ * up to n.  Worst-case algorithmic delay: a sample leaves once (rf - halo) * h + half FURTHER samples have arrived (plus one row's compute time).
+ * A session keeps its input from the start of the previous regular row on: the last row starts at most S - h before the next regular start.
+ * Normalisation that needs no whole file: a fixed factor, or CAUSAL -- row j is scaled by fd_normfac of everything up to the row's end
+ * (a running maximum: exact, and independent of how the input was pushed).  Overlapping rows then differ slightly in scale; the
+ * cross-fade absorbs it.
+ * One step of a pool of sessions = one table upload and three launches whatever the number of sessions:
+ *   fd_stream_gather (rings -> y [B][L], lengths' zero tails, causal factors) -> fd_enhance_chunks -> fd_stream_emit (x_hat -> outputs, tails).
+ * Both read ONE DEVICE table, an entry per row of the call (at most one row of a session per call): */
+typedef struct fd_stream_row {
+  const float* ring;     /* gather: the session's input ring, ring_cap floats; absolute sample i lives at ring[i % ring_cap] */
+  long long start;       /* gather: absolute index of the row's first sample (>= 0) */
+  int ring_cap;          /* gather: >= length */
+  int length;            /* gather: samples of the row, 1 .. L */
+  int peak_slot;         /* gather: the session's slot in peak[] (causal normalisation) */
+  int emit_lo;           /* emit: row-local index of the first finished sample (boundary with the previous row - half; 0 for a first row) */
+  int emit_count;        /* emit: finished samples, written to out[0 .. emit_count) */
+  int tail_lo;           /* emit: row-local index of (boundary with the next row - half): the new tail is x_hat[b][tail_lo .. tail_lo + X) */
+  const float* tail_in;  /* emit: the previous row's tail [X], or NULL for a session's first row */
+  float* tail_out;       /* emit: where this row's tail [X] goes, or NULL for a session's last row.  NOT tail_in: the old tail is read and
+                          *       the new one written in the same launch -- keep two buffers per session and alternate by row parity */
+  float* out;            /* emit: destination of the finished samples */
+} fd_stream_row;
+/* y [B][L] float32: y[b][0 .. length_b) = the ring's samples [start_b, start_b + length_b), y[b][length_b .. L) = 0.  peak / normfac_out
+ * (both or neither; DEVICE float32 [slots] / [B]): peak[peak_slot_b] = max(peak[peak_slot_b], max |row b|), normfac_out[b] = that peak,
+ * 1 where it is <= 1e-8 (fd_normfac's rule).  Zero a session's slot when it opens.  One workgroup per row. */
+int fd_stream_gather(const fd_stream_row* table, int B, float* y, int L, float* peak, float* normfac_out, void* stream);
+/* x_hat [B][L] float32 (fd_enhance_chunks' output).  out_b[i] = x_hat[b][emit_lo_b + i], i < emit_count_b, except where a previous row
+ * exists (tail_in_b != NULL) and i < xfade: out_b[i] = a + w * (x - a) with a = tail_in_b[i], w = weights[i], x = x_hat[b][emit_lo_b + i]
+ * -- fd_stitch_chunks' arithmetic and weights table (three roundings, no fused multiply-add).  Then tail_out_b[k] = x_hat[b][tail_lo_b + k],
+ * k < xfade, unless tail_out_b is NULL.  Row-local indices are clamped into [0, L). */
+int fd_stream_emit(const fd_stream_row* table, int B, const float* x_hat, int L, const float* weights, int xfade, void* stream);
 /* normalize_mode of the model's front end: 1 = 'noisy' (default), 0 = 'none' (model.py:52, util/other.py:70). */
 int fd_model_set_normalize(fd_model* m, int normalize);
 
