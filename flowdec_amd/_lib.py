@@ -184,6 +184,10 @@ SIGNATURES = {
     "fd_ndac_decode": (c_int, [_P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_stft_plan_profile": (c_int, [_P, c_int]),
     "fd_stft_plan_profile_read": (c_int, [_P, C.POINTER(C.c_double * 6), C.POINTER(c_int * 2)]),
+    "fd_metrics_workspace_bytes": (c_size_t, [c_int] * 4),
+    "fd_metrics_sisxr": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "fd_metrics_logspec_mse": (c_int, [_P, _P, _P, _P, c_int, c_int, C.c_double, _P, _P, c_size_t, _P]),
+    "fd_metrics_power_spec": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -74,6 +74,11 @@ int fd_stft_forward(fd_stft_plan* p, const float* y, const int* lens, int B, int
 int fd_stft_inverse(fd_stft_plan* p, const float* X, const int* lens, int B, int T, int T_pad, float alpha, float beta, const float* normfac,
                     float* y, int L, void* ws, size_t ws_bytes, hipStream_t st);
 size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop);
+// for metrics.hip: the plan's geometry, the GEMM width of one n_fft, and framing (no normalisation) + DFT GEMM into caller buffers
+// frames / spec, both [B * (1 + L / hop)][kpad] float32
+void fd_stft_plan_dims(const fd_stft_plan* p, int* n_fft, int* hop, int* n_freq, int* kpad);
+int fd_stft_kpad(int n_fft);
+int fd_stft_raw_spectrum(fd_stft_plan* p, const float* y, const int* lens, int B, int L, float* frames, float* spec, hipStream_t st);
 // ndac_mfma.hip: the codec's wide convolutions on the matrix cores (split-bf16 operands, f32 tolerance)
 bool fd_ndac_mfma_supported(int Ci, int Co, int K, int stride, int dil, int transposed);
 // (fd_ndac_mfma_packed_bytes: public, include/flowdec_hip.h)

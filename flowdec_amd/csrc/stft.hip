@@ -64,8 +64,8 @@ __global__ __launch_bounds__(1024) void absmax_kernel(const float* __restrict__ 
   }
 }
 
-// frames[b*T + t][k] = y[b][reflect(hop*t + k - n_fft/2)] / normfac[b]; columns >= n_fft are zero (ragged: also the frames a
-// shorter clip does not have)
+// frames[b*T + t][k] = y[b][reflect(hop*t + k - n_fft/2)] / normfac[b] (normfac null: the samples as they are); columns >= n_fft are
+// zero (ragged: also the frames a shorter clip does not have)
 __global__ void frame_kernel(const float* __restrict__ y, const int* __restrict__ lens, const float* __restrict__ normfac, float* __restrict__ frames, int B,
                              int L, int T, int n_fft, int hop, int kpad) {
   const long long total = (long long)B * T * kpad;
@@ -80,7 +80,8 @@ __global__ void frame_kernel(const float* __restrict__ y, const int* __restrict_
       int s = hop * t + k - pad;
       s = s < 0 ? -s : s;
       s = s >= Lb ? 2 * (Lb - 1) - s : s;
-      v = y[(size_t)b * L + s] / normfac[b];
+      v = y[(size_t)b * L + s];
+      if (normfac) v /= normfac[b];
     }
     frames[i] = v;
   }
@@ -368,6 +369,24 @@ extern "C" int fd_stft_plan_profile_read(fd_stft_plan* p, double* ms6, int* call
     }
   }
   if (calls2) { calls2[0] = p->calls[0]; calls2[1] = p->calls[1]; }
+  return FD_OK;
+}
+
+void fd_stft_plan_dims(const fd_stft_plan* p, int* n_fft, int* hop, int* n_freq, int* kpad) {
+  *n_fft = p->n_fft; *hop = p->hop; *n_freq = p->n_freq; *kpad = p->kpad;
+}
+
+int fd_stft_kpad(int n_fft) { return stft_kpad(n_fft); }
+
+// The front end up to the raw spectrum, for callers with their own epilogue (metrics.hip): frames of y as they are (no normalisation, each
+// clip's own reflect boundary) -> spec[b*T + t][2f, 2f+1], both [B * T][kpad] float32 with T = 1 + L / hop
+int fd_stft_raw_spectrum(fd_stft_plan* p, const float* y, const int* lens, int B, int L, float* frames, float* spec, hipStream_t st) {
+  const int T = 1 + L / p->hop, K = p->kpad, M = B * T;
+  FD_REQUIRE(L > p->n_fft / 2, "stft: clip of %d samples is too short for reflect padding of %d", L, p->n_fft / 2);
+  hipLaunchKernelGGL(frame_kernel, dim3(grid_cap((long long)M * K)), dim3(256), 0, st, y, lens, (const float*)nullptr, frames, B, L, T, p->n_fft,
+                     p->hop, K);
+  FD_TRY(launch_sgemm(frames, p->Dt, spec, M, K, K, st));
+  FD_LAUNCH_CHECK();
   return FD_OK;
 }
 

@@ -61,6 +61,11 @@ ordinary error leaves the others to finish; the launcher then exits non-zero, na
 --skip-existing completes what is missing).  A worker that ends by a signal, an abort or a segmentation fault makes the launcher stop the
 others: nothing more is started on a GPU that may have faulted.  `--share-gpu` puts all ranks on cuda:0 (at most 8): a test aid for
 one-GPU boxes, not a speed-up.  The split is static (no work stealing): that is what makes rtfs.csv reproducible.
+
+Evaluation: `--eval` (pair lists only, default off; without it nothing changes) scores the `triples_list{suffix}.txt` the run has just
+written -- after the merge in the launcher of a --gpus N run -- with `flowdec_amd.eval_cli` on one GPU: SI-SDR / SI-SIR / SI-SAR and
+LogSpecMSE per triple into `metrics{suffix}.csv` beside the list.  The files are scored as they were written to disk, as the reference's
+evaluation scores them (flowdec/eval/metrics.py).
 """
 import argparse
 import collections
@@ -383,6 +388,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpus", type=int, default=1,
                    help="run the corpus on this many GPUs (cuda:0 .. cuda:N-1), one worker process each, batches spread by frame count; the "
                         "outputs, rtfs.csv and triples_list.txt are those of a one-process run (default 1: no child process)")
+    p.add_argument("--eval", action="store_true",
+                   help="pair lists only: after the run (after the merge of a --gpus N run), score the triples list just written with "
+                        "flowdec_amd.eval_cli on one GPU -> metrics{suffix}.csv next to it; the files are scored as written to disk")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -816,8 +824,17 @@ def launch_workers(argv: List[str], world: int, manifest: str, share_gpu: bool):
     return [(p.returncode, list(t)) for p, t in zip(procs, tails)]
 
 
+def evaluate_triples(args, suffix: str) -> None:
+    """--eval: SI-SxR and LogSpecMSE of `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it (flowdec_amd/eval_cli.py)."""
+    from . import eval_cli
+    with torch.cuda.device(args.device):
+        eval_cli.run(["--triples", os.path.join(args.outdir, f"triples_list{suffix}.txt"), "--out", os.path.join(args.outdir, f"metrics{suffix}.csv"),
+                      "--batch-files", str(max(args.batch_files, 1))])
+
+
 def run_launcher(args, parser, argv: List[str]) -> RunResult:
-    """The launching process of a --gpus N run (module docstring).  It opens no GPU and loads no checkpoint."""
+    """The launching process of a --gpus N run (module docstring).  It loads no checkpoint and opens no GPU, except for --eval after the
+    merge."""
     suffix = f"_{args.i_min}-{args.i_max}" if args.i_max else ""
     if not args.share_gpu:
         have = visible_gpus()
@@ -850,6 +867,8 @@ def run_launcher(args, parser, argv: List[str]) -> RunResult:
               f"({res.audio_seconds / wall:.1f} x real time)")
     else:
         print(f"{args.gpus} workers: {res.n_done} files in {wall:.3f} s of wall clock, start-up and checkpoint loading included")
+    if args.eval and clean is not None:
+        evaluate_triples(args, suffix)
     return res
 
 
@@ -943,6 +962,8 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
         with open(os.path.join(args.outdir, result_part_name(suffix, args.worker_rank)), "w") as f:
             json.dump(dict(n_done=res.n_done, n_over_precision_limit=res.n_over_precision_limit, n_too_long=res.n_too_long,
                            gpu_seconds=res.gpu_seconds, audio_seconds=res.audio_seconds), f)
+    elif args.eval and clean is not None:
+        evaluate_triples(args, suffix)
     return res
 
 

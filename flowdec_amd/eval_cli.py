@@ -1,0 +1,227 @@
+"""Scores a triples list on the GPU: the enhance -> evaluate loop of the reference (enhance.py:142 writes `triples_list.txt`,
+flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for the two of its metrics that need no outside model.
+
+    python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
+                                   [--sr 48000]
+
+Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (a comma inside an arrow line is part of the
+path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
+lowpass_filter_width=256 when its rate differs.  --crop-to-x then --crop-to-x-hat cut as in get_metrics_df (eval/metrics.py:85-90), in
+that order.
+
+Output: one CSV row per triple, in the list's order: name (the enhanced file's base name), x_hat, x, y, sisdr, sisir, sisar, logspec_mse
+(the reference's metric names), and a last printed block with the mean of every metric over its finite rows.  The metrics run on the GPU
+in length-sorted ragged batches of --batch-files triples (flowdec_amd/metrics.py: si_sxr_batch, logspec_mse_batch); a triple's numbers do
+not depend on the batch it ran in.
+
+A triple whose signals still differ in length after cropping gets NaN in all four columns and a warning (the reference gets there through
+its exception handler); so does the spectral column of a triple too short for the transform's reflect padding.  A triple with a file that
+cannot be read is skipped and counted, and the exit status is then 3 (enhance_cli's status of a partly done run), else 0.
+
+The reference's other metrics (PESQ, ESTOI, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside packages or models: out of
+scope.
+"""
+import argparse
+import csv
+import math
+import os
+import sys
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional
+
+import numpy as np
+import torch
+
+from .enhance_cli import _split_pair, load_wav, resample
+
+METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
+CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
+WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
+
+
+@dataclass
+class Triple:
+    x: str          # clean
+    y: str          # noisy
+    x_hat: str      # enhanced
+
+    @property
+    def name(self) -> str:
+        return os.path.basename(self.x_hat)
+
+
+def read_triples(listfile: str) -> List[Triple]:
+    """`clean ---> noisy ---> enhanced` per line; blank lines are skipped; any other field count is a ValueError naming the line."""
+    out = []
+    with open(listfile, "r") as f:
+        for lineno, raw in enumerate(f, 1):
+            entry = raw.strip()
+            if not entry:
+                continue
+            parts = [p.strip() for p in _split_pair(entry)]
+            if len(parts) != 3:
+                raise ValueError(f"{listfile}:{lineno}: {len(parts)} fields, a triples line is `clean ---> noisy ---> enhanced`")
+            out.append(Triple(parts[0], parts[1], parts[2]))
+    return out
+
+
+def load_mono(path: str, sr: int) -> torch.Tensor:
+    """load48000 (util/other.py:137-) for the rate `sr`: -> 1-D float32 tensor, the mean of the channels, resampled when the rate differs."""
+    au, fs = load_wav(path)
+    if au.shape[0] != 1:
+        au = au.mean(dim=0, keepdim=True)
+    if fs != sr:
+        au = resample(au, fs, sr, lowpass_filter_width=256)
+    return au[0].contiguous()
+
+
+def crop(x_hat: torch.Tensor, x: torch.Tensor, y: torch.Tensor, crop_to_x: bool, crop_to_x_hat: bool):
+    """get_metrics_df's crops (eval/metrics.py:85-90), in its order."""
+    if crop_to_x:
+        x_hat, y = x_hat[..., :x.shape[-1]], y[..., :x.shape[-1]]
+    if crop_to_x_hat:
+        x, y = x[..., :x_hat.shape[-1]], y[..., :x_hat.shape[-1]]
+    return x_hat, x, y
+
+
+def min_spectral_samples(sr: int) -> int:
+    """Shortest clip the spectral metric takes: reflect padding by n_fft / 2 needs one sample more."""
+    return int(WIN_DUR * sr) // 2 + 1
+
+
+@dataclass(frozen=True)
+class Scorer:
+    """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]."""
+    si_sxr: Callable
+    logspec: Callable
+
+
+def _gpu_si_sxr(x_hats, xs, ys, batch):
+    from . import metrics
+    return metrics.si_sxr_batch(x_hats, xs, ys, batch=batch)
+
+
+def _gpu_logspec(x_hats, xs, sr, batch):
+    from . import metrics
+    return metrics.logspec_mse_batch(x_hats, xs, sr=sr, win_dur=WIN_DUR, hop_dur=HOP_DUR, batch=batch)
+
+
+def _host_si_sxr(x_hats, xs, ys, batch):
+    from . import metrics
+    return np.array([metrics.si_sxr(h, x, y) for h, x, y in zip(x_hats, xs, ys)], np.float64).reshape(-1, 3)
+
+
+def _host_logspec(x_hats, xs, sr, batch):
+    from . import metrics
+    return np.array([metrics.logspec_mse(h, x, sr=sr, win_dur=WIN_DUR, hop_dur=HOP_DUR) for h, x in zip(x_hats, xs)], np.float64)
+
+
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec)        # ragged batches on the device (csrc/metrics.hip)
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec)     # the host functions of metrics.py, one triple at a time: the yardstick
+
+
+def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None) -> np.ndarray:
+    """signals: one (x_hat, x, y) of 1-D tensors per triple, cropped -> [n, 4] float64 in METRIC_NAMES order, row i for triple i whatever
+    order the batches ran in.  Unequal lengths: NaN in all four; too short for the transform: NaN in the spectral column."""
+    def warn(i, msg):
+        print(f"warning: {names[i] if names else 'triple %d' % i}: {msg}", file=sys.stderr)
+
+    def column(idx, k):
+        return [signals[i][k] for i in idx]
+
+    out = np.full((len(signals), 4), np.nan, np.float64)
+    ok = []
+    for i, (h, x, y) in enumerate(signals):
+        if not (h.shape[-1] == x.shape[-1] == y.shape[-1]):
+            warn(i, f"lengths differ (x_hat {h.shape[-1]}, x {x.shape[-1]}, y {y.shape[-1]}): NaN for every metric "
+                    f"(--crop-to-x / --crop-to-x-hat cut them to one length)")
+        elif x.shape[-1] < 1:
+            warn(i, "empty signals: NaN for every metric")
+        else:
+            ok.append(i)
+    spectral = [i for i in ok if signals[i][1].shape[-1] >= min_spectral_samples(sr)]
+    for i in sorted(set(ok) - set(spectral)):
+        warn(i, f"{signals[i][1].shape[-1]} samples are too few for the spectral metric (needs {min_spectral_samples(sr)}): NaN for logspec_mse")
+    if ok:
+        out[ok, :3] = scorer.si_sxr(column(ok, 0), column(ok, 1), column(ok, 2), batch)
+    if spectral:
+        out[spectral, 3] = scorer.logspec(column(spectral, 0), column(spectral, 1), sr, batch)
+    return out
+
+
+def fmt(v: float) -> str:
+    return "nan" if math.isnan(v) else repr(float(v))
+
+
+def write_csv(path: str, triples: List[Triple], values: np.ndarray) -> None:
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(CSV_HEADER)
+        for t, row in zip(triples, values):
+            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row])
+
+
+def summary(values: np.ndarray):
+    """-> [(metric, mean over its finite rows or NaN, count of finite rows)]."""
+    out = []
+    for k, name in enumerate(METRIC_NAMES):
+        col = values[:, k] if len(values) else np.zeros(0)
+        fin = col[np.isfinite(col)]
+        out.append((name, float(fin.mean()) if len(fin) else float("nan"), int(len(fin))))
+    return out
+
+
+@dataclass
+class EvalResult:
+    n_triples: int = 0
+    n_scored: int = 0          # rows written (NaN rows included)
+    n_unreadable: int = 0      # triples skipped: a file could not be read
+    means: list = field(default_factory=list)
+    csv_path: Optional[str] = None
+
+    @property
+    def exit_code(self) -> int:
+        return 3 if self.n_unreadable else 0
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Score a triples list (clean ---> noisy ---> enhanced) on MI355X: SI-SDR / SI-SIR / SI-SAR and LogSpecMSE")
+    p.add_argument("--triples", type=str, required=True, help="the triples_list.txt of an enhance_cli run on a pair list")
+    p.add_argument("--out", type=str, required=True, help="the CSV to write")
+    p.add_argument("--batch-files", type=int, default=8, help="triples per native call (length-sorted ragged batches)")
+    p.add_argument("--crop-to-x", action="store_true", help="cut x_hat and y to the length of x (eval/metrics.py:85-87)")
+    p.add_argument("--crop-to-x-hat", action="store_true", help="then cut x and y to the length of x_hat (eval/metrics.py:88-90)")
+    p.add_argument("--sr", type=int, default=48000, help="the rate every file is brought to (the reference evaluates at 48 kHz)")
+    return p
+
+
+def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    triples = read_triples(args.triples)
+    res = EvalResult(n_triples=len(triples), csv_path=args.out)
+    kept, signals = [], []
+    for t in triples:
+        try:
+            x_hat, x, y = load_mono(t.x_hat, args.sr), load_mono(t.x, args.sr), load_mono(t.y, args.sr)
+        except Exception as err:      # a missing or broken file: the reference skips the triple too (eval/metrics.py:95-96)
+            print(f"warning: skipping {t.name}: {type(err).__name__}: {err}", file=sys.stderr)
+            res.n_unreadable += 1
+            continue
+        kept.append(t)
+        signals.append(crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat))
+    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept])
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    write_csv(args.out, kept, values)
+    res.n_scored, res.means = len(kept), summary(values)
+    print(f"eval: {res.n_triples} triples, {res.n_scored} rows in {args.out}, {res.n_unreadable} skipped (unreadable)")
+    for name, mean, count in res.means:
+        print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
+    return res
+
+
+def cli(argv=None) -> int:
+    return run(argv).exit_code
+
+
+if __name__ == "__main__":
+    sys.exit(cli())

@@ -682,6 +682,39 @@ int fd_rvq_from_codes(fd_ndac* m, const int* codes, int B, int n_quantizers, int
 /* dac.DAC.decode: z [B][latent][T] -> audio [B][fd_ndac_decoded_length(T)] in (-1, 1) */
 int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics: the two metrics of the reference's evaluation (flowdec/eval/metrics.py) that need no outside model, over ragged
+ * batches -- what scores a `triples_list.txt` (flowdec_amd/eval_cli.py).  Rows [B][L] float32 on the device; lengths: DEVICE int32 [B],
+ * clip b is the first lengths[b] samples of its row (samples behind it are never read).  All three calls are asynchronous on `stream`,
+ * allocate nothing and launch nothing when they refuse.  A clip's result has the SAME BITS alone, in a batch, at any batch position and
+ * next to clips of any other lengths: every partition and order of summation depends on the clip's own length only; no atomics.
+ * ws: fd_metrics_workspace_bytes(B, L, n_fft, hop) bytes (covers all three; n_fft <= 0: fd_metrics_sisxr only; 0 for a bad B or L).
+ * A NULL pointer, a bad shape and a workspace that is too small are all FD_EINVAL here, with a message.
+ *
+ * fd_metrics_sisxr: SI-SDR / SI-SIR / SI-SAR (eval/metrics.py:256-270, :554-563) of estimate x_hat against reference x with degraded
+ *   input y, in float64, two passes.  The noise is n = y - x, or y + x when that has less power (the reference's phase-flip guard;
+ *   decided as x.y < 0); alpha_s = x_hat.x / x.x, alpha_n = x_hat.n / n.n; per sample s_target = alpha_s x, e_noise = alpha_n n,
+ *   e_art = x_hat - s_target - e_noise.  sums_out: DEVICE double [B][8] =
+ *     [0] x.x  [1] x_hat.x  [2] x_hat.n  [3] n.n  [4] |s_target|^2  [5] |e_noise|^2  [6] |e_art|^2  [7] |e_noise + e_art|^2
+ *   and the caller forms  si_sdr = 10 log10([4] / [7]),  si_sir = 10 log10([4] / [5]),  si_sar = 10 log10([4] / [6])  in float64.
+ *   A length is clamped into [0, L]; an empty clip gives zero sums.
+ * fd_metrics_logspec_mse: LogSpecMSE (eval/metrics.py:333-372): mean over all bins and frames of (10 log10 max(|X_hat|^2, eps) -
+ *   10 log10 max(|X|^2, eps))^2 of the one-sided power spectrograms of the plan's transform -- the reference's is
+ *   fd_stft_plan_create(1536, 384) at 48 kHz: symmetric Hann, center = True with reflect padding, T_b = 1 + lengths[b] / hop frames --,
+ *   |X|^2 in float32, everything after it in float64.  mse_out: DEVICE double [B].  L <= n_fft / 2 (torch.stft raises: the clip cannot be
+ *   reflect-padded) is FD_EINVAL; a DEVICE length outside (n_fft / 2, L] cannot be seen by the host and gives NaN for that clip (no
+ *   out-of-bounds access).
+ * fd_metrics_power_spec (operator level, for tests): P_out DEVICE float [B][1 + L / hop][n_fft / 2 + 1] = re^2 + im^2 exactly as the
+ *   call above forms it, zero in the frames t >= T_b.
+ * ---------------------------------------------------------------------------------------------- */
+size_t fd_metrics_workspace_bytes(int B, int L, int n_fft, int hop);
+int fd_metrics_sisxr(const float* x_hat, const float* x, const float* y, const int* lengths, int B, int L, double* sums_out, void* ws,
+                     size_t ws_bytes, void* stream);
+int fd_metrics_logspec_mse(const fd_stft_plan* plan, const float* x_hat, const float* x, const int* lengths, int B, int L, double eps,
+                           double* mse_out, void* ws, size_t ws_bytes, void* stream);
+int fd_metrics_power_spec(const fd_stft_plan* plan, const float* x, const int* lengths, int B, int L, float* P_out, void* ws, size_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
