@@ -188,6 +188,10 @@ SIGNATURES = {
     "fd_metrics_sisxr": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_metrics_logspec_mse": (c_int, [_P, _P, _P, _P, c_int, c_int, C.c_double, _P, _P, c_size_t, _P]),
     "fd_metrics_power_spec": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "fd_estimate_workspace_bytes": (c_size_t, [c_int] * 4),
+    "fd_estimate_pair_stats": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "fd_select_workspace_bytes": (c_size_t, [c_int]),
+    "fd_select_f32": (c_int, [_P, c_ll, C.POINTER(c_ll), c_int, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

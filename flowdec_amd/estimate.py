@@ -1,0 +1,187 @@
+"""Estimates the two data-dependent parameters of a FlowDec model from (clean, coded) pairs on the GPU: the reference's
+scripts/estimate_flowdec_params.py (the tool that made the `flowdec_autoparams_*.npy` curves under flowdec_amd/data/).
+
+* beta    = 1 / q_qx(|X_c|): the reciprocal of the qx quantile of the magnitudes of the amplitude-compressed (beta = 1) clean spectra,
+            over every bin of every pair.
+* sigma_y = q_qrmse(RMSE(Y_c, X_c)) / 3: the quantile over the pairs of the coded-vs-clean spectral RMSE, global or per frequency band.
+
+The transform, the compression, the magnitudes and the per-band squared differences come from fd_estimate_pair_stats, the order
+statistics of the magnitudes from fd_select_f32 (csrc/estimate.hip, include/flowdec_hip.h "Parameter estimation"); the reference
+concatenates every bin on the host and runs np.quantile over them.  What is left on the host is arithmetic on a handful of numbers, and
+it follows NumPy's own: `quantile_position` / `lerp` restate np.quantile(method='linear') so that two order statistics give np.quantile's
+bits (tests/test_estimate_host.py).
+
+The host-side randomness of the script (which pairs, where each is cropped) is reproduced call for call by `select_pairs` and
+`crop_or_pad_pair`; flowdec_amd/estimate_cli.py is the command line."""
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+
+# ---- the script's host-side randomness ---------------------------------------------------------------------------------------------------
+def select_pairs(lines: Sequence[str], n_samples: int, seed: int, delim: str = " ---> ") -> Tuple[List[int], List[Tuple[str, str]]]:
+    """The script's draw of `n_samples` pair lines (estimate_flowdec_params.py:137-142): np.random.seed(seed), then ONE
+    np.random.choice(..., n_samples, replace=False) over the lines -- NumPy's GLOBAL generator, like there, because the crop starts of
+    `crop_or_pad_pair` continue the same stream.  (choice over the line count draws what choice over the lines draws: both take
+    permutation(len(lines))[:n_samples].)  -> (line indices, [(clean path, coded path)]) in drawn order."""
+    lines = list(lines)
+    if n_samples > len(lines):
+        raise ValueError(f"select_pairs: {n_samples} samples asked of a list of {len(lines)} lines")
+    np.random.seed(seed)
+    idx = [int(i) for i in np.random.choice(len(lines), n_samples, replace=False)]
+    pairs = []
+    for i in idx:
+        parts = lines[i].split(delim)
+        if len(parts) < 2:
+            raise ValueError(f"select_pairs: line {i + 1} {lines[i]!r} is no `clean{delim}coded` pair")
+        pairs.append((parts[0], parts[1]))
+    return idx, pairs
+
+
+def crop_or_pad_pair(x: torch.Tensor, y: torch.Tensor, target: int, name: str = "pair", rng=np.random):
+    """random_crop_or_pad_pair of the script (:28-48) on the last axis: y is cut to x's length first; x of `target` samples: as it is;
+    shorter: both zero-padded at the end; longer: both cropped at ONE np.random.randint(0, len_x - target) (the upper end is exclusive,
+    so the last possible start is never drawn -- as there).  -> (x, y, start), start = None where nothing was drawn.
+    A y that ends up shorter than x makes the script fail at its subtraction of the spectra: ValueError naming the pair."""
+    y = y[..., :x.shape[-1]]
+    if y.shape[-1] < x.shape[-1]:
+        raise ValueError(f"{name}: the coded signal has {y.shape[-1]} samples, fewer than the clean signal's {x.shape[-1]}")
+    n = x.shape[-1]
+    if n == target:
+        return x, y, None
+    if n < target:
+        pad = (0, target - n)
+        return torch.nn.functional.pad(x, pad), torch.nn.functional.pad(y, pad), None
+    start = int(rng.randint(0, n - target))
+    return x[..., start:start + target], y[..., start:start + target], start
+
+
+# ---- np.quantile(method='linear') from order statistics ----------------------------------------------------------------------------------
+def quantile_position(n: int, q: float, dtype=np.float32) -> Tuple[int, int, np.ndarray]:
+    """Where np.quantile(a, q) of `n` values of `dtype` looks: -> (lower rank, upper rank, gamma).  NumPy (2.x) takes a Python-float q in
+    the ARRAY's dtype, so for float32 data the virtual index (n - 1) q is a float32 product: floor((n - 1) q) up to that rounding.  At or
+    beyond n - 1 both ranks are n - 1."""
+    dtype = np.dtype(dtype)
+    qa = np.asanyarray(q, dtype=dtype) if dtype.kind == "f" else np.asanyarray(q)
+    if not (0.0 <= float(qa) <= 1.0):
+        raise ValueError("Quantiles must be in the range [0, 1]")
+    virtual = np.asanyarray((n - 1) * qa)
+    if virtual >= n - 1:
+        lo = hi = n - 1
+    else:
+        lo = int(np.floor(virtual))
+        hi = lo + 1
+    gamma = np.asanyarray(virtual - np.intp(lo), dtype=virtual.dtype)
+    return lo, hi, gamma
+
+
+def lerp(a, b, gamma):
+    """NumPy's interpolation between two order statistics (its _lerp): a + (b - a) gamma, from the other end for gamma >= 0.5, in the
+    dtype NumPy's promotion gives (float32 values and a float32 gamma: float32)."""
+    a, b, t = np.asanyarray(a), np.asanyarray(b), np.asanyarray(gamma)
+    d = np.subtract(b, a)
+    r = np.asanyarray(np.add(a, d * t))
+    np.subtract(b, d * (1 - t), out=r, where=t >= 0.5, casting="unsafe", dtype=type(r.dtype))
+    return r[()] if r.ndim == 0 else r
+
+
+# ---- the estimate ------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class EstimateResult:
+    beta: float                                  # 1 / abs_quantile_x
+    abs_quantile_x: float                        # q_qx(|X_c|) over every bin of every pair (a float32 value)
+    max_abs_x: float                             # max |X_c|
+    sigma_y: Union[float, np.ndarray]            # rmse_quantile / 3: a float, or float32 [F] per band
+    rmse_quantile: Union[float, np.ndarray]      # q_qrmse over the pairs
+    rmse_max: Union[float, np.ndarray]           # max over the pairs
+    rmses: np.ndarray                            # [n_pairs] float64, or [n_pairs, F] float32 per band
+    n_bins: int = 0                              # n_pairs * F * T
+
+
+def rmses_from_band_sq(band_sq: np.ndarray, T: int, per_band: bool) -> np.ndarray:
+    """band_sq [n, F] float64 (sum over the T frames of |Y_c - X_c|^2) -> the script's RMSEs (:163-176).
+    Global: float32 norm of the whole difference, then / sqrt(F T) in float64: [n] float64.
+    Per band: float32 norm over the frames / sqrt(F) -- the script divides by sqrt(diff.shape[-2]), the number of BANDS and not of
+    frames; the shipped curves were made that way, so this keeps it: [n, F] float32."""
+    band_sq = np.asarray(band_sq, np.float64)
+    F = band_sq.shape[-1]
+    if per_band:
+        return np.sqrt(band_sq).astype(np.float32) / F ** 0.5
+    return np.sqrt(band_sq.sum(axis=-1)).astype(np.float32).astype(np.float64) / (F * T) ** 0.5
+
+
+def estimate_params(x_clips, y_clips, *, alpha: float, n_fft: int, hop: int, qx: float = 0.997, qrmse: float = 0.997, per_band: bool = False,
+                    batch_pairs: int = 64, device="cuda") -> EstimateResult:
+    """x_clips / y_clips: one 1-D signal per pair, clean and coded, ALL of one length (crop_or_pad_pair).  Runs the pairs through
+    fd_estimate_pair_stats in batches of `batch_pairs`, keeps |X_c| of all pairs in ONE device buffer (n_pairs F T floats: 1.9 GB for the
+    script's 2500 pairs of 2 s) and takes its order statistics with ONE fd_select_f32 call; the quantile over the pairs runs on the host.
+
+    Per-band RMSE is sqrt(band_sq[f]) / sqrt(F): the reference divides by the number of bands, not of frames (see rmses_from_band_sq)."""
+    from . import _lib as L, ops
+    lib = L.load()
+    xs = [torch.as_tensor(c).reshape(-1).float() for c in x_clips]
+    ys = [torch.as_tensor(c).reshape(-1).float() for c in y_clips]
+    n_pairs = len(xs)
+    if n_pairs < 1 or len(ys) != n_pairs:
+        raise ValueError(f"estimate_params: {len(xs)} clean and {len(ys)} coded clips (one of each per pair, at least one pair)")
+    Lc = int(xs[0].numel())
+    for i, (x, y) in enumerate(zip(xs, ys)):
+        if x.numel() != Lc or y.numel() != Lc:
+            raise ValueError(f"estimate_params: pair {i} has {x.numel()} / {y.numel()} samples, pair 0 has {Lc}: crop or pad every pair to one length")
+    if Lc <= n_fft // 2:
+        raise ValueError(f"estimate_params: clips of {Lc} samples cannot be reflect-padded by {n_fft // 2} (n_fft {n_fft})")
+    F, T = n_fft // 2 + 1, 1 + Lc // hop
+    batch_pairs = max(1, min(int(batch_pairs), n_pairs))
+    n_bins = n_pairs * F * T
+    with torch.cuda.device(device):
+        nws = int(lib.fd_estimate_workspace_bytes(batch_pairs, Lc, n_fft, hop))
+        nsel = int(lib.fd_select_workspace_bytes(3))
+        need = 4 * n_bins + nws + nsel + 8 * batch_pairs * (Lc + F + 1)
+        free = torch.cuda.mem_get_info()[0]
+        if need > free:
+            raise RuntimeError(f"estimate_params: |X_c| of {n_pairs} pairs ({4 * n_bins / 1e9:.2f} GB) and the workspace of {batch_pairs} pairs "
+                               f"({nws / 1e9:.2f} GB) do not fit in the {free / 1e9:.2f} GB of free device memory: fewer pairs, or a smaller batch_pairs")
+        plan = ops.stft_plan(n_fft, hop, device)
+        absx = torch.empty(n_pairs, F, T, dtype=torch.float32, device=device)
+        band_sq = torch.empty(n_pairs, F, dtype=torch.float64, device=device)
+        normfac = torch.empty(n_pairs, dtype=torch.float32, device=device)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        for i0 in range(0, n_pairs, batch_pairs):
+            i1 = min(i0 + batch_pairs, n_pairs)
+            xb, yb = torch.stack(xs[i0:i1]).to(device), torch.stack(ys[i0:i1]).to(device)
+            L.check(lib.fd_estimate_pair_stats(plan, L.ptr(xb), L.ptr(yb), i1 - i0, Lc, float(alpha), L.ptr(normfac[i0:i1]), L.ptr(absx[i0:i1]),
+                                               L.ptr(band_sq[i0:i1]), L.ptr(ws), nws, L.stream()))
+        lo, hi, gamma = quantile_position(n_bins, qx, np.float32)
+        order = select_f32(absx, [lo, hi, n_bins - 1])
+        band = band_sq.cpu().numpy()
+    q_x = lerp(order[0], order[1], gamma)
+    rmses = rmses_from_band_sq(band, T, per_band)
+    rq = np.quantile(rmses, qrmse, axis=0) if per_band else np.quantile(rmses, qrmse)
+    rmax = rmses.max(axis=0) if per_band else float(rmses.max())
+    return EstimateResult(beta=float(1 / q_x), abs_quantile_x=float(q_x), max_abs_x=float(order[2]), sigma_y=(rq / 3 if per_band else float(rq / 3)),
+                          rmse_quantile=(rq if per_band else float(rq)), rmse_max=rmax, rmses=rmses, n_bins=n_bins)
+
+
+def select_f32(values: torch.Tensor, ranks: Sequence[int]) -> np.ndarray:
+    """Exact order statistics of a device tensor of non-negative float32 values (fd_select_f32): -> float32 [len(ranks)], entry r the value
+    at position ranks[r] of the sorted values.  A negative value or a NaN among them is a ValueError."""
+    import ctypes as C
+    from . import _lib as L
+    lib = L.load()
+    L.require_cuda(values)
+    if values.dtype != torch.float32 or not values.is_contiguous():
+        raise ValueError("select_f32: a contiguous float32 tensor is needed")
+    R = len(ranks)
+    with torch.cuda.device(values.device):
+        nws = int(lib.fd_select_workspace_bytes(R))
+        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=values.device)
+        out = torch.empty(max(R, 1), dtype=torch.float32, device=values.device)
+        bad = torch.empty(1, dtype=torch.int64, device=values.device)
+        L.check(lib.fd_select_f32(L.ptr(values), int(values.numel()), (C.c_longlong * max(R, 1))(*[int(r) for r in ranks]), R, L.ptr(out), L.ptr(bad),
+                                  L.ptr(ws), nws, L.stream()))
+        n_bad = int(bad.item())
+        if n_bad:
+            raise ValueError(f"select_f32: {n_bad} of the {values.numel()} values are negative or NaN")
+        return out[:R].cpu().numpy()

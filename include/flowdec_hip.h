@@ -715,6 +715,37 @@ int fd_metrics_logspec_mse(const fd_stft_plan* plan, const float* x_hat, const f
 int fd_metrics_power_spec(const fd_stft_plan* plan, const float* x, const int* lengths, int B, int L, float* P_out, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Parameter estimation: the statistics behind a FlowDec model's beta and sigma_y (the reference's scripts/estimate_flowdec_params.py;
+ * flowdec_amd/estimate.py, flowdec_amd/estimate_cli.py).  Both calls are asynchronous on `stream`, allocate nothing, keep no state and
+ * launch nothing when they refuse; a NULL pointer, a bad shape and a workspace that is too small are FD_EINVAL with a message.
+ *
+ * fd_estimate_pair_stats: x (clean) and y (coded) are DEVICE float [B][L], every pair already cropped or padded to the one length L (not
+ *   ragged).  Per pair: normfac = max|y| + 1e-5 in float32 (the script's normalize_noisy: NO zero guard, unlike enhance's rule); x and y
+ *   divided by it sample by sample in float32; the plan's transform (symmetric Hann, reflect-centred, T = 1 + L / hop frames) of both;
+ *   amplitude compression |.|^alpha e^{j angle} with beta = 1 of both (fd_stft_compress's arithmetic, bit for bit).
+ *     normfac_out  DEVICE float [B]
+ *     absx_out     DEVICE float [B][F][T], F = n_fft / 2 + 1: |X_c| of the compressed CLEAN spectrum, formed from its float32 parts as
+ *                  (float) sqrt((double) re^2 + (double) im^2) (both roundings IEEE).  May be NULL.
+ *     band_sq_out  DEVICE double [B][F]: sum over t of |Y_c - X_c|^2, the difference per component in float32 (complex64 subtraction),
+ *                  squared and summed in float64 in a fixed order that depends on T only; no floating-point atomics.
+ *   A pair's three outputs have the SAME BITS alone, in a batch and at any batch position.
+ *   ws: fd_estimate_workspace_bytes(B, L, n_fft, hop) bytes (0 for a bad argument).
+ * fd_select_f32: exact order statistics of n non-negative DEVICE float values: out[r] (DEVICE float [R]) is bit for bit the value at
+ *   position ranks[r] of the sorted array.  ranks: HOST long long [R], 1 <= R <= 8, each in [0, n); 1 <= n <= 2^40, every count 64-bit.
+ *   A most-significant-digit radix select on the bit pattern (monotone for non-negative floats, denormals and +inf included), four
+ *   passes of 8 bits, integer atomics only, no host synchronisation between the passes; `values` is only read.  -0.0 counts as +0.0 (and
+ *   comes out as +0.0).  Every other value with the sign bit set and every NaN is counted in bad_out (DEVICE int64, written by every
+ *   call); the caller treats a non-zero count as an error, `out` is then meaningless.
+ *   ws: fd_select_workspace_bytes(R) bytes (0 for a bad R).
+ * ---------------------------------------------------------------------------------------------- */
+size_t fd_estimate_workspace_bytes(int B, int L, int n_fft, int hop);
+int fd_estimate_pair_stats(const fd_stft_plan* plan, const float* x, const float* y, int B, int L, float alpha, float* normfac_out,
+                           float* absx_out, double* band_sq_out, void* ws, size_t ws_bytes, void* stream);
+size_t fd_select_workspace_bytes(int R);
+int fd_select_f32(const float* values, long long n, const long long* ranks, int R, float* out, long long* bad_out, void* ws, size_t ws_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
