@@ -192,6 +192,11 @@ SIGNATURES = {
     "fd_estimate_pair_stats": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "fd_select_workspace_bytes": (c_size_t, [c_int]),
     "fd_select_f32": (c_int, [_P, c_ll, C.POINTER(c_ll), c_int, _P, _P, _P, c_size_t, _P]),
+    "fd_resample_plan_create": (c_int, [_P, c_int, c_int, c_int, C.POINTER(_P)]),
+    "fd_resample_plan_destroy": (None, [_P]),
+    "fd_resample_out_length": (c_ll, [c_ll, c_int, c_int]),
+    "fd_resample": (c_int, [_P, _P, _P, c_int, c_int, _P, c_ll, _P]),
+    "fd_resample_span": (c_int, [_P, _P, c_ll, c_ll, c_ll, c_ll, c_ll, _P, _P]),
 }
 
 _lib = None

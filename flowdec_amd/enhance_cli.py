@@ -385,6 +385,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "rows of that length, in fixed device memory, instead of being skipped by --max-seconds; needs --rng native and a flow "
                         "model (default: off)")
     p.add_argument("--batch-files", type=int, default=8, help="files of one T_pad bucket per native call (1 = one file per call, the reference's loop)")
+    p.add_argument("--resample", type=str, default="host", choices=["host", "device"],
+                   help="where a file that is not at the model's rate is resampled.  host: `resample` on the CPU (the default).  device: the same "
+                        "polyphase filter as a HIP kernel on the model's device (flowdec_amd.resample), summed in float64 and rounded once -- "
+                        "the output files then differ from host mode by float32 rounding of the FIR.  A rate pair whose filter bank is over "
+                        "the device resampler's cap falls back to the host path, with one printed line")
     p.add_argument("--gpus", type=int, default=1,
                    help="run the corpus on this many GPUs (cuda:0 .. cuda:N-1), one worker process each, batches spread by frame count; the "
                         "outputs, rtfs.csv and triples_list.txt are those of a one-process run (default 1: no child process)")
@@ -570,11 +575,22 @@ def chunk_samples(model, args) -> Optional[int]:
     return longform.row_samples(longform.chunk_row_frames(args.chunk_seconds, model.sampling_rate, hop), hop)
 
 
+def resample_for_model(y: torch.Tensor, sr: int, model, mode: str = "host") -> torch.Tensor:
+    """--resample: `resample` on the host, or `resample_device` on the model's device (the result stays there).  A rate pair over the
+    bank cap of the device resampler takes the host path."""
+    if mode == "device":
+        from . import resample as fd_resample
+        if fd_resample.bank_fits(sr, model.sampling_rate):
+            return fd_resample.resample_device(y.to(model.device), sr, model.sampling_rate)
+        print(f"--resample device: the filter bank of {sr} -> {model.sampling_rate} Hz is over the device resampler's cap; resampling on the host")
+    return resample(y, sr, model.sampling_rate)
+
+
 def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS,
-                   long_samples: Optional[int] = None):
-    """Load -> the reference's length rule (enhance.py:115,139; `length_limit` = --max-seconds) -> resample to the model rate.
-    -> waveform [C, L] or None (skipped).  A file of more than `long_samples` samples at the model's rate (--chunk-seconds) is exempt
-    from the length rule: it runs in rows."""
+                   long_samples: Optional[int] = None, resample_mode: str = "host"):
+    """Load -> the reference's length rule (enhance.py:115,139; `length_limit` = --max-seconds) -> resample to the model rate
+    (`resample_mode` = --resample).  -> waveform [C, L] or None (skipped).  A file of more than `long_samples` samples at the model's rate
+    (--chunk-seconds) is exempt from the length rule: it runs in rows."""
     y, sr = load_wav(job.src)
     seconds = y.shape[-1] / sr
     if long_samples is not None and resampled_length(y.shape[-1], sr, model.sampling_rate) > long_samples:
@@ -590,7 +606,7 @@ def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: 
         return None
     if sr != model.sampling_rate:
         print("RESAMPLING from", sr, "to", model.sampling_rate)
-        y = resample(y, sr, model.sampling_rate)
+        y = resample_for_model(y, sr, model, resample_mode)
     return y
 
 
@@ -604,7 +620,7 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
     waveform when the caller has already loaded (and resampled) it."""
     long_samples = chunk_samples(model, args)
     if y is None:
-        y = load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds, long_samples)
+        y = load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds, long_samples, resample_mode=getattr(args, "resample", "host"))
     if y is None:
         return
     sr = model.sampling_rate
@@ -666,7 +682,8 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length
 
 def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLog, res: RunResult, max_seconds: float) -> None:
     """One ragged native call for the files of `batch` (same T_pad bucket).  Every output equals the one-file call bit for bit."""
-    loaded = [(job, load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds)) for job in batch]
+    loaded = [(job, load_for_model(model, job, res, max_seconds, args.precision, args.max_seconds, resample_mode=getattr(args, "resample", "host")))
+              for job in batch]
     loaded = [(job, y) for job, y in loaded if y is not None]
     if not loaded:
         return

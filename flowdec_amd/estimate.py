@@ -150,7 +150,8 @@ def estimate_params(x_clips, y_clips, *, alpha: float, n_fft: int, hop: int, qx:
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         for i0 in range(0, n_pairs, batch_pairs):
             i1 = min(i0 + batch_pairs, n_pairs)
-            xb, yb = torch.stack(xs[i0:i1]).to(device), torch.stack(ys[i0:i1]).to(device)
+            # (clips a device resampler left on the GPU go over one by one; host clips as one block)
+            xb, yb = (torch.stack([c.to(device) for c in l]) if any(c.is_cuda for c in l) else torch.stack(l).to(device) for l in (xs[i0:i1], ys[i0:i1]))
             L.check(lib.fd_estimate_pair_stats(plan, L.ptr(xb), L.ptr(yb), i1 - i0, Lc, float(alpha), L.ptr(normfac[i0:i1]), L.ptr(absx[i0:i1]),
                                                L.ptr(band_sq[i0:i1]), L.ptr(ws), nws, L.stream()))
         lo, hi, gamma = quantile_position(n_bins, qx, np.float32)

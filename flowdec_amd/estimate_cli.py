@@ -15,6 +15,7 @@ and --overwrite is not given, its contents are printed and nothing is computed.
 
 --compare-ckpt CKPT then prints the checkpoint's beta and sigma_y beside the estimates (see `compare_with_ckpt`)."""
 import argparse
+import contextlib
 import os
 import sys
 import tempfile
@@ -105,6 +106,7 @@ def compare_with_ckpt(res: E.EstimateResult, ckpt: dict) -> List[str]:
 
 # ---- the run -----------------------------------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
+    from .eval_cli import RESAMPLE_HELP
     p = argparse.ArgumentParser(description="Estimate a FlowDec model's beta and sigma_y from (clean, coded) pairs on MI355X")
     p.add_argument("--pairs-file", type=str, required=True)
     p.add_argument("--delim", type=str, default=" ---> ")
@@ -126,6 +128,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device", type=int, default=0, help="Index of the GPU to use")
     p.add_argument("--batch-pairs", type=int, default=64, help="pairs per native call")
     p.add_argument("--compare-ckpt", type=str, default=None, help="a checkpoint whose beta and sigma_y are printed beside the estimates")
+    p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
     return p
 
 
@@ -148,10 +151,12 @@ def run(argv=None, out=None) -> Optional[E.EstimateResult]:
     _, pairs = E.select_pairs(lines, args.n_samples, args.seed, args.delim)
     target = int(args.sample_duration * args.sr)
     xs, ys = [], []
-    for fx, fy in pairs:
-        x, y, _ = E.crop_or_pad_pair(load_mono(fx, args.sr), load_mono(fy, args.sr), target, name=f"{fx}{args.delim}{fy}")
-        xs.append(x)
-        ys.append(y)
+    with (torch.cuda.device(args.device) if args.resample == "device" else contextlib.nullcontext()):
+        for fx, fy in pairs:
+            x, y, _ = E.crop_or_pad_pair(load_mono(fx, args.sr, args.resample), load_mono(fy, args.sr, args.resample), target,
+                                         name=f"{fx}{args.delim}{fy}")
+            xs.append(x)
+            ys.append(y)
     res = E.estimate_params(xs, ys, alpha=args.alpha, n_fft=args.nfft, hop=args.hop, qx=args.qx, qrmse=args.qrmse, per_band=args.per_band,
                             batch_pairs=args.batch_pairs, device=f"cuda:{args.device}")
     if args.per_band:

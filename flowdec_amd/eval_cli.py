@@ -32,7 +32,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from .enhance_cli import _split_pair, load_wav, resample
+from .enhance_cli import _split_pair, load_wav
+from .enhance_cli import resample as host_resample
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
@@ -65,13 +66,26 @@ def read_triples(listfile: str) -> List[Triple]:
     return out
 
 
-def load_mono(path: str, sr: int) -> torch.Tensor:
-    """load48000 (util/other.py:137-) for the rate `sr`: -> 1-D float32 tensor, the mean of the channels, resampled when the rate differs."""
+RESAMPLE_HELP = ("where a file that is not at --sr is resampled.  host: on the CPU (the default).  device: the same polyphase filter as a HIP "
+                 "kernel on the current GPU (flowdec_amd.resample), summed in float64 and rounded once -- the values differ from host mode by "
+                 "float32 rounding of the FIR.  A rate pair over the device resampler's bank cap falls back to the host path, with one printed line")
+
+
+def load_mono(path: str, sr: int, resample: str = "host") -> torch.Tensor:
+    """load48000 (util/other.py:137-) for the rate `sr`: -> 1-D float32 tensor, the mean of the channels, resampled when the rate differs
+    (lowpass_filter_width=256): resample='host' on the CPU, 'device' on the current GPU (the signal then stays there)."""
     au, fs = load_wav(path)
     if au.shape[0] != 1:
         au = au.mean(dim=0, keepdim=True)
     if fs != sr:
-        au = resample(au, fs, sr, lowpass_filter_width=256)
+        if resample not in ("host", "device"):
+            raise ValueError(f"load_mono: resample is 'host' or 'device' (got {resample!r})")
+        if resample == "device":
+            from . import resample as fd_resample
+            if fd_resample.bank_fits(fs, sr, 256):
+                return fd_resample.resample_device(au.to("cuda"), fs, sr, lowpass_filter_width=256)[0].contiguous()
+            print(f"--resample device: the filter bank of {fs} -> {sr} Hz is over the device resampler's cap; resampling on the host")
+        au = host_resample(au, fs, sr, lowpass_filter_width=256)
     return au[0].contiguous()
 
 
@@ -192,6 +206,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--crop-to-x", action="store_true", help="cut x_hat and y to the length of x (eval/metrics.py:85-87)")
     p.add_argument("--crop-to-x-hat", action="store_true", help="then cut x and y to the length of x_hat (eval/metrics.py:88-90)")
     p.add_argument("--sr", type=int, default=48000, help="the rate every file is brought to (the reference evaluates at 48 kHz)")
+    p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
     return p
 
 
@@ -202,7 +217,7 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
     kept, signals = [], []
     for t in triples:
         try:
-            x_hat, x, y = load_mono(t.x_hat, args.sr), load_mono(t.x, args.sr), load_mono(t.y, args.sr)
+            x_hat, x, y = (load_mono(f, args.sr, args.resample) for f in (t.x_hat, t.x, t.y))
         except Exception as err:      # a missing or broken file: the reference skips the triple too (eval/metrics.py:95-96)
             print(f"warning: skipping {t.name}: {type(err).__name__}: {err}", file=sys.stderr)
             res.n_unreadable += 1

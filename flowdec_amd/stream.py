@@ -314,14 +314,26 @@ class EnhanceStream:
         st = EnhanceStream(model, seed=7, N=6, solver="euler", row_frames=256, halo_frames=64, normfac="causal")
         for block in blocks: out.append(st.push(block))     # whatever became final (often empty)
         out.append(st.flush())                               # torch.cat(out) == model.enhance_long(cat(blocks), seed=7, normfac="causal", ...)
-    """
 
-    def __init__(self, model, seed, **pool_kwargs):
+    `in_rate` / `out_rate` (Hz; None or the model's rate: as above) put a `resample.ResampleStream` in front of the pool and one behind
+    it: the concatenated output is then R_out(model.enhance_long(R_in(all input), ...)) bit for bit, R = `resample.resample_device` at
+    lowpass_filter_width 64, however the input was cut.  `delays` = (resampler in, pool, resampler out) in samples at the input rate,
+    the model's rate and the model's rate; `delay_samples` stays the pool's."""
+
+    def __init__(self, model, seed, in_rate: Optional[int] = None, out_rate: Optional[int] = None, **pool_kwargs):
+        from . import resample as R
         self.pool = StreamPool(model, capacity=1, **pool_kwargs)
         self.sid = self.pool.open(seed)
         self.delay_samples = self.pool.delay_samples
+        sr = int(model.sampling_rate)
+        self.in_rate, self.out_rate = int(in_rate or sr), int(out_rate or sr)
+        self._rin = R.ResampleStream(R.get_resampler(self.in_rate, sr, device=self.pool.dev)) if self.in_rate != sr else None
+        self._rout = R.ResampleStream(R.get_resampler(sr, self.out_rate, device=self.pool.dev)) if self.out_rate != sr else None
+        self.delays = (self._rin.delay_samples if self._rin else 0, self.delay_samples, self._rout.delay_samples if self._rout else 0)
 
     def push(self, x) -> torch.Tensor:
+        if self._rin is not None:
+            x = self._rin.push(x)
         self.pool.push(self.sid, x)
         outs = []
         while True:
@@ -329,7 +341,13 @@ class EnhanceStream:
             if not got:
                 break
             outs.append(got[self.sid])
-        return torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=self.pool.dev)
+        y = torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=self.pool.dev)
+        return self._rout.push(y) if self._rout is not None else y
 
     def flush(self) -> torch.Tensor:
-        return self.pool.flush(self.sid)
+        if self._rin is not None:
+            self.pool.push(self.sid, self._rin.flush())
+        y = self.pool.flush(self.sid)
+        if self._rout is not None:
+            y = torch.cat([self._rout.push(y), self._rout.flush()])
+        return y

@@ -1,12 +1,17 @@
 """Pipe front end of the streaming enhancer: raw PCM in, raw PCM out, written as it becomes final.
 
     python -m flowdec_amd.stream_cli --ckpt C --N 6 --solver euler --seed 7 [--row-frames 256 --halo-frames 64] \\
-        --normfac causal|FLOAT --format s16le|f32le [--in - --out -] [--block-samples 4800]
+        --normfac causal|FLOAT --format s16le|f32le [--in - --out -] [--block-samples 4800] [--in-rate R] [--out-rate R]
 
-The input is mono PCM at the model's sampling rate (no resampling), little endian, without a header.  The output -- same format -- is,
-as float32, `model.enhance_long(input, seed=SEED, normfac=..., row_frames=..., halo_frames=...)` bit for bit (flowdec_amd.stream);
-s16le output is that rounded to 16 bits with clipping.  A sample leaves once (row_frames - halo_frames) * hop + xfade / 2 further
-samples have arrived, plus one row's compute time."""
+The input is mono PCM, little endian, without a header, at the model's sampling rate unless --in-rate says otherwise.  The output -- same
+format -- is, as float32, `model.enhance_long(input, seed=SEED, normfac=..., row_frames=..., halo_frames=...)` bit for bit
+(flowdec_amd.stream); s16le output is that rounded to 16 bits with clipping.  A sample leaves once (row_frames - halo_frames) * hop +
+xfade / 2 further samples have arrived, plus one row's compute time.
+
+--in-rate / --out-rate (default: the model's rate) resample the stream on the device on its way in and out (flowdec_amd.resample:
+torchaudio's sinc resampler at lowpass_filter_width 64, stateful, independent of the cut into blocks): the float32 output is then
+resample_device(enhance_long(resample_device(input, IN, model rate)), model rate, OUT) bit for bit.  Each resampler adds width + o
+samples of delay at its own input rate; the line on stderr reports the three delays."""
 import argparse
 import sys
 from typing import List, Optional
@@ -43,6 +48,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--in", dest="inp", type=str, default="-", help="input file (default -: stdin)")
     p.add_argument("--out", type=str, default="-", help="output file (default -: stdout)")
     p.add_argument("--block-samples", type=int, default=4800, help="samples read per push")
+    p.add_argument("--in-rate", type=int, default=None, help="sampling rate of the input in Hz (default: the model's rate)")
+    p.add_argument("--out-rate", type=int, default=None, help="sampling rate of the output in Hz (default: the model's rate)")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--ema", type=lambda s: str(s).lower() not in ("0", "false", "no"), default=True)
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
@@ -56,6 +63,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--block-samples must be >= 1")
     if args.N < 1:
         p.error("--N must be >= 1")
+    for name in ("in_rate", "out_rate"):
+        if getattr(args, name) is not None and getattr(args, name) < 1:
+            p.error(f"--{name.replace('_', '-')} must be >= 1")
     return args
 
 
@@ -75,7 +85,7 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
     if model is None:
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model="flow")
     st = EnhanceStream(model, seed=args.seed, N=args.N, solver=args.solver, row_frames=args.row_frames, halo_frames=args.halo_frames,
-                       normfac=args.normfac)
+                       normfac=args.normfac, in_rate=args.in_rate, out_rate=args.out_rate)
     dt = FORMATS[args.format]
     fin = sys.stdin.buffer if args.inp == "-" else open(args.inp, "rb")
     fout = sys.stdout.buffer if args.out == "-" else open(args.out, "wb")
@@ -106,7 +116,11 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
             fin.close()
         if fout is not sys.stdout.buffer:
             fout.close()
-    print(f"stream_cli: {written} samples written (delay {st.delay_samples} samples)", file=sys.stderr)
+    sr = model.sampling_rate
+    d_in, d_pool, d_out = st.delays
+    print(f"stream_cli: {written} samples written (delay {st.delay_samples} samples; resampler in {d_in} samples at {st.in_rate} Hz = "
+          f"{1e3 * d_in / st.in_rate:.2f} ms, pool {d_pool} samples at {sr} Hz = {1e3 * d_pool / sr:.2f} ms, resampler out {d_out} samples at {sr} Hz = "
+          f"{1e3 * d_out / sr:.2f} ms)", file=sys.stderr)
     return written
 
 

@@ -746,6 +746,43 @@ size_t fd_select_workspace_bytes(int R);
 int fd_select_f32(const float* values, long long n, const long long* ranks, int R, float* out, long long* bad_out, void* ws, size_t ws_bytes,
                   void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Resampling: torchaudio.functional.resample (sinc_interp_hann) as a polyphase FIR on the device, with an order of summation that is
+ * part of the contract (flowdec_amd/resample.py; csrc/resample.hip).  With o = orig / gcd, n = new / gcd, f = min(o, n) * rolloff,
+ * width = ceil(lowpass_filter_width * o / f) and K = 2 width + o, the bank is h[n][K] float32,
+ *     t = clamp((k' / o - i / n) f, -lpw, lpw),  h[i][k' + width] = sinc(t) cos^2(pi t / (2 lpw)) f / o,   k' in [-width, width + o)
+ * computed in float64 and rounded once.  The CALLER supplies it (flowdec_amd.enhance_cli.sinc_resample_kernel): the library has no
+ * generator, so the bits are those of the pinned host restatement.  An input of L samples has M = ceil(n L / o) outputs; output
+ * m = q n + i (0 <= i < n) is
+ *     acc = 0.0 (double);  for k = 0 .. K-1 ascending:  j = q o + k - width;  if 0 <= j < L: acc += (double)h[i][k] * (double)x[j]
+ *     y[m] = (float)acc                                   one rounding, to nearest even
+ * The product of two float32 values is exact in float64, so the float64 add is the loop's only rounding and a fused multiply-add
+ * gives the same bits; a tap outside [0, L) may equally be multiplied by a zero (acc starts at +0.0).  One thread owns an output's
+ * whole sum -- no matrix instruction, no atomics, no split K -- so an output has the SAME BITS alone, in a batch, at any batch
+ * position and in any span of a stream, and a plain float64 loop on the host reproduces it.  Inputs are finite float32.
+ *
+ * fd_resample_plan_create: bank_host is HOST float [n][K]; it is uploaded synchronously here (in a layout of the kernel's choosing)
+ *   and nothing on the call path allocates.  Checked before any HIP call, FD_EINVAL otherwise: o, n >= 1, width >= 0, bank_host and out
+ *   non-NULL, n K <= 2^24 (a pair like 47999 -> 48000 would ask for a 9 GB bank).
+ * fd_resample_out_length: ceil(n L / o) in 64 bits, host only (-1 for L < 0 or o, n < 1).
+ * fd_resample: the ragged batch.  x DEVICE float [B][L]; lengths DEVICE int32 [B] (row b is its first lengths[b] samples, clamped
+ *   into [0, L]) or NULL: every row has L samples; y DEVICE float [B][L_out]: row b's ceil(n len_b / o) outputs followed by zeros.
+ *   L_out < ceil(n L / o) is FD_EINVAL (checked from L: device lengths cannot be seen); 1 <= B <= 65535.
+ * fd_resample_span: the streaming building block.  x DEVICE float [nx] holds the samples [x0, x0 + nx) of a recording of `total`
+ *   samples (-1: not known yet, L = +infinity in the formula); the call writes the outputs [m0, m0 + count) of the recording's resampled
+ *   signal to y[0 .. count).  x0, total, m0, count are absolute 64-bit indices (each at most 2^46).  FD_EINVAL, from the integers alone:
+ *   a span that reads a sample outside [x0, x0 + nx) that is neither below 0 nor at or beyond a known total; m0 + count beyond
+ *   ceil(n total / o) of a known total.  count = 0 is a no-op.
+ * Both calls are asynchronous on `stream` and launch nothing when they refuse.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fd_resample_plan fd_resample_plan;
+int fd_resample_plan_create(const float* bank_host, int o, int n, int width, fd_resample_plan** out);
+void fd_resample_plan_destroy(fd_resample_plan* plan);
+long long fd_resample_out_length(long long L, int o, int n);
+int fd_resample(const fd_resample_plan* plan, const float* x, const int* lengths, int B, int L, float* y, long long L_out, void* stream);
+int fd_resample_span(const fd_resample_plan* plan, const float* x, long long x0, long long nx, long long total, long long m0, long long count,
+                     float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
