@@ -423,10 +423,14 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino44f_kernel(ConvArgs p) {
 
 // ---- weight packing: [Cout][Cin][3][3] f32 (+ optional [Cout][S] 1x1 shortcut) -> [cout block of 128][chunk (+ 1 zero chunk)][wave 8]
 // [18 = position group x channel quad][lane 64][4 positions]; U = G g G^T (3x3) or G[:,1] G[:,1]^T w (1x1: centre tap)
-__device__ __forceinline__ float g_row(int i, int a) {   // G (6 x 3) of F(4,3)
-  constexpr float G[6][3] = {{0.25f, 0.f, 0.f}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
-                             {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
-  return G[i][a];
+// 24 G (6 x 3) of F(4,3): integer numerators.  G itself has the entries 1/6, 1/12, 1/24, which float32 cannot hold: a product with the
+// rounded constants on both sides is off by up to an ulp at the 16 inner positions.  The numerators are exact, every integer x float32
+// product is exact in double, their sum is exact for weights of similar magnitude (nine terms within 53 bits; otherwise rounded at
+// double precision), and U = G g G^T is rounded to float32 ONCE, after the division by 576 -- exactly U for weights on a 72 x 2^-k grid
+// (tests/test_hip_wino_exact.py).
+__device__ __forceinline__ int g24_row(int i, int a) {
+  constexpr int G24[6][3] = {{6, 0, 0}, {-4, -4, -4}, {-4, 4, -4}, {1, 2, 4}, {1, -2, 4}, {0, 0, 24}};
+  return G24[i][a];
 }
 
 __global__ void wino44f_pack_kernel(const float* __restrict__ w, const float* __restrict__ w_sc, float* __restrict__ dst, int Cout, int Cin, int S) {
@@ -447,10 +451,10 @@ __global__ void wino44f_pack_kernel(const float* __restrict__ w, const float* __
       const float* gp = w + ((size_t)co * Cin + chunk * CK + k) * 9;
       double acc = 0.0;
       for (int a = 0; a < 3; ++a)
-        for (int bq = 0; bq < 3; ++bq) acc += (double)g_row(i, a) * (double)gp[a * 3 + bq] * (double)g_row(j, bq);
-      v = (float)acc;
+        for (int bq = 0; bq < 3; ++bq) acc += (double)(g24_row(i, a) * g24_row(j, bq)) * (double)gp[a * 3 + bq];
+      v = (float)(acc / 576.0);
     } else if (chunk < nchunk) {
-      v = (float)((double)g_row(i, 1) * (double)g_row(j, 1) * (double)w_sc[(size_t)co * S + (chunk - n3) * CK + k]);
+      v = (float)((double)(g24_row(i, 1) * g24_row(j, 1)) * (double)w_sc[(size_t)co * S + (chunk - n3) * CK + k] / 576.0);
     }
     dst[o] = v;
   }

@@ -7,7 +7,8 @@ matrix cores, the float32 result must then EQUAL the float64 convolution, and th
 the store.  A dropped tap, channel, pixel, chunk or bias row changes some output by at least 1/8 and fails the comparison however few
 outputs it touches -- which the relative-L2 tolerances of test_hip_ops.py (6e-3 / 4e-4 / 2e-5 on random data) cannot promise.  Integers
 of this size are exact in bf16, so the same data also pins the bf16-operand modes of float32 storage (FD_BF16_OPERANDS, and
-FD_BF16X3_OPERANDS, whose lo halves are zero here).  The Winograd kernels are out of scope: their transforms are not exact.
+FD_BF16X3_OPERANDS, whose lo halves are zero here).  The Winograd kernels are out of scope HERE: their weight transform divides by 6 and
+24, which is exact only for weights on a 24 * 2^-k grid -- tests/test_hip_wino_exact.py covers them on such data.
 
 Every launch is attributed to its kernel through fd_conv_kernel_counts (ops.conv_kernel_counts), against `expected_kernel`, a mirror of
 the dispatch rule of fd_conv2d: if a change to the rule moves a case to another kernel, the case fails."""
