@@ -13,10 +13,15 @@
 // Design (round 4; what the round-2 F(2,3) kernel conv_wino.hip got wrong: MEASUREMENTS.md, "conv_wino_kernel"):
 //   * one workgroup = 16 x 16 output pixels (64 Winograd tiles of 1 x 4) x ALL 256 output channels: the input is activated once
 //     per pixel tile, as in the direct kernel (the F(2,3) kernel's 128-channel workgroups activated everything twice);
-//   * the input transform happens ONCE per workgroup and chunk, at halo-store time: raw bf16 halo --(direct-to-LDS DMA)--> RAW -->
-//     silu(a x + d) (the wave's 8 channels are wave-uniform: (a, d) live in 16 SGPRs) -> fp16 -> LDS (z) -> packed-fp16 B^T transform
-//     -> LDS (V planes, double-buffered).  The K loop then reads plain fragments: no VALU work per fragment (the F(2,3) kernel
-//     transformed at fragment-read time, in every wave, for every cout tile: 6.9 VALU per MFMA; here 2.2);
+//   * the input transform happens ONCE per workgroup and chunk, in ONE producer pass: raw bf16 halo --(direct-to-LDS DMA)--> RAW -->
+//     registers: silu(a x + d) -> fp16 -> packed-fp16 B^T transform --> LDS (V planes, double-buffered).  A lane owns one channel
+//     pair of one tile of one halo row: it reads the tile's six halo columns from RAW (a layout without bank conflicts for these
+//     reads: "halo loader and producer" below), activates them with the (a, d) of its two channels (four registers, read per chunk
+//     from the affine table the prologue stages in LDS), transforms and stores the six V words.  Adjacent tiles share two of six
+//     columns, so a column is activated 1.33 times -- cheaper than the activated-halo staging buffer (z) this pass replaced: one LDS
+//     store phase, one LDS read phase, an s_waitcnt lgkmcnt(0) and a barrier per chunk inside every wave's MFMA stream
+//     (MEASUREMENTS.md "One-pass producer").  The K loop then reads plain fragments: no VALU work per fragment (the F(2,3) kernel
+//     transformed at fragment-read time, in every wave, for every cout tile: 6.9 VALU per MFMA);
 //   * 6 x 256 x 64 accumulators = 96 K registers = 192 per lane of the 8 waves: wave (cq, xt) owns positions xi = 0, 1, 2 (xt = 0) or 5, 3, 4
 //     (xt = 1) for couts {ct * 128 + cq * 32 + 0..31, ct = 0, 1} and all 64 tiles: 3 x (2 x 2) MFMA tiles of 32 x 32
 //     (v_mfma_f32_32x32x16_f16); fragments rotate through three 16-byte quads per operand, 4 MFMAs per 4 ds_read_b128;
@@ -24,8 +29,9 @@
 //     only THIS wave reads: every wave streams its own pieces through a private ring of 6 LDS slots by direct-to-LDS DMA -- no
 //     barrier for the weights at all, counted s_waitcnt vmcnt for this wave's own traffic (every vector-memory operation of the
 //     loop is inline asm and counted by hand);
-//   * two barriers per chunk (z complete / V planes complete + raw halo landed), both in the middle of a step with the fragments
-//     pipelined across; the producer work (conversion, transform) is spread over the steps of the two wave groups;
+//   * one barrier per chunk (V planes complete + raw halo landed) and one more per chunk PAIR (the pair's RAW bytes consumed: the
+//     next pair may be requested), both in the middle of a step with the fragments pipelined across; the producer pass runs in
+//     different steps in the two wave groups;
 //   * epilogue: partial output transforms in registers (xt = 0: M0+M1+M2, M1-M2, M1+M2; xt = 1: M3+M4, 2(M3-M4), 4(M3+M4),
 //     8(M3-M4)+M5), the two waves of a cout block swap two planes each through LDS, then the direct kernel's staged sweep
 //     (bias / residual (prefetched by DMA) / scale / statistics / bf16 store with 16 bytes per lane); with a folded 1x1 shortcut
@@ -59,15 +65,14 @@ constexpr int RING_BYTES = 8 * NRING * RSLOT;       // 96 KiB
 constexpr int VXI = HH * 4 * 32;                    // one position plane: [18 halo rows][4 tiles][32 B]
 constexpr int V_BYTES = 6 * VXI;                    // 13824
 constexpr int V_OFF = RING_BYTES;
-constexpr int Z_OFF = V_OFF + 2 * V_BYTES;
-constexpr int ZROW = HW + 4;                        // z row: halo column c at position c + (c >> 2) (one pad slot per four columns), 22 slots
-constexpr int ZPLANE = HH * ZROW * 16;              // 6336 = 64 (mod 128): the two channel-half planes are 16 banks apart
-constexpr int Z_BYTES = 2 * ZPLANE;                 // activated halo, [channel half 2][18 rows][22 slots][16 B]: conflict-free for the
-                                                    // wave-uniform-half stores of the conversion AND the word-wise reads of the transform
-constexpr int RAW_OFF = Z_OFF + Z_BYTES;            // raw halo (bf16) of a chunk PAIR as the DMA delivers it: 64 B per pixel = [chunk parity][half][16 B],
-constexpr int RAW_PASSES = 3;                       // piece s = 4 * pixel + 2 * parity + half at s * 16; 1296 pieces, padded to 3 passes of 512 lanes
+constexpr int AFF_OFF = V_OFF + 2 * V_BYTES;        // GroupNorm affine (a, d) of ALL input channels of this image, f32 pairs in concat order
+                                                    // (fd_wino4_supported: at most AFF_BYTES), staged once by DMA in the prologue
+constexpr int RAW_OFF = AFF_OFF + AFF_BYTES;        // raw halo (bf16) of a chunk PAIR as the DMA delivers it: one 64-byte slot per pixel,
+constexpr int RROW = 20;                            // 20 slots per halo row (raw_slot below), the four 16-byte pieces [chunk parity][half]
+constexpr int RROW_BYTES = RROW * 64;               // of a pixel inside its slot (raw_flip): 1440 pieces, padded to 3 passes of 512 lanes
+constexpr int RAW_PASSES = 3;
 constexpr int RAW_BYTES = RAW_PASSES * NTH * 16;    // 24576
-constexpr int MAIN_BYTES = RAW_OFF + RAW_BYTES;     // 163200
+constexpr int MAIN_BYTES = RAW_OFF + RAW_BYTES;     // 154624
 // epilogue: exchange buffer [wave][plane][4][64 lanes x 16 B] = the staging of one round (128 pixels x 128 couts f32, padded rows)
 // in the same bytes (a barrier apart), two residual buffers (one round each: 4 passes x 512 threads x 16 B), bias, statistics
 constexpr int X_BYTES = 8 * 8192;                   // exchange buffer (two of them: one barrier per round)
@@ -83,8 +88,14 @@ static_assert(BIAS_OFF >= 2 * X_BYTES && BIAS_OFF >= SK_OFF + 2 * SK_BYTES && XS
 constexpr int ISC_OFF = BIAS_OFF + 1024;            // [256] f32: inverse of the per-cout power-of-two weight scale (wino4_scale_kernel)
 constexpr int STAT_OFF = ISC_OFF + 1024;            // [2][8 waves][16 octets][16] f32 = 16 KiB
 constexpr int LDS_BYTES = cmax(MAIN_BYTES, STAT_OFF + 16384);
-constexpr int NPIECE = HH * HW * 4;                 // 1296 raw pieces of 16 B (8 channels) per chunk pair
-static_assert(LDS_BYTES <= 160 * 1024 && NPIECE <= RAW_PASSES * NTH && HH * HW <= 2 * 256, "LDS layout");
+constexpr int NPIECE = HH * RROW * 4;               // 1440 raw pieces of 16 B (8 channels) per chunk pair, pad slots included
+static_assert(LDS_BYTES <= 160 * 1024 && NPIECE <= RAW_PASSES * NTH && AFF_BYTES <= 4 * 1024 && RAW_OFF % 128 == 0, "LDS layout");
+// RAW slot of halo column c inside its row: one pad slot behind every four columns (a tile's columns 4 wt + j, j = 0..3, sit at
+// 5 wt + j: the four tiles of a row alternate between the two 64-byte halves of a 128-byte bank row); columns 16 and 17 take the
+// pad slots 14 and 19 (an even and an odd one), so that a row needs 20 slots and the pair's halo still fits three DMA passes.
+constexpr int raw_slot(int c) { return c < 16 ? c + (c >> 2) : (c == 16 ? 14 : 19); }
+// ... and where the two pieces of a chunk parity sit inside the slot: piece q = 2 parity + half at position q ^ (2 raw_flip(c))
+constexpr int raw_flip(int c) { return c < 16 ? (c >> 3) & 1 : 0; }
 constexpr int U_EXP = 9;                            // packed weights: every cout's row of U = G g is scaled by a power of two so that its
                                                     // largest magnitude lies in [2^(U_EXP-1), 2^U_EXP) -- fp16 keeps 23 binades below that
 constexpr float RAW_MAX = 6000.f;                   // raw (not activated) inputs saturate here: |V| <= 10 |z| stays finite in fp16
@@ -136,15 +147,25 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int cq = wave & 3, xt = wave >> 2;
 
-  // ---- halo loader.  The halo of a chunk PAIR (32 channels) is requested at once: 324 pixels x 64 contiguous bytes, FOUR adjacent
-  // lanes per pixel (one memory request per pixel and pair: the 32-byte gathers of a per-chunk request were a third of the vector L1's
-  // time), three passes of 512 lanes, straight to LDS by DMA (RAW: piece 4 pixel + 2 parity + half at 16 bytes each, pass i of wave w
-  // at (i * 8 + w) KiB in lane order).  CONVERSION, per chunk: wave w converts channel half hq = w & 1 of the pixels hp = i * 256 +
-  // (w >> 1) * 64 + lane in pass i = 0, 1 (pass 1: 68 pixels, waves 0..3 only) -- the half is WAVE-UNIFORM, so the GroupNorm affine
-  // (a, d) of the wave's 8 channels is 16 scalar registers (one s_load_dwordx16 per chunk: no LDS table); the lane reads the piece back
-  // (written by another lane's request), activates it and stores it as fp16 into z -- nothing is held in registers while the load is in
-  // flight.  The K loop is bound by vector-instruction issue as soon as the per-chunk work costs more than a few hundred instructions
-  // per wave (SQ counters, profiles/r04_wino4_*): everything a lane needs per chunk is computed ONCE here and kept in registers. -----
+  // ---- halo loader and producer.  The halo of a chunk PAIR (32 channels) is requested at once: 324 pixels x 64 contiguous bytes, FOUR
+  // adjacent lanes per pixel (one memory request per pixel and pair: the 32-byte gathers of a per-chunk request were a third of the vector
+  // L1's time), three passes of 512 lanes, straight to LDS by DMA (RAW; pass i of wave w at (i * 8 + w) KiB in lane order).  The DMA fixes
+  // the LDS byte of every lane, the SOURCE address is free: LDS slot S = (t + 512 i) >> 2 holds the pixel (row S / 20, the column c with
+  // raw_slot(c) = S % 20; slots 4 and 9 of a row and those behind row 17 are padding), lane position q = t & 3 of the slot the pixel's
+  // piece q ^ (2 raw_flip(c)).  PRODUCER, once per chunk, ONE pass RAW -> registers -> V: a lane takes one channel pair (32-bit word
+  // l & 7: half (l >> 2) & 1, word l & 3 of the 16-byte piece) of one Winograd tile (l >> 3) & 3 of one halo row -- it reads the tile's
+  // six halo columns straight from RAW, applies silu(a x + d) -> fp16 (or the saturation) and the zero padding to the six words, and
+  // the packed-fp16 B^T transform, and stores the six V words.  The (a, d) of a lane's two channels come from the affine table that the
+  // prologue stages in LDS (AFF: one ds_read_b128 per chunk, 8 distinct 16-byte addresses per wave: a broadcast).
+  // Bank conflicts of the RAW reads (ds_read_b32: banks = (byte / 4) % 32, a 32-lane group at a time).  A 32-lane group = one halo row x 4
+  // tiles x 8 words; the 8 words of a tile are the 32 contiguous bytes of one (slot, chunk parity): a quarter of the 128-byte bank row,
+  // quarter number 2 (slot & 1) + (parity ^ flip).  For read j the four tiles wt need four different quarters:
+  //   j = 0..3: columns 4 wt + j in slots 5 wt + j (slot parity wt + j), flip = wt >> 1            -> (wt & 1, wt >> 1): all four
+  //   j = 4:    columns 4 8 12 16 in slots 5 10 15 14 (parities 1 0 1 0), flips 0 1 1 0               -> all four
+  //   j = 5:    columns 5 9 13 17 in slots 6 11 16 19 (parities 0 1 0 1), flips 0 1 1 0               -> all four
+  // (the row pitch, 1280 bytes, is a multiple of the bank row).  The V stores of a group are 128 contiguous bytes, as before.
+  // The K loop is bound by vector-instruction issue as soon as the per-chunk work costs more than a few hundred instructions per wave
+  // (SQ counters, profiles/r04_wino4_*): everything a lane needs per chunk is computed ONCE here and kept in (packed) registers. -----
   auto opaque = [&](int v) { asm volatile("" : "+v"(v)); return v; };
   const size_t img_elems = (size_t)H * W;
   // The halo is addressed from its BAND: the first halo row of this tile (row hb of image b, a 64-bit wave-uniform base), so the
@@ -157,40 +178,38 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   const bf16* const sb1 = two3 ? reinterpret_cast<const bf16*>(p.seg[1].src) + band_pix * p.seg[1].C : sb0;
   const int sC0 = p.seg[0].C, sC1 = two3 ? p.seg[1].C : 0;
   const int nch0 = sC0 / CK, n3 = nch0 + sC1 / CK;
-  const int hq = wave & 1;
-  const bool pass1 = wave < 4;       // (the other waves request a duplicate in pass 1 -- every wave has the same number of
-                                     //  vector-memory operations in flight -- and skip its conversion)
-  // per-lane halo constants.  Ordering between the request side (lane t, piece t + 512 i) and the conversion side (piece (hp * 4 + 2 e +
-  // hq), written by another lane): "request after the barrier of step 3 of an even chunk (every conversion of the previous pair is done),
-  // landed before the barrier of step 8 (every wave waits for its own requests first), converted after it".  Pixels outside the image:
-  // the request reads pixel 0 of the band (inside the image; harmless), the conversion masks the value.  Lanes without a pixel in pass 1 redo pass 0.
-  int hpix[RAW_PASSES], zadr[2];
-  unsigned hvalid = 0;
+  // per-lane halo constants.  Ordering between the request side (lane t fills piece t + 512 i) and the producer side (which reads pieces
+  // written by other waves' requests): "request after the barrier of step 3 of an even chunk (every producer pass over the previous pair
+  // is done), landed before the barrier of step 8 (every wave waits for its own requests first), read after it".  Pixels outside the
+  // image and padding slots: the request reads pixel 0 of the band (inside the image; harmless), the producer masks the value.
+  int hpix[RAW_PASSES];                    // (pixel offset inside the band) * 4 + source piece
 #pragma unroll
-  for (int i = 0; i < RAW_PASSES; ++i) {   // request side: piece sl = t + 512 i -> pixel sl >> 2 (four adjacent lanes share a pixel's 64 bytes)
+  for (int i = 0; i < RAW_PASSES; ++i) {   // request side: four adjacent lanes share a pixel's 64 bytes
     const int sl = t + i * NTH;
-    const int hp = sl < NPIECE ? sl >> 2 : 0;
-    const int hr = hp / HW, hc = hp - hr * HW;
+    const int slot = sl >> 2;
+    const int hr = slot / RROW, ps = slot - hr * RROW;
+    const int hc = (ps == 4 || ps == 9 || hr >= HH) ? -1 : ps == 14 ? 16 : ps == 19 ? 17 : ps - ps / 5;
     const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
-    hpix[i] = (gh >= 0 && gh < H && gw >= 0 && gw < W) ? (gh - hb) * W + gw : 0;
+    const bool ok = hc >= 0 && gh >= 0 && gh < H && gw >= 0 && gw < W;
+    hpix[i] = ((ok ? (gh - hb) * W + gw : 0) << 2) | ((sl & 3) ^ (ok ? 2 * raw_flip(hc) : 0));
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {            // conversion side
-    const int base = ((t >> 7) << 6) + lane;
-    const bool has = i == 0 || base + 256 < HH * HW;
-    const int hp = has ? base + i * 256 : base;
-    const int hr = hp / HW, hc = hp - hr * HW;
-    const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
-    const bool ok = gh >= 0 && gh < H && gw >= 0 && gw < W;
-    zadr[i] = (hp * 4 + hq) * 16 + ((hq * ZPLANE + (hr * ZROW + hc + (hc >> 2)) * 16) << 16);   // low half: RAW piece offset (parity 0), high half: z offset
-    if (ok) hvalid |= 1u << i;
+  // producer side: item (halo row t >> 5, tile wt, word).  Columns 4 wt + j, j = 0..3, are 64 bytes apart; j = 4 and 5 have their own
+  // offsets (the next group of four: another flip; columns 16, 17: the pad slots).  Rows 16, 17: wave 1 (rows 2, 3) + 14 rows.
+  int pA, pB, vbits;
+  {
+    const int hrow = t >> 5, wt = (t >> 3) & 3, word = t & 7;
+    auto raw_at = [&](int c) { return hrow * RROW_BYTES + raw_slot(c) * 64 + raw_flip(c) * 32 + word * 4; };
+    const int tidx = hrow * 4 + wt;
+    const int vrel = tidx * 32 + (((word >> 2) ^ ((tidx >> 3) & 1)) * 16) + (word & 3) * 4;   // V plane: [18 rows][4 tiles][32 B], halves swizzled
+    pA = raw_at(4 * wt) | (vrel << 16);
+    pB = raw_at(4 * wt + 4) | (raw_at(4 * wt + 5) << 16);
+    const int gh = h0 - 1 + hrow, ghe = gh + 14;
+    vbits = (w0 - 1 + 4 * wt >= 0 ? 1 : 0) | (gh >= 0 && gh < H ? 2 : 0) | (w0 + 4 * wt + 4 < W ? 4 : 0) | (ghe >= 0 && ghe < H ? 8 : 0);
   }
   // state of the chunk whose halo is in flight / being converted (wave-uniform)
   const bf16* nbase = sb0;
   int nC2 = 0, ncb = 0;              // bytes per pixel, byte offset of the chunk's 16 channels inside a pixel
   int cnext = 0;                     // index of the next chunk to request
-  f32x16 aff;                        // (a, d) x 8 channels of the chunk being converted (scalar registers)
-  const float* const affp = ACT ? p.affine + ((size_t)b * p.affC + hq * 8) * 2 : nullptr;
   auto next_chunk = [&]() {          // (past the last chunk the state stays: load_halo turns the request into a harmless re-read)
     if (cnext < n3) {
       const bool first = cnext < nch0;
@@ -198,63 +217,64 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
       nbase = first ? sb0 : sb1;
       nC2 = (first ? sC0 : sC1) * 2;
       ncb = cch * CK * 2;
-      if constexpr (ACT)             // affine table = [C0 + C1] pairs in concat order (fd_conv2d: aff_off = 0 / C0)
-        asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(aff) : "s"(affp + (size_t)cnext * CK * 2) : "memory");
     }
     ++cnext;
-  };
-  auto aff_wait = [&]() {            // the scalar load is invisible to hipcc: wait for it (and re-define the registers) before the first use
-    if constexpr (ACT) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(aff)::"memory");
   };
   // past the end of the K loop every lane re-reads element 0 of the last tensor (one cache line; the data is never used)
   const unsigned rawdst = (unsigned)(RAW_OFF + wave * 1024);
   auto load_halo = [&]() {                // the 32 channels of the chunk pair that starts at the chunk next_chunk has just set up
     const int on = cnext <= n3 ? 1 : 0;   // (next_chunk has already counted this request)
-    const int h16 = (opaque(t) & 3) * 16;
 #pragma unroll
-    for (int i = 0; i < RAW_PASSES; ++i) glds16s(nbase, (unsigned)((hpix[i] * nC2 + ncb + h16) * on), rawdst + i * 8192);
+    for (int i = 0; i < RAW_PASSES; ++i) {
+      const int hp = opaque(hpix[i]);
+      glds16s(nbase, (unsigned)(((hp >> 2) * nC2 + ncb + (hp & 3) * 16) * on), rawdst + i * 8192);
+    }
   };
-  // one slot: RAW (bf16) -> [silu(a x + d)] -> fp16 -> z, zero padding AFTER the activation (an AND: no branch)
-  auto conv_slot = [&](int i, int e) {   // e = parity of the chunk inside its pair (compile-time)
-    const int za = opaque(zadr[i]);
-    const u32x4 raw = *reinterpret_cast<const u32x4*>(smem + RAW_OFF + e * 32 + (za & 0xffff));
-    const unsigned vm = ((hvalid >> i) & 1u) ? 0xffffffffu : 0u;
-    u32x4 o;
+  // affine table of image b = [C0 + C1] (a, d) pairs in concat order (fd_conv2d: aff_off = 0 / C0): chunk cc, word wd at cc * 128 + wd * 16
+  int affa = AFF_OFF + (t & 7) * 16;
+  auto load_affine = [&]() {
+    if constexpr (ACT) {
+      if (wave < AFF_BYTES / 1024) {       // 1 KiB per wave; lanes behind the table re-read its start
+        const int o = opaque(t) * 16;
+        glds16s(p.affine + (size_t)b * p.affC * 2, (unsigned)(o < n3 * CK * 8 ? o : 0), (unsigned)(AFF_OFF + wave * 1024));
+      }
+    }
+  };
+
+  // ---- the producer pass of one item: RAW (bf16) -> [silu(a x + d)] -> fp16, zero padding AFTER the activation (an AND: no branch) ->
+  // packed-fp16 B^T -> V planes.  e = parity of the chunk inside its pair, affo = byte offset of its affine records behind affa
+  // (both compile-time).  Halo rows 0..15 = the sixteen 32-lane groups of the workgroup (rows 0..7 wave group 0, rows 8..15 wave
+  // group 1), rows 16, 17 = the two halves of wave 1 two steps later (`extra`).
+  auto produce = [&](const bool extra, const int e, const int vbuf, const int affo) {
+    // (opaque: hipcc otherwise hoists the unpacked addresses out of the K loop -- registers it does not have)
+    const int pa = opaque(pA), pb = opaque(pB), vbt = opaque(vbits);
+    const char* const rp = smem + RAW_OFF + (extra ? 14 * RROW_BYTES : 0);
+    const int a0 = (pa & 0xffff) ^ (e << 5), a4 = (pb & 0xffff) ^ (e << 5), a5 = (int)((unsigned)pb >> 16) ^ (e << 5);
+    const int vrel = (int)((unsigned)pa >> 16);
+    char* const vb = smem + V_OFF + vbuf * V_BYTES + (extra ? (vrel ^ 16) + 14 * 4 * 32 : vrel);   // (rows 16, 17: the other swizzle phase)
+    unsigned w_[6];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const unsigned u = raw[j];
+    for (int j = 0; j < 4; ++j) w_[j] = *reinterpret_cast<const unsigned*>(rp + a0 + j * 64);   // halo column 4 wt + j
+    w_[4] = *reinterpret_cast<const unsigned*>(rp + a4);
+    w_[5] = *reinterpret_cast<const unsigned*>(rp + a5);
+    f32x4 af = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (ACT) af = *reinterpret_cast<const f32x4*>(smem + opaque(affa) + affo);
+    const unsigned mrow = (unsigned)((int)((unsigned)vbt << (extra ? 28 : 30)) >> 31);
+    const unsigned m0 = mrow & (unsigned)((int)((unsigned)vbt << 31) >> 31), m5 = mrow & (unsigned)((int)((unsigned)vbt << 29) >> 31);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const unsigned u = w_[j];
       const float x0 = __builtin_bit_cast(float, u << 16), x1 = __builtin_bit_cast(float, u & 0xffff0000u);
       unsigned r;
       if constexpr (ACT) {   // silu >= -0.28: only the upper side can leave the range the transform tolerates (one packed min per pair)
         const f16x2 zc = {(f16)RAW_MAX, (f16)RAW_MAX};
-        r = u2(__builtin_elementwise_min(h2(pack_f16(fd_silu(fmaf(x0, aff[4 * j], aff[4 * j + 1])), fd_silu(fmaf(x1, aff[4 * j + 2], aff[4 * j + 3])))), zc));
+        r = u2(__builtin_elementwise_min(h2(pack_f16(fd_silu(fmaf(x0, af[0], af[1])), fd_silu(fmaf(x1, af[2], af[3])))), zc));
       } else   // raw input (activated / resampled upstream): saturate so that the transform cannot overflow to inf
         r = pack_f16(__builtin_amdgcn_fmed3f(x0, -RAW_MAX, RAW_MAX), __builtin_amdgcn_fmed3f(x1, -RAW_MAX, RAW_MAX));
-      o[j] = r & vm;
+      w_[j] = r & (j == 0 ? m0 : j == 5 ? m5 : mrow);
     }
-    *reinterpret_cast<u32x4*>(smem + Z_OFF + ((unsigned)za >> 16)) = o;
-  };
-
-  // ---- input transform z -> V planes, two channels (one 32-bit word) per lane: 6 words in, 6 words out.  Lane l of a 32-lane group
-  // takes word l & 7 (channel pair) of tile l >> 3 of ONE halo row: the group's reads cover four 16-byte slots per channel half that
-  // the z layout keeps in distinct banks, its stores 128 contiguous bytes of a V plane -- no bank conflicts (the first version's
-  // item order cost 430 LDS cycles per chunk in conflicts, SQ_LDS_BANK_CONFLICT).  Halo rows 0..15 = the sixteen 32-lane groups of
-  // the workgroup (rows 0..7 wave group 0, rows 8..15 wave group 1), rows 16, 17 = the two halves of wave 1 one step later.
-  auto item_z = [&](int hrow, int wt, int word) { return Z_OFF + (word >> 2) * ZPLANE + (hrow * ZROW + 5 * wt) * 16 + (word & 3) * 4; };
-  auto item_v = [&](int hrow, int wt, int word) {
-    const int tidx = hrow * 4 + wt;
-    return V_OFF + tidx * 32 + (((word >> 2) ^ ((tidx >> 3) & 1)) * 16) + (word & 3) * 4;
-  };
-  const int tz0 = item_z(t >> 5, (t >> 3) & 3, t & 7), tv0 = item_v(t >> 5, (t >> 3) & 3, t & 7);
-  auto transform_at = [&](int za, int va, int vbuf) {
-    // (opaque: hipcc otherwise hoists one address register per plane and buffer out of the K loop -- twelve registers it does not have)
-    const char* const zp = smem + opaque(za);
-    char* const vb = smem + opaque(va) + vbuf * V_BYTES;
     const f16x2 c4 = {(f16)4.f, (f16)4.f}, cm4 = {(f16)-4.f, (f16)-4.f}, cm5 = {(f16)-5.f, (f16)-5.f}, c2 = {(f16)2.f, (f16)2.f},
                 cm2 = {(f16)-2.f, (f16)-2.f};
-    unsigned w_[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) w_[j] = *reinterpret_cast<const unsigned*>(zp + (j + (j >> 2)) * 16);   // halo column 4 wt + j
     const f16x2 z0 = h2(w_[0]), z1 = h2(w_[1]), z2 = h2(w_[2]), z3 = h2(w_[3]), z4 = h2(w_[4]), z5 = h2(w_[5]);
     const f16x2 t1 = __builtin_elementwise_fma(z2, cm4, z4);   // z4 - 4 z2
     const f16x2 t2 = __builtin_elementwise_fma(z1, cm4, z3);   // z3 - 4 z1
@@ -268,9 +288,6 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
     *reinterpret_cast<unsigned*>(vb + 3 * VXI) = u2(__builtin_elementwise_fma(z1, c4, __builtin_elementwise_fma(z3, cm5, z5)));   // xi = 5
   };
   const bool extra_wave = wave == 1;
-  auto transform_extra = [&](int vbuf) {
-    if (extra_wave) transform_at(item_z(16 + (lane >> 5), (lane >> 3) & 3, lane & 7), item_v(16 + (lane >> 5), (lane >> 3) & 3, lane & 7), vbuf);
-  };
 
   // ---- weight stream: this wave's 2 KiB (cout blocks ct = 0, 1: two consecutive 1-KiB pieces) of its step f -> ring slot f % NRING.
   // packed layout: [chunk][xt][xi][dy][cq][ct][32 couts][32 B]; the wave's 9 steps of a chunk are 9 consecutive slabs.  The stream
@@ -324,37 +341,36 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
     return (dy == 0 ? vb0 : dy == 1 ? vb1 : (vb0 ^ 16) + 256) + half * V_BYTES + (s / 3) * VXI + nt * 1024;
   };
 
-  // ---- prologue: first halo, the first ring of weight steps and the affine of chunk 0 in one memory round trip ----------------------
+  // ---- prologue: first halo, the first ring of weight steps and the affine table in one memory round trip; chunk 0 -> V[0] -------
   next_chunk();
   load_halo();
+  load_affine();
 #pragma unroll
   for (int k = 0; k < NRING; ++k) dma_step(k, k);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  aff_wait();
-  barrier();                // every lane's halo slots have landed
-  conv_slot(0, 0);
-  if (pass1) conv_slot(1, 0);
+  barrier();                // every lane's halo slots and the affine table have landed
+  produce(false, 0, 0, 0);
+  if (extra_wave) produce(true, 0, 0, 0);
   next_chunk();             // (chunk 1: its halo arrived with chunk 0's)
   lds_wait();
-  barrier();                // z complete
-  transform_at(tz0, tv0, 0);
-  transform_extra(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  lds_wait();
-  barrier();
-  aff_wait();
-  if (xt == 0) conv_slot(0, 1);   // wave group 0 is one step ahead with its conversions (see below)
+  barrier();                // V[0] complete
   FD_T2(const unsigned long long t2_first = __builtin_amdgcn_s_memtime();)
   qa[0] = rd(a_off(0, 0)); qb[0] = rd(b_off(0, 0)); qb[1] = rd(b_off(0, 1)); qa[1] = rd(a_off(0, 1));
 
-  // ---- K loop.  Chunk c multiplies V[c & 1]; meanwhile the halo of chunk c + 1 (in RAW) is activated and stored into z, transformed
-  // into V[(c + 1) & 1], and the halo of chunk c + 2 is requested.  z may be written between the barrier of step 8 (all transforms of
-  // the previous chunk have read it) and the barrier of step 3; the transforms run between the barrier of step 3 and that of step 8.
-  // The two waves of a SIMD (groups xt = 0 / 1) do this vector work in DIFFERENT steps:
-  //   group 0: pass 0 converted in step 8 (of the previous chunk), pass 1 in step 0, transform of halo rows 0..7 in step 4, of rows
-  //            16, 17 in step 5 (wave 1)
-  //   group 1: conversions in steps 1 and 2, transform of halo rows 8..15 in step 5
-  //   both:    next affine requested in step 3 of every chunk, the halo of the next chunk PAIR in step 3 of the even chunks
+  // ---- K loop.  Chunk c multiplies V[c & 1]; meanwhile the halo of chunk c + 1 (in RAW) is activated and transformed into V[(c + 1) & 1]
+  // by the producer pass, and (in the even chunks) the halo of the pair c + 2, c + 3 is requested.  LDS ordering, one barrier per chunk:
+  //   V[(c + 1) & 1]: last read by the fragments of chunk c - 1, which every wave has before it passes the barrier of step 8 of chunk
+  //                   c - 1 (lds_wait in front of it); written in steps 0 .. 2 of chunk c; complete (lds_wait) at the barrier of step 8
+  //                   of chunk c; read from step 8 of chunk c on (the fragments of step 0 of chunk c + 1).
+  //   RAW (one buffer for a chunk PAIR): parity 1 is read in steps 0 .. 2 of the even chunk, parity 0 in steps 0 .. 2 of the odd chunk
+  //                   before it.  The barrier of step 3 of the EVEN chunks says "every producer pass over this pair is done": the request
+  //                   for the next pair follows it, lands before the barrier of step 8 of the same chunk (every wave waits for its own
+  //                   pieces first), and is read from step 0 of the odd chunk on.  The odd chunks have no barrier at step 3.
+  //   AFF:            written once in the prologue, read only.
+  // The two waves of a SIMD (groups xt = 0 / 1) do the producer's vector work in DIFFERENT steps:
+  //   group 0: halo rows 0..7 in step 0, rows 16, 17 in step 2 (wave 1)
+  //   group 1: halo rows 8..15 in step 1
+  //   both:    the halo of the next chunk PAIR is requested in step 3 of the even chunks
   // A step starts with a counted wait for the weights of the NEXT step (its first fragments are requested right away); in flight on
   // this wave's vector-memory counter at that wait, oldest first: the weight pieces of steps s + 1 .. s + 5 (2 each) and, in the four
   // steps after a halo request, its three pieces: vmcnt(8 / 11).  The weights of step s + 6 are requested after the third MFMA of step
@@ -376,7 +392,9 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
       // older than those of step 8: that wait also covers it, and the barrier behind it publishes the RAW slots
       if (s >= 4 && s <= 7 && half == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW + RAW_PASSES) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NW) : "memory");
-      if (s == 3 || s == 8) { lds_wait(); barrier(); }   // s == 3: z complete;  s == 8: V[vn] complete, every wave has its last V[vc] fragments
+      // s == 8: V[vn] complete (and the raw halo of the next pair landed), every wave has its last V[vc] fragments;
+      // s == 3 of the even chunks: every producer pass has read the pair's RAW bytes (the request below overwrites them)
+      if (s == 8 || (s == 3 && half == 0)) { lds_wait(); barrier(); }
       A2 = rd(a_off(k + 1, 0));
       B2 = rd(b_off(k + 1, 0));
       __builtin_amdgcn_sched_barrier(0);
@@ -391,18 +409,15 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
       dma_step(k + NRING, k % NRING);              // step s + 6 into the slot whose fragments have both arrived
       mma(xl, 1, 1, A1, B1);
       __builtin_amdgcn_sched_barrier(0);
-      // the chunk's vector work, while the quads A1 / B1 are dead
-      // (step 8 converts the chunk two ahead: same parity as the current one; steps 0 .. 2 the next chunk: the other parity)
-      if (s == 8) { if (xg == 0) { aff_wait(); conv_slot(0, half); } }
-      if (s == 0) { if (xg == 0 && pass1) conv_slot(1, half ^ 1); }
-      if (s == 1) { if (xg == 1) { aff_wait(); conv_slot(0, half ^ 1); } }
-      if (s == 2) { if (xg == 1 && pass1) conv_slot(1, half ^ 1); }
-      if (s == 4) { if (xg == 0) transform_at(tz0, tv0, vn); }
-      if (s == 5) { if (xg == 1) transform_at(tz0, tv0, vn); else transform_extra(vn); }
+      // the chunk's vector work, while the quads A1 / B1 are dead: the NEXT chunk (the other parity) -> V[vn]
+      if (s == 0) { if (xg == 0) produce(false, half ^ 1, vn, 128 * (1 + half)); }
+      if (s == 1) { if (xg == 1) produce(false, half ^ 1, vn, 128 * (1 + half)); }
+      if (s == 2) { if (extra_wave) produce(true, half ^ 1, vn, 128 * (1 + half)); }
       __builtin_amdgcn_sched_barrier(0);
     }
     wp += 36 * SLAB;
     asm volatile("" : "+s"(wp));
+    affa += 2 * CK * 8;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // all fragment reads / DMA done before the epilogue reuses the LDS
