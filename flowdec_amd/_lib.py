@@ -64,6 +64,14 @@ class FdScoreConfig(C.Structure):
                 ("N", c_int), ("predictor", c_int), ("corrector", c_int), ("corrector_steps", c_int), ("denoise", c_int)]
 
 
+class FdLossConfig(C.Structure):
+    """fd_loss_config (include/flowdec_hip.h "Validation loss")."""
+    _fields_ = [("kind", c_int), ("sigma_x", c_float), ("theta", c_float), ("sigma_min", c_float), ("sigma_max", c_float), ("t_eps", c_float)]
+
+
+LOSS_KINDS = {"flow": 0, "score": 1, "regression": 2}   # FD_LOSS_*
+
+
 class FdStreamRow(C.Structure):
     """fd_stream_row: one entry per row of a streaming step (include/flowdec_hip.h "Streaming"); 64 bytes."""
     _fields_ = [("ring", c_void_p), ("start", c_ll), ("ring_cap", c_int), ("length", c_int), ("peak_slot", c_int), ("emit_lo", c_int),
@@ -192,6 +200,13 @@ SIGNATURES = {
     "fd_estimate_pair_stats": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "fd_select_workspace_bytes": (c_size_t, [c_int]),
     "fd_select_f32": (c_int, [_P, c_ll, C.POINTER(c_ll), c_int, _P, _P, _P, c_size_t, _P]),
+    "fd_loss_num_draws": (c_int, [C.POINTER(FdLossConfig)]),
+    "fd_loss_times": (c_int, [_P, c_int, c_float, c_float, _P, _P]),
+    "fd_loss_state": (c_int, [C.POINTER(FdLossConfig), _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "fd_loss_sqerr_workspace_bytes": (c_size_t, [c_int] * 3),
+    "fd_loss_sqerr": (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "fd_valid_loss_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "fd_valid_loss": (c_int, [_P, C.POINTER(FdLossConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "fd_resample_plan_create": (c_int, [_P, c_int, c_int, c_int, C.POINTER(_P)]),
     "fd_resample_plan_destroy": (None, [_P]),
     "fd_resample_out_length": (c_ll, [c_ll, c_int, c_int]),

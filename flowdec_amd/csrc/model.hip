@@ -1656,6 +1656,92 @@ extern "C" int fd_regression_enhance_ragged(fd_model* m, const float* y, const i
   return regression_enhance_impl(m, "fd_regression_enhance_ragged", y, lengths, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
+// ---- validation loss (include/flowdec_hip.h "Validation loss"; kernels: loss.hip) ---------------------------------------------------
+// _loss of the three model classes without gradients: _preprocess(y, x = x) -> fd_loss_state -> ONE network evaluation at the per-clip
+// times -> fd_loss_sqerr.  Workspace: Y | X | Xt | target | V (five states), t [B], std [B], the reduction's partials, then the larger
+// of the transform's and the network's scratch.
+namespace {
+struct loss_layout { size_t state, vec, sq, rest, total; int T, Tp; };
+bool loss_bytes(const fd_model* m, int B, int L, loss_layout& s) {
+  if (!m || B <= 0 || B > fd_model::MAX_NT || L <= m->cfg.n_fft / 2 || L > 0x7fffffff - 1024) return false;
+  s.T = 1 + L / m->cfg.hop; s.Tp = fd_padded_frames(s.T);
+  if (check_shape(m, B, s.Tp) != FD_OK) return false;
+  s.state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * s.Tp);
+  s.vec = fd_align(sizeof(float) * B);
+  s.sq = fd_loss_sqerr_workspace_bytes(B, m->n_freq, s.Tp);
+  if (!s.sq) return false;
+  const size_t a = fd_stft_ws_bytes(B, L, m->cfg.n_fft, m->cfg.hop), b = forward_ws_bytes(m, B, s.Tp);
+  s.rest = a > b ? a : b;
+  s.total = 5 * s.state + 2 * s.vec + s.sq + s.rest + 256;
+  return true;
+}
+}  // namespace
+
+extern "C" size_t fd_valid_loss_workspace_bytes(const fd_model* m, int B, int L) {
+  loss_layout s;
+  if (!m || !m->finalized || !loss_bytes(m, B, L, s)) return 0;
+  return s.total;
+}
+
+extern "C" int fd_valid_loss(fd_model* m, const fd_loss_config* cfg, const float* x, const float* y, const int* lengths, const float* noise,
+                             const unsigned long long* seeds, const float* t, double* sums_out, long long* bad_out, float* normfac_out, int B, int L,
+                             void* ws, size_t ws_bytes, void* stream) {
+  FD_MODEL_ENTER(m, "fd_valid_loss");
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(cfg, "fd_valid_loss: null cfg");
+  FD_REQUIRE(x, "fd_valid_loss: null x");
+  FD_REQUIRE(y, "fd_valid_loss: null y");
+  FD_REQUIRE(sums_out, "fd_valid_loss: null sums_out");
+  FD_REQUIRE(bad_out, "fd_valid_loss: null bad_out");
+  FD_REQUIRE(normfac_out, "fd_valid_loss: null normfac_out");
+  FD_REQUIRE(ws, "fd_valid_loss: null ws");
+  const int kind = cfg->kind;
+  FD_REQUIRE(kind == FD_LOSS_FLOW || kind == FD_LOSS_SCORE || kind == FD_LOSS_REGRESSION, "fd_valid_loss: unknown kind %d", kind);
+  FD_REQUIRE(B > 0 && B <= fd_model::MAX_NT, "fd_valid_loss: B = %d clips (1 <= B <= %d: one time per clip)", B, fd_model::MAX_NT);
+  FD_REQUIRE(L > m->cfg.n_fft / 2 && L <= 0x7fffffff - 1024, "fd_valid_loss: clips must be longer than %d samples (L = %d)", m->cfg.n_fft / 2, L);
+  float lo = 0.f;
+  if (kind != FD_LOSS_REGRESSION) {
+    FD_REQUIRE((noise != nullptr) != (seeds != nullptr), "fd_valid_loss: exactly one of noise and seeds must be given (got %s)", noise ? "both" : "neither");
+    FD_REQUIRE(t || seeds, "fd_valid_loss: t is NULL and there are no seeds to draw it from");
+  }
+  if (kind == FD_LOSS_FLOW) FD_REQUIRE(cfg->sigma_x >= 0.f, "fd_valid_loss: sigma_x must not be negative");
+  if (kind == FD_LOSS_SCORE) {
+    FD_REQUIRE(cfg->sigma_min > 0.f && cfg->sigma_max > cfg->sigma_min && cfg->theta > 0.f, "fd_valid_loss: bad OUVE parameters");
+    FD_REQUIRE(cfg->t_eps > 0.f && cfg->t_eps < 1.f, "fd_valid_loss: t_eps must be in (0, 1)");
+    lo = cfg->t_eps;
+  }
+  loss_layout s;
+  FD_REQUIRE(loss_bytes(m, B, L, s), "fd_valid_loss: bad shape B %d L %d for this model", B, L);
+  FD_REQUIRE(ws_bytes >= s.total, "fd_valid_loss: workspace too small (%zu < %zu bytes, fd_valid_loss_workspace_bytes)", ws_bytes, s.total);
+  hipStream_t st = fd_stream(stream);
+  char* base = reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256);
+  float* Y = (float*)base;
+  float* X = (float*)(base + s.state);
+  float* Xt = (float*)(base + 2 * s.state);
+  float* target = (float*)(base + 3 * s.state);
+  float* V = (float*)(base + 4 * s.state);
+  float* t_ws = (float*)(base + 5 * s.state);
+  float* std_ws = (float*)(base + 5 * s.state + s.vec);
+  char* sq = base + 5 * s.state + 2 * s.vec;
+  char* rest = sq + s.sq;
+  const int F = m->n_freq, Tp = s.Tp;
+  // _preprocess(y, x = x): the factor comes from y alone; x is divided by the same one
+  FD_TRY(fd_stft_forward(m->stft, y, lengths, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac_out, Y, Tp, rest, s.rest, st));
+  FD_TRY(fd_stft_forward(m->stft, x, lengths, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, nullptr, X, Tp, rest, s.rest, st, normfac_out));
+  OutSpec os; os.dst = V; os.coef = 1.f;
+  if (kind == FD_LOSS_REGRESSION) {
+    FD_TRY(forward_call(m, Y, Y, nullptr, 0.f, 1, os, B, Tp, rest, s.rest, st));
+    return fd_loss_sqerr(kind, V, X, nullptr, sums_out, bad_out, B, F, Tp, sq, s.sq, stream);
+  }
+  if (!t) {
+    FD_TRY(fd_loss_times(seeds, B, lo, 1.0f, t_ws, stream));
+    t = t_ws;
+  }
+  FD_TRY(fd_loss_state(cfg, Y, X, t, noise, seeds, m->sigma_dev, m->sigma_n, Xt, target, std_ws, nullptr, B, F, Tp, stream));
+  FD_TRY(forward_call(m, Xt, Y, t, 0.f, B, os, B, Tp, rest, s.rest, st));
+  return fd_loss_sqerr(kind, V, target, std_ws, sums_out, bad_out, B, F, Tp, sq, s.sq, stream);
+}
+
 // ---- one ResnetBlockBigGANpp as a stand-alone call (layerspp.py:252-284; the fusion unit of SURVEY 8(a13)) -----------
 namespace {
 int resblock_run(const fd_resblock_desc& d, const void* x0, const void* x1, void* out, int B, int H, int W, int dtype, bool dry, void* ws,

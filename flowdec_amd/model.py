@@ -629,7 +629,11 @@ class FlowModel(nn.Module):
         assert normalize_mode in ("noisy", "none")
         self.sampling_rate, self.normalize_mode, self.lr, self.flow_matcher = sampling_rate, normalize_mode, lr, flow_matcher
         self.backbone, self.feature_extractor = backbone, feature_extractor
-        self.sigma_x = nn.Parameter(sigma_x if isinstance(sigma_x, torch.Tensor) else torch.tensor(float(sigma_x)), requires_grad=False)
+        if callable(sigma_x) and not isinstance(sigma_x, torch.Tensor):   # model.py:408-413: kept as given; only `valid_loss` reads sigma_x, and refuses it
+            self.sigma_x = sigma_x
+        else:
+            self.sigma_x = nn.Parameter(sigma_x if isinstance(sigma_x, torch.Tensor) else torch.tensor(float(sigma_x)), requires_grad=False)
+        self.error_weighting = kwargs.get("error_weighting")
         self.sigma_y = nn.Parameter(sigma_y if isinstance(sigma_y, torch.Tensor) else torch.tensor(float(sigma_y)), requires_grad=False)
         self._io = {}
         self._side_stream = None
@@ -837,6 +841,18 @@ class FlowModel(nn.Module):
             outs[b].record_stream(cur)
             res.append(outs[b].reshape(c.shape).to(c.device))
         return res
+
+    def valid_loss(self, x, y, *, seed=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, comp_eps=None):
+        """FlowModel._loss (model.py:421-468) on clean x / coded y of one length, without gradients: the `valid_loss` of validation_step.
+        seed= (the library's noise and time), noise= [n_draws, B, 1, F, T_pad] (draw 0: Ys, draw 1: Xs when sigma_x != 0), t= [B];
+        reduce='none' -> per-clip values (float64); return_t=True adds the times.  See flowdec_amd/loss.py."""
+        from . import loss as fd_loss
+        return fd_loss.valid_loss(self, "flow", x, y, seed=seed, noise=noise, t=t, reduce=reduce, return_t=return_t, comp_eps=comp_eps)
+
+    def valid_loss_batch(self, xs, ys, *, seeds=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, max_batch: int = 8):
+        """`valid_loss` for lists of pairs of any lengths, bucketed by padded frame count; every pair bit-identical to its one-pair call."""
+        from . import loss as fd_loss
+        return fd_loss.valid_loss_batch(self, "flow", xs, ys, seeds=seeds, noise=noise, t=t, reduce=reduce, return_t=return_t, max_batch=max_batch)
 
     def _long_buffers(self, B, Lrow, dev):
         """The device arrays of `enhance_long`'s native calls.  They live as long as the shape does: a captured graph is keyed on their
@@ -1321,6 +1337,15 @@ class ScoreModel(_WaveModel):
         std = self.sde_std(t_batch.float())
         return -self.backbone(xt, y, t_batch) / std.reshape(-1, 1, 1, 1)
 
+    def valid_loss(self, x, y, *, seed=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, comp_eps=None):
+        """ScoreModel._loss (model.py:590-611) without gradients; the time is drawn over [t_eps, 1).  See FlowModel.valid_loss."""
+        from . import loss as fd_loss
+        return fd_loss.valid_loss(self, "score", x, y, seed=seed, noise=noise, t=t, reduce=reduce, return_t=return_t, comp_eps=comp_eps)
+
+    def valid_loss_batch(self, xs, ys, *, seeds=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, max_batch: int = 8):
+        from . import loss as fd_loss
+        return fd_loss.valid_loss_batch(self, "score", xs, ys, seeds=seeds, noise=noise, t=t, reduce=reduce, return_t=return_t, max_batch=max_batch)
+
     def _pc_config(self, predictor, corrector, N, corrector_steps, snr, denoise, eps=None):
         """-> (fd_score_config of the predictor-corrector sampler, the number of Gaussian planes it consumes)."""
         if predictor not in L.PREDICTORS:
@@ -1449,6 +1474,15 @@ class RegressionModel(_WaveModel):
             t = t.unsqueeze(0)
         self._sync_native()
         return self.backbone(xt, y, t)
+
+    def valid_loss(self, x, y, *, reduce: str = "mean", comp_eps=None):
+        """RegressionModel._loss (model.py:552-559) without gradients: mean |backbone(Y, Y, 0) - X|^2.  No random draws."""
+        from . import loss as fd_loss
+        return fd_loss.valid_loss(self, "regression", x, y, reduce=reduce, comp_eps=comp_eps)
+
+    def valid_loss_batch(self, xs, ys, *, reduce: str = "mean", max_batch: int = 8):
+        from . import loss as fd_loss
+        return fd_loss.valid_loss_batch(self, "regression", xs, ys, reduce=reduce, max_batch=max_batch)
 
     @torch.no_grad()
     def enhance(self, y, return_preprocess_info=False, use_graph: bool = True, **kwargs):

@@ -436,7 +436,9 @@ int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths, const flo
  * that consumes it -- no noise buffer exists.  The value at (clip seed s, draw index d >= 0, frequency row f, frame t) is a pure
  * function (NORMATIVE):
  *   - Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
- *     (s & 0xffffffff, s >> 32) and counter (t >> 1, f, d, 0) gives r0..r3.  Counter word 3 is reserved and stays 0.
+ *     (s & 0xffffffff, s >> 32) and counter (t >> 1, f, d, 0) gives r0..r3.  Counter word 3 is reserved: the noise uses value 0 only.
+ *     Value 1 is the clip's validation-loss time ("Validation loss" below): counter (0, 0, 0, 1), u = (r0 >> 8) * 2^-24 in [0, 1).
+ *     Every other value of word 3 stays unused.
  *   - t is the ABSOLUTE frame: frame0[b] + the local frame (column) of row b, where frame0 (DEVICE int32 [B], fd_noise_fill_at /
  *     fd_enhance_chunks) says where in a longer recording the row starts; 0 <= frame0[b] and frame0[b] + T_pad < 2^31.  Every other
  *     entry point, and a NULL frame0, has frame0 = 0: t is the local frame.
@@ -745,6 +747,76 @@ int fd_estimate_pair_stats(const fd_stft_plan* plan, const float* x, const float
 size_t fd_select_workspace_bytes(int R);
 int fd_select_f32(const float* values, long long n, const long long* ranks, int R, float* out, long long* bad_out, void* ws, size_t ws_bytes,
                   void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Validation loss: the quantity the reference's validation_step logs as `valid_loss` (flowdec/model.py:221-223; `_loss` of FlowModel
+ * :421-468, ScoreModel :590-611, RegressionModel :552-559) for (clean, coded) pairs -- one front end on the pair, the random draws, ONE
+ * network evaluation at a random time and per-clip sums of squared errors.  No gradient, no optimiser.  flowdec_amd/loss.py drives these
+ * calls; csrc/loss.hip holds the kernels.  Every call is asynchronous on `stream`, allocates nothing and launches nothing when it
+ * refuses; a NULL pointer, a bad shape and a workspace that is too small are FD_EINVAL with a message that names the argument.
+ *
+ * fd_loss_config: kind = FD_LOSS_FLOW / FD_LOSS_SCORE / FD_LOSS_REGRESSION; sigma_x (flow: the scalar sigma_x of the model, >= 0);
+ *   theta, sigma_min, sigma_max, t_eps (score: OUVESDE and ScoreModel.t_eps).  fd_loss_num_draws: the Gaussian planes a kind consumes:
+ *   flow 1, or 2 with sigma_x != 0; score 1; regression 0 (-1 for a NULL cfg or an unknown kind).
+ *
+ * fd_loss_times: t_out[b] (DEVICE float [B]) = lo + u[b] * (hi - lo) in float32 (product and sum rounded separately, as
+ *   torch.rand(B) * (T - t_eps) + t_eps), u[b] = (r0 >> 8) * 2^-24 with r0 from Philox4x32-10, key = seeds[b] (DEVICE uint64 [B]), counter
+ *   (0, 0, 0, 1) -- value 1 of the reserved counter word of "Seeded noise" (NORMATIVE).  (lo, hi) = (0, 1) for flow, (t_eps, 1) for score;
+ *   0 <= lo < hi <= 1.  Every value lies in [lo, hi] and below hi unless the float32 sum rounds up to it.
+ *
+ * fd_loss_state: Y, X = complex64 [B][1][F][T_pad] (the compressed spectrograms, zero tail as fd_stft_compress_ragged leaves it), t =
+ *   DEVICE float [B] -> xt_out (the network input) and target_out, both complex64 [B][1][F][T_pad], in one pass.  Exactly one of noise
+ *   (complex64 [fd_loss_num_draws][B][F][T_pad]) and seeds (DEVICE uint64 [B]: draw k is draw index k of "Seeded noise") is given; the
+ *   seeded form equals the buffer form on fd_noise_fill's planes bit for bit.  Every product and sum below is rounded to float32 on its
+ *   own (no fused multiply-add), per component:
+ *     flow        Ys = Y + (float)(sigma_y[f] * (double)z0) -- fd_ode_solve's x0 with sigma_fac = 1, bit for bit, padded frames included
+ *                 (randn_like(Ymu) covers them);  Xs = X + sigma_x * z1, or X itself when sigma_x == 0 (no draw is consumed);
+ *                 xt = t * Xs + (1 - t) * Ys with 1 - t rounded once;  target = Ut = Xs - Ys.  (ConditionalFlowMatcher with sigma = 0.)
+ *                 sigma_y = DEVICE double [sigma_n], sigma_n = 1 or F.  ys_out (optional) receives Ys.
+ *     score       e = expf(-theta t), mean = e * X + (1 - e) * Y, std = the OUVE closed form fd_score_* uses (sdes.py:183-196) evaluated
+ *                 in float32 on the device at the clip's t;  xt = mean + z0 * std;  target = z0;  std_out (optional, DEVICE float [B]).
+ *     regression  xt = Y, target = X (t, noise, seeds are not read; the network runs at t = 0).
+ * fd_loss_sqerr: V (the network output), target: complex64 [B][1][F][T_pad]; std DEVICE float [B] (score only).  err per component in
+ *   float32 as the reference forms it -- flow V - Ut; score std * ((-V / std) - (-z0 / std)); regression V - X -- then
+ *   sums_out[b] (DEVICE double) = sum over the clip of (double)re^2 + (double)im^2, and bad_out[b] (DEVICE int64) = its number of elements
+ *   with a non-finite component.  Two stages in a fixed order that depends on F * T_pad only; no floating-point atomics; a clip's sum
+ *   has the SAME BITS alone, in a batch and at any batch position.  ws: fd_loss_sqerr_workspace_bytes(B, F, T_pad) (0 for a bad shape).
+ *
+ * fd_valid_loss: x (clean), y (coded) = DEVICE float [B][L] rows; lengths = DEVICE int32 [B] of ONE T_pad bucket (the contract of
+ *   fd_enhance_ragged) or NULL: every pair is L samples long.  The front end is EnhancementModel._preprocess(y, x=x): normfac from y
+ *   with enhance's zero guard (fd_normfac's rule; NOT fd_estimate_pair_stats' + 1e-5), x divided by the same factor, both transformed,
+ *   compressed and zero-padded to T_pad.  Then fd_loss_state, fd_ncsnpp_forward at the per-clip times (regression: t = 0, input Y) and
+ *   fd_loss_sqerr.
+ *     noise / seeds  exactly one for flow and score (noise = complex64 [fd_loss_num_draws][B][F][T_pad]); regression reads neither.
+ *     t              DEVICE float [B], or NULL: drawn from `seeds` as fd_loss_times does, over [0, 1) (flow) / [t_eps, 1) (score);
+ *                    NULL without seeds is FD_EINVAL.  Regression ignores it.
+ *     sums_out       DEVICE double [B]: sum |err|^2 of clip b over its F * T_pad bins.  The HOST turns the sums into the loss: flow
+ *                    mean_b(sums[b] / (F T_pad)) with NaN clips dropped; score 0.5 mean_b sums[b]; regression sum_b sums[b] / (B F T_pad).
+ *     bad_out        DEVICE int64 [B];  normfac_out DEVICE float [B].
+ *     B              at most 256 clips (the per-sample time table of the network).
+ *   Clip b's three outputs have the SAME BITS alone, in a batch and at any batch position.
+ *   ws: fd_valid_loss_workspace_bytes(m, B, L) bytes (0 for a bad shape).
+ * ---------------------------------------------------------------------------------------------- */
+#define FD_LOSS_FLOW 0
+#define FD_LOSS_SCORE 1
+#define FD_LOSS_REGRESSION 2
+typedef struct fd_loss_config {
+  int kind;
+  float sigma_x;
+  float theta, sigma_min, sigma_max, t_eps;
+} fd_loss_config;
+int fd_loss_num_draws(const fd_loss_config* cfg);
+int fd_loss_times(const unsigned long long* seeds, int B, float lo, float hi, float* t_out, void* stream);
+int fd_loss_state(const fd_loss_config* cfg, const float* Y, const float* X, const float* t, const float* noise, const unsigned long long* seeds,
+                  const double* sigma_y, int sigma_n, float* xt_out, float* target_out, float* std_out, float* ys_out, int B, int F, int T_pad,
+                  void* stream);
+size_t fd_loss_sqerr_workspace_bytes(int B, int F, int T_pad);
+int fd_loss_sqerr(int kind, const float* V, const float* target, const float* std, double* sums_out, long long* bad_out, int B, int F, int T_pad,
+                  void* ws, size_t ws_bytes, void* stream);
+size_t fd_valid_loss_workspace_bytes(const fd_model* m, int B, int L);
+int fd_valid_loss(fd_model* m, const fd_loss_config* cfg, const float* x, const float* y, const int* lengths, const float* noise,
+                  const unsigned long long* seeds, const float* t, double* sums_out, long long* bad_out, float* normfac_out, int B, int L, void* ws,
+                  size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Resampling: torchaudio.functional.resample (sinc_interp_hann) as a polyphase FIR on the device, with an order of summation that is
