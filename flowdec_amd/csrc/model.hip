@@ -1438,54 +1438,78 @@ extern "C" int fd_ode_solve_adaptive_clips(fd_model* m, const float* Y, const fl
   return FD_OK;
 }
 
+// The workspace of every enhance entry point: Y | X | normfac[B] | rest (the larger of the transform's and the body's scratch).
+namespace {
+struct enhance_layout_t { size_t state, normfac, rest, total; int T, Tp; };
+bool enhance_layout(const fd_model* m, int B, int L, enhance_layout_t& s) {
+  if (!m || B <= 0 || L <= 0) return false;
+  s.T = 1 + L / m->cfg.hop; s.Tp = fd_padded_frames(s.T);
+  if (check_shape(m, B, s.Tp) != FD_OK) return false;
+  const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * s.Tp);
+  s.state = state;
+  s.normfac = 2 * state;
+  s.rest = 2 * state + fd_align(sizeof(float) * B);
+  const size_t a = fd_stft_ws_bytes(B, L, m->cfg.n_fft, m->cfg.hop), b = ode_ws_bytes(m, B, s.Tp);
+  s.total = s.rest + (a > b ? a : b) + 256;
+  return true;
+}
+}  // namespace
+
 extern "C" size_t fd_enhance_workspace_bytes(const fd_model* m, int B, int L) {
-  if (!m || B <= 0 || L <= 0) return 0;
-  const int T = 1 + L / m->cfg.hop, Tp = fd_padded_frames(T);
-  if (check_shape(m, B, Tp) != FD_OK) return 0;
-  const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * Tp);
-  const size_t a = fd_stft_ws_bytes(B, L, m->cfg.n_fft, m->cfg.hop), b = ode_ws_bytes(m, B, Tp);
-  return 2 * state + fd_align(sizeof(float) * B) + (a > b ? a : b) + 256;
+  enhance_layout_t s;
+  return enhance_layout(m, B, L, s) ? s.total : 0;
 }
 
 extern "C" size_t fd_enhance_normfac_offset(const fd_model* m, int B, int L) {
-  if (!m || B <= 0 || L <= 0) return 0;
-  const int Tp = fd_padded_frames(1 + L / m->cfg.hop);
-  return 2 * fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * Tp);
+  enhance_layout_t s;
+  return enhance_layout(m, B, L, s) ? s.normfac : 0;
 }
 
-namespace {
-int enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, float sigma_fac, int N, int solver, float* x_hat, int B,
-                 int L, void* ws, size_t ws_bytes, int use_graph, void* stream, const float* normfac_in = nullptr) {
+// Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT.  lens (device int32 [B]) = a ragged batch
+// (see fd_enhance_ragged), nullptr = every clip is L samples long.  normfac_in (device float [B], fd_enhance_chunks) replaces the clips' own
+// maxima: the front end divides by it, the back end multiplies by it, and the workspace's normfac slot stays unwritten.
+template <typename Body>
+static int enhance_common(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                          GraphKey key, int use_graph, void* stream, Body&& body, const float* normfac_in = nullptr) {
   FD_TRY(check_ready(m));
-  FD_REQUIRE(y && (noise.ptr || noise.seeds) && x_hat && ws, "%s: null pointer", who);
-  FD_REQUIRE(N >= 1 && solver_nfe(solver, N) > 0, "%s: bad N / solver", who);
+  FD_REQUIRE(y && x_hat && ws, "%s: null pointer", who);
   FD_REQUIRE(B > 0 && L > m->cfg.n_fft / 2, "%s: clips must be longer than %d samples", who, m->cfg.n_fft / 2);
-  const int T = 1 + L / m->cfg.hop, Tp = fd_padded_frames(T);
-  FD_TRY(check_shape(m, B, Tp));
-  const size_t need = fd_enhance_workspace_bytes(m, B, L);
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
+  enhance_layout_t lay;
+  if (!enhance_layout(m, B, L, lay)) return FD_EINVAL;   // check_shape has left the message
+  if (ws_bytes < lay.total) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, lay.total);
   hipStream_t st = fd_stream(stream);
-  const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * Tp);
+  const int T = lay.T, Tp = lay.Tp;
   float* Y = (float*)ws;
-  float* X = (float*)((char*)ws + state);
-  float* normfac = (float*)((char*)ws + 2 * state);
-  char* rest = (char*)ws + 2 * state + fd_align(sizeof(float) * B);
-  const size_t rest_bytes = ws_bytes - (2 * state + fd_align(sizeof(float) * B));
-  GraphKey key; key.y = y; key.noise = noise.ptr; key.seeds = noise.seeds; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.N = N; key.solver = solver; key.kind = 2;
-  key.sigma_fac = sigma_fac; key.normalize = m->normalize; key.frame0 = noise.frame0; key.normfac_in = normfac_in;
+  float* X = (float*)((char*)ws + lay.state);
+  float* normfac = (float*)((char*)ws + lay.normfac);
+  char* rest = (char*)ws + lay.rest;
+  const size_t rest_bytes = ws_bytes - lay.rest;
+  key.y = y; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.normalize = m->normalize; key.normfac_in = normfac_in;
   return run_maybe_graph(m, key, use_graph != 0, st, [&]() {
     FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st, normfac_in));
-    FD_TRY(ode_enqueue(m, Y, noise, sigma_fac, N, solver, X, nullptr, B, Tp, rest, rest_bytes, st));
+    FD_TRY(body(Y, X, Tp, (void*)rest, rest_bytes, st));
     FD_TRY(fd_stft_inverse(m->stft, X, lens, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac_in ? normfac_in : normfac, x_hat, L, rest, rest_bytes, st));
     return FD_OK;
   });
 }
-}  // namespace
+
+// The flow model's entry points: the noise source, N and the solver are theirs; the body is the fixed-step solver.
+static int flow_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, float sigma_fac, int N, int solver,
+                             float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream, const float* normfac_in = nullptr) {
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(noise.ptr || noise.seeds, "%s: null pointer", who);
+  FD_REQUIRE(N >= 1 && solver_nfe(solver, N) > 0, "%s: bad N / solver", who);
+  GraphKey key; key.noise = noise.ptr; key.seeds = noise.seeds; key.frame0 = noise.frame0; key.N = N; key.solver = solver; key.sigma_fac = sigma_fac; key.kind = 2;
+  return enhance_common(m, who, y, lens, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
+                        [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
+                          return ode_enqueue(m, Y, noise, sigma_fac, N, solver, X, nullptr, B, Tp, rest, rest_bytes, st);
+                        }, normfac_in);
+}
 
 extern "C" int fd_enhance(fd_model* m, const float* y, const float* noise, float sigma_fac, int N, int solver, float* x_hat, int B, int L, void* ws,
                           size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance");
-  return enhance_impl(m, "fd_enhance", y, nullptr, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return flow_enhance_impl(m, "fd_enhance", y, nullptr, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // FlowModel.enhance on a RAGGED batch: the reference's driver enhances a directory file by file (enhance.py:96-137), every file its
@@ -1499,7 +1523,7 @@ extern "C" int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths
                                  float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance_ragged");
   FD_REQUIRE(lengths, "fd_enhance_ragged: null lengths");
-  return enhance_impl(m, "fd_enhance_ragged", y, lengths, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return flow_enhance_impl(m, "fd_enhance_ragged", y, lengths, fd_noise_src{noise}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // fd_enhance (lengths == NULL) / fd_enhance_ragged with the initial noise generated from the clips' seeds (DEVICE uint64 [B], draw index 0):
@@ -1507,7 +1531,7 @@ extern "C" int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths
 extern "C" int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, float sigma_fac, int N, int solver,
                                  float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance_seeded");
-  return enhance_impl(m, "fd_enhance_seeded", y, lengths, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+  return flow_enhance_impl(m, "fd_enhance_seeded", y, lengths, fd_noise_src{nullptr, seeds, 0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
 // Long-form: the rows are CHUNKS of longer recordings.  fd_enhance_seeded on ragged rows plus two optional device arrays: frame0 (int32 [B]:
@@ -1520,36 +1544,8 @@ extern "C" int fd_enhance_chunks(fd_model* m, const float* y, const int* lengths
                                  int use_graph, void* stream) {
   FD_MODEL_ENTER(m, "fd_enhance_chunks");
   FD_REQUIRE(seeds, "fd_enhance_chunks: null seeds");
-  return enhance_impl(m, "fd_enhance_chunks", y, lengths, fd_noise_src{nullptr, seeds, 0, frame0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph,
+  return flow_enhance_impl(m, "fd_enhance_chunks", y, lengths, fd_noise_src{nullptr, seeds, 0, frame0}, sigma_fac, N, solver, x_hat, B, L, ws, ws_bytes, use_graph,
                       stream, normfac_in);
-}
-
-// Shared front end / back end of the three enhancement models:  STFT -> body(Y, X) -> iSTFT.  lens (device int32 [B]) = a ragged batch
-// (see fd_enhance_ragged), nullptr = every clip is L samples long.
-template <typename Body>
-static int enhance_common(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
-                          GraphKey key, int use_graph, void* stream, Body&& body) {
-  FD_TRY(check_ready(m));
-  FD_REQUIRE(y && x_hat && ws, "%s: null pointer", who);
-  FD_REQUIRE(B > 0 && L > m->cfg.n_fft / 2, "%s: clips must be longer than %d samples", who, m->cfg.n_fft / 2);
-  const int T = 1 + L / m->cfg.hop, Tp = fd_padded_frames(T);
-  FD_TRY(check_shape(m, B, Tp));
-  const size_t need = fd_enhance_workspace_bytes(m, B, L);
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
-  hipStream_t st = fd_stream(stream);
-  const size_t state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * Tp);
-  float* Y = (float*)ws;
-  float* X = (float*)((char*)ws + state);
-  float* normfac = (float*)((char*)ws + 2 * state);
-  char* rest = (char*)ws + 2 * state + fd_align(sizeof(float) * B);
-  const size_t rest_bytes = ws_bytes - (2 * state + fd_align(sizeof(float) * B));
-  key.y = y; key.xhat = x_hat; key.ws = ws; key.lens = lens; key.B = B; key.L = L; key.normalize = m->normalize;
-  return run_maybe_graph(m, key, use_graph != 0, st, [&]() {
-    FD_TRY(fd_stft_forward(m->stft, y, lens, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, Tp, rest, rest_bytes, st));
-    FD_TRY(body(Y, X, Tp, (void*)rest, rest_bytes, st));
-    FD_TRY(fd_stft_inverse(m->stft, X, lens, B, T, Tp, m->cfg.alpha, m->cfg.beta, normfac, x_hat, L, rest, rest_bytes, st));
-    return FD_OK;
-  });
 }
 
 extern "C" int fd_score_num_draws(const fd_score_config* c) {

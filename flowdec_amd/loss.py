@@ -211,11 +211,8 @@ def valid_loss(model, kind: str, x, y, *, seed=None, noise=None, t=None, reduce:
     if x.shape != y.shape:
         raise RuntimeError(f"valid_loss: x and y must have the same shape (got {tuple(x.shape)} vs {tuple(y.shape)})")   # model.py:141
     dev = _require_gpu(model)
-    y3 = y
-    while y3.ndim < 3:
-        y3 = y3.unsqueeze(0)
-    if y3.ndim != 3 or y3.shape[1] != 1:
-        raise RuntimeError(f"valid_loss expects [L], [1, L] or [B, 1, L] waveforms (got {tuple(y.shape)})")
+    from .model import _to_3d
+    y3, _ = _to_3d(y, "valid_loss expects")
     B, Lw = y3.shape[0], y3.shape[-1]
     stft = model.feature_extractor._cfg()
     lib = L.load()

@@ -488,7 +488,7 @@ class AmplitudeCompressedComplexSTFT(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-# FlowModel
+# the staging base of the three model classes
 # ------------------------------------------------------------------------------------------------
 def sigma_y_from_file(filename: str, factor: float = 1.0, kernel_bandwidth: Optional[float] = None) -> torch.Tensor:
     """flowdec/data/sigma_models/__init__.py:21-47 (gaussian_filter(mode='nearest') restated in NumPy)."""
@@ -551,11 +551,25 @@ def _per_clip_generators(generator, noise, B):
     return gens
 
 
-def _info_from_ws(lib, h, ws, B, Lw, T, squeeze_dims):
-    """preprocess_info of the reference (model.py:161-162); normfac is read where fd_enhance's front end left it."""
-    off = lib.fd_enhance_normfac_offset(h, B, Lw)
-    normfac = ws[off:off + 4 * B].view(torch.float32).clone().reshape(B, 1, 1)
-    return dict(orig_length=Lw, normfac=normfac, undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
+def _to_3d(y, who, rows="B"):
+    """[L] / [1, L] / [B, 1, L] -> ([B, 1, L], the number of axes added in front: `squeeze_dims`, model.py:146-149), or raise."""
+    y3, squeeze_dims = y, 0
+    while y3.ndim < 3:
+        y3 = y3.unsqueeze(0); squeeze_dims += 1
+    if y3.ndim != 3 or y3.shape[1] != 1:
+        raise RuntimeError(f"{who} [L], [1, L] or [{rows}, 1, L] waveforms (got {tuple(y.shape)})")
+    return y3, squeeze_dims
+
+
+def _preprocess_info(Lw, normfac, T, squeeze_dims):
+    """preprocess_info of the reference (model.py:161-162); normfac: the B factors of the clips, T: the frames before pad_spec."""
+    return dict(orig_length=Lw, normfac=normfac.reshape(-1, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
+
+
+def _traj_waveforms(traj, T, Lw, normfac, cfg, lengths=None):
+    """Every state of a solver trajectory [N + 1, B, 1, F, T_pad] back in the time domain -> list of N + 1 waveforms [B, 1, Lw]."""
+    from . import ops
+    return [ops.decompress_istft(X, T, Lw, normfac, lengths=lengths, **cfg).reshape(-1, 1, Lw) for X in traj]
 
 
 def _preprocess(model, y, x=None, comp_eps=None):
@@ -568,12 +582,7 @@ def _preprocess(model, y, x=None, comp_eps=None):
     if x is not None and x.shape != y.shape:
         raise RuntimeError(f"x and y must have the same shape (got {tuple(x.shape)} vs {tuple(y.shape)})")   # model.py:141
     dev = model.device
-    squeeze_dims = 0
-    while y.ndim < 3:
-        y = y.unsqueeze(0); squeeze_dims += 1
-        x = x.unsqueeze(0) if x is not None else x
-    if y.ndim != 3 or y.shape[1] != 1:
-        raise RuntimeError(f"expected [L], [1, L] or [B, 1, L] waveforms (got {tuple(y.shape)})")
+    y, squeeze_dims = _to_3d(y, "expected")
     B, Lw = y.shape[0], y.shape[-1]
     cfg = model.feature_extractor._cfg()
     with torch.cuda.device(dev):
@@ -582,8 +591,7 @@ def _preprocess(model, y, x=None, comp_eps=None):
         if x is not None:   # x / normfac(y) (util/other.py:79-81), then the same feature extractor and padding, without a second normalisation
             xn = x.reshape(B, Lw).to(dev, torch.float32) / normfac.reshape(B, 1)
             X, _, _ = ops.stft_compress(xn.contiguous(), normalize=False, **cfg)
-    info = dict(orig_length=Lw, normfac=normfac.reshape(B, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
-    return Y, X, info
+    return Y, X, _preprocess_info(Lw, normfac, T, squeeze_dims)
 
 
 def _postprocess(model, X_hat, preprocess_info, inv_kwargs=None, batch_filter=None):
@@ -612,46 +620,20 @@ def _postprocess(model, X_hat, preprocess_info, inv_kwargs=None, batch_filter=No
     return x_hat
 
 
-class FlowModel(nn.Module):
-    """Drop-in for flowdec.model.FlowModel on the inference path (model.py:391-536).
-
-    Extensions over the reference signature: ``enhance(..., noise=None, generator=None)`` to inject /
-    seed the initial Gaussian noise (the reference draws it from the global device RNG, model.py:512),
-    ``seed=`` (the library's own counter-based noise, generated on the GPU from one 64-bit seed per clip: an int -- clip b
-    uses ``flowdec_amd.noise.clip_seed(seed, b)`` --, B ints or an int64 / uint64 tensor [B]; no noise tensor is filled),
-    and ``use_graph`` (hipGraph replay of the whole solve).  ``with_grad=True`` is not supported.
-    """
+class _WaveModel(nn.Module):
+    """What FlowModel, ScoreModel and RegressionModel share: the reference's waveform plumbing (EnhancementModel._preprocess /
+    _postprocess, model.py:129-190) and the staging of every native enhance call -- resident device buffers, the capture-safe side
+    stream, the equal-length call (`_wave_call`) and the ragged call (`_ragged_call`).  A model class adds its argument checks and a
+    `launch` closure around its own native entry point."""
     strict_loading = False
 
-    def __init__(self, backbone: NCSNpp, feature_extractor: AmplitudeCompressedComplexSTFT, sampling_rate: int,
-                 sigma_x=0.0, sigma_y=0.66, flow_matcher=None, lr: float = 1e-4, normalize_mode: str = "noisy", **kwargs):
+    def __init__(self, backbone: NCSNpp, feature_extractor: AmplitudeCompressedComplexSTFT, sampling_rate: int = 48000,
+                 lr: float = 1e-4, normalize_mode: str = "noisy", **kwargs):
         super().__init__()
         assert normalize_mode in ("noisy", "none")
-        self.sampling_rate, self.normalize_mode, self.lr, self.flow_matcher = sampling_rate, normalize_mode, lr, flow_matcher
+        self.sampling_rate, self.normalize_mode, self.lr = sampling_rate, normalize_mode, lr
         self.backbone, self.feature_extractor = backbone, feature_extractor
-        if callable(sigma_x) and not isinstance(sigma_x, torch.Tensor):   # model.py:408-413: kept as given; only `valid_loss` reads sigma_x, and refuses it
-            self.sigma_x = sigma_x
-        else:
-            self.sigma_x = nn.Parameter(sigma_x if isinstance(sigma_x, torch.Tensor) else torch.tensor(float(sigma_x)), requires_grad=False)
-        self.error_weighting = kwargs.get("error_weighting")
-        self.sigma_y = nn.Parameter(sigma_y if isinstance(sigma_y, torch.Tensor) else torch.tensor(float(sigma_y)), requires_grad=False)
-        self._io = {}
-        self._side_stream = None
-
-    # -- helpers ------------------------------------------------------------------------------------
-    @property
-    def device(self):
-        return self.sigma_y.device
-
-    def load_state_dict(self, state_dict, strict: bool = False, **kw):
-        # the reference sets strict_loading = False (model.py:397)
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    def _sync_native(self):
-        self.backbone._sigma_y = self.sigma_y
-        self.backbone._stft_cfg = self.feature_extractor._cfg()
-        self.backbone._normalize = self.normalize_mode == "noisy"
-        return self.backbone.handle()
+        self._io, self._side_stream = {}, None
 
     # EnhancementModel._preprocess / _postprocess (model.py:129-190) as stand-alone calls
     def _preprocess(self, y, x=None, comp_eps=None):
@@ -660,15 +642,179 @@ class FlowModel(nn.Module):
     def _postprocess(self, X_hat, preprocess_info, inv_kwargs=None, batch_filter=None):
         return _postprocess(self, X_hat, preprocess_info, inv_kwargs, batch_filter)
 
-    def _io_buffers(self, B, Lw, Tp, F, dev):
+    @property
+    def device(self):
+        return next(self.backbone.parameters()).device
+
+    def load_state_dict(self, state_dict, strict: bool = False, **kw):
+        # the reference sets strict_loading = False (model.py:397)
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def _sync_native(self):
+        self.backbone._sigma_y = getattr(self, "sigma_y", None)   # the flow model's; the baselines have none
+        self.backbone._stft_cfg = self.feature_extractor._cfg()
+        self.backbone._normalize = self.normalize_mode == "noisy"
+        return self.backbone.handle()
+
+    def _gpu(self):
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
+        return dev
+
+    def _frames(self, Lw):
+        """-> (F, T, T_pad) of a clip of Lw samples."""
+        lib, cfg = L.load(), self.feature_extractor._cfg()
+        T = lib.fd_num_frames(Lw, cfg["hop"])
+        return cfg["n_fft"] // 2 + 1, T, lib.fd_padded_frames(T)
+
+    @contextlib.contextmanager
+    def _on_side_stream(self, dev):
+        """Stream capture is illegal on the legacy default stream: the native calls run on a side stream that is ordered after / before
+        the caller's current stream (yielded, for the `record_stream` of what the caller gets back)."""
+        cur = torch.cuda.current_stream(dev)
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(dev)
+        side = self._side_stream
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            yield cur
+        cur.wait_stream(side)
+
+    def _io_entry(self, B, Lw, dev, n_draws=0, seeded=False, ragged=False):
+        """The resident device buffers of the enhance calls: ONE shape (rows, row length, device) per model.  A captured graph is keyed on
+        their addresses, so y and out live as long as the shape does, lens and seeds come with the first call that needs them and stay,
+        and noise [n_draws, B, 1, F, T_pad] lives until n_draws changes -- to 0 (a seeded call, or a model without noise): to None, so
+        a seeded call holds no noise plane."""
         key = (B, Lw, str(dev))
         io = self._io.get(key)
         if io is None:
-            io = dict(y=torch.empty(B, Lw, dtype=torch.float32, device=dev),
-                      noise=torch.empty(B, 1, F, Tp, dtype=torch.complex64, device=dev),
-                      out=torch.empty(B, Lw, dtype=torch.float32, device=dev))
-            self._io = {key: io}  # keep one shape resident
+            io = dict(y=torch.empty(B, Lw, dtype=torch.float32, device=dev), out=torch.empty(B, Lw, dtype=torch.float32, device=dev),
+                      lens=None, seeds=None, noise=None)
+            self._io = {key: io}
+        if ragged and io["lens"] is None:
+            io["lens"] = torch.empty(B, dtype=torch.int32, device=dev)
+        if seeded and io["seeds"] is None:
+            io["seeds"] = torch.empty(B, dtype=torch.int64, device=dev)
+        if n_draws != (0 if io["noise"] is None else io["noise"].shape[0]):
+            F, _, Tp = self._frames(Lw)
+            io["noise"] = None   # (released before its successor is allocated)
+            if n_draws:
+                io["noise"] = torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev)
         return io
+
+    def _enhance_workspace(self, lib, h, B, Lw, dev):
+        need = lib.fd_enhance_workspace_bytes(h, B, Lw)
+        if need == 0:
+            raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
+        return self.backbone.workspace(("enh", B, Lw), need, dev)
+
+    @_serialized
+    def _wave_call(self, y, n_draws, noise, generator, launch, return_preprocess_info=False, seed=None, return_traj=False):
+        """The staging of `enhance`: y [L] / [1, L] / [B, 1, L] into the resident buffers, then launch(lib, h, io, B, L, ws) on the side
+        stream; io = dict(y [B, L], out [B, L], noise [n_draws, B, 1, F, Tp], seeds int64 [B], ...).  With `seed` the seeds are filled and
+        no noise tensor is (a member the call does not fill is None or stale).  launch returns None -- the result is io["out"], its
+        normfac where fd_enhance's front end left it in ws -- or its own (x_hat [B, 1, L], normfac [B]); with return_traj the pair
+        (trajectory, list of waveforms [B, 1, L]), which is returned on the model's device like the reference does."""
+        dev = self._gpu()
+        orig_device = y.device
+        y3, squeeze_dims = _to_3d(y, "enhance expects")
+        lib = L.load()
+        h = self._sync_native()
+        B, Lw = y3.shape[0], y3.shape[-1]
+        with torch.cuda.device(dev):
+            io = self._io_entry(B, Lw, dev, 0 if seed is not None else n_draws, seeded=seed is not None)
+            io["y"].copy_(y3.reshape(B, Lw))
+            if seed is not None:
+                io["seeds"].copy_(fd_noise.seeds_to_tensor(seed, B, dev))
+            elif n_draws:
+                if noise is not None:
+                    io["noise"].copy_(noise.to(dev, torch.complex64).reshape(io["noise"].shape))
+                else:
+                    io["noise"].copy_(torch.randn(io["noise"].shape, dtype=torch.complex64, device=dev, generator=generator))
+            ws = self._enhance_workspace(lib, h, B, Lw, dev)
+            with self._on_side_stream(dev) as cur:
+                res = launch(lib, h, io, B, Lw, ws)
+                if res is None:
+                    res = io["out"].reshape(B, 1, Lw).clone(), None
+                    if return_preprocess_info:
+                        off = lib.fd_enhance_normfac_offset(h, B, Lw)
+                        res = res[0], ws[off:off + 4 * B].view(torch.float32).clone()
+        first, second = res
+        first.record_stream(cur)
+        if return_traj:
+            for w in second:
+                w.record_stream(cur)
+            return first, [w.reshape(w.shape[squeeze_dims:]) for w in second]
+        x_hat = first.reshape(first.shape[squeeze_dims:]).to(orig_device)
+        return (x_hat, _preprocess_info(Lw, second, self._frames(Lw)[1], squeeze_dims)) if return_preprocess_info else x_hat
+
+    @_serialized
+    def _ragged_call(self, clips, n_draws, noise, generator, seeds, launch):
+        """The staging of `enhance_batch`: clips of ONE T_pad bucket as zero-padded rows of a [B, hop * T_pad - 1] buffer, then
+        launch(lib, h, io, B, Lrow, ws) on the side stream; io as in `_wave_call` plus lens int32 [B].  Clip b's planes are noise[b]
+        ([n_draws, 1, 1, F, Tp]) or one draw of that shape from its generator -- what `_wave_call` draws for the clip alone; with `seeds`
+        no noise tensor is filled.  launch returns None (the rows are io["out"]) or its own rows [B, Lrow].  -> list of waveforms, each
+        with the shape and on the device of its clip."""
+        dev = self._gpu()
+        clips = list(clips)
+        if not clips:
+            return []
+        lib = L.load()
+        h = self._sync_native()
+        flat, lens, Tp, Lrow = _ragged_bucket(clips, self.feature_extractor._cfg())
+        B = len(flat)
+        gens = _per_clip_generators(generator, noise, B)
+        with torch.cuda.device(dev):
+            if seeds is not None:
+                n_draws = 0
+            io = self._io_entry(B, Lrow, dev, n_draws, seeded=seeds is not None, ragged=True)
+            io["y"].zero_()
+            for b, c in enumerate(flat):
+                io["y"][b, :lens[b]].copy_(c)
+                if n_draws:
+                    shape = (n_draws, 1, 1) + tuple(io["noise"].shape[3:])
+                    z = noise[b].to(dev, torch.complex64).reshape(shape) if noise is not None else \
+                        torch.randn(shape, dtype=torch.complex64, device=dev, generator=gens[b])
+                    io["noise"][:, b:b + 1].copy_(z)
+            io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
+            if seeds is not None:
+                io["seeds"].copy_(fd_noise.seeds_to_tensor(list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev))
+            ws = self._enhance_workspace(lib, h, B, Lrow, dev)
+            with self._on_side_stream(dev) as cur:
+                rows = launch(lib, h, io, B, Lrow, ws)
+                rows = io["out"] if rows is None else rows
+                outs = [rows[b, :lens[b]].clone() for b in range(B)]
+        res = []
+        for b, c in enumerate(clips):
+            outs[b].record_stream(cur)
+            res.append(outs[b].reshape(c.shape).to(c.device))
+        return res
+
+
+# ------------------------------------------------------------------------------------------------
+# FlowModel
+# ------------------------------------------------------------------------------------------------
+class FlowModel(_WaveModel):
+    """Drop-in for flowdec.model.FlowModel on the inference path (model.py:391-536).
+
+    Extensions over the reference signature: ``enhance(..., noise=None, generator=None)`` to inject /
+    seed the initial Gaussian noise (the reference draws it from the global device RNG, model.py:512),
+    ``seed=`` (the library's own counter-based noise, generated on the GPU from one 64-bit seed per clip: an int -- clip b
+    uses ``flowdec_amd.noise.clip_seed(seed, b)`` --, B ints or an int64 / uint64 tensor [B]; no noise tensor is filled),
+    and ``use_graph`` (hipGraph replay of the whole solve).  ``with_grad=True`` is not supported.
+    """
+
+    def __init__(self, backbone: NCSNpp, feature_extractor: AmplitudeCompressedComplexSTFT, sampling_rate: int,
+                 sigma_x=0.0, sigma_y=0.66, flow_matcher=None, lr: float = 1e-4, normalize_mode: str = "noisy", **kwargs):
+        super().__init__(backbone, feature_extractor, sampling_rate, lr=lr, normalize_mode=normalize_mode)
+        self.flow_matcher = flow_matcher
+        if callable(sigma_x) and not isinstance(sigma_x, torch.Tensor):   # model.py:408-413: kept as given; only `valid_loss` reads sigma_x, and refuses it
+            self.sigma_x = sigma_x
+        else:
+            self.sigma_x = nn.Parameter(sigma_x if isinstance(sigma_x, torch.Tensor) else torch.tensor(float(sigma_x)), requires_grad=False)
+        self.error_weighting = kwargs.get("error_weighting")
+        self.sigma_y = nn.Parameter(sigma_y if isinstance(sigma_y, torch.Tensor) else torch.tensor(float(sigma_y)), requires_grad=False)
 
     def forward(self, xt, y, t):
         if t.ndim == 0:
@@ -676,20 +822,7 @@ class FlowModel(nn.Module):
         self._sync_native()
         return self.backbone(xt, y, t)
 
-    def _set_seeds(self, io, seed, B, dev):
-        """The clips' seeds in a buffer that lives as long as `io`: a captured graph is keyed on its address."""
-        if "seeds" not in io:
-            io["seeds"] = torch.empty(B, dtype=torch.int64, device=dev)
-        io["seeds"].copy_(fd_noise.seeds_to_tensor(seed, B, dev))
-        return io["seeds"]
-
-    def _get_noise_tensor(self, shape, dev, noise, generator):
-        if noise is not None:
-            return noise.to(dev, torch.complex64).reshape(shape)
-        return torch.randn(shape, dtype=torch.complex64, device=dev, generator=generator)
-
     @torch.no_grad()
-    @_serialized
     def enhance(self, y, return_preprocess_info: bool = False, N: int = 50, solver: str = "euler", with_grad: bool = False,
                 sigma_fac: float = 1.0, return_traj: bool = False, noise=None, generator=None, use_graph: bool = True, seed=None,
                 step_control: Optional[str] = None, **kwargs):
@@ -708,62 +841,25 @@ class FlowModel(nn.Module):
         if not adaptive and solver not in L.SOLVERS:
             raise ValueError(f"unknown solver {solver!r}; supported: {sorted(L.SOLVERS) + sorted(L.ADAPTIVE_SOLVERS)}")
         per_clip = _check_step_control(step_control, solver, "enhance")
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
-        orig_device = y.device
-        squeeze_dims = 0
-        y3 = y
-        while y3.ndim < 3:  # model.py:146-149
-            y3 = y3.unsqueeze(0); squeeze_dims += 1
-        if y3.ndim != 3 or y3.shape[1] != 1:
-            raise RuntimeError(f"enhance expects [L], [1, L] or [B, 1, L] waveforms (got {tuple(y.shape)})")
-        lib = L.load()
-        h = self._sync_native()
-        cfg = self.feature_extractor._cfg()
-        B, Lw = y3.shape[0], y3.shape[-1]
-        F = cfg["n_fft"] // 2 + 1
-        T = lib.fd_num_frames(Lw, cfg["hop"]); Tp = lib.fd_padded_frames(T)
-        with torch.cuda.device(dev):
-            io = self._io_buffers(B, Lw, Tp, F, dev)
-            io["y"].copy_(y3.reshape(B, Lw))
-            seeds = None
-            if seed is None:
-                io["noise"].copy_(self._get_noise_tensor((B, 1, F, Tp), dev, noise, generator))
-            elif adaptive and not per_clip:   # the batch-global driver only needs the initial plane: filled by the library, then the unseeded call
-                io["noise"].copy_(fd_noise.noise_fill(fd_noise.seeds_to_tensor(seed, B, dev), F, Tp)[0])
+        atol, rtol = float(kwargs.get("atol", ADAPTIVE_DEFAULT_TOL)), float(kwargs.get("rtol", ADAPTIVE_DEFAULT_TOL))
+
+        def launch(lib, h, io, B, Lw, ws):
+            z, seeds = (io["noise"], None) if seed is None else (None, io["seeds"])
+            if adaptive:
+                if seeds is not None and not per_clip:   # the batch-global driver only needs the initial plane: filled by the library, then the unseeded call
+                    z, seeds = fd_noise.noise_fill(seeds, *self._frames(Lw)[::2]), None
+                return self._enhance_adaptive(lib, h, io["y"], z, seeds, B, Lw, N, sigma_fac, return_traj, atol, rtol, L.ADAPTIVE_SOLVERS[solver], per_clip)
+            if return_traj:
+                return self._enhance_traj(lib, h, io["y"], z, seeds, B, Lw, N, solver, sigma_fac)
+            if seeds is not None:
+                L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), None, L.ptr(seeds), float(sigma_fac), int(N),
+                                              L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
             else:
-                seeds = self._set_seeds(io, seed, B, dev)
-            # stream capture is illegal on the legacy default stream: run the solve on a side stream that is
-            # ordered after / before the caller's current stream
-            cur = torch.cuda.current_stream(dev)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                if adaptive:
-                    res = self._enhance_adaptive(lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev,
-                                                 float(kwargs.get("atol", ADAPTIVE_DEFAULT_TOL)), float(kwargs.get("rtol", ADAPTIVE_DEFAULT_TOL)), L.ADAPTIVE_SOLVERS[solver],
-                                                 per_clip=per_clip, seeds=seeds)
-                else:
-                    res = self._enhance_native(lib, h, cfg, io, B, Lw, F, T, Tp, N, solver, sigma_fac, return_traj,
-                                               return_preprocess_info, squeeze_dims, use_graph, dev, seeds)
-            cur.wait_stream(side)
-        if return_traj:
-            res[0].record_stream(cur)
-            for w in res[1]:
-                w.record_stream(cur)
-            return res
-        x_hat, info = res
-        x_hat.record_stream(cur)
-        for _ in range(squeeze_dims):
-            x_hat = x_hat.squeeze(0)
-        x_hat = x_hat.to(orig_device)
-        return (x_hat, info) if return_preprocess_info else x_hat
+                L.check(lib.fd_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(z)), float(sigma_fac), int(N),
+                                       L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        return self._wave_call(y, 1, noise, generator, launch, return_preprocess_info, seed=seed, return_traj=return_traj)
 
     @torch.no_grad()
-    @_serialized
     def enhance_batch(self, clips, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, noise=None, generator=None,
                       use_graph: bool = True, seeds=None, step_control: Optional[str] = None, atol: float = ADAPTIVE_DEFAULT_TOL,
                       rtol: float = ADAPTIVE_DEFAULT_TOL):
@@ -789,58 +885,21 @@ class FlowModel(nn.Module):
         if solver not in L.SOLVERS and solver not in L.ADAPTIVE_SOLVERS:
             raise ValueError(f"enhance_batch: unknown solver {solver!r}; supported: {sorted(L.SOLVERS) + sorted(L.ADAPTIVE_SOLVERS)}")
         per_clip = _check_step_control(step_control, solver, "enhance_batch")
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
         clips = list(clips)
-        if not clips:
-            return []
-        lib = L.load()
-        h = self._sync_native()
-        cfg = self.feature_extractor._cfg()
-        F = cfg["n_fft"] // 2 + 1
-        flat, lens, Tp, Lrow = _ragged_bucket(clips, cfg)
-        B = len(flat)
-        gens = _per_clip_generators(generator, noise, B)
-        with torch.cuda.device(dev):
-            io = self._io_buffers(B, Lrow, Tp, F, dev)
-            if "lens" not in io:
-                io["lens"] = torch.empty(B, dtype=torch.int32, device=dev)
-            io["y"].zero_()
-            for b, c in enumerate(flat):
-                io["y"][b, :lens[b]].copy_(c)
-                if seeds is None:
-                    io["noise"][b:b + 1].copy_(self._get_noise_tensor((1, 1, F, Tp), dev, None if noise is None else noise[b], gens[b]))
-            io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
-            seeds_dev = None if seeds is None else self._set_seeds(io, list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev)
-            cur = torch.cuda.current_stream(dev)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                if per_clip:   # ragged STFT -> per-clip adaptive solve -> ragged iSTFT
-                    x_hat, _ = self._enhance_adaptive(lib, h, cfg, io, B, Lrow, F, lib.fd_num_frames(Lrow, cfg["hop"]), Tp, N, sigma_fac, False, 0, dev,
-                                                      float(atol), float(rtol), L.ADAPTIVE_SOLVERS[solver], per_clip=True, seeds=seeds_dev, lengths=lens)
-                    outs = [x_hat[b, 0, :lens[b]].clone() for b in range(B)]
-                else:
-                    need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
-                    if need == 0:
-                        raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-                    ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
-                    if seeds_dev is not None:
-                        L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(seeds_dev), float(sigma_fac), int(N),
-                                                      L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-                    else:
-                        L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                                                      L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-                    outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
-            cur.wait_stream(side)
-        res = []
-        for b, c in enumerate(clips):
-            outs[b].record_stream(cur)
-            res.append(outs[b].reshape(c.shape).to(c.device))
-        return res
+
+        def launch(lib, h, io, B, Lrow, ws):
+            z, sd = (io["noise"], None) if seeds is None else (None, io["seeds"])
+            if per_clip:   # ragged STFT -> per-clip adaptive solve -> ragged iSTFT
+                x_hat, _ = self._enhance_adaptive(lib, h, io["y"], z, sd, B, Lrow, N, sigma_fac, False, float(atol), float(rtol), L.ADAPTIVE_SOLVERS[solver],
+                                                  True, lengths=[int(c.numel()) for c in clips])
+                return x_hat.reshape(B, Lrow)
+            if sd is not None:
+                L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(sd), float(sigma_fac), int(N),
+                                              L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+            else:
+                L.check(lib.fd_enhance_ragged(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(torch.view_as_real(z)), float(sigma_fac), int(N),
+                                              L.SOLVERS[solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        return self._ragged_call(clips, 1, noise, generator, seeds, launch)
 
     def valid_loss(self, x, y, *, seed=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, comp_eps=None):
         """FlowModel._loss (model.py:421-468) on clean x / coded y of one length, without gradients: the `valid_loss` of validation_step.
@@ -856,7 +915,8 @@ class FlowModel(nn.Module):
 
     def _long_buffers(self, B, Lrow, dev):
         """The device arrays of `enhance_long`'s native calls.  They live as long as the shape does: a captured graph is keyed on their
-        addresses, so every group of rows of every file of that shape replays one graph."""
+        addresses, so every group of rows of every file of that shape replays one graph.  Not an entry of `_io`: a caller that alternates
+        `enhance` and `enhance_long` keeps both shapes, and both graphs, resident."""
         key = (B, Lrow, str(dev))
         if getattr(self, "_io_long_key", None) != key:
             self._io_long = dict(y=torch.zeros(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
@@ -947,14 +1007,8 @@ class FlowModel(nn.Module):
             raise ValueError(f"enhance_long: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
         if int(rows_per_call) < 1:
             raise ValueError(f"enhance_long: rows_per_call must be >= 1 (got {rows_per_call})")
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
-        y3 = y
-        while y3.ndim < 3:
-            y3 = y3.unsqueeze(0)
-        if y3.ndim != 3 or y3.shape[1] != 1:
-            raise RuntimeError(f"enhance_long expects [L], [1, L] or [C, 1, L] waveforms (got {tuple(y.shape)})")
+        dev = self._gpu()
+        y3, _ = _to_3d(y, "enhance_long expects", rows="C")
         lib = L.load()
         cfg = self.feature_extractor._cfg()
         hop = cfg["hop"]
@@ -984,21 +1038,14 @@ class FlowModel(nn.Module):
 
     @contextlib.contextmanager
     def _long_stream(self, plan, upload: bool = True):
-        """The side stream the long-form native calls run on, ordered after / before the caller's current stream.  -> (lib, handle, the
-        recording [C, n] on the device, or None without `upload`)."""
+        """The long-form native calls run on the side stream, after the upload of the recording.  -> (lib, handle, the recording [C, n] on
+        the device, or None without `upload`)."""
         lib = L.load()
         h = self._sync_native()
-        dev = plan.dev
-        with torch.cuda.device(dev):
-            y_dev = plan.y3.reshape(plan.C, plan.n).to(dev, torch.float32).contiguous() if upload else None
-            cur = torch.cuda.current_stream(dev)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+        with torch.cuda.device(plan.dev):
+            y_dev = plan.y3.reshape(plan.C, plan.n).to(plan.dev, torch.float32).contiguous() if upload else None
+            with self._on_side_stream(plan.dev):
                 yield lib, h, y_dev
-            cur.wait_stream(side)
 
     def _long_run_jobs(self, lib, h, plan, y_dev, jobs, N, solver, sigma_fac, rows_per_call, use_graph):
         """`jobs` (a slice of plan.jobs) through fd_enhance_chunks in balanced groups of at most `rows_per_call` -> [len(jobs), Lrow]."""
@@ -1021,10 +1068,7 @@ class FlowModel(nn.Module):
             file_normfac = file_normfac.reshape(-1)
         elif normalize:
             file_normfac = plan.normfac.to(dev)
-        need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
-        if need == 0:
-            raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-        ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
+        ws = self._enhance_workspace(lib, h, B, Lrow, dev)
         for g0 in range(0, len(jobs), B):
             group = jobs[g0:g0 + B]
             group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
@@ -1057,26 +1101,28 @@ class FlowModel(nn.Module):
                                          xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
         return x_hat
 
-    def _enhance_adaptive(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, sigma_fac, return_traj, squeeze_dims, dev, atol, rtol, method=0,
-                          per_clip=False, seeds=None, lengths=None):
-        """solver='dopri5' / 'tsit5': adaptive 5(4) pair over t_span = linspace(0, 1, N+1) (torchdyn semantics restated, unpinned);
-        host-driven (one read-back per attempted step), so no hipGraph.  The realised NFE is left in `self.last_nfe`.
-        per_clip: every clip under its own controller (fd_ode_solve_adaptive_clips); then `seeds` (device int64 [B]) replaces
-        io["noise"], and `lengths` makes the batch ragged (rows of Lw samples, clip b = the first lengths[b])."""
+    def _enhance_adaptive(self, lib, h, y_rows, noise, seeds, B, Lw, N, sigma_fac, return_traj, atol, rtol, method, per_clip, lengths=None):
+        """solver='dopri5' / 'tsit5' on the staged rows y_rows [B, Lw]: adaptive 5(4) pair over t_span = linspace(0, 1, N+1) (torchdyn
+        semantics restated, unpinned); host-driven (one read-back per attempted step), so no hipGraph.  The realised NFE is left in
+        `self.last_nfe`.  per_clip: every clip under its own controller (fd_ode_solve_adaptive_clips); then `seeds` (device int64 [B])
+        may replace `noise` ([1, B, 1, F, Tp]), and `lengths` makes the batch ragged (clip b = the first lengths[b] samples of its row).
+        -> (x_hat [B, 1, Lw], normfac [B]), or with return_traj (the trajectory, its waveforms)."""
         from . import ops
-        Y, normfac, _ = ops.stft_compress(io["y"], normalize=self.normalize_mode == "noisy", lengths=lengths, **cfg)
+        cfg, dev = self.feature_extractor._cfg(), y_rows.device
+        F, T, Tp = self._frames(Lw)
+        Y, normfac, _ = ops.stft_compress(y_rows, normalize=self.normalize_mode == "noisy", lengths=lengths, **cfg)
         traj = torch.empty(N + 1, B, 1, F, Tp, dtype=torch.complex64, device=dev) if return_traj else None
         X = torch.empty_like(Y)
         traj_ptr = L.ptr(torch.view_as_real(traj)) if return_traj else None
+        noise_ptr = None if seeds is not None else L.ptr(torch.view_as_real(noise))
         if per_clip:
             need = lib.fd_ode_adaptive_clips_workspace_bytes(h, B, Tp)
             if need == 0:
                 raise RuntimeError(f"flowdec_hip: step_control='clip' takes at most 256 clips of a valid shape per call (got B={B}, T_pad={Tp})")
             ws = self.backbone.workspace(("ode", B, Tp), need, dev)
             nfe, rej, evals = (C.c_int * B)(), (C.c_int * B)(), C.c_int(0)
-            L.check(lib.fd_ode_solve_adaptive_clips(h, L.ptr(torch.view_as_real(Y)), None if seeds is not None else L.ptr(torch.view_as_real(io["noise"])),
-                                                    L.ptr(seeds), float(sigma_fac), int(N), int(method), atol, rtol, L.ptr(torch.view_as_real(X)), traj_ptr,
-                                                    nfe, rej, C.byref(evals), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
+            L.check(lib.fd_ode_solve_adaptive_clips(h, L.ptr(torch.view_as_real(Y)), noise_ptr, L.ptr(seeds), float(sigma_fac), int(N), int(method), atol, rtol,
+                                                    L.ptr(torch.view_as_real(X)), traj_ptr, nfe, rej, C.byref(evals), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
             self.last_nfe_per_clip = torch.tensor(list(nfe), dtype=torch.int64)
             self.last_rejected_per_clip = torch.tensor(list(rej), dtype=torch.int64)
             self.last_evals = int(evals.value)
@@ -1085,57 +1131,27 @@ class FlowModel(nn.Module):
             need = lib.fd_ode_adaptive_workspace_bytes(h, B, Tp)
             ws = self.backbone.workspace(("ode", B, Tp), need, dev)
             nfe = C.c_int(0)
-            L.check(lib.fd_ode_solve_adaptive_method(h, L.ptr(torch.view_as_real(Y)), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N), int(method),
+            L.check(lib.fd_ode_solve_adaptive_method(h, L.ptr(torch.view_as_real(Y)), noise_ptr, float(sigma_fac), int(N), int(method),
                                                      atol, rtol, L.ptr(torch.view_as_real(X)), traj_ptr, C.byref(nfe), B, Tp, L.ptr(ws), ws.numel(), L.stream()))
             self.last_nfe = int(nfe.value)
         if return_traj:
-            x_hats = []
-            for i in range(N + 1):
-                xh = ops.decompress_istft(traj[i], T, Lw, normfac, lengths=lengths, **cfg).reshape(B, 1, Lw)
-                for _ in range(squeeze_dims):
-                    xh = xh.squeeze(0)
-                x_hats.append(xh)
-            return traj, x_hats
-        x_hat = ops.decompress_istft(X, T, Lw, normfac, lengths=lengths, **cfg).reshape(B, 1, Lw)
-        info = dict(orig_length=Lw, normfac=normfac.reshape(B, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
-        return x_hat, info
+            return traj, _traj_waveforms(traj, T, Lw, normfac, cfg, lengths)
+        return ops.decompress_istft(X, T, Lw, normfac, lengths=lengths, **cfg).reshape(B, 1, Lw), normfac
 
-    def _enhance_native(self, lib, h, cfg, io, B, Lw, F, T, Tp, N, solver, sigma_fac, return_traj, return_preprocess_info,
-                        squeeze_dims, use_graph, dev, seeds=None):
-        """Fixed-step solve; `seeds` (device int64 [B]) selects the seeded entry points, which never read io["noise"]."""
-        if return_traj:   # every solver state is needed: front end, solver and back end as separate native calls
-            from . import ops
-            Y, normfac, _ = ops.stft_compress(io["y"], normalize=self.normalize_mode == "noisy", **cfg)
-            traj = torch.empty(N + 1, B, 1, F, Tp, dtype=torch.complex64, device=dev)
-            X = torch.empty_like(Y)
-            need = lib.fd_model_workspace_bytes(h, B, Tp)
-            ws = self.backbone.workspace(("ode", B, Tp), need, dev)
-            solve, src = (lib.fd_ode_solve, torch.view_as_real(io["noise"])) if seeds is None else (lib.fd_ode_solve_seeded, seeds)
-            L.check(solve(h, L.ptr(torch.view_as_real(Y)), L.ptr(src), float(sigma_fac), int(N),
-                          L.SOLVERS[solver], L.ptr(torch.view_as_real(X)), L.ptr(torch.view_as_real(traj)), B, Tp,
-                          L.ptr(ws), ws.numel(), 0, L.stream()))
-            x_hats = []
-            for i in range(N + 1):
-                xh = ops.decompress_istft(traj[i], T, Lw, normfac, **cfg).reshape(B, 1, Lw)
-                for _ in range(squeeze_dims):
-                    xh = xh.squeeze(0)
-                x_hats.append(xh)
-            return traj, x_hats
-        need = lib.fd_enhance_workspace_bytes(h, B, Lw)
-        if need == 0:
-            raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-        ws = self.backbone.workspace(("enh", B, Lw), need, dev)
-        if seeds is not None:
-            L.check(lib.fd_enhance_seeded(h, L.ptr(io["y"]), None, L.ptr(seeds), float(sigma_fac), int(N),
-                                          L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-        else:
-            L.check(lib.fd_enhance(h, L.ptr(io["y"]), L.ptr(torch.view_as_real(io["noise"])), float(sigma_fac), int(N),
-                                   L.SOLVERS[solver], L.ptr(io["out"]), B, Lw, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-        x_hat = io["out"].reshape(B, 1, Lw).clone()
-        info = None
-        if return_preprocess_info:
-            info = _info_from_ws(lib, h, ws, B, Lw, T, squeeze_dims)
-        return x_hat, info
+    def _enhance_traj(self, lib, h, y_rows, noise, seeds, B, Lw, N, solver, sigma_fac):
+        """A fixed-step solve that keeps every solver state: front end, solver and back end as separate native calls; `seeds` (device int64
+        [B]) selects the seeded solver, which reads no noise.  -> (the trajectory, its waveforms)."""
+        from . import ops
+        cfg, dev = self.feature_extractor._cfg(), y_rows.device
+        F, T, Tp = self._frames(Lw)
+        Y, normfac, _ = ops.stft_compress(y_rows, normalize=self.normalize_mode == "noisy", **cfg)
+        traj = torch.empty(N + 1, B, 1, F, Tp, dtype=torch.complex64, device=dev)
+        X = torch.empty_like(Y)
+        ws = self.backbone.workspace(("ode", B, Tp), lib.fd_model_workspace_bytes(h, B, Tp), dev)
+        solve, src = (lib.fd_ode_solve, torch.view_as_real(noise)) if seeds is None else (lib.fd_ode_solve_seeded, seeds)
+        L.check(solve(h, L.ptr(torch.view_as_real(Y)), L.ptr(src), float(sigma_fac), int(N), L.SOLVERS[solver], L.ptr(torch.view_as_real(X)),
+                      L.ptr(torch.view_as_real(traj)), B, Tp, L.ptr(ws), ws.numel(), 0, L.stream()))
+        return traj, _traj_waveforms(traj, T, Lw, normfac, cfg)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1165,156 +1181,6 @@ class OUVESDE:
 
     def marginal_prob(self, x0, t, y):
         return self._mean(x0, t, y), self._std(t)
-
-
-class _WaveModel(nn.Module):
-    """Shared waveform plumbing of the baselines (EnhancementModel._preprocess/_postprocess, model.py:129-190)."""
-    strict_loading = False
-
-    def __init__(self, backbone: NCSNpp, feature_extractor: AmplitudeCompressedComplexSTFT, sampling_rate: int = 48000,
-                 lr: float = 1e-4, normalize_mode: str = "noisy", **kwargs):
-        super().__init__()
-        assert normalize_mode in ("noisy", "none")
-        self.sampling_rate, self.normalize_mode, self.lr = sampling_rate, normalize_mode, lr
-        self.backbone, self.feature_extractor = backbone, feature_extractor
-        self._io, self._side_stream = {}, None
-
-    def _preprocess(self, y, x=None, comp_eps=None):
-        return _preprocess(self, y, x, comp_eps)
-
-    def _postprocess(self, X_hat, preprocess_info, inv_kwargs=None, batch_filter=None):
-        return _postprocess(self, X_hat, preprocess_info, inv_kwargs, batch_filter)
-
-    @property
-    def device(self):
-        return next(self.backbone.parameters()).device
-
-    def load_state_dict(self, state_dict, strict: bool = False, **kw):
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    def _sync_native(self):
-        self.backbone._sigma_y = None
-        self.backbone._stft_cfg = self.feature_extractor._cfg()
-        self.backbone._normalize = self.normalize_mode == "noisy"
-        return self.backbone.handle()
-
-    @_serialized
-    def _wave_call(self, y, n_draws, noise, generator, launch, return_preprocess_info=False, seed=None):
-        """launch(lib, h, io, B, L, ws) on a capture-safe side stream; io = dict(y [B, L], out [B, L], noise [n_draws, B, 1, F, Tp] | None,
-        seeds int64 [B] | None).  With `seed` no noise tensor exists (io["noise"] is None): the kernels generate it."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
-        orig_device, squeeze_dims, y3 = y.device, 0, y
-        while y3.ndim < 3:
-            y3 = y3.unsqueeze(0); squeeze_dims += 1
-        if y3.ndim != 3 or y3.shape[1] != 1:
-            raise RuntimeError(f"enhance expects [L], [1, L] or [B, 1, L] waveforms (got {tuple(y.shape)})")
-        lib = L.load()
-        h = self._sync_native()
-        cfg = self.feature_extractor._cfg()
-        B, Lw = y3.shape[0], y3.shape[-1]
-        F = cfg["n_fft"] // 2 + 1
-        Tp = lib.fd_padded_frames(lib.fd_num_frames(Lw, cfg["hop"]))
-        with torch.cuda.device(dev):
-            if seed is not None:
-                n_draws = 0
-            key = (B, Lw, n_draws, seed is not None, str(dev))
-            io = self._io.get(key)
-            if io is None:
-                io = dict(y=torch.empty(B, Lw, dtype=torch.float32, device=dev), out=torch.empty(B, Lw, dtype=torch.float32, device=dev),
-                          noise=torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev) if n_draws else None,
-                          seeds=torch.empty(B, dtype=torch.int64, device=dev) if seed is not None else None)
-                self._io = {key: io}
-            io["y"].copy_(y3.reshape(B, Lw))
-            if seed is not None:
-                io["seeds"].copy_(fd_noise.seeds_to_tensor(seed, B, dev))
-            if n_draws:
-                if noise is not None:
-                    io["noise"].copy_(noise.to(dev, torch.complex64).reshape(io["noise"].shape))
-                else:
-                    io["noise"].copy_(torch.randn(io["noise"].shape, dtype=torch.complex64, device=dev, generator=generator))
-            need = lib.fd_enhance_workspace_bytes(h, B, Lw)
-            if need == 0:
-                raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-            ws = self.backbone.workspace(("enh", B, Lw), need, dev)
-            cur = torch.cuda.current_stream(dev)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                launch(lib, h, io, B, Lw, ws)
-                x_hat = io["out"].reshape(B, 1, Lw).clone()
-                info = _info_from_ws(lib, h, ws, B, Lw, lib.fd_num_frames(Lw, cfg["hop"]), squeeze_dims) if return_preprocess_info else None
-            cur.wait_stream(side)
-        x_hat.record_stream(cur)
-        for _ in range(squeeze_dims):
-            x_hat = x_hat.squeeze(0)
-        x_hat = x_hat.to(orig_device)
-        return (x_hat, info) if return_preprocess_info else x_hat
-
-
-    @_serialized
-    def _ragged_call(self, clips, n_draws, noise, generator, seeds, launch):
-        """The staging of `enhance_batch`: clips of ONE T_pad bucket as zero-padded rows of a [B, hop * T_pad - 1] buffer, then
-        launch(lib, h, io, B, Lrow, ws) on a capture-safe side stream; io = dict(y, out [B, Lrow], lens int32 [B], noise [n_draws, B, 1, F,
-        Tp] | None, seeds int64 [B] | None).  Clip b's planes are noise[b] ([n_draws, 1, 1, F, Tp]) or one draw of that shape from its
-        generator -- what `_wave_call` draws for the clip alone; with `seeds` no noise tensor exists.  -> list of waveforms, each with the
-        shape and on the device of its clip."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
-        clips = list(clips)
-        if not clips:
-            return []
-        lib = L.load()
-        h = self._sync_native()
-        cfg = self.feature_extractor._cfg()
-        F = cfg["n_fft"] // 2 + 1
-        flat, lens, Tp, Lrow = _ragged_bucket(clips, cfg)
-        B = len(flat)
-        gens = _per_clip_generators(generator, noise, B)
-        with torch.cuda.device(dev):
-            if seeds is not None:
-                n_draws = 0
-            key = ("ragged", B, Lrow, n_draws, seeds is not None, str(dev))
-            io = self._io.get(key)
-            if io is None:
-                io = dict(y=torch.empty(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
-                          lens=torch.empty(B, dtype=torch.int32, device=dev),
-                          noise=torch.empty(n_draws, B, 1, F, Tp, dtype=torch.complex64, device=dev) if n_draws else None,
-                          seeds=torch.empty(B, dtype=torch.int64, device=dev) if seeds is not None else None)
-                self._io = {key: io}
-            io["y"].zero_()
-            for b, c in enumerate(flat):
-                io["y"][b, :lens[b]].copy_(c)
-                if n_draws:
-                    shape = (n_draws, 1, 1, F, Tp)
-                    z = noise[b].to(dev, torch.complex64).reshape(shape) if noise is not None else \
-                        torch.randn(shape, dtype=torch.complex64, device=dev, generator=gens[b])
-                    io["noise"][:, b:b + 1].copy_(z)
-            io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
-            if seeds is not None:
-                io["seeds"].copy_(fd_noise.seeds_to_tensor(list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev))
-            need = lib.fd_enhance_workspace_bytes(h, B, Lrow)
-            if need == 0:
-                raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
-            ws = self.backbone.workspace(("enh", B, Lrow), need, dev)
-            cur = torch.cuda.current_stream(dev)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                launch(lib, h, io, B, Lrow, ws)
-                outs = [io["out"][b, :lens[b]].clone() for b in range(B)]
-            cur.wait_stream(side)
-        res = []
-        for b, c in enumerate(clips):
-            outs[b].record_stream(cur)
-            res.append(outs[b].reshape(c.shape).to(c.device))
-        return res
 
 
 class ScoreModel(_WaveModel):
@@ -1413,14 +1279,9 @@ class ScoreModel(_WaveModel):
         twice per evaluation) -- it exists for API parity with ScoreModel.enhance."""
         from scipy import integrate
         from . import ops
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
-        orig_device, squeeze_dims, y3 = y.device, 0, y
-        while y3.ndim < 3:
-            y3 = y3.unsqueeze(0); squeeze_dims += 1
-        if y3.ndim != 3 or y3.shape[1] != 1:
-            raise RuntimeError(f"enhance expects [L], [1, L] or [B, 1, L] waveforms (got {tuple(y.shape)})")
+        dev = self._gpu()
+        orig_device = y.device
+        y3, squeeze_dims = _to_3d(y, "enhance expects")
         N = self.sde.N if N is None else int(N)
         t_eps = float(self.t_eps if eps is None else eps)
         lib = L.load()
@@ -1457,8 +1318,7 @@ class ScoreModel(_WaveModel):
             x_hat = x_hat.squeeze(0)
         x_hat = x_hat.to(orig_device)
         if return_preprocess_info:
-            info = dict(orig_length=Lw, normfac=normfac.reshape(B, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
-            return x_hat, info
+            return x_hat, _preprocess_info(Lw, normfac, T, squeeze_dims)
         return (x_hat, int(sol.nfev)) if return_nfe else x_hat
 
 

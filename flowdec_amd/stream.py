@@ -16,8 +16,8 @@ row's compute time.  Device memory per session: a ring of S + W input samples an
 Normalisation cannot be the recording's maximum (it is not known yet): `normfac` is a fixed float, or "causal" -- a row is scaled by the
 peak of everything up to its end, `enhance_long(..., normfac="causal")`.  A normalize_mode='none' model takes normfac=None.
 """
+import contextlib
 import ctypes as C
-from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
@@ -175,7 +175,7 @@ class StreamPool:
     @torch.no_grad()
     @_serialized
     def _step(self) -> Dict[int, torch.Tensor]:
-        with self._side() as (_, h, _y):
+        with self._side() as h:
             ready = []
             for s in self._sessions.values():
                 if s.planner.ready():
@@ -205,7 +205,7 @@ class StreamPool:
         ss = [self._session(sid) for sid in dict.fromkeys(sids)]
         outs = {s.sid: [] for s in ss}
         try:
-            with self._side() as (_, h, _y):
+            with self._side() as h:
                 while True:                                      # the regular rows that are still ready
                     ready = []
                     for s in ss:
@@ -240,9 +240,12 @@ class StreamPool:
         self._free.append(s.slot)
 
     # -- the native step ----------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
     def _side(self):
-        """The model's side stream, ordered after / before the caller's current stream (FlowModel._long_stream)."""
-        return self.model._long_stream(SimpleNamespace(dev=self.dev), upload=False)
+        """The model's side stream, ordered after / before the caller's current stream.  -> the model's native handle."""
+        h = self.model._sync_native()
+        with torch.cuda.device(self.dev), self.model._on_side_stream(self.dev):
+            yield h
 
     def _hand_over(self, outs):
         cur = torch.cuda.current_stream(self.dev)

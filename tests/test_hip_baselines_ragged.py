@@ -177,6 +177,80 @@ def test_native_ragged_calls_zero_the_tail_and_equal_the_plain_calls():
         assert torch.isfinite(want).all() and want.abs().max() > 0 and torch.equal(got, want), f"{kind}: ragged with equal lengths != the plain call"
 
 
+def test_normfac_slot_of_the_enhance_workspace():
+    """The workspace layout Y | X | normfac[B] | rest from outside: fd_enhance_normfac_offset is two 256-byte-aligned complex64 states
+    [B][F][T_pad], and after fd_enhance the four bytes per clip found there are the clips' maxima as ops.stft_compress takes them."""
+    from flowdec_amd import _lib as L, ops
+    from test_hip_noise import _flow
+    lib = L.load()
+    m = _flow(8, "bf16")
+    h = m._sync_native()
+    B, Lw = 2, 12000
+    fd_align = lambda n: (n + 255) // 256 * 256
+    off = lib.fd_enhance_normfac_offset(h, B, Lw)
+    assert off == 2 * fd_align(8 * B * F * TP)
+    need = lib.fd_enhance_workspace_bytes(h, B, Lw)
+    assert need > off + 4 * B
+    y = _rows(clips_of([Lw, Lw], 6), Lw)
+    nz = torch.view_as_real(torch.randn(B, 1, F, TP, dtype=torch.complex64, device="cuda")).contiguous()
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    out = torch.full((B, Lw), float("nan"), device="cuda")
+    L.check(lib.fd_enhance(h, L.ptr(y), L.ptr(nz), 1.0, 2, L.SOLVERS["euler"], L.ptr(out), B, Lw, L.ptr(ws), ws.numel(), 0, L.stream()))
+    _, normfac, _ = ops.stft_compress(y, normalize=True, **m.feature_extractor._cfg())
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all() and normfac.shape == (B,) and normfac[0] != normfac[1] and normfac.min() > 0
+    assert torch.equal(ws[off:off + 4 * B].view(torch.float32), normfac)
+
+
+@pytest.mark.parametrize("kind", ["flow", "score", "regression"])
+def test_one_resident_staging_entry(kind):
+    """The staging buffers of the three classes (`model._io`: one resident shape): a seeded call allocates no noise plane, a repeated call
+    finds every buffer where it was (a captured graph is keyed on the addresses), seeded and unseeded calls of one shape share y and out,
+    and a ragged batch leaves one entry behind."""
+    from test_hip_noise import _flow
+    m = _flow(8, "bf16") if kind == "flow" else baseline(kind, "bf16")
+    kw = {"flow": dict(N=2, solver="euler"), "score": dict(N=2), "regression": {}}[kind]
+    random = kind != "regression"
+    y = torch.stack(clips_of([12000, 12000], 7))[:, None]
+
+    def ptrs():
+        assert len(m._io) == 1
+        io = m._io[next(iter(m._io))]
+        return {k: None if io[k] is None else io[k].data_ptr() for k in ("y", "out", "seeds", "noise")}
+
+    # -- a seeded call: seeds, and no noise plane; the repeat finds the same addresses
+    m._io = {}
+    sd = dict(seed=[21, 22]) if random else {}
+    s0 = m.enhance(y, **sd, **kw)
+    p = ptrs()
+    assert p["noise"] is None and (p["seeds"] is not None) == random and p["y"] is not None and p["out"] is not None
+    assert torch.equal(m.enhance(y, **sd, **kw), s0) and ptrs() == p
+    if random:
+        # -- unseeded, then seeded, then unseeded again at one shape: y, out (and the seeds, once they exist) stay in place; the seeded
+        # call lets the noise plane go
+        m._io = {}
+        gen = lambda: torch.Generator(device="cuda").manual_seed(3)
+        u0 = m.enhance(y, generator=gen(), **kw)
+        p = ptrs()
+        assert p["noise"] is not None and p["seeds"] is None
+        assert torch.equal(m.enhance(y, generator=gen(), **kw), u0) and ptrs() == p          # the second sighting of the key: captured
+        s1 = m.enhance(y, **sd, **kw)
+        q = ptrs()
+        assert q["noise"] is None and q["seeds"] is not None and (q["y"], q["out"]) == (p["y"], p["out"])
+        u1 = m.enhance(y, generator=gen(), **kw)
+        r = ptrs()
+        assert r["noise"] is not None and (r["y"], r["out"], r["seeds"]) == (q["y"], q["out"], q["seeds"])
+        assert torch.equal(u1, u0) and torch.equal(s1, s0) and not torch.equal(u0, s0)
+        assert torch.equal(u0, m.enhance(y, generator=gen(), use_graph=False, **kw)) and ptrs() == r
+        assert torch.equal(s1, m.enhance(y, use_graph=False, **sd, **kw))
+    # -- a ragged batch of one T_pad = 64 bucket: one resident shape (rows, row length), every clip equal to its one-clip call
+    clips = clips_of([12000, 20000], 8)
+    outs = m.enhance_batch(clips, **(dict(seeds=[31, 32]) if random else {}), **kw)
+    ptrs()
+    assert next(iter(m._io))[:2] == (2, HOP * TP - 1)
+    assert_all_equal(outs, [m.enhance(c, **(dict(seed=[s]) if random else {}), **kw) for c, s in zip(clips, [31, 32])], kind)
+
+
 def test_enhance_batch_errors():
     s, r = baseline("score", "bf16"), baseline("regression", "bf16")
     clips = clips_of(LENS_A, 1)

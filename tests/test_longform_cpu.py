@@ -156,6 +156,41 @@ def test_symbols_and_python_surface():
     assert lib.fd_enhance_chunks(None, None, None, None, None, None, 1.0, 2, 0, None, 1, 30000, None, 0, 0, None) == -1
 
 
+def test_one_staging_base_and_the_enhance_signatures():
+    """FlowModel, ScoreModel and RegressionModel stage their waveforms through ONE base class, and the parameters (names, order, defaults)
+    of their `enhance` / `enhance_batch` are the literal ones below."""
+    import inspect
+    import torch
+    import flowdec_amd
+    from flowdec_amd import model as M
+    classes = (flowdec_amd.FlowModel, flowdec_amd.ScoreModel, flowdec_amd.RegressionModel)
+    assert all(c.__bases__ == (M._WaveModel,) for c in classes) and M._WaveModel.__bases__ == (torch.nn.Module,)
+    for name in ("_wave_call", "_ragged_call", "_io_entry", "_on_side_stream", "_sync_native", "_preprocess", "_postprocess", "device", "load_state_dict"):
+        assert all(name not in vars(c) for c in classes), name                       # owned by the base, overridden nowhere
+    assert not hasattr(flowdec_amd.ScoreModel, "enhance_long") and not hasattr(flowdec_amd.RegressionModel, "enhance_long")
+    E, VK = inspect.Parameter.empty, "**"
+    want = {
+        ("FlowModel", "enhance"): [("self", E), ("y", E), ("return_preprocess_info", False), ("N", 50), ("solver", "euler"), ("with_grad", False),
+                                   ("sigma_fac", 1.0), ("return_traj", False), ("noise", None), ("generator", None), ("use_graph", True), ("seed", None),
+                                   ("step_control", None), ("kwargs", VK)],
+        ("FlowModel", "enhance_batch"): [("self", E), ("clips", E), ("N", 50), ("solver", "euler"), ("sigma_fac", 1.0), ("noise", None), ("generator", None),
+                                         ("use_graph", True), ("seeds", None), ("step_control", None), ("atol", 0.001), ("rtol", 0.001)],
+        ("ScoreModel", "enhance"): [("self", E), ("y", E), ("sampler_type", "pc"), ("predictor", "reverse_diffusion"), ("corrector", "ald"), ("N", 30),
+                                    ("corrector_steps", 1), ("snr", 0.5), ("return_preprocess_info", False), ("denoise", True), ("noise", None),
+                                    ("generator", None), ("use_graph", True), ("seed", None), ("kwargs", VK)],
+        ("ScoreModel", "enhance_batch"): [("self", E), ("clips", E), ("predictor", "reverse_diffusion"), ("corrector", "ald"), ("N", 30), ("corrector_steps", 1),
+                                          ("snr", 0.5), ("denoise", True), ("noise", None), ("generator", None), ("seeds", None), ("use_graph", True),
+                                          ("kwargs", VK)],
+        ("RegressionModel", "enhance"): [("self", E), ("y", E), ("return_preprocess_info", False), ("use_graph", True), ("kwargs", VK)],
+        ("RegressionModel", "enhance_batch"): [("self", E), ("clips", E), ("use_graph", True)],
+    }
+    for c in classes:
+        for fn in ("enhance", "enhance_batch"):
+            got = [(k, VK if p.kind is p.VAR_KEYWORD else p.default) for k, p in inspect.signature(getattr(c, fn)).parameters.items()]
+            assert got == want[c.__name__, fn], (c.__name__, fn, got)
+            assert all(p.kind in (p.POSITIONAL_OR_KEYWORD, p.VAR_KEYWORD) for p in inspect.signature(getattr(c, fn)).parameters.values())
+
+
 def test_cli_argument_errors(tmp_path, capsys):
     from flowdec_amd import enhance_cli
     from test_cli_baselines_cpu import SDE, T_EPS, ckpt_of
