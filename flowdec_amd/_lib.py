@@ -212,6 +212,12 @@ SIGNATURES = {
     "fd_resample_out_length": (c_ll, [c_ll, c_int, c_int]),
     "fd_resample": (c_int, [_P, _P, _P, c_int, c_int, _P, c_ll, _P]),
     "fd_resample_span": (c_int, [_P, _P, c_ll, c_ll, c_ll, c_ll, c_ll, _P, _P]),
+    "fd_estoi_plan_create": (c_int, [C.POINTER(_P)]),
+    "fd_estoi_plan_destroy": (None, [_P]),
+    "fd_metrics_estoi_workspace_bytes": (c_size_t, [c_int] * 4),
+    "fd_metrics_estoi_max_frames": (c_int, [c_int] * 3),
+    "fd_metrics_estoi": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "fd_metrics_estoi_bands": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -79,6 +79,8 @@ size_t fd_stft_ws_bytes(int B, int L, int n_fft, int hop);
 void fd_stft_plan_dims(const fd_stft_plan* p, int* n_fft, int* hop, int* n_freq, int* kpad);
 int fd_stft_kpad(int n_fft);
 int fd_stft_raw_spectrum(fd_stft_plan* p, const float* y, const int* lens, int B, int L, float* frames, float* spec, hipStream_t st);
+// resample.hip, for stoi.hip: the plan's rates and bank geometry (any pointer may be null)
+void fd_resample_plan_dims(const fd_resample_plan* p, int* o, int* n, int* width, int* K);
 // ndac_mfma.hip: the codec's wide convolutions on the matrix cores (split-bf16 operands, f32 tolerance)
 bool fd_ndac_mfma_supported(int Ci, int Co, int K, int stride, int dil, int transposed);
 // (fd_ndac_mfma_packed_bytes: public, include/flowdec_hip.h)

@@ -178,6 +178,13 @@ extern "C" int fd_resample_plan_create(const float* bank_host, int o, int n, int
   return FD_OK;
 }
 
+void fd_resample_plan_dims(const fd_resample_plan* p, int* o, int* n, int* width, int* K) {
+  if (o) *o = p->o;
+  if (n) *n = p->n;
+  if (width) *width = p->width;
+  if (K) *K = p->K;
+}
+
 extern "C" void fd_resample_plan_destroy(fd_resample_plan* p) {
   if (!p) return;
   (void)hipFree(p->bank);

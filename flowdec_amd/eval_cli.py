@@ -1,8 +1,8 @@
 """Scores a triples list on the GPU: the enhance -> evaluate loop of the reference (enhance.py:142 writes `triples_list.txt`,
-flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for the two of its metrics that need no outside model.
+flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for those of its metrics that need no outside model or program.
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
-                                   [--sr 48000]
+                                   [--sr 48000] [--estoi]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -18,8 +18,15 @@ A triple whose signals still differ in length after cropping gets NaN in all fou
 its exception handler); so does the spectral column of a triple too short for the transform's reflect padding.  A triple with a file that
 cannot be read is skipped and counted, and the exit status is then 3 (enhance_cli's status of a partly done run), else 0.
 
-The reference's other metrics (PESQ, ESTOI, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside packages or models: out of
-scope.
+--estoi (off by default; without it every byte of the output is what it was) adds a last CSV column `estoi` and a fifth summary line: the
+reference's ESTOI (eval/metrics.py:273-283, pystoi.stoi(extended=True)) of x_hat against x, resampled to 10 kHz and scored on the GPU in the
+same ragged batches (csrc/stoi.hip; flowdec_amd/metrics.py estoi_batch, host yardstick estoi).  A triple that leaves fewer than 30 spectral
+frames after the silent frames are removed gets pystoi's value 1e-05 and a warning naming the rule.  pystoi itself is not available to the
+tests: the host function is pinned against SciPy's resampler and the published algorithm, parity with the package is UNPINNED
+(scripts/pin_estoi.py prints it where pystoi is importable).
+
+The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
+(DESIGN section 9).
 """
 import argparse
 import csv
@@ -37,6 +44,7 @@ from .enhance_cli import resample as host_resample
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
+ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), always the last column
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -105,9 +113,11 @@ def min_spectral_samples(sr: int) -> int:
 
 @dataclass(frozen=True)
 class Scorer:
-    """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]."""
+    """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]; estoi(x_hats, xs, sr,
+    batch) -> [n] (optional: only --estoi calls it)."""
     si_sxr: Callable
     logspec: Callable
+    estoi: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -130,20 +140,31 @@ def _host_logspec(x_hats, xs, sr, batch):
     return np.array([metrics.logspec_mse(h, x, sr=sr, win_dur=WIN_DUR, hop_dur=HOP_DUR) for h, x in zip(x_hats, xs)], np.float64)
 
 
-GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec)        # ragged batches on the device (csrc/metrics.hip)
-HOST_SCORER = Scorer(_host_si_sxr, _host_logspec)     # the host functions of metrics.py, one triple at a time: the yardstick
+def _gpu_estoi(x_hats, xs, sr, batch):
+    from . import metrics
+    return metrics.estoi_batch(x_hats, xs, sr=sr, batch=batch)
 
 
-def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None) -> np.ndarray:
+def _host_estoi(x_hats, xs, sr, batch):
+    from . import metrics
+    return np.array([metrics.estoi(h, x, sr) for h, x in zip(x_hats, xs)], np.float64)
+
+
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi)        # ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip)
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi)    # the host functions of metrics.py, one triple at a time: the yardstick
+
+
+def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None, estoi: bool = False) -> np.ndarray:
     """signals: one (x_hat, x, y) of 1-D tensors per triple, cropped -> [n, 4] float64 in METRIC_NAMES order, row i for triple i whatever
-    order the batches ran in.  Unequal lengths: NaN in all four; too short for the transform: NaN in the spectral column."""
+    order the batches ran in.  Unequal lengths: NaN in all four; too short for the transform: NaN in the spectral column.
+    estoi=True: [n, 5], the last column ESTOI (1e-5 and a warning under the 30-frame rule; NaN with the others for unequal lengths)."""
     def warn(i, msg):
         print(f"warning: {names[i] if names else 'triple %d' % i}: {msg}", file=sys.stderr)
 
     def column(idx, k):
         return [signals[i][k] for i in idx]
 
-    out = np.full((len(signals), 4), np.nan, np.float64)
+    out = np.full((len(signals), 5 if estoi else 4), np.nan, np.float64)
     ok = []
     for i, (h, x, y) in enumerate(signals):
         if not (h.shape[-1] == x.shape[-1] == y.shape[-1]):
@@ -160,6 +181,14 @@ def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Opti
         out[ok, :3] = scorer.si_sxr(column(ok, 0), column(ok, 1), column(ok, 2), batch)
     if spectral:
         out[spectral, 3] = scorer.logspec(column(spectral, 0), column(spectral, 1), sr, batch)
+    if estoi and ok:
+        from . import metrics
+        if scorer.estoi is None:
+            raise ValueError("score: estoi=True needs a Scorer with an estoi function")
+        out[ok, 4] = scorer.estoi(column(ok, 0), column(ok, 1), sr, batch)
+        for i in ok:
+            if out[i, 4] == metrics.ESTOI_TOO_SHORT:
+                warn(i, metrics.ESTOI_SHORT_RULE)
     return out
 
 
@@ -170,15 +199,15 @@ def fmt(v: float) -> str:
 def write_csv(path: str, triples: List[Triple], values: np.ndarray) -> None:
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER)
+        w.writerow(CSV_HEADER + ((ESTOI_NAME,) if values.shape[1] == len(METRIC_NAMES) + 1 else ()))
         for t, row in zip(triples, values):
             w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row])
 
 
 def summary(values: np.ndarray):
-    """-> [(metric, mean over its finite rows or NaN, count of finite rows)]."""
+    """-> [(metric, mean over its finite rows or NaN, count of finite rows)]; five entries for the [n, 5] values of --estoi."""
     out = []
-    for k, name in enumerate(METRIC_NAMES):
+    for k, name in enumerate(METRIC_NAMES + ((ESTOI_NAME,) if values.ndim == 2 and values.shape[1] == len(METRIC_NAMES) + 1 else ())):
         col = values[:, k] if len(values) else np.zeros(0)
         fin = col[np.isfinite(col)]
         out.append((name, float(fin.mean()) if len(fin) else float("nan"), int(len(fin))))
@@ -207,6 +236,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--crop-to-x-hat", action="store_true", help="then cut x and y to the length of x_hat (eval/metrics.py:88-90)")
     p.add_argument("--sr", type=int, default=48000, help="the rate every file is brought to (the reference evaluates at 48 kHz)")
     p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
+    p.add_argument("--estoi", action="store_true",
+                   help="also score ESTOI (pystoi.stoi(extended=True) restated; 10 kHz, on the GPU): a last CSV column `estoi` and a fifth mean")
     return p
 
 
@@ -224,7 +255,7 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
             continue
         kept.append(t)
         signals.append(crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat))
-    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept])
+    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept], estoi=args.estoi)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     write_csv(args.out, kept, values)
     res.n_scored, res.means = len(kept), summary(values)

@@ -9,6 +9,10 @@ to express build-vs-reference differences in the units the paper reports.  Host-
 
 The two of them also run on the GPU over ragged batches (csrc/metrics.hip, include/flowdec_hip.h "Evaluation metrics"): si_sxr_batch and
 logspec_mse_batch below, which score a triples list in flowdec_amd/eval_cli.py.  The host functions stay the yardstick of those.
+
+* estoi       -- extended STOI (eval/metrics.py:273-283: pystoi.stoi(x, x_hat, sr, extended=True)), restated from the published
+                 algorithm at the end of this file, with estoi_batch on the GPU (csrc/stoi.hip).  The resampler is pinned against
+                 scipy.signal.resample_poly; parity with the pystoi package is unpinned (absent offline: scripts/pin_estoi.py).
 """
 import numpy as np
 import torch
@@ -150,3 +154,229 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
             L.check(lib.fd_metrics_logspec_mse(plan, L.ptr(h), L.ptr(x), L.ptr(lens), B, Lmax, float(eps), L.ptr(mse), L.ptr(ws), nws, L.stream()))
             out[idx] = mse.cpu().numpy()
     return out
+
+
+# ---- ESTOI: the extended short-time objective intelligibility measure ------------------------------------------------------------------
+# The reference's ESTOI (eval/metrics.py:273-283) is pystoi.stoi(x, x_hat, sr, extended=True).  pystoi is not in this image, so its
+# published arithmetic (Jensen & Taal 2016; pystoi/stoi.py, pystoi/utils.py) is restated here in NumPy float64 -- the yardstick of the
+# kernels in csrc/stoi.hip -- and parity with the package itself is UNPINNED (scripts/pin_estoi.py prints it where pystoi is importable).
+# What is pinned: the resampling bank against scipy.signal.resample_poly, the band edges and the frame arithmetic (tests/test_estoi_cpu.py).
+#   1. resample to 10 kHz when sr differs (pystoi.utils.resample_oct): p = 10000 / g, q = sr / g, fc = 1 / (2 max(p, q)),
+#      L = ceil(52 / (28.714 fc / 10)), h = 2 p fc sinc(2 fc t) kaiser(2 L + 1, 0.1102 (60 - 8.7)) over t = -L..L, w = h / sum(h);
+#      output m = sum_j x[j] p w[q m - p j + L], ceil(p len / q) outputs
+#   2. frames of 256 at hop 128 from range(0, len - 256, 128), window hanning(258)[1:-1]; e_t = 20 log10(||win x_t|| + eps); frame t is
+#      kept iff max e - 40 - e_t < 0 (from x alone); the kept windowed frames of both signals are overlap-added at hop 128
+#   3. the same framing of the compacted signals (k kept frames -> k - 1 spectral frames), windowed again, rfft(512), 15 third-octave
+#      bands from 150 Hz: sqrt of the sum of |X|^2 over [lo_i, hi_i)
+#   4. fewer than 30 spectral frames: 1e-5 (pystoi's value, with its warning)
+#   5. every block of 30 consecutive frames x 15 bands of either signal: rows centred and divided by their 2-norm, then columns;
+#      estoi = sum(x_n y_n) / 30 / segments
+# The one deliberate deviation: pystoi adds eps * randn before each normalisation (an effect below 1e-12); it is left out, and a row or
+# column whose sum of squares is exactly 0 normalises to zeros (pystoi: a random unit vector, expected contribution 0).
+ESTOI_FS, ESTOI_FRAME, ESTOI_HOP, ESTOI_NFFT, ESTOI_NBANDS, ESTOI_SEG, ESTOI_DYN_DB = 10000, 256, 128, 512, 15, 30, 40.0
+ESTOI_TOO_SHORT = 1e-5
+ESTOI_EPS = float(np.finfo(float).eps)
+ESTOI_SHORT_RULE = (f"fewer than {ESTOI_SEG} spectral frames are left at 10 kHz after the silent frames are removed "
+                    f"(frames of {ESTOI_FRAME} at hop {ESTOI_HOP}): ESTOI is {ESTOI_TOO_SHORT:g} by pystoi's rule")
+
+
+def estoi_band_edges():
+    """-> [(lo, hi)] * 15: the rfft bins [lo, hi) of the third-octave bands (pystoi.utils.thirdoct(10000, 512, 15, 150))."""
+    f = np.linspace(0, ESTOI_FS, ESTOI_NFFT + 1)[:ESTOI_NFFT // 2 + 1]
+    k = np.arange(ESTOI_NBANDS, dtype=np.float64)
+    lo, hi = 150.0 * np.power(2.0, (2 * k - 1) / 6), 150.0 * np.power(2.0, (2 * k + 1) / 6)
+    return [(int(np.argmin(np.square(f - a))), int(np.argmin(np.square(f - b)))) for a, b in zip(lo, hi)]
+
+
+def estoi_filter(sr: int):
+    """-> (w float64 [2 L + 1], p, q, L): the normalised Kaiser-windowed sinc of pystoi.utils.resample_oct for sr -> 10 kHz."""
+    import math
+    sr = int(sr)
+    if sr < 1:
+        raise ValueError(f"estoi: the rate must be positive (got {sr})")
+    g = math.gcd(ESTOI_FS, sr)
+    p, q = ESTOI_FS // g, sr // g
+    fc = 1.0 / (2 * max(p, q))
+    L = int(math.ceil(52.0 / (28.714 * fc / 10)))
+    t = np.arange(-L, L + 1, dtype=np.float64)
+    h = 2 * p * fc * np.sinc(2 * fc * t) * np.kaiser(2 * L + 1, 0.1102 * (60 - 8.7))
+    return h / np.sum(h), p, q, L
+
+
+def _estoi_bank64(sr: int):
+    w, p, q, L = estoi_filter(sr)
+    o, n = q, p
+    width = -(-L // p)
+    K = 2 * width + o
+    idx = o * np.arange(n)[:, None] - n * (np.arange(K)[None, :] - width) + L
+    ok = (idx >= 0) & (idx <= 2 * L)
+    return np.where(ok, p * w[np.clip(idx, 0, 2 * L)], 0.0), o, n, width
+
+
+def estoi_bank(sr: int):
+    """-> (bank float32 [n][K], o, n, width): pystoi's resampling filter for sr -> 10 kHz as the polyphase bank of fd_resample_plan_create
+    (K = 2 width + o; bank[i][k] = p w[o i - n (k - width) + L] inside the filter, else 0), computed in float64 and rounded once."""
+    bank, o, n, width = _estoi_bank64(sr)
+    return np.ascontiguousarray(bank.astype(np.float32)), o, n, width
+
+
+def polyphase_resample(x: np.ndarray, bank: np.ndarray, o: int, n: int, width: int) -> np.ndarray:
+    """fd_resample's documented loop on the host: output q n + i = sum_k bank[i][k] x[q o + k - width] (zero outside the signal), float64
+    sums, ceil(n len / o) outputs."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    K = bank.shape[1]
+    M = -(-n * len(x) // o)
+    Q = max(-(-M // n), 1)
+    xp = np.zeros(max((Q - 1) * o + K, width + len(x)), np.float64)
+    xp[width:width + len(x)] = x
+    win = np.lib.stride_tricks.sliding_window_view(xp, K)[::o][:Q]
+    return (win @ np.asarray(bank, np.float64).T).reshape(-1)[:M]
+
+
+def _estoi_frames(sig: np.ndarray) -> np.ndarray:
+    """[T, 256] frames from range(0, len - 256, 128) (a view): the frame that would end exactly at len is not taken (pystoi's loop)."""
+    starts = np.arange(0, len(sig) - ESTOI_FRAME, ESTOI_HOP)
+    if len(starts) == 0:
+        return np.zeros((0, ESTOI_FRAME), np.float64)
+    return np.lib.stride_tricks.sliding_window_view(sig, ESTOI_FRAME)[starts]
+
+
+def _unit_rows(a: np.ndarray, axis: int) -> np.ndarray:
+    a = a - a.mean(axis=axis, keepdims=True)
+    nrm = np.sqrt(np.sum(a * a, axis=axis, keepdims=True))
+    return np.divide(a, nrm, out=np.zeros_like(a), where=nrm > 0)
+
+
+def estoi_detail(x_hat, x, sr: int, precision: str = "float64", keep_spectra: bool = False) -> dict:
+    """ESTOI with its intermediate results: value, too_short, frames / kept (source frame of every kept frame) / spectral_frames,
+    margin_db (the least distance of a frame's energy from the 40 dB threshold), tob_x / tob_x_hat ([T, 15] band magnitudes or None).
+    precision='float32' rounds to float32 where the kernels of csrc/stoi.hip round (the resampled signals -- through the float32 bank --,
+    |X|^2 and the band magnitudes): it measures what those roundings move, it is not a second yardstick.
+    keep_spectra adds spec_x / spec_x_hat ([T, 257] complex rfft of the doubly windowed frames) and abs1_x / abs1_x_hat ([T], the sum of
+    |samples| of every such frame): what an error bound of a float32 transform needs."""
+    if precision not in ("float64", "float32"):
+        raise ValueError(f"estoi: precision is 'float64' or 'float32' (got {precision!r})")
+    f32 = precision == "float32"
+    x, y = (np.asarray(_flat(a), dtype=np.float64) for a in (x, x_hat))
+    if len(x) != len(y):
+        raise ValueError(f"estoi: the signals differ in length (x_hat {len(y)}, x {len(x)})")
+    if int(sr) != ESTOI_FS:
+        if f32:
+            bank, o, n, width = estoi_bank(sr)
+            x, y = (polyphase_resample(a.astype(np.float32), bank, o, n, width).astype(np.float32).astype(np.float64) for a in (x, y))
+        else:
+            bank, o, n, width = _estoi_bank64(sr)
+            x, y = (polyphase_resample(a, bank, o, n, width) for a in (x, y))
+    win = np.hanning(ESTOI_FRAME + 2)[1:-1]
+    out = dict(value=ESTOI_TOO_SHORT, too_short=True, frames=0, kept=np.zeros(0, np.int64), spectral_frames=0, margin_db=float("inf"), tob_x=None,
+               tob_x_hat=None)
+    xf, yf = _estoi_frames(x) * win, _estoi_frames(y) * win
+    out["frames"] = len(xf)
+    if len(xf) == 0:
+        return out
+    e = 20 * np.log10(np.linalg.norm(xf, axis=1) + ESTOI_EPS)
+    gap = np.max(e) - ESTOI_DYN_DB - e
+    kept = np.nonzero(gap < 0)[0]
+    k = len(kept)
+    out.update(kept=kept, spectral_frames=max(k - 1, 0), margin_db=float(np.min(np.abs(gap))))
+    if k < 2:
+        return out
+
+    def bands(fr):
+        sig = np.zeros((k + 1) * ESTOI_HOP, np.float64)                   # overlap-add of the kept frames: (k - 1) 128 + 256 samples
+        sig[:k * ESTOI_HOP].reshape(k, ESTOI_HOP)[:] += fr[kept, :ESTOI_HOP]
+        sig[ESTOI_HOP:].reshape(k, ESTOI_HOP)[:] += fr[kept, ESTOI_HOP:]
+        z = _estoi_frames(sig) * win
+        X = np.fft.rfft(z, n=ESTOI_NFFT, axis=1)
+        P = np.abs(X) ** 2
+        if f32:
+            P = P.astype(np.float32).astype(np.float64)
+        tob = np.sqrt(np.stack([P[:, lo:hi].sum(axis=1) for lo, hi in estoi_band_edges()], axis=1))
+        return (tob.astype(np.float32).astype(np.float64) if f32 else tob), X, np.abs(z).sum(axis=1)
+
+    (tx, Xx, ax), (ty, Xy, ay) = bands(xf), bands(yf)
+    out.update(tob_x=tx, tob_x_hat=ty)
+    if keep_spectra:
+        out.update(spec_x=Xx, spec_x_hat=Xy, abs1_x=ax, abs1_x_hat=ay)
+    T = len(tx)
+    if T < ESTOI_SEG:
+        return out
+
+    def segments(tob):                                                      # [J, 15, 30], rows then columns normalised
+        s = np.lib.stride_tricks.sliding_window_view(tob, ESTOI_SEG, axis=0)
+        return _unit_rows(_unit_rows(s, 2), 1)
+
+    xn, yn = segments(tx), segments(ty)
+    out.update(value=float(np.sum(xn * yn / ESTOI_SEG) / xn.shape[0]), too_short=False)
+    return out
+
+
+def estoi(x_hat, x, sr: int, precision: str = "float64") -> float:
+    """ESTOI of estimate x_hat against clean x at rate sr (the algorithm above; float64, NumPy only).  1e-5 under the 30-frame rule."""
+    return estoi_detail(x_hat, x, sr, precision)["value"]
+
+
+_ESTOI_PLANS = {}
+
+
+class _EstoiPlans:
+    """The device tables of fd_metrics_estoi and the 10 kHz resample plan of one rate (None at 10 kHz), created on first use."""
+
+    def __init__(self, sr):
+        import ctypes as C
+        from . import _lib as L
+        lib = L.load()
+        self.estoi, self.resample, self.o, self.n = C.c_void_p(), None, 1, 1
+        if int(sr) != ESTOI_FS:
+            bank, o, n, width = estoi_bank(sr)
+            if n * bank.shape[1] > (1 << 24):
+                raise ValueError(f"estoi: the 10 kHz filter bank of {sr} Hz has {n} x {bank.shape[1]} coefficients, over the device resampler's cap")
+            self.resample, self.o, self.n = C.c_void_p(), o, n
+            L.check(lib.fd_resample_plan_create(bank.ctypes.data_as(C.c_void_p), o, n, width, C.byref(self.resample)))
+        L.check(lib.fd_estoi_plan_create(C.byref(self.estoi)))
+
+    def __del__(self):
+        try:
+            from . import _lib as L
+            if getattr(self, "resample", None):
+                L.load().fd_resample_plan_destroy(self.resample)
+            if getattr(self, "estoi", None):
+                L.load().fd_estoi_plan_destroy(self.estoi)
+        except Exception:
+            pass
+
+
+def estoi_plans(sr: int, device="cuda") -> _EstoiPlans:
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (int(sr), str(dev))
+    if key not in _ESTOI_PLANS:
+        with torch.cuda.device(dev):
+            _ESTOI_PLANS[key] = _EstoiPlans(sr)
+    return _ESTOI_PLANS[key]
+
+
+def estoi_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", return_frames: bool = False):
+    """estoi of every (x_hat, x) on the GPU -> [n] float64 (with return_frames also [n, 3] int32: frames, kept, spectral frames; fewer than
+    30 spectral frames: 1e-5).  Length-sorted ragged batches of `batch` clips; the plans are cached per (sr, device)."""
+    from . import _lib as L
+    lib = L.load()
+    x_hats, xs = _as_clips(x_hats, xs)
+    lengths = [int(c.numel()) for c in xs]
+    out, frames = np.zeros(len(xs), np.float64), np.zeros((len(xs), 3), np.int32)
+    plans = estoi_plans(sr, device)
+    with torch.cuda.device(device):
+        for idx in length_sorted_batches(lengths, batch):
+            h, x = (_rows(l, idx, device) for l in (x_hats, xs))
+            lens = torch.tensor([lengths[i] for i in idx], dtype=torch.int32, device=device)
+            B, Lmax = x.shape
+            nws = lib.fd_metrics_estoi_workspace_bytes(B, Lmax, plans.o, plans.n)
+            ws = torch.empty(nws, dtype=torch.uint8, device=device)
+            val = torch.empty(B, dtype=torch.float64, device=device)
+            fr = torch.empty(B, 3, dtype=torch.int32, device=device)
+            L.check(lib.fd_metrics_estoi(plans.estoi, plans.resample, L.ptr(h), L.ptr(x), L.ptr(lens), B, Lmax, L.ptr(val), L.ptr(fr), L.ptr(ws), nws,
+                                         L.stream()))
+            out[idx] = val.cpu().numpy()
+            frames[idx] = fr.cpu().numpy()
+    return (out, frames) if return_frames else out

@@ -855,6 +855,48 @@ int fd_resample(const fd_resample_plan* plan, const float* x, const int* lengths
 int fd_resample_span(const fd_resample_plan* plan, const float* x, long long x0, long long nx, long long total, long long m0, long long count,
                      float* y, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * ESTOI: the extended short-time objective intelligibility measure (Jensen & Taal 2016) of estimate x_hat against clean x, the metric
+ * the reference computes as pystoi.stoi(x, x_hat, sr, extended=True) (flowdec/eval/metrics.py:273-283), over ragged batches
+ * (csrc/stoi.hip; host yardstick and the algorithm in full: flowdec_amd/metrics.py estoi).  Rows [B][L] float32 on the device; lengths:
+ * DEVICE int32 [B], clamped into [0, L]; samples behind a clip's end are never read.  The calls are asynchronous on `stream`, allocate
+ * nothing and launch nothing when they refuse: a NULL pointer, a bad shape (1 <= B <= 65535, L >= 1, the resampled row at most 2^30
+ * samples) and a workspace that is too small are FD_EINVAL with a message.  A clip's results have the SAME BITS alone, in a batch, at
+ * any batch position and next to clips of any other lengths: every partition and order of summation depends on the clip's own length
+ * only; no atomics.  Parity with the pystoi package itself is UNPINNED (the package is not available to the tests; scripts/pin_estoi.py
+ * prints the comparison where it is); what is pinned is the host function, and this against it.
+ *
+ *   1. both signals to 10 kHz with the caller's resample plan (the pystoi bank: flowdec_amd.metrics.estoi_bank), fd_resample's
+ *      arithmetic, rounded to float32; resample = NULL: the rows are at 10 kHz already
+ *   2. frames of 256 samples at hop 128 starting below len - 256, window w = hanning(258)[1:-1]; frame t of x is kept iff
+ *      (||w x_t|| + eps) > (max_t ||w x_t|| + eps) 10^-2 (40 dB), norms in float64, eps = 2^-52; the kept windowed frames of either signal
+ *      are overlap-added at hop 128 in order (never stored: a gather), k kept frames give k - 1 spectral frames
+ *   3. each spectral frame windowed again (formed in float64, rounded once to float32), the 512-point DFT bins 7..218 as an exact-float32
+ *      fma chain in ascending sample order on the matrix cores, re^2 + im^2 in float32; 15 third-octave bands (edges 7 9 11 14 17 22 27
+ *      34 43 55 69 87 109 138 174 219) summed in float64 in ascending bin order, square root, rounded to float32
+ *   4. fewer than 30 spectral frames: 1e-5 (pystoi's value).  Else every block of 30 consecutive frames x 15 bands of either signal is
+ *      normalised by row (mean over the frames removed, divided by the 2-norm) and then by column, in float64; a row or column whose sum
+ *      of squares is exactly 0 becomes zeros (pystoi adds eps-sized noise instead: the one deliberate deviation);
+ *      estoi = sum(x_n y_n) / 30 / segments.
+ *
+ * fd_estoi_plan_create: the window and the DFT table, uploaded synchronously; nothing on the call path allocates.
+ * fd_metrics_estoi_workspace_bytes(B, L, o, n): o, n = the resample plan's rates over their gcd (orig, 10000), o = n = 1 without a
+ *   resample plan; 0 for a bad argument.  fd_metrics_estoi_max_frames(L, o, n): T_max = max(1, frames of a clip of L samples).
+ * fd_metrics_estoi: estoi_out DEVICE double [B]; frames_out DEVICE int32 [B][3] = frames, kept frames, spectral frames.
+ * fd_metrics_estoi_bands (stage call, for tests): steps 1-3.  kept_out DEVICE int32 [B][T_max] = the source frame of every kept frame
+ *   in order, -1 behind the clip's own count; tob_out DEVICE float [B][2][T_max][15] = the band magnitudes of x ([b][0]) and x_hat
+ *   ([b][1]), zero behind the clip's own spectral frames.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fd_estoi_plan fd_estoi_plan;
+int fd_estoi_plan_create(fd_estoi_plan** out);
+void fd_estoi_plan_destroy(fd_estoi_plan* plan);
+size_t fd_metrics_estoi_workspace_bytes(int B, int L, int o, int n);
+int fd_metrics_estoi_max_frames(int L, int o, int n);
+int fd_metrics_estoi(const fd_estoi_plan* plan, const fd_resample_plan* resample, const float* x_hat, const float* x, const int* lengths, int B,
+                     int L, double* estoi_out, int* frames_out, void* ws, size_t ws_bytes, void* stream);
+int fd_metrics_estoi_bands(const fd_estoi_plan* plan, const fd_resample_plan* resample, const float* x_hat, const float* x, const int* lengths,
+                           int B, int L, int* frames_out, int* kept_out, float* tob_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
