@@ -121,7 +121,7 @@ class PowerSampler:
 def calibrate(device=0, repeats=5, iters=0):
     """`box_calibration` of a bench line: the fixed MFMA issue loop for ~0.25 s with clock / power sampled while it runs."""
     import torch
-    from . import _lib as L
+    from . import _lib as L     # lazy, like torch above: the power sampler of this module runs without either
     lib = L.load()
     dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
     with torch.cuda.device(dev):

@@ -16,9 +16,14 @@ The corpus path shards by WORK instead of by count: `sharded_enhance_batch` take
 batches, the batches spread over the ranks by `balance`), `sharded_enhance_long` the (channel, row) jobs of one long recording.  Both
 use the library's seeded noise only, and both return what one process returns, bit for bit, for every world size.
 """
+import time
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
+
+from .batching import plan_clip_batches
+from .model import RegressionModel
+from .noise import clip_seed
 
 
 def shard_range(n_items: int, rank: int, world: int) -> Tuple[int, int]:
@@ -122,7 +127,6 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
     y may live on the host (pinned or not): only this rank's rows are copied to the model's device, and the gathered result
     is copied back -- the "H2D of waveform -> D2H of waveform" path of SURVEY 8(d).  `stats`, if given, receives
     {"local_s", "gather_s"} host-clock seconds (it synchronises the device, use it for measurements only)."""
-    import time
     if y.ndim != 3 or y.shape[1] != 1:
         raise RuntimeError(f"sharded_enhance expects a batch [B, 1, L] (got {tuple(y.shape)})")
     if rng not in ("torch", "native"):
@@ -142,7 +146,6 @@ def sharded_enhance(model, y: torch.Tensor, N: int = 50, solver: str = "euler", 
         if seed is None:
             seed = _shared_seed(dev, group)   # (every rank, idle ones included, takes part in the broadcast)
         if hi > lo:
-            from .noise import clip_seed
             local = model.enhance(y[lo:hi].to(dev, non_blocking=True), N=N, solver=solver, seed=[clip_seed(seed, i) for i in range(lo, hi)],
                                   **enhance_kwargs)
     elif hi > lo:
@@ -231,17 +234,6 @@ def balance(costs: Sequence[float], world: int) -> List[List[int]]:
     return [sorted(p) for p in plan]
 
 
-def plan_clip_batches(lengths: Sequence[int], hop: int, batch_clips: int) -> List[Tuple[int, List[int]]]:
-    """Clips of `lengths` samples bucketed by the frame count their spectrogram pads to (`padded_frames_of`), buckets in ascending
-    T_pad, every bucket cut in clip order into batches of at most `batch_clips`.  -> [(T_pad, clip indices)], the same on every rank."""
-    from .model import padded_frames_of
-    batch_clips = max(int(batch_clips), 1)
-    buckets = {}
-    for i, n in enumerate(lengths):
-        buckets.setdefault(padded_frames_of(int(n), hop), []).append(i)
-    return [(tp, buckets[tp][k:k + batch_clips]) for tp in sorted(buckets) for k in range(0, len(buckets[tp]), batch_clips)]
-
-
 def sharded_enhance_batch(model, clips, group=None, batch_clips: int = 8, seed: Optional[int] = None, seeds=None, always_gather: bool = False,
                           stats: Optional[dict] = None, **enhance_kwargs) -> List[torch.Tensor]:
     """`[model.enhance(c, seed=[s_i], ...) for c in clips]` for a list of clips of ANY lengths ([L], [1, L] or [1, 1, L]), sharded over
@@ -262,9 +254,6 @@ def sharded_enhance_batch(model, clips, group=None, batch_clips: int = 8, seed: 
     Without a process group (world 1) the clips still run bucketed and batched; there is no collective unless `always_gather`.
     `stats`, if given, receives {"local_s", "gather_s"} like `sharded_enhance`, plus "plan" (every batch as a list of clip indices) and
     "mine" (the positions in the plan of the batches this rank ran)."""
-    import time
-    from .model import RegressionModel
-    from .noise import clip_seed
     for k in ("noise", "generator"):
         if enhance_kwargs.get(k) is not None:
             raise ValueError(f"sharded_enhance_batch takes seed= / seeds= only, not {k}=: a generator's stream (and a noise list drawn from one) "

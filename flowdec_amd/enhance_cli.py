@@ -16,11 +16,11 @@ sampler (a FlowModel ignores the first three); `--solver` is the flow model's (t
 three classes run in ragged batches; the regression model draws no noise and ignores `--seed` / `--rng`.
 
 Checkpoints: a Lightning `.ckpt` (dict with `_pl_ema_state_dict` and/or `state_dict`, optionally `hyper_parameters`
-holding the resolved config: callbacks/ema.py:201-215, model.py:100,119) or a bare state_dict.  `--ema` (default)
-selects the EMA weights exactly like `demo.ipynb` cell 2.
+holding the resolved config: callbacks/ema.py:201-215, model.py:100,119) or a bare state_dict (flowdec_amd/checkpoint.py).  `--ema`
+(default) selects the EMA weights exactly like `demo.ipynb` cell 2.
 
 Non-48 kHz input is resampled with a restatement of torchaudio.functional.resample(..., lowpass_filter_width=64)
-(enhance.py:118; torchaudio itself is not a dependency): `sinc_resample_kernel` / `resample` below.
+(enhance.py:118; torchaudio itself is not a dependency): `sinc_resample_kernel` / `resample` of flowdec_amd/audio.py.
 
 Batching (round 6): the reference enhances one file per call (enhance.py:96-137).  This driver reads the lengths first, buckets the
 files by the frame count their spectrogram pads to (T_pad, util/other.py:25-52) and runs up to `--batch-files` files of a bucket as
@@ -72,23 +72,25 @@ import collections
 import contextlib
 import glob
 import json
-import math
 import os
 import re
 import subprocess
 import sys
 import threading
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
-import numpy as np
 import torch
 
-from . import longform
+from . import eval_cli, longform
+from .audio import (load_wav, read_list, resample, resample_to, resampled_length, save_wav, sinc_resample_kernel,  # noqa: F401
+                    wav_info)
+from .batching import padded_frames_of, plan_clip_batches
+from .checkpoint import load_from_checkpoint, model_from_checkpoint  # noqa: F401
+from .dist import balance
+from .model import FlowModel, RegressionModel, ScoreModel, WorkspaceTooLarge
 from .noise import clip_seed
-from .model import (BACKBONE_FINAL_NO_ATTN, OUVESDE, PRESETS, AmplitudeCompressedComplexSTFT, FlowModel, NCSNpp, RegressionModel, ScoreModel,
-                    WorkspaceTooLarge, from_preset)
 
 MAX_SECONDS = 30.0  # enhance.py:115
 SHARE_GPU_MAX_RANKS = 8   # --share-gpu: worker processes on the one GPU
@@ -99,250 +101,6 @@ PRECISION_NOTE = {   # printed at start-up so that a log says which arithmetic p
     "bf16x3": "f32 storage, split-bf16 operands (3 MFMAs per product): meets the fp32 tolerances (~3e-5)",
     "fp32": "exact f32 MFMA (~6e-6); slowest",
 }
-
-
-# ------------------------------------------------------------------------------------------------
-# file lists / wav I/O
-# ------------------------------------------------------------------------------------------------
-@dataclass
-class FileList:
-    """A parsed `--files` list: the inputs to enhance and, for pair lists, the clean reference each one belongs to."""
-    inputs: List[str] = field(default_factory=list)
-    clean: Optional[List[str]] = None     # None for a plain list
-
-    @property
-    def from_pairs(self) -> bool:
-        return self.clean is not None
-
-
-def _split_pair(entry: str) -> List[str]:
-    """`clean ---> coded` if the arrow is present, else `clean,coded` if a comma is (the reference's precedence, enhance.py:153-158:
-    a path with commas in an arrow line is not cut at the comma)."""
-    if " ---> " in entry:
-        return entry.split(" ---> ")
-    if "," in entry:
-        return entry.split(",")
-    return [entry]
-
-
-def read_list(listfile: str) -> FileList:
-    """The list formats of the reference (enhance.py:146-164): one path per line, or pair lines `clean ---> coded` /
-    `clean,coded` of which the SECOND entry is the file to enhance; further fields are ignored like there (the tool's own
-    `triples_list` output `clean ---> noisy ---> out` can be fed back in), with a warning.  A plain line after a pair line is an
-    error there (an assert); here it is a ValueError naming the line."""
-    out = FileList()
-    with open(listfile, "r") as f:
-        for lineno, raw in enumerate(f, 1):
-            entry = raw.strip()
-            if not entry:
-                continue
-            parts = _split_pair(entry)
-            if len(parts) > 2:
-                print(f"warning: {listfile}:{lineno}: {len(parts)} fields in a pair line, using the first two (clean, coded)", file=sys.stderr)
-            if len(parts) >= 2:
-                if out.clean is None:
-                    if out.inputs:
-                        raise ValueError(f"{listfile}:{lineno}: pair line after plain paths -- inconsistent file list format")
-                    out.clean = []
-                out.clean.append(parts[0]); out.inputs.append(parts[1])
-            elif out.from_pairs:
-                raise ValueError(f"{listfile}:{lineno}: plain path after pair lines -- inconsistent file list format")
-            else:
-                out.inputs.append(entry)
-    return out
-
-
-def load_wav(path: str) -> Tuple[torch.Tensor, int]:
-    """-> (float32 tensor [C, L] in [-1, 1], sampling rate), like torchaudio.load."""
-    from scipy.io import wavfile
-    sr, data = wavfile.read(path)
-    if data.dtype == np.int16:
-        x = data.astype(np.float32) / 32768.0
-    elif data.dtype == np.int32:
-        x = data.astype(np.float32) / 2147483648.0
-    elif data.dtype == np.uint8:
-        x = (data.astype(np.float32) - 128.0) / 128.0
-    else:
-        x = data.astype(np.float32)
-    if x.ndim == 1:
-        x = x[:, None]
-    return torch.from_numpy(np.ascontiguousarray(x.T)), int(sr)
-
-
-def wav_info(path: str) -> Tuple[int, int, int]:
-    """-> (samples per channel, sampling rate, channels) from the header only (memory-mapped: the data is not read)."""
-    from scipy.io import wavfile
-    sr, data = wavfile.read(path, mmap=True)
-    return int(data.shape[0]), int(sr), (1 if data.ndim == 1 else int(data.shape[1]))
-
-
-def resampled_length(length: int, sr: int, target: int) -> int:
-    """Samples `resample` returns for `length` input samples: ceil(n * L / o) with o, n = sr, target over their gcd."""
-    if int(sr) == int(target):
-        return int(length)
-    g = math.gcd(int(sr), int(target))
-    return int(math.ceil((int(target) // g) * length / (int(sr) // g)))
-
-
-def save_wav(path: str, x: torch.Tensor, sr: int) -> None:
-    """float32 wav, [C, L] or [L] (the reference saves float tensors through torchaudio.save)."""
-    from scipy.io import wavfile
-    a = x.detach().cpu().float().numpy()
-    if a.ndim == 2:
-        a = a.T
-    wavfile.write(path, sr, np.ascontiguousarray(a, dtype=np.float32))
-
-
-def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 64, rolloff: float = 0.99):
-    """The polyphase filter bank of torchaudio.functional.resample (resampling_method='sinc_interp_hann', the default), restated
-    from its published definition: with o = orig/gcd, n = new/gcd, f = min(o, n) * rolloff and width = ceil(lpw * o / f),
-    phase i in [0, n) and tap k in [-width, width + o):
-        t = clamp((k / o - i / n) * f, -lpw, lpw);   h[i, k] = sinc(t) * cos^2(pi * t / (2 * lpw)) * f / o      (sinc(t) = sin(pi t)/(pi t))
-    Returns (kernel [n, 2 * width + o] float32 computed in float64 like torchaudio, width, o, n)."""
-    g = math.gcd(int(orig_freq), int(new_freq))
-    o, n = int(orig_freq) // g, int(new_freq) // g
-    f = min(o, n) * rolloff
-    width = math.ceil(lowpass_filter_width * o / f)
-    k = np.arange(-width, width + o, dtype=np.float64)[None, :] / o
-    i = np.arange(0, -n, -1, dtype=np.float64)[:, None] / n
-    t = np.clip((i + k) * f, -lowpass_filter_width, lowpass_filter_width)
-    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
-    tp = t * math.pi
-    with np.errstate(invalid="ignore", divide="ignore"):
-        sinc = np.where(tp == 0, 1.0, np.sin(tp) / tp)
-    return (sinc * window * (f / o)).astype(np.float32), width, o, n
-
-
-def resample(y: torch.Tensor, sr: int, target: int, lowpass_filter_width: int = 64, rolloff: float = 0.99) -> torch.Tensor:
-    """torchaudio.functional.resample(y, sr, target, lowpass_filter_width=64) as the reference calls it (enhance.py:118):
-    zero-pad by (width, width + o), correlate with the n-phase filter bank at stride o, interleave the phases, keep
-    ceil(n * L / o) samples.  Host-side float32 (file pre-processing, not on the hot path)."""
-    if int(sr) == int(target):
-        return y
-    kern, width, o, n = sinc_resample_kernel(sr, target, lowpass_filter_width, rolloff)
-    shape = y.shape
-    w = y.reshape(-1, shape[-1]).float()
-    length = w.shape[-1]
-    w = torch.nn.functional.pad(w, (width, width + o))
-    r = torch.nn.functional.conv1d(w[:, None], torch.from_numpy(kern)[:, None], stride=o)       # [num, n, frames]
-    r = r.transpose(1, 2).reshape(w.shape[0], -1)[:, : int(math.ceil(n * length / o))]
-    return r.reshape(*shape[:-1], r.shape[-1])
-
-
-# ------------------------------------------------------------------------------------------------
-# checkpoint reader
-# ------------------------------------------------------------------------------------------------
-def _to_plain(obj):
-    """hyper_parameters of a real Lightning checkpoint are an OmegaConf DictConfig (the reference calls
-    save_hyperparameters(self.full_config), model.py:60-63), not a dict: convert any Mapping / sequence tree to plain
-    Python containers (OmegaConf.to_container when omegaconf is importable, so that interpolations are resolved)."""
-    from collections.abc import Mapping, Sequence
-    try:
-        from omegaconf import OmegaConf
-        if OmegaConf.is_config(obj):
-            return OmegaConf.to_container(obj, resolve=True)
-    except ImportError:
-        pass
-    if isinstance(obj, Mapping):
-        return {k: _to_plain(v) for k, v in obj.items()}
-    if isinstance(obj, Sequence) and not isinstance(obj, (str, bytes)):
-        return [_to_plain(v) for v in obj]
-    return obj
-
-
-def _cfg_get(cfg, *path, default=None):
-    for k in path:
-        if isinstance(cfg, dict) and k in cfg:
-            cfg = cfg[k]
-        else:
-            return default
-    return cfg
-
-
-MODEL_KINDS = {"flow": FlowModel, "score": ScoreModel, "regression": RegressionModel}
-
-
-def model_kind(mcfg: dict, model: str = "auto") -> str:
-    """'flow' / 'score' / 'regression': `model` unless it is 'auto', else the class `hyper_parameters.model._target_` names (the class
-    EnhancementModel.load_from_checkpoint would build, enhance.py:66); a checkpoint without a `_target_` is a FlowModel."""
-    if model != "auto":
-        if model not in MODEL_KINDS:
-            raise ValueError(f"model must be one of {['auto'] + sorted(MODEL_KINDS)} (got {model!r})")
-        return model
-    target = mcfg.get("_target_")
-    if target is None:
-        return "flow"
-    for kind, cls in MODEL_KINDS.items():
-        if str(target).split(".")[-1] == cls.__name__:
-            return kind
-    raise RuntimeError(f"checkpoint names the model class {target!r}: only FlowModel, ScoreModel and RegressionModel are implemented "
-                       f"(--model overrides the checkpoint)")
-
-
-def score_settings(mcfg: dict) -> Tuple[OUVESDE, float]:
-    """(sde, t_eps) of a ScoreModel checkpoint: `model.sde` (theta, sigma_min, sigma_max, N) and `model.t_eps`; what is absent comes from
-    config/model/sde/ouve_final.yaml and score_model_final.yaml's t_eps (the preset baseline_scoredec_75s).  Only the OUVE SDE exists here."""
-    default = PRESETS["baseline_scoredec_75s"]
-    sde_cfg = mcfg.get("sde") or {}
-    target = sde_cfg.get("_target_")
-    if target is not None and str(target).split(".")[-1] != "OUVESDE":
-        raise RuntimeError(f"checkpoint names the SDE {target!r}: only OUVESDE is implemented")
-    par = {k: sde_cfg.get(k, v) for k, v in default["sde"].items()}
-    t_eps = mcfg.get("t_eps")
-    return OUVESDE(**par), float(default["t_eps"] if t_eps is None else t_eps)
-
-
-def model_from_checkpoint(ckpt, ema: bool = True, precision: str = "bf16", preset: str = "flowdec_75m", model: str = "auto"):
-    """Build the FlowModel, ScoreModel or RegressionModel of a loaded checkpoint object (see module docstring for the accepted layouts
-    and `model_kind` for the choice of the class)."""
-    if not isinstance(ckpt, dict):
-        raise RuntimeError("checkpoint must be a dict")
-    if "_pl_ema_state_dict" in ckpt or "state_dict" in ckpt:
-        key = "_pl_ema_state_dict" if (ema and "_pl_ema_state_dict" in ckpt) else "state_dict"
-        if key not in ckpt:
-            raise RuntimeError(f"checkpoint has no '{key}' (available: {[k for k in ckpt if 'state_dict' in k]})")
-        sd = ckpt[key]
-    else:
-        sd = ckpt  # bare state_dict
-    hp = None
-    if ckpt.get("hyper_parameters", None) is not None:
-        hp = _to_plain(ckpt["hyper_parameters"])
-        if not isinstance(hp, dict):   # silently falling back to the defaults would produce wrong audio for e.g. the ablation configs
-            raise RuntimeError(f"checkpoint 'hyper_parameters' of type {type(ckpt['hyper_parameters']).__name__} cannot be read as a mapping")
-    mcfg = _cfg_get(hp, "model") or {}
-    bb_cfg = dict(BACKBONE_FINAL_NO_ATTN)
-    for k, v in (mcfg.get("backbone") or {}).items():
-        if k != "_target_":
-            bb_cfg[k] = tuple(v) if isinstance(v, list) else v
-    if not mcfg.get("backbone") and "backbone.all_modules.0.W" in sd:      # infer the width from the weights
-        bb_cfg["nf"] = int(sd["backbone.all_modules.0.W"].shape[0])
-    fe_cfg = mcfg.get("feature_extractor") or {}
-    fe = AmplitudeCompressedComplexSTFT(window_fn=fe_cfg.get("window_fn", "hann"), n_fft=int(fe_cfg.get("n_fft", 1534)),
-                                        n_hops=int(fe_cfg.get("n_hops", 4)) if "hop_length" not in fe_cfg else None,
-                                        hop_length=fe_cfg.get("hop_length"), sampling_rate=int(_cfg_get(hp, "sampling_rate", default=48000)),
-                                        alpha=float(fe_cfg.get("alpha", 0.3)), beta=float(fe_cfg.get("beta", 0.33)))
-    kind = model_kind(mcfg, model)
-    common = dict(backbone=NCSNpp(precision=precision, **bb_cfg), feature_extractor=fe, sampling_rate=int(_cfg_get(hp, "sampling_rate", default=48000)))
-    if kind == "score":
-        sde, t_eps = score_settings(mcfg)
-        net = ScoreModel(sde=sde, t_eps=t_eps, **common)
-    elif kind == "regression":
-        net = RegressionModel(**common)
-    else:
-        sigma_y = sd["sigma_y"] if "sigma_y" in sd else from_preset(preset, nf=8).sigma_y.data
-        net = FlowModel(sigma_x=0.0, sigma_y=sigma_y.clone(), **common)
-    res = net.load_state_dict(sd, strict=False)  # strict_loading = False in the reference (model.py:397)
-    missing = [k for k in res.missing_keys if k.startswith("backbone.")]
-    if missing:
-        raise RuntimeError(f"checkpoint is missing backbone parameters, e.g. {missing[:3]}")
-    return net.eval()
-
-
-def load_from_checkpoint(path: str, map_location="cpu", ema: bool = True, precision: str = "bf16", model: str = "auto"):
-    """Replacement for `EnhancementModel.load_from_checkpoint(ckpt, map_location=..., ema=...)` (enhance.py:66)."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=False)
-    net = model_from_checkpoint(ckpt, ema=ema, precision=precision, model=model)
-    return net.to(map_location) if map_location is not None else net
 
 
 # ------------------------------------------------------------------------------------------------
@@ -577,14 +335,8 @@ def chunk_samples(model, args) -> Optional[int]:
 
 
 def resample_for_model(y: torch.Tensor, sr: int, model, mode: str = "host") -> torch.Tensor:
-    """--resample: `resample` on the host, or `resample_device` on the model's device (the result stays there).  A rate pair over the
-    bank cap of the device resampler takes the host path."""
-    if mode == "device":
-        from . import resample as fd_resample
-        if fd_resample.bank_fits(sr, model.sampling_rate):
-            return fd_resample.resample_device(y.to(model.device), sr, model.sampling_rate)
-        print(f"--resample device: the filter bank of {sr} -> {model.sampling_rate} Hz is over the device resampler's cap; resampling on the host")
-    return resample(y, sr, model.sampling_rate)
+    """--resample: to the model's rate, on the host or on the model's device (`audio.resample_to`)."""
+    return resample_to(y, sr, model.sampling_rate, mode, model.device)
 
 
 def load_for_model(model: FlowModel, job: FileJob, res: RunResult, max_seconds: float, precision: str, length_limit: float = MAX_SECONDS,
@@ -661,9 +413,8 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length
     every bucket into batches of at most `batch_files` files, in work-list order.  Multi-channel files, unreadable headers and files
     the length rule will skip go through the one-file path (their own messages), and so do files of more than `long_samples` samples
     (--chunk-seconds: they run in rows).  -> list of lists of FileJob."""
-    from .model import padded_frames_of
     hop = model.feature_extractor._cfg()["hop"]
-    buckets, singles = {}, []
+    bucketed, lengths, singles = [], [], []
     for job in jobs:
         try:
             n, sr, channels = wav_info(job.src)
@@ -673,12 +424,8 @@ def plan_batches(model: FlowModel, jobs: List[FileJob], batch_files: int, length
             singles.append([job]); continue
         if channels != 1 or n / sr > length_limit or batch_files <= 1:
             singles.append([job]); continue
-        buckets.setdefault(padded_frames_of(resampled_length(n, sr, model.sampling_rate), hop), []).append(job)
-    batches = []
-    for tp in sorted(buckets):
-        group = buckets[tp]
-        batches += [group[i:i + batch_files] for i in range(0, len(group), batch_files)]
-    return batches + singles
+        bucketed.append(job); lengths.append(resampled_length(n, sr, model.sampling_rate))
+    return [[bucketed[i] for i in idx] for _, idx in plan_clip_batches(lengths, hop, batch_files)] + singles
 
 
 def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLog, res: RunResult, max_seconds: float) -> None:
@@ -728,7 +475,6 @@ def batch_cost(model, batch: List[FileJob], args) -> int:
     channels x padded frames, a --chunk-seconds file channels x rows x row frames (`longform.plan_rows`); an unreadable header costs 0 (the
     file fails in its own call), and so does a file the length rule will skip.  A heuristic -- GPU time taken as proportional to the frames
     in flight, whatever the batch size and the bucket; how evenly it spreads a real corpus over the ranks has not been measured."""
-    from .model import padded_frames_of
     hop = model.feature_extractor._cfg()["hop"]
     long_samples = chunk_samples(model, args)
     try:
@@ -845,7 +591,6 @@ def launch_workers(argv: List[str], world: int, manifest: str, share_gpu: bool):
 def evaluate_triples(args, suffix: str) -> None:
     """--eval: SI-SxR and LogSpecMSE (--eval-estoi: and ESTOI) of `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it
     (flowdec_amd/eval_cli.py)."""
-    from . import eval_cli
     with torch.cuda.device(args.device):
         eval_cli.run(["--triples", os.path.join(args.outdir, f"triples_list{suffix}.txt"), "--out", os.path.join(args.outdir, f"metrics{suffix}.csv"),
                       "--batch-files", str(max(args.batch_files, 1))] + (["--estoi"] if getattr(args, "eval_estoi", False) else []))
@@ -960,7 +705,6 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
                         chunk_samples(model, args))
     mine = range(len(plan))
     if worker:      # the plan is the one-process plan; this rank runs its share of it, in plan order
-        from .dist import balance
         mine = balance([batch_cost(model, batch, args) for batch in plan], args.worker_world)[args.worker_rank]
         print(f"flowdec_amd: worker {args.worker_rank} of {args.worker_world} on {args.device}: {len(mine)} of {len(plan)} batches")
     with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None, part=args.worker_rank) as log:

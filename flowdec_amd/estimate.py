@@ -13,11 +13,16 @@ bits (tests/test_estimate_host.py).
 
 The host-side randomness of the script (which pairs, where each is cropped) is reproduced call for call by `select_pairs` and
 `crop_or_pad_pair`; flowdec_amd/estimate_cli.py is the command line."""
+import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
+
+from . import _lib as L
+from . import ops
+from .batching import padded_rows
 
 
 # ---- the script's host-side randomness ---------------------------------------------------------------------------------------------------
@@ -119,7 +124,6 @@ def estimate_params(x_clips, y_clips, *, alpha: float, n_fft: int, hop: int, qx:
     script's 2500 pairs of 2 s) and takes its order statistics with ONE fd_select_f32 call; the quantile over the pairs runs on the host.
 
     Per-band RMSE is sqrt(band_sq[f]) / sqrt(F): the reference divides by the number of bands, not of frames (see rmses_from_band_sq)."""
-    from . import _lib as L, ops
     lib = L.load()
     xs = [torch.as_tensor(c).reshape(-1).float() for c in x_clips]
     ys = [torch.as_tensor(c).reshape(-1).float() for c in y_clips]
@@ -150,8 +154,7 @@ def estimate_params(x_clips, y_clips, *, alpha: float, n_fft: int, hop: int, qx:
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         for i0 in range(0, n_pairs, batch_pairs):
             i1 = min(i0 + batch_pairs, n_pairs)
-            # (clips a device resampler left on the GPU go over one by one; host clips as one block)
-            xb, yb = (torch.stack([c.to(device) for c in l]) if any(c.is_cuda for c in l) else torch.stack(l).to(device) for l in (xs[i0:i1], ys[i0:i1]))
+            xb, yb = (padded_rows(l, Lc, device)[0] for l in (xs[i0:i1], ys[i0:i1]))
             L.check(lib.fd_estimate_pair_stats(plan, L.ptr(xb), L.ptr(yb), i1 - i0, Lc, float(alpha), L.ptr(normfac[i0:i1]), L.ptr(absx[i0:i1]),
                                                L.ptr(band_sq[i0:i1]), L.ptr(ws), nws, L.stream()))
         lo, hi, gamma = quantile_position(n_bins, qx, np.float32)
@@ -168,8 +171,6 @@ def estimate_params(x_clips, y_clips, *, alpha: float, n_fft: int, hop: int, qx:
 def select_f32(values: torch.Tensor, ranks: Sequence[int]) -> np.ndarray:
     """Exact order statistics of a device tensor of non-negative float32 values (fd_select_f32): -> float32 [len(ranks)], entry r the value
     at position ranks[r] of the sorted values.  A negative value or a NaN among them is a ValueError."""
-    import ctypes as C
-    from . import _lib as L
     lib = L.load()
     L.require_cuda(values)
     if values.dtype != torch.float32 or not values.is_contiguous():

@@ -25,6 +25,9 @@ import numpy as np
 import torch
 
 from . import estimate as E
+from .audio import RESAMPLE_HELP, load_mono
+from .checkpoint import _cfg_get, _to_plain
+from .model import sigma_y_from_file
 
 
 def rreplace(s: str, old: str, new: str, occurrence: int = 1) -> str:
@@ -54,9 +57,8 @@ def result_lines(args, res: E.EstimateResult, curve_path: Optional[str]) -> List
 # ---- --compare-ckpt ----------------------------------------------------------------------------------------------------------------------
 def ckpt_params(ckpt: dict):
     """-> (beta, sigma_y, kernel_bandwidth, factor) of a loaded checkpoint object: beta from hyper_parameters.model.feature_extractor
-    (0.33 where absent, as enhance_cli builds it), sigma_y from the state dict (a float, or float64 [F] for a curve; None where the
+    (0.33 where absent, as checkpoint.model_from_checkpoint builds it), sigma_y from the state dict (a float, or float64 [F] for a curve; None where the
     checkpoint has none), and the smoothing its config applied to the curve file (hyper_parameters.model.sigma_y; the presets' 3 and 1)."""
-    from .enhance_cli import _cfg_get, _to_plain
     hp = _to_plain(ckpt["hyper_parameters"]) if ckpt.get("hyper_parameters") is not None else None
     mcfg = _cfg_get(hp, "model") or {}
     beta = float((mcfg.get("feature_extractor") or {}).get("beta", 0.33))
@@ -71,7 +73,6 @@ def ckpt_params(ckpt: dict):
 
 def smoothed(curve: np.ndarray, kernel_bandwidth: float, factor: float) -> np.ndarray:
     """The curve as a model built from its file would hold it: model.sigma_y_from_file on a temporary copy."""
-    from .model import sigma_y_from_file
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "curve.npy")
         np.save(path, np.asarray(curve))
@@ -106,7 +107,6 @@ def compare_with_ckpt(res: E.EstimateResult, ckpt: dict) -> List[str]:
 
 # ---- the run -----------------------------------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    from .eval_cli import RESAMPLE_HELP
     p = argparse.ArgumentParser(description="Estimate a FlowDec model's beta and sigma_y from (clean, coded) pairs on MI355X")
     p.add_argument("--pairs-file", type=str, required=True)
     p.add_argument("--delim", type=str, default=" ---> ")
@@ -134,7 +134,6 @@ def build_parser() -> argparse.ArgumentParser:
 
 def run(argv=None, out=None) -> Optional[E.EstimateResult]:
     """-> the estimate, or None where an existing results file was printed instead."""
-    from .eval_cli import load_mono
     out = out or sys.stdout
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     print(args, file=sys.stderr)

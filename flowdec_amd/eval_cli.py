@@ -4,7 +4,7 @@ flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for t
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
                                    [--sr 48000] [--estoi]
 
-Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (a comma inside an arrow line is part of the
+Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
 lowpass_filter_width=256 when its rate differs.  --crop-to-x then --crop-to-x-hat cut as in get_metrics_df (eval/metrics.py:85-90), in
 that order.
@@ -39,8 +39,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from .enhance_cli import _split_pair, load_wav
-from .enhance_cli import resample as host_resample
+from . import metrics
+from .audio import RESAMPLE_HELP, load_mono, split_pair
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
@@ -67,34 +67,11 @@ def read_triples(listfile: str) -> List[Triple]:
             entry = raw.strip()
             if not entry:
                 continue
-            parts = [p.strip() for p in _split_pair(entry)]
+            parts = [p.strip() for p in split_pair(entry)]
             if len(parts) != 3:
                 raise ValueError(f"{listfile}:{lineno}: {len(parts)} fields, a triples line is `clean ---> noisy ---> enhanced`")
             out.append(Triple(parts[0], parts[1], parts[2]))
     return out
-
-
-RESAMPLE_HELP = ("where a file that is not at --sr is resampled.  host: on the CPU (the default).  device: the same polyphase filter as a HIP "
-                 "kernel on the current GPU (flowdec_amd.resample), summed in float64 and rounded once -- the values differ from host mode by "
-                 "float32 rounding of the FIR.  A rate pair over the device resampler's bank cap falls back to the host path, with one printed line")
-
-
-def load_mono(path: str, sr: int, resample: str = "host") -> torch.Tensor:
-    """load48000 (util/other.py:137-) for the rate `sr`: -> 1-D float32 tensor, the mean of the channels, resampled when the rate differs
-    (lowpass_filter_width=256): resample='host' on the CPU, 'device' on the current GPU (the signal then stays there)."""
-    au, fs = load_wav(path)
-    if au.shape[0] != 1:
-        au = au.mean(dim=0, keepdim=True)
-    if fs != sr:
-        if resample not in ("host", "device"):
-            raise ValueError(f"load_mono: resample is 'host' or 'device' (got {resample!r})")
-        if resample == "device":
-            from . import resample as fd_resample
-            if fd_resample.bank_fits(fs, sr, 256):
-                return fd_resample.resample_device(au.to("cuda"), fs, sr, lowpass_filter_width=256)[0].contiguous()
-            print(f"--resample device: the filter bank of {fs} -> {sr} Hz is over the device resampler's cap; resampling on the host")
-        au = host_resample(au, fs, sr, lowpass_filter_width=256)
-    return au[0].contiguous()
 
 
 def crop(x_hat: torch.Tensor, x: torch.Tensor, y: torch.Tensor, crop_to_x: bool, crop_to_x_hat: bool):
@@ -121,32 +98,26 @@ class Scorer:
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
-    from . import metrics
     return metrics.si_sxr_batch(x_hats, xs, ys, batch=batch)
 
 
 def _gpu_logspec(x_hats, xs, sr, batch):
-    from . import metrics
     return metrics.logspec_mse_batch(x_hats, xs, sr=sr, win_dur=WIN_DUR, hop_dur=HOP_DUR, batch=batch)
 
 
 def _host_si_sxr(x_hats, xs, ys, batch):
-    from . import metrics
     return np.array([metrics.si_sxr(h, x, y) for h, x, y in zip(x_hats, xs, ys)], np.float64).reshape(-1, 3)
 
 
 def _host_logspec(x_hats, xs, sr, batch):
-    from . import metrics
     return np.array([metrics.logspec_mse(h, x, sr=sr, win_dur=WIN_DUR, hop_dur=HOP_DUR) for h, x in zip(x_hats, xs)], np.float64)
 
 
 def _gpu_estoi(x_hats, xs, sr, batch):
-    from . import metrics
     return metrics.estoi_batch(x_hats, xs, sr=sr, batch=batch)
 
 
 def _host_estoi(x_hats, xs, sr, batch):
-    from . import metrics
     return np.array([metrics.estoi(h, x, sr) for h, x in zip(x_hats, xs)], np.float64)
 
 
@@ -182,7 +153,6 @@ def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Opti
     if spectral:
         out[spectral, 3] = scorer.logspec(column(spectral, 0), column(spectral, 1), sr, batch)
     if estoi and ok:
-        from . import metrics
         if scorer.estoi is None:
             raise ValueError("score: estoi=True needs a Scorer with an estoi function")
         out[ok, 4] = scorer.estoi(column(ok, 0), column(ok, 1), sr, batch)

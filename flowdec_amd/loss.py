@@ -23,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import noise as fd_noise
+from .batching import _ragged_bucket, _to_3d, padded_rows, plan_clip_batches
 
 log = logging.getLogger(__name__)
 
@@ -121,16 +122,15 @@ def loss_times(seeds: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
 
 # ---- one native call -----------------------------------------------------------------------------------------------------------------------
 def _native(model, kind, cfg, x_rows, y_rows, lens, seeds, noise, t):
-    """fd_valid_loss on rows [B, Lrow] that live on the model's device.  lens: list of ints (ragged, one T_pad bucket) or None.
+    """fd_valid_loss on rows [B, Lrow] that live on the model's device.  lens: int32 [B] on the device (ragged, one T_pad bucket) or None.
     seeds: int64 [B] device | None; noise: complex64 [n_draws, B, 1, F, Tp] device | None; t: float32 [B] device | None.
     -> dict(sums float64 [B], bad int64 [B], normfac float32 [B], t float32 [B] | None (tensors on the device), n_bins)."""
-    from .model import _NativeCall
     lib = L.load()
     dev = model.device
     B, Lrow = y_rows.shape
     stft = model.feature_extractor._cfg()
     F = stft["n_fft"] // 2 + 1
-    with _NativeCall(model.backbone), torch.cuda.device(dev):
+    with model._native_call(), torch.cuda.device(dev):
         h = model._sync_native()
         Tp = int(lib.fd_padded_frames(lib.fd_num_frames(Lrow, stft["hop"])))
         need = int(lib.fd_valid_loss_workspace_bytes(h, B, Lrow))
@@ -141,10 +141,9 @@ def _native(model, kind, cfg, x_rows, y_rows, lens, seeds, noise, t):
         sums = torch.empty(B, dtype=torch.float64, device=dev)
         bad = torch.empty(B, dtype=torch.int64, device=dev)
         normfac = torch.empty(B, dtype=torch.float32, device=dev)
-        lens_dev = None if lens is None else torch.tensor(lens, dtype=torch.int32).to(dev)
         if kind != "regression" and t is None and seeds is not None:
             t = loss_times(seeds, *time_range(model, kind))
-        L.check(lib.fd_valid_loss(h, C.byref(cfg), L.ptr(x_rows), L.ptr(y_rows), L.ptr(lens_dev), None if noise is None else L.ptr(torch.view_as_real(noise)),
+        L.check(lib.fd_valid_loss(h, C.byref(cfg), L.ptr(x_rows), L.ptr(y_rows), L.ptr(lens), None if noise is None else L.ptr(torch.view_as_real(noise)),
                                   L.ptr(seeds), L.ptr(t), L.ptr(sums), L.ptr(bad), L.ptr(normfac), B, Lrow, L.ptr(ws), ws.numel(), L.stream()))
     return dict(sums=sums, bad=bad, normfac=normfac, t=t, n_bins=F * Tp)
 
@@ -211,7 +210,6 @@ def valid_loss(model, kind: str, x, y, *, seed=None, noise=None, t=None, reduce:
     if x.shape != y.shape:
         raise RuntimeError(f"valid_loss: x and y must have the same shape (got {tuple(x.shape)} vs {tuple(y.shape)})")   # model.py:141
     dev = _require_gpu(model)
-    from .model import _to_3d
     y3, _ = _to_3d(y, "valid_loss expects")
     B, Lw = y3.shape[0], y3.shape[-1]
     stft = model.feature_extractor._cfg()
@@ -223,20 +221,6 @@ def valid_loss(model, kind: str, x, y, *, seed=None, noise=None, t=None, reduce:
     return _finish(model, kind, _native(model, kind, cfg, xr, yr, None, seeds_dev, noise, t), reduce, return_t)
 
 
-def _rows(flat, lens, Lrow, dev):
-    """Clips of one bucket as zero-padded rows [B, Lrow] on the device: host clips are staged in ONE host block and copied once; clips that
-    already live on the GPU (a device resampler left them there) go over one by one."""
-    if any(c.is_cuda for c in flat):
-        rows = torch.zeros(len(flat), Lrow, dtype=torch.float32, device=dev)
-        for b, c in enumerate(flat):
-            rows[b, :lens[b]].copy_(c)
-        return rows
-    rows = torch.zeros(len(flat), Lrow, dtype=torch.float32)
-    for b, c in enumerate(flat):
-        rows[b, :lens[b]] = c
-    return rows.to(dev)
-
-
 @torch.no_grad()
 def valid_loss_batch(model, kind: str, xs, ys, *, seeds=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, max_batch: int = 8):
     """The same for LISTS of clips of any lengths: pair i is (xs[i], ys[i]), [L_i], [1, L_i] or [1, 1, L_i].  The pairs are bucketed by
@@ -245,7 +229,6 @@ def valid_loss_batch(model, kind: str, xs, ys, *, seeds=None, noise=None, t=None
     seeds: an int (pair i is seeded flowdec_amd.noise.clip_seed(seeds, i)) or one 64-bit seed per pair; noise: one tensor
     [n_draws, 1, F, T_pad_i] per pair; t: one time per pair.  reduce='mean' applies the class's reduction to all per-pair values (pairs of
     different T_pad have different bin counts: the regression mean is then the mean of the per-pair means)."""
-    from .model import _ragged_bucket, padded_frames_of
     if reduce not in ("mean", "none"):
         raise ValueError(f"valid_loss_batch: reduce must be 'mean' or 'none' (got {reduce!r})")
     cfg = _config(model, kind)
@@ -271,29 +254,22 @@ def valid_loss_batch(model, kind: str, xs, ys, *, seeds=None, noise=None, t=None
                 raise ValueError(f"valid_loss_batch: one time per pair: got {t.numel()} for {n} pairs")
     stft = model.feature_extractor._cfg()
     F = stft["n_fft"] // 2 + 1
-    buckets = {}
-    for i, c in enumerate(ys):
-        buckets.setdefault(padded_frames_of(c.shape[-1], stft["hop"]), []).append(i)
     max_batch = max(1, min(int(max_batch), 256))
     sums, bad = np.zeros(n, np.float64), np.zeros(n, np.int64)
     n_bins = np.zeros(n, np.float64)
     normfac, times = torch.zeros(n, dtype=torch.float32), (None if kind == "regression" else torch.zeros(n, dtype=torch.float32))
     done = []
-    for Tp in sorted(buckets):
-        idx = buckets[Tp]
-        for k in range(0, len(idx), max_batch):
-            part = idx[k:k + max_batch]
-            flat_y, lens, Tp_, Lrow = _ragged_bucket([ys[i] for i in part], stft)
-            flat_x = [xs[i].reshape(-1) for i in part]
-            B = len(part)
-            xr, yr = _rows(flat_x, lens, Lrow, dev), _rows(flat_y, lens, Lrow, dev)
-            if kind == "regression":
-                sd = nz = tt = None
-            else:
-                nz = None if noise is None else torch.stack([torch.as_tensor(noise[i]).to(dev, torch.complex64).reshape(-1, 1, F, Tp) for i in part], dim=1)
-                sd, nz, tt = _draws(model, kind, cfg, B, F, Tp, None if seeds is None else [seeds[i] for i in part], nz,
-                                    None if t is None else t[part], dev)
-            done.append((part, _native(model, kind, cfg, xr, yr, lens, sd, nz, tt)))
+    for Tp, part in plan_clip_batches([c.shape[-1] for c in ys], stft["hop"], max_batch):
+        flat_y, _, _, Lrow = _ragged_bucket([ys[i] for i in part], stft)
+        B = len(part)
+        (xr, _), (yr, lens) = padded_rows([xs[i].reshape(-1) for i in part], Lrow, dev), padded_rows(flat_y, Lrow, dev)
+        if kind == "regression":
+            sd = nz = tt = None
+        else:
+            nz = None if noise is None else torch.stack([torch.as_tensor(noise[i]).to(dev, torch.complex64).reshape(-1, 1, F, Tp) for i in part], dim=1)
+            sd, nz, tt = _draws(model, kind, cfg, B, F, Tp, None if seeds is None else [seeds[i] for i in part], nz,
+                                None if t is None else t[part], dev)
+        done.append((part, _native(model, kind, cfg, xr, yr, lens, sd, nz, tt)))
     for part, res in done:      # read back after the last call is enqueued: no host synchronisation between the native calls
         sums[part], bad[part] = res["sums"].cpu().numpy(), res["bad"].cpu().numpy()
         n_bins[part] = res["n_bins"]

@@ -4,13 +4,13 @@
     python -m flowdec_amd.loss_cli --ckpt C --pairs-file P [--target-duration 2] [--no-crop] [--batch 8] [--seed 0]
                                    [--precision bf16|fp32|mixed|bf16x3] [--resample host|device] [--out losses.csv]
 
-Input: the pair lines of enhance_cli (`clean ---> coded` or `clean,coded`; enhance_cli.read_list).  Every file is loaded like eval_cli's:
+Input: the pair lines of enhance_cli (`clean ---> coded` or `clean,coded`; audio.read_list).  Every file is loaded like eval_cli's:
 mean of the channels, resampled to the model's rate when its rate differs.  Each pair then gets the validation set's rule
 (data/data_module.py:146-171 with random_crop=False): y is cut to x's length (a y shorter than x is an error), a pair longer than
 --target-duration seconds is cropped around its centre (start = int((len - target) / 2)), a shorter one is zero-padded on both sides
 (pad // 2 before, pad // 2 + pad % 2 after).  --no-crop keeps every pair at its own length.
 
-The class the checkpoint names runs (enhance_cli.model_from_checkpoint).  Pair i of the list is seeded
+The class the checkpoint names runs (checkpoint.model_from_checkpoint).  Pair i of the list is seeded
 flowdec_amd.noise.clip_seed(--seed, i): its noise, its time t and therefore its loss do not depend on --batch or on how the pairs were
 bucketed.  Prints `valid_loss = ...` (the class's own reduction over all pairs) and, with --out, writes `name,t,loss` per pair."""
 import argparse
@@ -22,6 +22,11 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
+
+from . import loss as fd_loss
+from .audio import RESAMPLE_HELP, load_mono, read_list
+from .checkpoint import load_from_checkpoint
+from .model import RegressionModel, ScoreModel
 
 
 def crop_or_pad_valid(x: torch.Tensor, y: torch.Tensor, target: int, name: str = "pair") -> Tuple[torch.Tensor, torch.Tensor]:
@@ -56,12 +61,10 @@ class LossResult:
 
 
 def model_kind_of(model) -> str:
-    from .model import RegressionModel, ScoreModel
     return "score" if isinstance(model, ScoreModel) else "regression" if isinstance(model, RegressionModel) else "flow"
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .eval_cli import RESAMPLE_HELP
     p = argparse.ArgumentParser(description="valid_loss of a FlowDec / ScoreDec / regression checkpoint on (clean, coded) pairs, on MI355X")
     p.add_argument("--ckpt", type=str, required=True)
     p.add_argument("--pairs-file", type=str, required=True, help="lines `clean ---> coded` (or `clean,coded`)")
@@ -77,8 +80,6 @@ def build_parser() -> argparse.ArgumentParser:
 
 def load_pairs(args, sr: int):
     """-> (names, xs, ys): the list's pairs, loaded, brought to `sr` and cropped / padded by the validation set's rule."""
-    from .enhance_cli import read_list
-    from .eval_cli import load_mono
     fl = read_list(args.pairs_file)
     if not fl.from_pairs or not fl.inputs:
         raise ValueError(f"{args.pairs_file}: no `clean ---> coded` pair lines")
@@ -103,8 +104,6 @@ def write_csv(path: str, res: LossResult) -> None:
 
 def run(argv=None, model=None, out=None) -> LossResult:
     """`model`: an already built model (tests); otherwise the checkpoint's."""
-    from . import loss as fd_loss
-    from .enhance_cli import load_from_checkpoint
     out = out or sys.stdout
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     if model is None:

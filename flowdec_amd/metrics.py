@@ -14,8 +14,15 @@ logspec_mse_batch below, which score a triples list in flowdec_amd/eval_cli.py. 
                  algorithm at the end of this file, with estoi_batch on the GPU (csrc/stoi.hip).  The resampler is pinned against
                  scipy.signal.resample_poly; parity with the pystoi package is unpinned (absent offline: scripts/pin_estoi.py).
 """
+import ctypes as C
+import math
+
 import numpy as np
 import torch
+
+from . import _lib as L
+from . import ops
+from .batching import length_sorted_batches, padded_rows  # noqa: F401  (length_sorted_batches: callers take it from here)
 
 
 def _flat(a) -> np.ndarray:
@@ -72,23 +79,6 @@ def sisxr_from_sums(sums) -> np.ndarray:
         return np.stack([10 * np.log10(s[:, 4] / s[:, 7]), 10 * np.log10(s[:, 4] / s[:, 5]), 10 * np.log10(s[:, 4] / s[:, 6])], axis=1)
 
 
-def length_sorted_batches(lengths, batch: int):
-    """Indices sorted by length (ties by index) and cut into batches of at most `batch`: the clips of one call have similar lengths, so
-    little of a row is padding.  The results do not depend on this (a clip's bits are the same in any batch)."""
-    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
-    batch = max(int(batch), 1)
-    return [order[i:i + batch] for i in range(0, len(order), batch)]
-
-
-def _rows(clips, idx, device):
-    """-> (rows [B, Lmax] float32 on the device, zero behind each clip; lengths int32 [B] on the device)."""
-    Lmax = max(int(clips[i].numel()) for i in idx)
-    rows = torch.zeros(len(idx), Lmax, dtype=torch.float32)
-    for r, i in enumerate(idx):
-        rows[r, :clips[i].numel()] = clips[i].detach().reshape(-1).float().cpu()
-    return rows.to(device)
-
-
 def _as_clips(*lists):
     out = [[torch.as_tensor(c).reshape(-1) for c in l] for l in lists]
     n = len(out[0])
@@ -103,23 +93,33 @@ def _as_clips(*lists):
     return out
 
 
+def _ragged_batches(lists, batch, device, call, outs):
+    """The loop of the three batch functions: the clips of `lists` (one list per signal, `_as_clips`) in length-sorted batches of `batch`
+    as zero-padded rows; call(rows of every list, lens, B, Lmax) makes the native call and returns one host array per entry of `outs`,
+    which lands in its rows `idx`."""
+    lengths = [int(c.numel()) for c in lists[0]]
+    with torch.cuda.device(device):
+        for idx in length_sorted_batches(lengths, batch):
+            Lmax = max(lengths[i] for i in idx)
+            staged = [padded_rows([l[i] for i in idx], Lmax, device) for l in lists]
+            for out, got in zip(outs, call([rows for rows, _ in staged], staged[0][1], len(idx), Lmax)):
+                out[idx] = got
+
+
 def si_sxr_sums_batch(x_hats, xs, ys, batch: int = 8, device="cuda") -> np.ndarray:
     """The float64 sums of fd_metrics_sisxr per clip, [n, 8] (layout SISXR_SUMS)."""
-    from . import _lib as L
     lib = L.load()
     x_hats, xs, ys = _as_clips(x_hats, xs, ys)
     out = np.zeros((len(xs), 8), np.float64)
-    lengths = [int(c.numel()) for c in xs]
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches(lengths, batch):
-            h, x, y = (_rows(l, idx, device) for l in (x_hats, xs, ys))
-            lens = torch.tensor([lengths[i] for i in idx], dtype=torch.int32, device=device)
-            B, Lmax = x.shape
-            nws = lib.fd_metrics_workspace_bytes(B, Lmax, 0, 0)
-            ws = torch.empty(nws, dtype=torch.uint8, device=device)
-            sums = torch.empty(B, 8, dtype=torch.float64, device=device)
-            L.check(lib.fd_metrics_sisxr(L.ptr(h), L.ptr(x), L.ptr(y), L.ptr(lens), B, Lmax, L.ptr(sums), L.ptr(ws), nws, L.stream()))
-            out[idx] = sums.cpu().numpy()
+
+    def call(rows, lens, B, Lmax):
+        nws = lib.fd_metrics_workspace_bytes(B, Lmax, 0, 0)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        sums = torch.empty(B, 8, dtype=torch.float64, device=device)
+        L.check(lib.fd_metrics_sisxr(L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(rows[2]), L.ptr(lens), B, Lmax, L.ptr(sums), L.ptr(ws), nws, L.stream()))
+        return [sums.cpu().numpy()]
+
+    _ragged_batches((x_hats, xs, ys), batch, device, call, [out])
     return out
 
 
@@ -133,7 +133,6 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
                       device="cuda") -> np.ndarray:
     """logspec_mse of every (x_hat, x) on the GPU -> [n] float64.  One cached transform plan per (n_fft, hop) (ops.stft_plan).  A clip of
     n_fft / 2 samples or fewer cannot be reflect-padded (torch.stft raises): ValueError naming the clip."""
-    from . import _lib as L, ops
     lib = L.load()
     n_fft, hop = int(win_dur * sr), int(hop_dur * sr)
     x_hats, xs = _as_clips(x_hats, xs)
@@ -143,16 +142,16 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
             raise ValueError(f"logspec_mse: clip {i} has {l} samples, reflect padding of n_fft {n_fft} needs more than {n_fft // 2}")
     out = np.zeros(len(xs), np.float64)
     plan = ops.stft_plan(n_fft, hop, device)
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches(lengths, batch):
-            h, x = (_rows(l, idx, device) for l in (x_hats, xs))
-            lens = torch.tensor([lengths[i] for i in idx], dtype=torch.int32, device=device)
-            B, Lmax = x.shape
-            nws = lib.fd_metrics_workspace_bytes(B, Lmax, n_fft, hop)
-            ws = torch.empty(nws, dtype=torch.uint8, device=device)
-            mse = torch.empty(B, dtype=torch.float64, device=device)
-            L.check(lib.fd_metrics_logspec_mse(plan, L.ptr(h), L.ptr(x), L.ptr(lens), B, Lmax, float(eps), L.ptr(mse), L.ptr(ws), nws, L.stream()))
-            out[idx] = mse.cpu().numpy()
+
+    def call(rows, lens, B, Lmax):
+        nws = lib.fd_metrics_workspace_bytes(B, Lmax, n_fft, hop)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        mse = torch.empty(B, dtype=torch.float64, device=device)
+        L.check(lib.fd_metrics_logspec_mse(plan, L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(lens), B, Lmax, float(eps), L.ptr(mse), L.ptr(ws), nws,
+                                           L.stream()))
+        return [mse.cpu().numpy()]
+
+    _ragged_batches((x_hats, xs), batch, device, call, [out])
     return out
 
 
@@ -190,7 +189,6 @@ def estoi_band_edges():
 
 def estoi_filter(sr: int):
     """-> (w float64 [2 L + 1], p, q, L): the normalised Kaiser-windowed sinc of pystoi.utils.resample_oct for sr -> 10 kHz."""
-    import math
     sr = int(sr)
     if sr < 1:
         raise ValueError(f"estoi: the rate must be positive (got {sr})")
@@ -323,8 +321,6 @@ class _EstoiPlans:
     """The device tables of fd_metrics_estoi and the 10 kHz resample plan of one rate (None at 10 kHz), created on first use."""
 
     def __init__(self, sr):
-        import ctypes as C
-        from . import _lib as L
         lib = L.load()
         self.estoi, self.resample, self.o, self.n = C.c_void_p(), None, 1, 1
         if int(sr) != ESTOI_FS:
@@ -337,7 +333,6 @@ class _EstoiPlans:
 
     def __del__(self):
         try:
-            from . import _lib as L
             if getattr(self, "resample", None):
                 L.load().fd_resample_plan_destroy(self.resample)
             if getattr(self, "estoi", None):
@@ -360,23 +355,19 @@ def estoi_plans(sr: int, device="cuda") -> _EstoiPlans:
 def estoi_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", return_frames: bool = False):
     """estoi of every (x_hat, x) on the GPU -> [n] float64 (with return_frames also [n, 3] int32: frames, kept, spectral frames; fewer than
     30 spectral frames: 1e-5).  Length-sorted ragged batches of `batch` clips; the plans are cached per (sr, device)."""
-    from . import _lib as L
     lib = L.load()
     x_hats, xs = _as_clips(x_hats, xs)
-    lengths = [int(c.numel()) for c in xs]
     out, frames = np.zeros(len(xs), np.float64), np.zeros((len(xs), 3), np.int32)
     plans = estoi_plans(sr, device)
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches(lengths, batch):
-            h, x = (_rows(l, idx, device) for l in (x_hats, xs))
-            lens = torch.tensor([lengths[i] for i in idx], dtype=torch.int32, device=device)
-            B, Lmax = x.shape
-            nws = lib.fd_metrics_estoi_workspace_bytes(B, Lmax, plans.o, plans.n)
-            ws = torch.empty(nws, dtype=torch.uint8, device=device)
-            val = torch.empty(B, dtype=torch.float64, device=device)
-            fr = torch.empty(B, 3, dtype=torch.int32, device=device)
-            L.check(lib.fd_metrics_estoi(plans.estoi, plans.resample, L.ptr(h), L.ptr(x), L.ptr(lens), B, Lmax, L.ptr(val), L.ptr(fr), L.ptr(ws), nws,
-                                         L.stream()))
-            out[idx] = val.cpu().numpy()
-            frames[idx] = fr.cpu().numpy()
+
+    def call(rows, lens, B, Lmax):
+        nws = lib.fd_metrics_estoi_workspace_bytes(B, Lmax, plans.o, plans.n)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        val = torch.empty(B, dtype=torch.float64, device=device)
+        fr = torch.empty(B, 3, dtype=torch.int32, device=device)
+        L.check(lib.fd_metrics_estoi(plans.estoi, plans.resample, L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(lens), B, Lmax, L.ptr(val), L.ptr(fr),
+                                     L.ptr(ws), nws, L.stream()))
+        return [val.cpu().numpy(), fr.cpu().numpy()]
+
+    _ragged_batches((x_hats, xs), batch, device, call, [out, frames])
     return (out, frames) if return_frames else out

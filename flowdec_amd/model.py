@@ -22,7 +22,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import longform, ops
+from . import loss as fd_loss
 from . import noise as fd_noise
+from .batching import _ragged_bucket, _to_3d, padded_frames_of, padded_rows  # noqa: F401  (padded_frames_of: the bucket key callers import from here)
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -414,7 +417,6 @@ class ComplexSTFT(nn.Module):
 
     def forward(self, x):
         """x: [..., L] real (GPU) -> complex64 [..., n_fft/2+1, 1 + L // hop]  (feature_extractors.py:86-96)."""
-        from . import ops
         shp = x.shape
         Y, _, T = ops.stft_compress(x.reshape(-1, shp[-1]).float().contiguous(), n_fft=self.n_fft, hop=self.hop_length, alpha=1.0, beta=1.0,
                                     normalize=False)
@@ -422,7 +424,6 @@ class ComplexSTFT(nn.Module):
 
     def invert(self, X, orig_length: Optional[int] = None, **kwargs):
         """torch.istft(..., length=orig_length)  (feature_extractors.py:98-109)."""
-        from . import ops
         shp = X.shape
         T = shp[-1]
         if orig_length is None:
@@ -471,13 +472,11 @@ class AmplitudeCompressedComplexSTFT(nn.Module):
 
     def forward(self, x, **kwargs):
         """x: [B, C, T] or [B, T] real (GPU) -> complex STFT, compressed (no normalisation, no padding)."""
-        from . import ops
         shp = x.shape
         Y, _, T = ops.stft_compress(x.reshape(-1, shp[-1]).float().contiguous(), normalize=False, **self._cfg())
         return Y[:, 0, :, :T].reshape(*shp[:-1], Y.shape[2], T)
 
     def invert(self, X, orig_length: Optional[int] = None, **kwargs):
-        from . import ops
         shp = X.shape
         T = shp[-1]
         if orig_length is None:
@@ -504,35 +503,6 @@ def sigma_y_from_file(filename: str, factor: float = 1.0, kernel_bandwidth: Opti
     return factor * torch.from_numpy(curve).unsqueeze(-1)
 
 
-def padded_frames_of(num_samples: int, hop: int = 384) -> int:
-    """T_pad of a clip of `num_samples` samples: pad_spec(1 + L // hop) (util/other.py:25-52) -- the bucket key of `enhance_batch`."""
-    lib = L.load()
-    return int(lib.fd_padded_frames(lib.fd_num_frames(int(num_samples), int(hop))))
-
-
-def _ragged_bucket(clips, cfg):
-    """The bucket rule of every `enhance_batch`: clips [L], [1, L] or [1, 1, L] that all pad to ONE frame count.  -> (the clips flattened,
-    their lengths, T_pad, the row length).  The row length is the bucket's LARGEST possible clip (1 + Lrow // hop == T_pad): one
-    workspace / one hipGraph per (B, T_pad)."""
-    from . import ops
-    lib = L.load()
-    hop = cfg["hop"]
-    flat = []
-    for i, c in enumerate(clips):
-        if c.ndim > 3 or any(d != 1 for d in c.shape[:-1]):
-            raise RuntimeError(f"enhance_batch: clip {i} must be [L], [1, L] or [1, 1, L] (got {tuple(c.shape)})")
-        flat.append(c.reshape(-1))
-    lens = [int(c.numel()) for c in flat]
-    Tps = {lib.fd_padded_frames(lib.fd_num_frames(l, hop)) for l in lens}
-    if len(Tps) != 1:
-        raise RuntimeError(f"enhance_batch: the clips pad to different frame counts {sorted(Tps)}; one call takes one T_pad bucket "
-                           f"(bucket with flowdec_amd.model.padded_frames_of)")
-    Tp = Tps.pop()
-    Lrow = hop * Tp - 1
-    ops.check_ragged_lengths(lens, Lrow, cfg["n_fft"], hop)
-    return flat, lens, Tp, Lrow
-
-
 def _check_step_control(step_control, solver, who):
     """`step_control` of the adaptive solvers: None / 'batch' (one controller for the batch) or 'clip' (one per clip) -> per-clip?"""
     if step_control not in (None, "batch", "clip"):
@@ -551,16 +521,6 @@ def _per_clip_generators(generator, noise, B):
     return gens
 
 
-def _to_3d(y, who, rows="B"):
-    """[L] / [1, L] / [B, 1, L] -> ([B, 1, L], the number of axes added in front: `squeeze_dims`, model.py:146-149), or raise."""
-    y3, squeeze_dims = y, 0
-    while y3.ndim < 3:
-        y3 = y3.unsqueeze(0); squeeze_dims += 1
-    if y3.ndim != 3 or y3.shape[1] != 1:
-        raise RuntimeError(f"{who} [L], [1, L] or [{rows}, 1, L] waveforms (got {tuple(y.shape)})")
-    return y3, squeeze_dims
-
-
 def _preprocess_info(Lw, normfac, T, squeeze_dims):
     """preprocess_info of the reference (model.py:161-162); normfac: the B factors of the clips, T: the frames before pad_spec."""
     return dict(orig_length=Lw, normfac=normfac.reshape(-1, 1, 1), undo_pad_fn=(lambda Y_, T=T: Y_[..., :T]), squeeze_dims=squeeze_dims)
@@ -568,7 +528,6 @@ def _preprocess_info(Lw, normfac, T, squeeze_dims):
 
 def _traj_waveforms(traj, T, Lw, normfac, cfg, lengths=None):
     """Every state of a solver trajectory [N + 1, B, 1, F, T_pad] back in the time domain -> list of N + 1 waveforms [B, 1, Lw]."""
-    from . import ops
     return [ops.decompress_istft(X, T, Lw, normfac, lengths=lengths, **cfg).reshape(-1, 1, Lw) for X in traj]
 
 
@@ -576,7 +535,6 @@ def _preprocess(model, y, x=None, comp_eps=None):
     """EnhancementModel._preprocess (model.py:129-163): [L] / [1, L] / [B, 1, L] waveform(s) -> the reference's 3-tuple
     (Y, X, preprocess_info): Y [B, 1, F, T_pad] complex64 with the frame axis zero-padded to a multiple of 64, X the same
     features of the optional clean waveform `x` normalised by y's factor (None when x is None)."""
-    from . import ops
     if comp_eps is not None:
         raise NotImplementedError("flowdec_amd: comp_eps (a training-time regulariser, feature_extractors.py:124-125) is not supported")
     if x is not None and x.shape != y.shape:
@@ -598,7 +556,6 @@ def _postprocess(model, X_hat, preprocess_info, inv_kwargs=None, batch_filter=No
     """EnhancementModel._postprocess (model.py:165-190): undo padding, invert the features, [select batch items,] restore the
     level and the rank.  `inv_kwargs` is forwarded to the feature extractor's invert like the reference does; the native
     inverse has no optional arguments, so a non-empty dict is rejected instead of being silently ignored."""
-    from . import ops
     I = preprocess_info
     assert {"orig_length", "normfac", "undo_pad_fn", "squeeze_dims"} <= I.keys()   # model.py:180
     if inv_kwargs:
@@ -655,6 +612,10 @@ class _WaveModel(nn.Module):
         self.backbone._stft_cfg = self.feature_extractor._cfg()
         self.backbone._normalize = self.normalize_mode == "noisy"
         return self.backbone.handle()
+
+    def _native_call(self):
+        """The `_NativeCall` of this model's backbone, for native calls made outside this module (flowdec_amd/loss.py)."""
+        return _NativeCall(self.backbone)
 
     def _gpu(self):
         dev = self.device
@@ -769,15 +730,12 @@ class _WaveModel(nn.Module):
             if seeds is not None:
                 n_draws = 0
             io = self._io_entry(B, Lrow, dev, n_draws, seeded=seeds is not None, ragged=True)
-            io["y"].zero_()
-            for b, c in enumerate(flat):
-                io["y"][b, :lens[b]].copy_(c)
-                if n_draws:
-                    shape = (n_draws, 1, 1) + tuple(io["noise"].shape[3:])
-                    z = noise[b].to(dev, torch.complex64).reshape(shape) if noise is not None else \
-                        torch.randn(shape, dtype=torch.complex64, device=dev, generator=gens[b])
-                    io["noise"][:, b:b + 1].copy_(z)
-            io["lens"].copy_(torch.tensor(lens, dtype=torch.int32))
+            io["lens"].copy_(padded_rows(flat, Lrow, dev, out=io["y"])[1])
+            for b in range(B if n_draws else 0):
+                shape = (n_draws, 1, 1) + tuple(io["noise"].shape[3:])
+                z = noise[b].to(dev, torch.complex64).reshape(shape) if noise is not None else \
+                    torch.randn(shape, dtype=torch.complex64, device=dev, generator=gens[b])
+                io["noise"][:, b:b + 1].copy_(z)
             if seeds is not None:
                 io["seeds"].copy_(fd_noise.seeds_to_tensor(list(seeds) if not isinstance(seeds, torch.Tensor) else seeds, B, dev))
             ws = self._enhance_workspace(lib, h, B, Lrow, dev)
@@ -905,12 +863,10 @@ class FlowModel(_WaveModel):
         """FlowModel._loss (model.py:421-468) on clean x / coded y of one length, without gradients: the `valid_loss` of validation_step.
         seed= (the library's noise and time), noise= [n_draws, B, 1, F, T_pad] (draw 0: Ys, draw 1: Xs when sigma_x != 0), t= [B];
         reduce='none' -> per-clip values (float64); return_t=True adds the times.  See flowdec_amd/loss.py."""
-        from . import loss as fd_loss
         return fd_loss.valid_loss(self, "flow", x, y, seed=seed, noise=noise, t=t, reduce=reduce, return_t=return_t, comp_eps=comp_eps)
 
     def valid_loss_batch(self, xs, ys, *, seeds=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, max_batch: int = 8):
         """`valid_loss` for lists of pairs of any lengths, bucketed by padded frame count; every pair bit-identical to its one-pair call."""
-        from . import loss as fd_loss
         return fd_loss.valid_loss_batch(self, "flow", xs, ys, seeds=seeds, noise=noise, t=t, reduce=reduce, return_t=return_t, max_batch=max_batch)
 
     def _long_buffers(self, B, Lrow, dev):
@@ -1002,7 +958,6 @@ class FlowModel(_WaveModel):
     def _long_plan(self, y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, normfac=None):
         """Argument checks and the host-side geometry of a long-form call: rows, bucket, the (channel, row) job pool, per-channel seeds."""
         from types import SimpleNamespace
-        from . import longform, ops
         if solver not in L.SOLVERS:
             raise ValueError(f"enhance_long: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
         if int(rows_per_call) < 1:
@@ -1090,7 +1045,6 @@ class FlowModel(_WaveModel):
 
     def _long_stitch_rows(self, lib, plan, row_out):
         """fd_stitch_chunks per channel over the outputs of all jobs -> [C, n]."""
-        from . import longform
         dev, rows, R, n, xfade = plan.dev, plan.rows, plan.R, plan.n, plan.xfade
         x_hat = torch.empty(plan.C, n, dtype=torch.float32, device=dev)
         starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
@@ -1107,7 +1061,6 @@ class FlowModel(_WaveModel):
         `self.last_nfe`.  per_clip: every clip under its own controller (fd_ode_solve_adaptive_clips); then `seeds` (device int64 [B])
         may replace `noise` ([1, B, 1, F, Tp]), and `lengths` makes the batch ragged (clip b = the first lengths[b] samples of its row).
         -> (x_hat [B, 1, Lw], normfac [B]), or with return_traj (the trajectory, its waveforms)."""
-        from . import ops
         cfg, dev = self.feature_extractor._cfg(), y_rows.device
         F, T, Tp = self._frames(Lw)
         Y, normfac, _ = ops.stft_compress(y_rows, normalize=self.normalize_mode == "noisy", lengths=lengths, **cfg)
@@ -1141,7 +1094,6 @@ class FlowModel(_WaveModel):
     def _enhance_traj(self, lib, h, y_rows, noise, seeds, B, Lw, N, solver, sigma_fac):
         """A fixed-step solve that keeps every solver state: front end, solver and back end as separate native calls; `seeds` (device int64
         [B]) selects the seeded solver, which reads no noise.  -> (the trajectory, its waveforms)."""
-        from . import ops
         cfg, dev = self.feature_extractor._cfg(), y_rows.device
         F, T, Tp = self._frames(Lw)
         Y, normfac, _ = ops.stft_compress(y_rows, normalize=self.normalize_mode == "noisy", **cfg)
@@ -1205,11 +1157,9 @@ class ScoreModel(_WaveModel):
 
     def valid_loss(self, x, y, *, seed=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, comp_eps=None):
         """ScoreModel._loss (model.py:590-611) without gradients; the time is drawn over [t_eps, 1).  See FlowModel.valid_loss."""
-        from . import loss as fd_loss
         return fd_loss.valid_loss(self, "score", x, y, seed=seed, noise=noise, t=t, reduce=reduce, return_t=return_t, comp_eps=comp_eps)
 
     def valid_loss_batch(self, xs, ys, *, seeds=None, noise=None, t=None, reduce: str = "mean", return_t: bool = False, max_batch: int = 8):
-        from . import loss as fd_loss
         return fd_loss.valid_loss_batch(self, "score", xs, ys, seeds=seeds, noise=noise, t=t, reduce=reduce, return_t=return_t, max_batch=max_batch)
 
     def _pc_config(self, predictor, corrector, N, corrector_steps, snr, denoise, eps=None):
@@ -1278,7 +1228,6 @@ class ScoreModel(_WaveModel):
         the GPU, the STFT / iSTFT run in libflowdec_hip.so.  Host-driven and slow by construction (the state crosses PCIe
         twice per evaluation) -- it exists for API parity with ScoreModel.enhance."""
         from scipy import integrate
-        from . import ops
         dev = self._gpu()
         orig_device = y.device
         y3, squeeze_dims = _to_3d(y, "enhance expects")
@@ -1337,11 +1286,9 @@ class RegressionModel(_WaveModel):
 
     def valid_loss(self, x, y, *, reduce: str = "mean", comp_eps=None):
         """RegressionModel._loss (model.py:552-559) without gradients: mean |backbone(Y, Y, 0) - X|^2.  No random draws."""
-        from . import loss as fd_loss
         return fd_loss.valid_loss(self, "regression", x, y, reduce=reduce, comp_eps=comp_eps)
 
     def valid_loss_batch(self, xs, ys, *, reduce: str = "mean", max_batch: int = 8):
-        from . import loss as fd_loss
         return fd_loss.valid_loss_batch(self, "regression", xs, ys, reduce=reduce, max_batch=max_batch)
 
     @torch.no_grad()

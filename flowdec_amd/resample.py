@@ -1,10 +1,10 @@
 """Resampling on the device: torchaudio's polyphase sinc resampler as an exact HIP kernel, one-shot, ragged and streaming.
 
-The filter bank is `enhance_cli.sinc_resample_kernel`'s array (the pinned restatement of torchaudio.functional.resample); the kernel
+The filter bank is `audio.sinc_resample_kernel`'s array (the pinned restatement of torchaudio.functional.resample); the kernel
 (csrc/resample.hip, include/flowdec_hip.h "Resampling") sums every output in float64 in ascending tap order and rounds once, so
 
   * `Resampler(o, n)(x)` is reproduced bit for bit by a plain NumPy loop (tests/resample_oracle.py), and differs from the host
-    `enhance_cli.resample` by float32 rounding of the FIR only;
+    `audio.resample` by float32 rounding of the FIR only;
   * a clip's output does not depend on the batch it is in (`Resampler.batch`: one ragged call);
   * a stream's concatenated output (`ResampleStream`) is the one-shot output whatever the cut of the input into pushes.
 
@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .audio import sinc_resample_kernel
+from .batching import padded_rows
 
 BANK_CAP = 1 << 24          # n * K coefficients (fd_resample_plan_create)
 
@@ -95,7 +97,6 @@ class Resampler:
     Equal rates return the input unchanged.  A pair whose bank is over the cap (n K > 2^24) raises ValueError."""
 
     def __init__(self, orig_freq: int, new_freq: int, lowpass_filter_width: int = 64, rolloff: float = 0.99, device="cuda"):
-        from .enhance_cli import sinc_resample_kernel
         self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff = int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff)
         self.o, self.n, self.width = rate_ratio(orig_freq, new_freq, lowpass_filter_width, rolloff)
         self.K = 2 * self.width + self.o
@@ -174,10 +175,7 @@ class Resampler:
         lens = [int(c.numel()) for c in clips]
         Lmax = max(max(lens), 1)
         Mmax = self.out_length(Lmax)
-        x = torch.zeros(len(clips), Lmax, dtype=torch.float32, device=self.device)
-        for b, c in enumerate(clips):
-            x[b, :lens[b]] = c
-        lengths = torch.tensor(lens, dtype=torch.int32).to(self.device)
+        x, lengths = padded_rows(clips, Lmax, self.device)
         y = torch.empty(len(clips), Mmax, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             L.check(L.load().fd_resample(self._plan, L.ptr(x), L.ptr(lengths), len(clips), Lmax, L.ptr(y), Mmax, L.stream()))
@@ -213,7 +211,7 @@ def get_resampler(orig_freq: int, new_freq: int, lowpass_filter_width: int = 64,
 
 
 def resample_device(y: torch.Tensor, sr: int, target: int, lowpass_filter_width: int = 64, rolloff: float = 0.99) -> torch.Tensor:
-    """`enhance_cli.resample` on the device `y` lives on: [..., L] float32 -> [..., ceil(n L / o)], plans cached per
+    """`audio.resample` on the device `y` lives on: [..., L] float32 -> [..., ceil(n L / o)], plans cached per
     (o, n, lowpass_filter_width, rolloff, device)."""
     if int(sr) == int(target):
         return y

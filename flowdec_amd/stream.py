@@ -26,6 +26,8 @@ import torch
 from . import _lib as L
 from . import longform
 from . import noise as fd_noise
+from . import ops
+from . import resample as R
 from .model import _serialized
 
 
@@ -200,7 +202,6 @@ class StreamPool:
     @_serialized
     def flush_many(self, sids) -> Dict[int, torch.Tensor]:
         """`flush` for several sessions that end together: their rows share native calls (still at most one row per session per call)."""
-        from . import ops
         lib, hop = L.load(), self.geom.hop
         ss = [self._session(sid) for sid in dict.fromkeys(sids)]
         outs = {s.sid: [] for s in ss}
@@ -324,7 +325,6 @@ class EnhanceStream:
     the model's rate and the model's rate; `delay_samples` stays the pool's."""
 
     def __init__(self, model, seed, in_rate: Optional[int] = None, out_rate: Optional[int] = None, **pool_kwargs):
-        from . import resample as R
         self.pool = StreamPool(model, capacity=1, **pool_kwargs)
         self.sid = self.pool.open(seed)
         self.delay_samples = self.pool.delay_samples

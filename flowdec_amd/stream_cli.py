@@ -19,6 +19,9 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from .checkpoint import load_from_checkpoint
+from .stream import EnhanceStream
+
 FORMATS = {"s16le": np.dtype("<i2"), "f32le": np.dtype("<f4")}
 
 
@@ -79,8 +82,6 @@ def encode(x: torch.Tensor, fmt: str) -> bytes:
 
 def run(argv: Optional[List[str]] = None, model=None) -> int:
     """-> the number of samples written.  `model`: an already loaded FlowModel (tests)."""
-    from .enhance_cli import load_from_checkpoint
-    from .stream import EnhanceStream
     args = parse_args(argv)
     if model is None:
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model="flow")

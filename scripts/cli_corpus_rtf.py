@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "r06_cli_corpus_rtf.json"))
     args = ap.parse_args()
     import flowdec_amd
-    from flowdec_amd import boxprobe, enhance_cli
+    from flowdec_amd import audio, boxprobe, enhance_cli
     from flowdec_amd.model import padded_frames_of
 
     tmp = tempfile.mkdtemp(prefix="fd_corpus_")
@@ -72,7 +72,7 @@ def main():
         rng = np.random.default_rng(0)
         lens = rng.integers(int(args.min_s * 48000), int(args.max_s * 48000) + 1, size=args.files)
         for i, n in enumerate(lens):
-            enhance_cli.save_wav(os.path.join(ind, f"clip{i:03d}.wav"), torch.from_numpy((0.1 * rng.standard_normal((1, int(n)))).astype(np.float32)), 48000)
+            audio.save_wav(os.path.join(ind, f"clip{i:03d}.wav"), torch.from_numpy((0.1 * rng.standard_normal((1, int(n)))).astype(np.float32)), 48000)
         buckets = {}
         for n in lens:
             buckets[padded_frames_of(int(n))] = buckets.get(padded_frames_of(int(n)), 0) + 1

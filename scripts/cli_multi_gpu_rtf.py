@@ -53,7 +53,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cli_multi_gpu_rtf.json"))
     args = ap.parse_args()
     import flowdec_amd
-    from flowdec_amd import enhance_cli
+    from flowdec_amd import audio, enhance_cli
 
     tmp = tempfile.mkdtemp(prefix="fd_multi_")
     try:
@@ -79,7 +79,7 @@ def main():
         rng = np.random.default_rng(0)
         lens = rng.integers(int(args.min_s * 48000), int(args.max_s * 48000) + 1, size=args.files)
         for i, n in enumerate(lens):
-            enhance_cli.save_wav(os.path.join(ind, f"clip{i:03d}.wav"), torch.from_numpy((0.1 * rng.standard_normal((1, int(n)))).astype(np.float32)), 48000)
+            audio.save_wav(os.path.join(ind, f"clip{i:03d}.wav"), torch.from_numpy((0.1 * rng.standard_normal((1, int(n)))).astype(np.float32)), 48000)
         devices = enhance_cli.visible_gpus()
         if devices < 1:
             raise RuntimeError("no GPU visible")

@@ -3,7 +3,7 @@
 scripts/estimate_flowdec_params.py computes, not the reference), on `--pairs` synthetic pairs of `--seconds` s at 48 kHz.
 
 Loading and computing are reported separately: the pairs are first written as PCM16 wavs into a temporary directory and read back with
-eval_cli.load_mono (what estimate_cli does per file), then both sides compute from the clips in host memory.  The GPU side includes its
+audio.load_mono (what estimate_cli does per file), then both sides compute from the clips in host memory.  The GPU side includes its
 host-to-device copies and the read-back.  The two sides run interleaved, `--repeats` times each after one warm-up of the GPU side.
 
     python scripts/estimate_timing.py [--pairs 256] [--seconds 2] [--batch-pairs 64] [--repeats 3] [--out profiles/estimate_timing.json]
@@ -57,7 +57,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "estimate_timing.json"))
     args = ap.parse_args()
     from flowdec_amd import estimate as E
-    from flowdec_amd.eval_cli import load_mono
+    from flowdec_amd.audio import load_mono
 
     n = int(args.seconds * 48000)
     rng = np.random.default_rng(0)

@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "estoi_timing.json"))
     args = ap.parse_args()
     from flowdec_amd import _lib as L, boxprobe, eval_cli, metrics
+    from flowdec_amd.batching import padded_rows
 
     sr = 48000
     rng = np.random.default_rng(0)
@@ -64,9 +65,8 @@ def main():
     # the batches of estoi_batch, staged on the device once
     staged = []
     for idx in metrics.length_sorted_batches([int(n) for n in lens], args.batch_files):
-        h, x = metrics._rows(hs, idx, "cuda"), metrics._rows(xs, idx, "cuda")
-        ln = torch.tensor([int(lens[i]) for i in idx], dtype=torch.int32, device="cuda")
-        B, Lmax = x.shape
+        B, Lmax = len(idx), max(int(lens[i]) for i in idx)
+        (h, _), (x, ln) = (padded_rows([torch.as_tensor(l[i]).reshape(-1) for i in idx], Lmax, "cuda") for l in (hs, xs))
         nws = lib.fd_metrics_estoi_workspace_bytes(B, Lmax, plans.o, plans.n)
         staged.append((idx, h, x, ln, torch.empty(nws, dtype=torch.uint8, device="cuda"), torch.empty(B, dtype=torch.float64, device="cuda"),
                        torch.empty(B, 3, dtype=torch.int32, device="cuda")))

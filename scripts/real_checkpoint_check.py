@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from flowdec_amd import enhance_cli, metrics  # noqa: E402
+from flowdec_amd import audio, checkpoint, enhance_cli, metrics  # noqa: E402
 
 
 def rel(a, b):
@@ -44,16 +44,16 @@ def run(argv=None, models=None):
     a = ap.parse_args(argv)
     noisy, _ = enhance_cli.collect_files(a.files, a.single_file)
     if models is None:
-        models = {p: enhance_cli.load_from_checkpoint(a.ckpt, map_location="cuda:0", ema=not a.no_ema, precision=p) for p in ("fp32", "bf16x3", "bf16")}
+        models = {p: checkpoint.load_from_checkpoint(a.ckpt, map_location="cuda:0", ema=not a.no_ema, precision=p) for p in ("fp32", "bf16x3", "bf16")}
     rows = []
     for path in noisy:
         if len(rows) >= a.max_files:
             break
-        y, sr = enhance_cli.load_wav(path)
+        y, sr = audio.load_wav(path)
         if y.shape[-1] / sr > enhance_cli.MAX_SECONDS:
             continue
         if sr != models["bf16"].sampling_rate:
-            y = enhance_cli.resample(y, sr, models["bf16"].sampling_rate)
+            y = audio.resample(y, sr, models["bf16"].sampling_rate)
         out, rtf = {}, {}
         for p, m in models.items():
             gen = torch.Generator(device=m.device).manual_seed(a.seed + len(rows))     # the same noise for the three precisions

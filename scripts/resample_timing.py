@@ -1,4 +1,4 @@
-"""Device resampler timing (MEASUREMENTS.md, "Device resampler"): host `enhance_cli.resample` against `resample_device`, what the float64
+"""Device resampler timing (MEASUREMENTS.md, "Device resampler"): host `audio.resample` against `resample_device`, what the float64
 contract costs, and the two places the resampler is wired in.
 
     python scripts/resample_timing.py [--seconds 30] [--repeats 20] [--f32-lib PATH] [--skip-eval] [--skip-stream] [--out profiles/resample_timing.json]
@@ -66,7 +66,7 @@ def host_clock(fn):
 
 def one_shot(args, say):
     from flowdec_amd import _lib as L
-    from flowdec_amd.enhance_cli import resample, sinc_resample_kernel
+    from flowdec_amd.audio import resample, sinc_resample_kernel
     from flowdec_amd.resample import get_resampler, resample_device
     lib64, lib32 = L.load(), bind(args.f32_lib if os.path.exists(args.f32_lib) else build_f32_variant(args.f32_lib))
     n_in = int(args.seconds * 44100)
@@ -119,7 +119,7 @@ def one_shot(args, say):
 
 def eval_corpus(args, say):
     from flowdec_amd import eval_cli
-    from flowdec_amd.enhance_cli import save_wav
+    from flowdec_amd.audio import save_wav
     rng = np.random.default_rng(0)
     lens = rng.integers(44100, 4 * 44100 + 1, size=args.files)
     with tempfile.TemporaryDirectory() as d:

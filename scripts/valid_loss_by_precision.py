@@ -52,7 +52,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from flowdec_amd import loss_cli
-    from flowdec_amd.enhance_cli import load_from_checkpoint
+    from flowdec_amd.checkpoint import load_from_checkpoint
     if args.ckpt:
         if not args.pairs_file:
             ap.error("--ckpt needs --pairs-file")

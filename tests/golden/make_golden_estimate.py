@@ -3,7 +3,7 @@
 Runs only where the reference is present; none of its code travels, only the numbers written here.
 
 Route taken: the script's REAL `__main__` through runpy.run_path (not a restatement), with make_golden.py's import stubs and two more:
-  * torchaudio.load -> flowdec_amd.enhance_cli.load_wav (torchaudio is not installed; the corpus is PCM16 at 48 kHz, so no resampling runs);
+  * torchaudio.load -> flowdec_amd.audio.load_wav (torchaudio is not installed; the corpus is PCM16 at 48 kHz, so no resampling runs);
   * Module.to / Tensor.to send `cuda:*` device strings to the CPU (the script hard-codes device=f'cuda:{args.device}').
 Four runs at --alpha 0.3 --nfft 1534 --hop 384 --n-samples 8 --seed 302: global and --per-band, each in float32 (the script as it is) and
 with every tensor in float64 (the wav reader returns float64 and torch's default dtype is float64, so the window, the transform, the
@@ -44,7 +44,7 @@ def _cpu(v):
 
 @contextlib.contextmanager
 def patched(double: bool):
-    from flowdec_amd.enhance_cli import load_wav
+    from flowdec_amd.audio import load_wav
     ta = sys.modules["torchaudio"]
 
     def load(path):

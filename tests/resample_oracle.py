@@ -1,6 +1,6 @@
 """NumPy restatement of the resampling contract of include/flowdec_hip.h ("Resampling").
 
-With o = orig / gcd, n = new / gcd, K = 2 width + o and the float32 bank h[n][K] of `enhance_cli.sinc_resample_kernel`, output
+With o = orig / gcd, n = new / gcd, K = 2 width + o and the float32 bank h[n][K] of `audio.sinc_resample_kernel`, output
 m = q n + i of an input of L samples is
     acc = 0.0 (float64);  for k = 0 .. K-1 ascending:  j = q o + k - width;  if 0 <= j < L: acc += float64(h[i][k]) * float64(x[j])
     y[m] = float32(acc)

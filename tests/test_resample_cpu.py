@@ -168,15 +168,14 @@ def test_pair_over_the_bank_cap_falls_back_to_the_host_with_one_line(tmp_path, c
     """47999 -> 48000 Hz asks for a 9 GB bank: --resample device then takes the host path (stubbed here: only the routing is under test)
     and says so in one line; no GPU is touched."""
     from types import SimpleNamespace
-    from flowdec_amd import enhance_cli, eval_cli
+    from flowdec_amd import audio, enhance_cli, eval_cli
     calls = []
 
     def host(y, sr, target, lowpass_filter_width=64, rolloff=0.99):
         calls.append((sr, target, lowpass_filter_width))
         return y + 1
 
-    monkeypatch.setattr(enhance_cli, "resample", host)
-    monkeypatch.setattr(eval_cli, "host_resample", host)
+    monkeypatch.setattr(audio, "resample", host)      # the one router (audio.resample_to) serves both command lines
     x = torch.from_numpy((0.1 * np.random.default_rng(5).standard_normal((1, 300))).astype(np.float32))
     capsys.readouterr()
     got = enhance_cli.resample_for_model(x, 47999, SimpleNamespace(sampling_rate=48000, device=torch.device("cuda:0")), "device")
