@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "align.h"
 #include "flowdec_hip.h"
 
 typedef __bf16 bf16;
@@ -37,7 +38,6 @@ int fd_set_error(int code, const char* fmt, ...);
   } while (0)
 
 static inline hipStream_t fd_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline size_t fd_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int fd_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t fd_dtype_size(int dtype) { return dtype == FD_BF16 ? 2 : 4; }
 

@@ -917,7 +917,7 @@ __global__ __launch_bounds__(256) void noise_fill_kernel(float2* __restrict__ ou
   }
 }
 
-// ---- adaptive Dormand-Prince driver helpers (model.hip: fd_ode_solve_adaptive) ------------------------------------
+// ---- adaptive Dormand-Prince driver helpers (solve.hip: adaptive_solve) ------------------------------------
 struct fd_lincomb_args { const float2* k[7]; float c[7]; };
 // dst = cx * x + dt * sum_i c[i] * k[i]   (null k[i] / zero c[i] are skipped by the host).  One body for the batch-global launch (off = 0,
 // n = the whole state) and the per-clip launch (off = the clip's first element, n = one clip): an element's bits depend on its operands only

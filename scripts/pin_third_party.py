@@ -12,7 +12,9 @@ real package are written next to the existing fixtures, and a JSON report says P
 are reported as "absent" and skipped (exit status 0): that is the state of the offline container, where this script cannot pin anything.
 tests/test_pin_third_party.py runs the same checks under pytest (skipped when both packages are absent).
 
-Rows this flips in DESIGN.md section 1 once it has run green somewhere: f4 (adaptive solvers, driver semantics of a6) and f2 (NDAC)."""
+Rows this flips in DESIGN.md section 1 once it has run green somewhere: f4 (adaptive solvers, driver semantics of a6) and f2 (NDAC).
+Row f4 also records a one-ulp difference in the stage times between the oracle's `dopri5_adapt_step` (float32 product under NumPy 2) and
+the library's `StepCtl::end` (double product, rounded once): the adaptive comparison here says which of the two is torchdyn's."""
 import argparse
 import json
 import os

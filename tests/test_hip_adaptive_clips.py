@@ -145,6 +145,24 @@ def test_equal_lengths_and_the_default_is_unchanged():
         m.enhance(y, N=N, solver="midpoint", step_control="clip", noise=nz)
 
 
+@pytest.mark.parametrize("source", ["noise", "seed"])
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_one_clip_batch_control_equals_clip_control(solver, source):
+    """ONE clip: step_control='batch' and 'clip' are the same solve, waveform and NFE, from a noise plane and from a seed.  The two modes
+    share their host loop (solve.hip: adaptive_solve) and differ in a policy; this case keeps the two policies one algorithm."""
+    from flowdec_amd.noise import clip_seed
+    m = model("bf16x3")
+    src = dict(noise=noises()[0]) if source == "noise" else dict(seed=[clip_seed(21, 0)])
+    kw = dict(N=N, solver=solver, atol=TOL, rtol=TOL, **src)
+    c = clips()[0]                                                   # 12000 samples
+    a = m.enhance(c, step_control="batch", **kw)
+    n_a = m.last_nfe
+    b = m.enhance(c, step_control="clip", **kw)
+    assert torch.isfinite(a).all() and a.abs().max() > 0
+    assert torch.equal(a, b), "one clip: the batch-global controller != the per-clip controller"
+    assert n_a == m.last_nfe == int(m.last_nfe_per_clip[0]) == m.last_evals and (n_a - 2) % 6 == 0 and (n_a - 2) // 6 >= N
+
+
 @pytest.mark.parametrize("solver", SOLVERS)
 def test_seeded(solver):
     """seeds= draws the initial plane inside the solver: clip b = enhance(clip_b, seed=[s_b]) of today, and = the buffer form on
