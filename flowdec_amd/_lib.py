@@ -218,6 +218,12 @@ SIGNATURES = {
     "fd_metrics_estoi_max_frames": (c_int, [c_int] * 3),
     "fd_metrics_estoi": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "fd_metrics_estoi_bands": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "fd_specdist_tables": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "fd_specdist_plan_create": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int), C.POINTER(_P)]),
+    "fd_specdist_plan_destroy": (None, [_P]),
+    "fd_metrics_specdist_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "fd_metrics_specdist": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "fd_metrics_specdist_spectra": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

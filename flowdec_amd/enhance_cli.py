@@ -65,7 +65,8 @@ one-GPU boxes, not a speed-up.  The split is static (no work stealing): that is 
 Evaluation: `--eval` (pair lists only, default off; without it nothing changes) scores the `triples_list{suffix}.txt` the run has just
 written -- after the merge in the launcher of a --gpus N run -- with `flowdec_amd.eval_cli` on one GPU: SI-SDR / SI-SIR / SI-SAR and
 LogSpecMSE per triple into `metrics{suffix}.csv` beside the list.  The files are scored as they were written to disk, as the reference's
-evaluation scores them (flowdec/eval/metrics.py).  `--eval-estoi` (with --eval) passes `--estoi` on: a fifth column, ESTOI.
+evaluation scores them (flowdec/eval/metrics.py).  `--eval-estoi` (with --eval) passes `--estoi` on: a fifth column, ESTOI;
+`--eval-spectral` passes `--spectral` on: two last columns, the multi-scale STFT and mel distances.
 """
 import argparse
 import collections
@@ -155,6 +156,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="pair lists only: after the run (after the merge of a --gpus N run), score the triples list just written with "
                         "flowdec_amd.eval_cli on one GPU -> metrics{suffix}.csv next to it; the files are scored as written to disk")
     p.add_argument("--eval-estoi", action="store_true", help="with --eval: also score ESTOI (eval_cli --estoi), a last column `estoi` of the CSV")
+    p.add_argument("--eval-spectral", action="store_true",
+                   help="with --eval: also score the multi-scale STFT and mel distances (eval_cli --spectral), two last columns `msstft` and `mel`")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -589,11 +592,12 @@ def launch_workers(argv: List[str], world: int, manifest: str, share_gpu: bool):
 
 
 def evaluate_triples(args, suffix: str) -> None:
-    """--eval: SI-SxR and LogSpecMSE (--eval-estoi: and ESTOI) of `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it
+    """--eval: SI-SxR and LogSpecMSE (--eval-estoi: and ESTOI; --eval-spectral: and msstft, mel) of `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it
     (flowdec_amd/eval_cli.py)."""
     with torch.cuda.device(args.device):
         eval_cli.run(["--triples", os.path.join(args.outdir, f"triples_list{suffix}.txt"), "--out", os.path.join(args.outdir, f"metrics{suffix}.csv"),
-                      "--batch-files", str(max(args.batch_files, 1))] + (["--estoi"] if getattr(args, "eval_estoi", False) else []))
+                      "--batch-files", str(max(args.batch_files, 1))] + (["--estoi"] if getattr(args, "eval_estoi", False) else [])
+                     + (["--spectral"] if getattr(args, "eval_spectral", False) else []))
 
 
 def run_launcher(args, parser, argv: List[str]) -> RunResult:

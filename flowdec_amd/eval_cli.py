@@ -2,7 +2,7 @@
 flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for those of its metrics that need no outside model or program.
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
-                                   [--sr 48000] [--estoi]
+                                   [--sr 48000] [--estoi] [--spectral]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -25,6 +25,15 @@ frames after the silent frames are removed gets pystoi's value 1e-05 and a warni
 tests: the host function is pinned against SciPy's resampler and the published algorithm, parity with the package is UNPINNED
 (scripts/pin_estoi.py prints it where pystoi is importable).
 
+--spectral (off by default; without it every byte of the output is what it was, with or without --estoi) adds two last CSV columns,
+`msstft` and `mel` (after `estoi` when both switches are given), and two summary lines: the multi-scale STFT distance and the multi-scale
+mel distance of x_hat against x -- the arithmetic of the reference's MultiScaleSTFTLoss and MelSpectrogramLoss (flowdec/losses.py) at their
+default parameters, as metrics -- scored on the GPU in the same ragged batches (csrc/specdist.hip: a fused in-LDS FFT per frame pair;
+flowdec_amd/specdist.py spectral_distances_batch, host yardsticks multiscale_stft_distance and mel_distance).  A triple of 2048 samples or
+fewer cannot be reflect-padded for the 4096-sample window (the 2049-sample rule): NaN in those two columns and a warning.  The reference
+builds its mel bank with torchaudio, which is not available to the tests: the bank is restated in float64 and pinned by its defining
+properties, parity with the package is UNPINNED (scripts/pin_mel.py prints it where torchaudio is importable).
+
 The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
 (DESIGN section 9).
 """
@@ -39,12 +48,13 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import metrics
+from . import metrics, specdist
 from .audio import RESAMPLE_HELP, load_mono, split_pair
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
-ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), always the last column
+ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), the last column without --spectral
+SPECTRAL_NAMES = specdist.NAMES     # the optional metrics of --spectral (msstft, mel), always the last two columns
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -91,10 +101,12 @@ def min_spectral_samples(sr: int) -> int:
 @dataclass(frozen=True)
 class Scorer:
     """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]; estoi(x_hats, xs, sr,
-    batch) -> [n] (optional: only --estoi calls it)."""
+    batch) -> [n] (optional: only --estoi calls it); spectral(x_hats, xs, sr, batch) -> [n, 2] (msstft, mel) (optional: only --spectral
+    calls it)."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
+    spectral: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -121,21 +133,39 @@ def _host_estoi(x_hats, xs, sr, batch):
     return np.array([metrics.estoi(h, x, sr) for h, x in zip(x_hats, xs)], np.float64)
 
 
-GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi)        # ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip)
-HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi)    # the host functions of metrics.py, one triple at a time: the yardstick
+def _gpu_spectral(x_hats, xs, sr, batch):
+    return specdist.spectral_distances_batch(x_hats, xs, sr=sr, batch=batch)
 
 
-def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None, estoi: bool = False) -> np.ndarray:
+def _host_spectral(x_hats, xs, sr, batch):
+    return np.array([(specdist.multiscale_stft_distance(h, x), specdist.mel_distance(h, x, sr)) for h, x in zip(x_hats, xs)], np.float64).reshape(-1, 2)
+
+
+# ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip)
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral)
+# the host functions of metrics.py and specdist.py, one triple at a time: the yardstick
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral)
+
+
+def metric_columns(estoi: bool = False, spectral: bool = False) -> tuple:
+    """The names of the value columns, in order: the four metrics, then estoi, then msstft and mel."""
+    return METRIC_NAMES + ((ESTOI_NAME,) if estoi else ()) + (SPECTRAL_NAMES if spectral else ())
+
+
+def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None, estoi: bool = False,
+          spectral: bool = False) -> np.ndarray:
     """signals: one (x_hat, x, y) of 1-D tensors per triple, cropped -> [n, 4] float64 in METRIC_NAMES order, row i for triple i whatever
     order the batches ran in.  Unequal lengths: NaN in all four; too short for the transform: NaN in the spectral column.
-    estoi=True: [n, 5], the last column ESTOI (1e-5 and a warning under the 30-frame rule; NaN with the others for unequal lengths)."""
+    estoi=True: [n, 5], the last column ESTOI (1e-5 and a warning under the 30-frame rule; NaN with the others for unequal lengths).
+    spectral=True: two more last columns, msstft and mel (metric_columns gives the layout); NaN and a warning for a triple under the
+    2049-sample rule, NaN with the others for unequal lengths."""
     def warn(i, msg):
         print(f"warning: {names[i] if names else 'triple %d' % i}: {msg}", file=sys.stderr)
 
     def column(idx, k):
         return [signals[i][k] for i in idx]
 
-    out = np.full((len(signals), 5 if estoi else 4), np.nan, np.float64)
+    out = np.full((len(signals), len(metric_columns(estoi, spectral))), np.nan, np.float64)
     ok = []
     for i, (h, x, y) in enumerate(signals):
         if not (h.shape[-1] == x.shape[-1] == y.shape[-1]):
@@ -145,13 +175,13 @@ def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Opti
             warn(i, "empty signals: NaN for every metric")
         else:
             ok.append(i)
-    spectral = [i for i in ok if signals[i][1].shape[-1] >= min_spectral_samples(sr)]
-    for i in sorted(set(ok) - set(spectral)):
+    framed = [i for i in ok if signals[i][1].shape[-1] >= min_spectral_samples(sr)]
+    for i in sorted(set(ok) - set(framed)):
         warn(i, f"{signals[i][1].shape[-1]} samples are too few for the spectral metric (needs {min_spectral_samples(sr)}): NaN for logspec_mse")
     if ok:
         out[ok, :3] = scorer.si_sxr(column(ok, 0), column(ok, 1), column(ok, 2), batch)
-    if spectral:
-        out[spectral, 3] = scorer.logspec(column(spectral, 0), column(spectral, 1), sr, batch)
+    if framed:
+        out[framed, 3] = scorer.logspec(column(framed, 0), column(framed, 1), sr, batch)
     if estoi and ok:
         if scorer.estoi is None:
             raise ValueError("score: estoi=True needs a Scorer with an estoi function")
@@ -159,6 +189,14 @@ def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Opti
         for i in ok:
             if out[i, 4] == metrics.ESTOI_TOO_SHORT:
                 warn(i, metrics.ESTOI_SHORT_RULE)
+    if spectral:
+        if scorer.spectral is None:
+            raise ValueError("score: spectral=True needs a Scorer with a spectral function")
+        long_enough = [i for i in ok if signals[i][1].shape[-1] >= specdist.MIN_SAMPLES]
+        for i in sorted(set(ok) - set(long_enough)):
+            warn(i, f"{signals[i][1].shape[-1]} samples: {specdist.SHORT_RULE}")
+        if long_enough:
+            out[long_enough, -2:] = scorer.spectral(column(long_enough, 0), column(long_enough, 1), sr, batch)
     return out
 
 
@@ -166,18 +204,28 @@ def fmt(v: float) -> str:
     return "nan" if math.isnan(v) else repr(float(v))
 
 
-def write_csv(path: str, triples: List[Triple], values: np.ndarray) -> None:
+def _columns_of(values: np.ndarray, columns) -> tuple:
+    """columns=None: the four metrics, and estoi for [n, 5] values; else the caller's names (metric_columns), one per column of values."""
+    if columns is None:
+        return METRIC_NAMES + ((ESTOI_NAME,) if values.ndim == 2 and values.shape[1] == len(METRIC_NAMES) + 1 else ())
+    if values.ndim != 2 or values.shape[1] != len(columns):
+        raise ValueError(f"eval: {len(columns)} column names for values of shape {values.shape}")
+    return tuple(columns)
+
+
+def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None) -> None:
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER + ((ESTOI_NAME,) if values.shape[1] == len(METRIC_NAMES) + 1 else ()))
+        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns))
         for t, row in zip(triples, values):
             w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row])
 
 
-def summary(values: np.ndarray):
-    """-> [(metric, mean over its finite rows or NaN, count of finite rows)]; five entries for the [n, 5] values of --estoi."""
+def summary(values: np.ndarray, columns=None):
+    """-> [(metric, mean over its finite rows or NaN, count of finite rows)]; five entries for the [n, 5] values of --estoi; with
+    columns= (metric_columns) one entry per name."""
     out = []
-    for k, name in enumerate(METRIC_NAMES + ((ESTOI_NAME,) if values.ndim == 2 and values.shape[1] == len(METRIC_NAMES) + 1 else ())):
+    for k, name in enumerate(_columns_of(values, columns)):
         col = values[:, k] if len(values) else np.zeros(0)
         fin = col[np.isfinite(col)]
         out.append((name, float(fin.mean()) if len(fin) else float("nan"), int(len(fin))))
@@ -208,6 +256,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
     p.add_argument("--estoi", action="store_true",
                    help="also score ESTOI (pystoi.stoi(extended=True) restated; 10 kHz, on the GPU): a last CSV column `estoi` and a fifth mean")
+    p.add_argument("--spectral", action="store_true",
+                   help="also score the multi-scale STFT and mel distances (the reference's MultiScaleSTFTLoss / MelSpectrogramLoss as metrics; on "
+                        "the GPU): two last CSV columns `msstft` and `mel` and two more means")
     return p
 
 
@@ -225,10 +276,11 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
             continue
         kept.append(t)
         signals.append(crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat))
-    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept], estoi=args.estoi)
+    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept], estoi=args.estoi, spectral=args.spectral)
+    columns = metric_columns(args.estoi, args.spectral)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    write_csv(args.out, kept, values)
-    res.n_scored, res.means = len(kept), summary(values)
+    write_csv(args.out, kept, values, columns=columns)
+    res.n_scored, res.means = len(kept), summary(values, columns=columns)
     print(f"eval: {res.n_triples} triples, {res.n_scored} rows in {args.out}, {res.n_unreadable} skipped (unreadable)")
     for name, mean, count in res.means:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")

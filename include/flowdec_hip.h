@@ -897,6 +897,55 @@ int fd_metrics_estoi(const fd_estoi_plan* plan, const fd_resample_plan* resample
 int fd_metrics_estoi_bands(const fd_estoi_plan* plan, const fd_resample_plan* resample, const float* x_hat, const float* x, const int* lengths,
                            int B, int L, int* frames_out, int* kept_out, float* tob_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Spectral distances: the multi-scale STFT distance and the multi-scale mel distance between an estimate x_hat and a reference x (the
+ * arithmetic of the reference's MultiScaleSTFTLoss and MelSpectrogramLoss, flowdec/losses.py, at their default parameters, as metrics
+ * without gradients), over ragged batches (csrc/specdist.hip; host yardsticks and the definitions in full: flowdec_amd/specdist.py).
+ * Rows [B][L] float32 on the device; lengths: DEVICE int32 [B]; samples behind a clip's end are never read.  A clip's results have the
+ * SAME BITS alone, in a batch, at any batch position and next to clips of any other lengths: every partition and order of summation
+ * depends on the clip's own length only; no atomics.  Parity of the mel filter bank with torchaudio's melscale_fbanks is UNPINNED (the
+ * package is not available to the tests; scripts/pin_mel.py prints the comparison where it is).
+ *
+ * Per scale N (a power of two in [128, 4096]): one-sided STFT, center = True with reflect padding by N / 2, hop N / 4, periodic Hann
+ * window w[k] = 0.5 - 0.5 cos(2 pi k / N), not normalised, T_b = 1 + lengths[b] / hop frames, F = N / 2 + 1 bins.  One workgroup
+ * transforms the frames of both signals at once as z = w x_hat + i w x (each product rounded once) with an N-point complex FFT in LDS
+ * (radix-2 decimation-in-time butterflies, two stages per LDS pass, float32, twiddles from the plan's table), separates A = |STFT(x_hat)|
+ * and R = |STFT(x)| in float32, and forms in float64, with c = 1e-5:
+ *     stft log   |2 log10(max(A, c) / max(R, c))|        stft mag   |A - R|        (scales with stft_term)
+ *     mel log    |2 log10(max(M_hat, c) / max(M, c))|,   M = (float) sum_f fb[f][j] A_f^2 over the filter's own bins in ascending order,
+ *                the products and the sum in float64                                                   (scales with n_mels > 0)
+ * Per-frame sums in a fixed order, a clip's frames added in an order that depends on T_b only, divided by F T_b or n_mels T_b.
+ * x_hat == x gives exactly 0 in every term (the transform's arithmetic is symmetric under the exchange of the two signals).
+ *
+ * fd_specdist_tables (HOST memory, no GPU needed): the tables of one (sr, N, n_mels), computed in double with exact integer phase
+ *   reduction and rounded once: window [N]; twiddle [N / 2][2] = cos(2 pi m / N), -sin(2 pi m / N); the mel bank fb [F][n_mels]
+ *   (melscale_fbanks(F, 0, sr / 2, n_mels, sr, norm = "slaney", mel_scale = "htk") in float64) as bands: first[j], count[j] = the bins
+ *   with a non-zero weight (contiguous), weights = their values filter after filter.  Returns the number of weights (sum of count), or a
+ *   negative FD_* code.  Every pointer NULL: the count only.  n_mels = 0: no bank (first, count, weights are not touched).
+ * fd_specdist_plan_create: n_scales in [1, 16]; window_lengths[i] a power of two in [128, 4096]; n_mels[i] = 0: no mel term at scale i,
+ *   else 1 <= n_mels[i] <= N / 2 and no filter may be empty; stft_term[i] != 0: the STFT terms at scale i.  Uploads the tables
+ *   synchronously; nothing on the call path allocates.  The reference's two metrics in one plan: N = 128 .. 4096, n_mels = 10 .. 320,
+ *   stft_term = 0 0 1 1 1 1.
+ * fd_metrics_specdist_workspace_bytes(plan, B, L): 0 for a bad plan, B or L (1 <= B <= 65535, L > max(N) / 2).
+ * fd_metrics_specdist: out DEVICE double [B][2] = msstft (sum over the scales of stft log mean + stft mag mean), mel (sum of the mel log
+ *   means); terms DEVICE double [B][n_scales][3] = stft log, stft mag, mel log means (0 for a term the scale does not have), may be
+ *   NULL.  A DEVICE length outside (max(N) / 2, L] gives NaN in everything of that clip and no out-of-bounds access.
+ * fd_metrics_specdist_spectra (operator level, for tests): mag_hat, mag_x DEVICE float [B][T][F] with T = 1 + L / hop: A and R of scale
+ *   `scale` exactly as the call above forms them; mel_hat, mel_x DEVICE float [B][T][n_mels]: M_hat and M (may be NULL; must be NULL at a
+ *   scale without a mel term).  Zero in the frames t >= T_b.
+ * The calls are asynchronous on `stream`, allocate nothing and launch nothing when they refuse: a NULL pointer, a bad B or L,
+ * L <= max(N) / 2 and a workspace that is too small are FD_EINVAL with a message.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fd_specdist_plan fd_specdist_plan;
+int fd_specdist_tables(int sr, int N, int n_mels, float* window, float* twiddle, int* first, int* count, float* weights);
+int fd_specdist_plan_create(int sr, int n_scales, const int* window_lengths, const int* n_mels, const int* stft_term, fd_specdist_plan** out);
+void fd_specdist_plan_destroy(fd_specdist_plan* plan);
+size_t fd_metrics_specdist_workspace_bytes(const fd_specdist_plan* plan, int B, int L);
+int fd_metrics_specdist(const fd_specdist_plan* plan, const float* x_hat, const float* x, const int* lengths, int B, int L, double* out,
+                        double* terms, void* ws, size_t ws_bytes, void* stream);
+int fd_metrics_specdist_spectra(const fd_specdist_plan* plan, int scale, const float* x_hat, const float* x, const int* lengths, int B, int L,
+                                float* mag_hat, float* mag_x, float* mel_hat, float* mel_x, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
