@@ -66,7 +66,8 @@ Evaluation: `--eval` (pair lists only, default off; without it nothing changes) 
 written -- after the merge in the launcher of a --gpus N run -- with `flowdec_amd.eval_cli` on one GPU: SI-SDR / SI-SIR / SI-SAR and
 LogSpecMSE per triple into `metrics{suffix}.csv` beside the list.  The files are scored as they were written to disk, as the reference's
 evaluation scores them (flowdec/eval/metrics.py).  `--eval-estoi` (with --eval) passes `--estoi` on: a fifth column, ESTOI;
-`--eval-spectral` passes `--spectral` on: two last columns, the multi-scale STFT and mel distances.
+`--eval-spectral` passes `--spectral` on: two last columns, the multi-scale STFT and mel distances; `--eval-align MS` passes `--align MS` on:
+the triples are aligned in time within +-MS milliseconds before they are scored, two last columns `lag_x_hat` and `lag_y`.
 """
 import argparse
 import collections
@@ -158,6 +159,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-estoi", action="store_true", help="with --eval: also score ESTOI (eval_cli --estoi), a last column `estoi` of the CSV")
     p.add_argument("--eval-spectral", action="store_true",
                    help="with --eval: also score the multi-scale STFT and mel distances (eval_cli --spectral), two last columns `msstft` and `mel`")
+    p.add_argument("--eval-align", type=float, default=None, metavar="MS",
+                   help="with --eval: align every triple in time within +-MS milliseconds before scoring (eval_cli --align MS), two last columns "
+                        "`lag_x_hat` and `lag_y`")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -592,12 +596,13 @@ def launch_workers(argv: List[str], world: int, manifest: str, share_gpu: bool):
 
 
 def evaluate_triples(args, suffix: str) -> None:
-    """--eval: SI-SxR and LogSpecMSE (--eval-estoi: and ESTOI; --eval-spectral: and msstft, mel) of `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it
-    (flowdec_amd/eval_cli.py)."""
+    """--eval: SI-SxR and LogSpecMSE (--eval-estoi: and ESTOI; --eval-spectral: and msstft, mel; --eval-align MS: aligned in time first) of
+    `triples_list{suffix}.txt` -> `metrics{suffix}.csv` beside it (flowdec_amd/eval_cli.py)."""
     with torch.cuda.device(args.device):
         eval_cli.run(["--triples", os.path.join(args.outdir, f"triples_list{suffix}.txt"), "--out", os.path.join(args.outdir, f"metrics{suffix}.csv"),
                       "--batch-files", str(max(args.batch_files, 1))] + (["--estoi"] if getattr(args, "eval_estoi", False) else [])
-                     + (["--spectral"] if getattr(args, "eval_spectral", False) else []))
+                     + (["--spectral"] if getattr(args, "eval_spectral", False) else [])
+                     + (["--align", repr(float(args.eval_align))] if getattr(args, "eval_align", None) is not None else []))
 
 
 def run_launcher(args, parser, argv: List[str]) -> RunResult:

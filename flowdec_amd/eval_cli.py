@@ -2,7 +2,7 @@
 flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for those of its metrics that need no outside model or program.
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
-                                   [--sr 48000] [--estoi] [--spectral]
+                                   [--sr 48000] [--estoi] [--spectral] [--align MS]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -34,6 +34,19 @@ fewer cannot be reflect-padded for the 4096-sample window (the 2049-sample rule)
 builds its mel bank with torchaudio, which is not available to the tests: the bank is restated in float64 and pinned by its defining
 properties, parity with the package is UNPINNED (scripts/pin_mel.py prints it where torchaudio is importable).
 
+--align MS (off by default; without it every byte of the output is what it was, with any of the switches above) is for a row of the
+comparison that does not come from this project's own chain -- a codec with look-ahead, a decoder that keeps or drops its priming samples,
+a file cut a few milliseconds off -- where x_hat[n] and y[n] no longer belong to x[n] and a delay of a few samples costs SI-SDR tens of
+dB.  With M = round(MS sr / 1000) samples (1 <= M <= 2^20, else a parser error), after loading and resampling and before the crop flags
+(which then find nothing to cut and may be given too), every triple gets lag_x_hat = best_lag(x, x_hat, M) and lag_y = best_lag(x, y, M):
+the lag of the peak of the bounded-lag cross-correlation c[l] = sum_n x[n] s[n + l], |l| <= M, in float64 (flowdec_amd/align.py: xcorr,
+pick_lag; ties go to the smallest |l| and to +l), found on the GPU for all triples of the run in length-sorted ragged batches
+(csrc/xcorr.hip; align.lags_batch, host yardstick align.host_lags).  The three signals are cut to their common support (align_triple) and
+scored as above.  Two last CSV columns, `lag_x_hat` and `lag_y` (after `mel` / `estoi` when those are on): integers in samples at --sr,
+positive = late; two summary lines with the minimum, the maximum and the count of non-zero lags.  A lag equal to +-M gets a warning (the
+peak sits at the edge of the search; the triple is still scored); a triple whose common support is empty gets NaN in every metric and a
+warning.  No fractional delays, no drift, no polarity or gain matching.
+
 The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
 (DESIGN section 9).
 """
@@ -48,13 +61,14 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import metrics, specdist
+from . import align, metrics, specdist
 from .audio import RESAMPLE_HELP, load_mono, split_pair
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
 ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), the last column without --spectral
 SPECTRAL_NAMES = specdist.NAMES     # the optional metrics of --spectral (msstft, mel), always the last two columns
+LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -102,11 +116,12 @@ def min_spectral_samples(sr: int) -> int:
 class Scorer:
     """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]; estoi(x_hats, xs, sr,
     batch) -> [n] (optional: only --estoi calls it); spectral(x_hats, xs, sr, batch) -> [n, 2] (msstft, mel) (optional: only --spectral
-    calls it)."""
+    calls it); align(as_, bs, max_lag, batch) -> int64 [n], the lag of each b against its a (optional: only --align calls it)."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
     spectral: Optional[Callable] = None
+    align: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -141,10 +156,10 @@ def _host_spectral(x_hats, xs, sr, batch):
     return np.array([(specdist.multiscale_stft_distance(h, x), specdist.mel_distance(h, x, sr)) for h, x in zip(x_hats, xs)], np.float64).reshape(-1, 2)
 
 
-# ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip)
-GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral)
-# the host functions of metrics.py and specdist.py, one triple at a time: the yardstick
-HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral)
+# ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/xcorr.hip)
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch)
+# the host functions of metrics.py, specdist.py and align.py, one triple at a time: the yardstick
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags)
 
 
 def metric_columns(estoi: bool = False, spectral: bool = False) -> tuple:
@@ -213,12 +228,13 @@ def _columns_of(values: np.ndarray, columns) -> tuple:
     return tuple(columns)
 
 
-def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None) -> None:
+def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None) -> None:
+    """lags (--align): int [n, 2], written as the two last columns LAG_NAMES."""
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns))
-        for t, row in zip(triples, values):
-            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row])
+        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LAG_NAMES if lags is not None else ()))
+        for i, (t, row) in enumerate(zip(triples, values)):
+            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([str(int(l)) for l in lags[i]] if lags is not None else []))
 
 
 def summary(values: np.ndarray, columns=None):
@@ -239,6 +255,7 @@ class EvalResult:
     n_unreadable: int = 0      # triples skipped: a file could not be read
     means: list = field(default_factory=list)
     csv_path: Optional[str] = None
+    lags: list = field(default_factory=list)   # --align: [(column, min, max, count of non-zero lags)], empty without it
 
     @property
     def exit_code(self) -> int:
@@ -259,11 +276,64 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--spectral", action="store_true",
                    help="also score the multi-scale STFT and mel distances (the reference's MultiScaleSTFTLoss / MelSpectrogramLoss as metrics; on "
                         "the GPU): two last CSV columns `msstft` and `mel` and two more means")
+    p.add_argument("--align", type=float, default=None, metavar="MS",
+                   help="before scoring, find the delay of x_hat and of y against x within +-MS milliseconds (peak of the cross-correlation, on "
+                        "the GPU) and cut the three signals to their common support: two last CSV columns `lag_x_hat` and `lag_y` in samples "
+                        "at --sr (positive = late)")
     return p
 
 
+def align_max_lag(ms: float, sr: int) -> int:
+    """--align MS at rate sr -> M = round(MS sr / 1000) samples; ValueError outside [1, 2^20]."""
+    if not math.isfinite(ms):
+        raise ValueError(f"--align {ms}: not a number of milliseconds")
+    M = int(round(ms * sr / 1000.0))
+    if M < 1 or M > align.MAX_LAG_CAP:
+        raise ValueError(f"--align {ms:g} ms is {M} samples at {sr} Hz: the search takes 1 to {align.MAX_LAG_CAP} samples")
+    return M
+
+
+def align_signals(loaded, M: int, batch: int, scorer: Scorer, names: Optional[List[str]] = None):
+    """loaded: one (x_hat, x, y) of 1-D tensors per triple, as read -> (the triples cut to their common support: views, int64 [n, 2] =
+    lag_x_hat, lag_y).  All lags come from ONE call of scorer.align.  |lag| = M: a warning; an empty support: a warning (and NaN later)."""
+    if scorer.align is None:
+        raise ValueError("align_signals: --align needs a Scorer with an align function")
+    n = len(loaded)
+    lags = np.zeros((n, 2), np.int64)
+    if n:
+        xs = [x for _, x, _ in loaded]
+        got = np.asarray(scorer.align(xs + xs, [h for h, _, _ in loaded] + [y for _, _, y in loaded], M, batch), np.int64).reshape(-1)
+        lags[:, 0], lags[:, 1] = got[:n], got[n:]
+    out = []
+    for i, (h, x, y) in enumerate(loaded):
+        who = names[i] if names else "triple %d" % i
+        for k, col in enumerate(LAG_NAMES):
+            if abs(int(lags[i, k])) == M:
+                print(f"warning: {who}: {col} = {int(lags[i, k])} is at the edge of the search (+-{M} samples): the true delay may lie "
+                      f"outside it (a larger --align)", file=sys.stderr)
+        cut = align.align_triple(h, x, y, int(lags[i, 0]), int(lags[i, 1]))
+        if cut[1].shape[-1] < 1:
+            print(f"warning: {who}: the common support of the aligned signals is empty (lag_x_hat {int(lags[i, 0])}, lag_y {int(lags[i, 1])}; "
+                  f"x_hat {h.shape[-1]}, x {x.shape[-1]}, y {y.shape[-1]} samples): NaN for every metric", file=sys.stderr)
+        out.append(cut)
+    return out, lags
+
+
+def lag_summary(lags: np.ndarray):
+    """-> [(column, min, max, count of non-zero lags)] of int [n, 2] lags; 0, 0, 0 for no rows."""
+    return [(name, int(lags[:, k].min()) if len(lags) else 0, int(lags[:, k].max()) if len(lags) else 0, int(np.count_nonzero(lags[:, k])))
+            for k, name in enumerate(LAG_NAMES)]
+
+
 def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
-    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    parser = build_parser()
+    args = parser.parse_args(list(sys.argv[1:] if argv is None else argv))
+    max_lag = None
+    if args.align is not None:
+        try:
+            max_lag = align_max_lag(args.align, args.sr)
+        except ValueError as err:
+            parser.error(str(err))
     triples = read_triples(args.triples)
     res = EvalResult(n_triples=len(triples), csv_path=args.out)
     kept, signals = [], []
@@ -275,15 +345,25 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
             res.n_unreadable += 1
             continue
         kept.append(t)
-        signals.append(crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat))
-    values = score(signals, args.sr, args.batch_files, scorer, names=[t.name for t in kept], estoi=args.estoi, spectral=args.spectral)
+        signals.append((x_hat, x, y))
+    names, lags = [t.name for t in kept], None
+    if max_lag is not None:
+        signals, lags = align_signals(signals, max_lag, args.batch_files, scorer, names=names)
+    signals = [crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat) for x_hat, x, y in signals]
+    values = score(signals, args.sr, args.batch_files, scorer, names=names, estoi=args.estoi, spectral=args.spectral)
     columns = metric_columns(args.estoi, args.spectral)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    write_csv(args.out, kept, values, columns=columns)
+    if lags is None:
+        write_csv(args.out, kept, values, columns=columns)
+    else:
+        write_csv(args.out, kept, values, columns=columns, lags=lags)
+        res.lags = lag_summary(lags)
     res.n_scored, res.means = len(kept), summary(values, columns=columns)
     print(f"eval: {res.n_triples} triples, {res.n_scored} rows in {args.out}, {res.n_unreadable} skipped (unreadable)")
     for name, mean, count in res.means:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
+    for name, lo, hi, nonzero in res.lags:
+        print(f"  {name:12s} min = {lo}  max = {hi}  non-zero in {nonzero} of {res.n_scored} rows")
     return res
 
 

@@ -717,6 +717,26 @@ int fd_metrics_logspec_mse(const fd_stft_plan* plan, const float* x_hat, const f
 int fd_metrics_power_spec(const fd_stft_plan* plan, const float* x, const int* lengths, int B, int L, float* P_out, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* Alignment in time (still "Evaluation metrics": what eval_cli --align runs before it scores; csrc/xcorr.hip, host yardstick and the
+ * definition in flowdec_amd/align.py).  The bounded-lag cross-correlation of every pair of a ragged batch and the lag of its peak:
+ *     c[b][l + M] = sum_n a_b[n] b_b[n + l],   l in [-M, M],   n over max(0, -l) <= n < min(la, lb - l),   M = max_lag
+ * with la, lb the clip's own lengths; an empty range gives exactly 0.0; a peak at l > 0 means b is a delayed by l samples.  a DEVICE
+ * float [B][La], b DEVICE float [B][Lb] (the two signals of a pair may differ in length); lens_a, lens_b DEVICE int32 [B], each clamped
+ * into its row.  Samples outside [0, len) of a clip are zeros by definition and are never loaded, neither from the row's tail nor from
+ * the next row.  The samples are finite float32, so every product is exact in float64; the sums are float64.  The same contract as
+ * above: a clip's c and lag have the SAME BITS alone, in a batch, at any batch position and next to clips of any other lengths -- every
+ * partition and order of addition is a function of (lens_a[b], lens_b[b], max_lag) only (per lag the products of a slice of 32768
+ * samples of a in ascending order, four per v_mfma_f64_16x16x4_f64; the slice of lag l starts (l + max_lag) % 16 samples before a
+ * multiple of 32768; the slices added in index order); no atomics.
+ * lags DEVICE int32 [B]: the l with the largest c, NaN counting as -inf; among equal maxima the smallest |l|, and of -l and +l it is
+ *   +l (so two silent signals give 0), picked on the device from the finished float64 values.  c DEVICE double [B][2 M + 1] or NULL.
+ * fd_xcorr_workspace_bytes: 0 for a bad argument.  fd_xcorr_lags is asynchronous on `stream`, allocates nothing and launches nothing
+ *   when it refuses: FD_EINVAL with a message for a NULL pointer (c alone may be NULL), B outside [1, 65535], max_lag outside
+ *   [1, 1 << 20] and a row length outside [1, 0x7fffffff - 1024]; FD_ENOMEM for a workspace that is too small. */
+size_t fd_xcorr_workspace_bytes(int B, int La, int Lb, int max_lag);
+int fd_xcorr_lags(const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag, double* c, int* lags,
+                  void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Parameter estimation: the statistics behind a FlowDec model's beta and sigma_y (the reference's scripts/estimate_flowdec_params.py;
  * flowdec_amd/estimate.py, flowdec_amd/estimate_cli.py).  Both calls are asynchronous on `stream`, allocate nothing, keep no state and
