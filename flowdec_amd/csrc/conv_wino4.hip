@@ -15,13 +15,16 @@
 //     per pixel tile, as in the direct kernel (the F(2,3) kernel's 128-channel workgroups activated everything twice);
 //   * the input transform happens ONCE per workgroup and chunk, in ONE producer pass: raw bf16 halo --(direct-to-LDS DMA)--> RAW -->
 //     registers: silu(a x + d) -> fp16 -> packed-fp16 B^T transform --> LDS (V planes, double-buffered).  A lane owns one channel
-//     pair of one tile of one halo row: it reads the tile's six halo columns from RAW (a layout without bank conflicts for these
-//     reads: "halo loader and producer" below), activates them with the (a, d) of its two channels (four registers, read per chunk
-//     from the affine table the prologue stages in LDS), transforms and stores the six V words.  Adjacent tiles share two of six
-//     columns, so a column is activated 1.33 times -- cheaper than the activated-halo staging buffer (z) this pass replaced: one LDS
-//     store phase, one LDS read phase, an s_waitcnt lgkmcnt(0) and a barrier per chunk inside every wave's MFMA stream
-//     (MEASUREMENTS.md "One-pass producer").  The K loop then reads plain fragments: no VALU work per fragment (the F(2,3) kernel
-//     transformed at fragment-read time, in every wave, for every cout tile: 6.9 VALU per MFMA);
+//     pair of one THIRD of one halo row: it reads six of the row's 18 halo columns from RAW (a layout in which the lanes of a row
+//     never conflict: "halo loader and producer" below, wino4_layout.h), activates them with the (a, d) of its two channels (four
+//     registers, read per chunk from the affine table the prologue stages in LDS) -- every column is activated once.  The outer
+//     lanes of a group of three hold the six columns of tiles 0 and 3; the middle lane takes two activated words from each
+//     neighbour by DPP and transforms tiles 1 and 2.  18 rows x 8 words x 3 thirds = 432 items = 54 lanes in each of the eight
+//     waves: ONE balanced pass per chunk (the 4-tile mapping before it needed 576 items for 512 lanes: rows 16 and 17 were a second
+//     pass on one wave, which every wave met at the chunk barrier -- MEASUREMENTS.md "One balanced producer pass").  No
+//     activated-halo staging buffer: that cost one LDS store phase, one LDS read phase, an s_waitcnt lgkmcnt(0) and a barrier per
+//     chunk inside every wave's MFMA stream (MEASUREMENTS.md "One-pass producer").  The K loop then reads plain fragments: no VALU
+//     work per fragment (the F(2,3) kernel transformed at fragment-read time, in every wave, for every cout tile: 6.9 VALU per MFMA);
 //   * 6 x 256 x 64 accumulators = 96 K registers = 192 per lane of the 8 waves: wave (cq, xt) owns positions xi = 0, 1, 2 (xt = 0) or 5, 3, 4
 //     (xt = 1) for couts {ct * 128 + cq * 32 + 0..31, ct = 0, 1} and all 64 tiles: 3 x (2 x 2) MFMA tiles of 32 x 32
 //     (v_mfma_f32_32x32x16_f16); fragments rotate through three 16-byte quads per operand, 4 MFMAs per 4 ds_read_b128;
@@ -42,6 +45,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "wino4_layout.h"
 
 namespace {
 
@@ -56,22 +60,21 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // ---- geometry -------------------------------------------------------------------------------------------------------------
-constexpr int NTH = 512, TH = 16, TW = 16, HH = TH + 2, HW = TW + 2, BN = 256;
+using fdw4::NTH, fdw4::HH, fdw4::HW, fdw4::RROW, fdw4::RROW_BYTES, fdw4::RAW_PASSES, fdw4::RAW_BYTES, fdw4::NPIECE, fdw4::VXI;   // (wino4_layout.h)
+constexpr int TH = 16, TW = 16, BN = 256;
+static_assert(HH == TH + 2 && HW == TW + 2, "wino4_layout.h describes this tile");
 constexpr int CK = 16;                              // channels per K chunk (one 32-byte LDS row: two 16-byte halves)
 constexpr int SLAB = BN * 32;                       // 8 KiB: the weights of one (chunk, xi, dy) step, [256 couts][16 ch] fp16
 constexpr int RSLOT = 2048, NRING = 6;              // per-wave ring: 6 slots of 64 couts x 32 B (18 % NRING == 0)
 static_assert(18 % NRING == 0, "the two-chunk loop body turns the ring a whole number of times");
 constexpr int RING_BYTES = 8 * NRING * RSLOT;       // 96 KiB
-constexpr int VXI = HH * 4 * 32;                    // one position plane: [18 halo rows][4 tiles][32 B]
 constexpr int V_BYTES = 6 * VXI;                    // 13824
 constexpr int V_OFF = RING_BYTES;
 constexpr int AFF_OFF = V_OFF + 2 * V_BYTES;        // GroupNorm affine (a, d) of ALL input channels of this image, f32 pairs in concat order
                                                     // (fd_wino4_supported: at most AFF_BYTES), staged once by DMA in the prologue
 constexpr int RAW_OFF = AFF_OFF + AFF_BYTES;        // raw halo (bf16) of a chunk PAIR as the DMA delivers it: one 64-byte slot per pixel,
-constexpr int RROW = 20;                            // 20 slots per halo row (raw_slot below), the four 16-byte pieces [chunk parity][half]
-constexpr int RROW_BYTES = RROW * 64;               // of a pixel inside its slot (raw_flip): 1440 pieces, padded to 3 passes of 512 lanes
-constexpr int RAW_PASSES = 3;
-constexpr int RAW_BYTES = RAW_PASSES * NTH * 16;    // 24576
+                                                    // 20 slots per halo row (fdw4::raw_slot), the four 16-byte pieces [chunk parity][half]
+                                                    // of a pixel inside its slot (fdw4::raw_flip): 1440 pieces = 3 passes of 512 lanes (24576 B)
 constexpr int MAIN_BYTES = RAW_OFF + RAW_BYTES;     // 154624
 // epilogue: exchange buffer [wave][plane][4][64 lanes x 16 B] = the staging of one round (128 pixels x 128 couts f32, padded rows)
 // in the same bytes (a barrier apart), two residual buffers (one round each: 4 passes x 512 threads x 16 B), bias, statistics
@@ -88,14 +91,7 @@ static_assert(BIAS_OFF >= 2 * X_BYTES && BIAS_OFF >= SK_OFF + 2 * SK_BYTES && XS
 constexpr int ISC_OFF = BIAS_OFF + 1024;            // [256] f32: inverse of the per-cout power-of-two weight scale (wino4_scale_kernel)
 constexpr int STAT_OFF = ISC_OFF + 1024;            // [2][8 waves][16 octets][16] f32 = 16 KiB
 constexpr int LDS_BYTES = cmax(MAIN_BYTES, STAT_OFF + 16384);
-constexpr int NPIECE = HH * RROW * 4;               // 1440 raw pieces of 16 B (8 channels) per chunk pair, pad slots included
 static_assert(LDS_BYTES <= 160 * 1024 && NPIECE <= RAW_PASSES * NTH && AFF_BYTES <= 4 * 1024 && RAW_OFF % 128 == 0, "LDS layout");
-// RAW slot of halo column c inside its row: one pad slot behind every four columns (a tile's columns 4 wt + j, j = 0..3, sit at
-// 5 wt + j: the four tiles of a row alternate between the two 64-byte halves of a 128-byte bank row); columns 16 and 17 take the
-// pad slots 14 and 19 (an even and an odd one), so that a row needs 20 slots and the pair's halo still fits three DMA passes.
-constexpr int raw_slot(int c) { return c < 16 ? c + (c >> 2) : (c == 16 ? 14 : 19); }
-// ... and where the two pieces of a chunk parity sit inside the slot: piece q = 2 parity + half at position q ^ (2 raw_flip(c))
-constexpr int raw_flip(int c) { return c < 16 ? (c >> 3) & 1 : 0; }
 constexpr int U_EXP = 9;                            // packed weights: every cout's row of U = G g is scaled by a power of two so that its
                                                     // largest magnitude lies in [2^(U_EXP-1), 2^U_EXP) -- fp16 keeps 23 binades below that
 constexpr float RAW_MAX = 6000.f;                   // raw (not activated) inputs saturate here: |V| <= 10 |z| stays finite in fp16
@@ -151,19 +147,22 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   // adjacent lanes per pixel (one memory request per pixel and pair: the 32-byte gathers of a per-chunk request were a third of the vector
   // L1's time), three passes of 512 lanes, straight to LDS by DMA (RAW; pass i of wave w at (i * 8 + w) KiB in lane order).  The DMA fixes
   // the LDS byte of every lane, the SOURCE address is free: LDS slot S = (t + 512 i) >> 2 holds the pixel (row S / 20, the column c with
-  // raw_slot(c) = S % 20; slots 4 and 9 of a row and those behind row 17 are padding), lane position q = t & 3 of the slot the pixel's
-  // piece q ^ (2 raw_flip(c)).  PRODUCER, once per chunk, ONE pass RAW -> registers -> V: a lane takes one channel pair (32-bit word
-  // l & 7: half (l >> 2) & 1, word l & 3 of the 16-byte piece) of one Winograd tile (l >> 3) & 3 of one halo row -- it reads the tile's
-  // six halo columns straight from RAW, applies silu(a x + d) -> fp16 (or the saturation) and the zero padding to the six words, and
-  // the packed-fp16 B^T transform, and stores the six V words.  The (a, d) of a lane's two channels come from the affine table that the
-  // prologue stages in LDS (AFF: one ds_read_b128 per chunk, 8 distinct 16-byte addresses per wave: a broadcast).
-  // Bank conflicts of the RAW reads (ds_read_b32: banks = (byte / 4) % 32, a 32-lane group at a time).  A 32-lane group = one halo row x 4
-  // tiles x 8 words; the 8 words of a tile are the 32 contiguous bytes of one (slot, chunk parity): a quarter of the 128-byte bank row,
-  // quarter number 2 (slot & 1) + (parity ^ flip).  For read j the four tiles wt need four different quarters:
-  //   j = 0..3: columns 4 wt + j in slots 5 wt + j (slot parity wt + j), flip = wt >> 1            -> (wt & 1, wt >> 1): all four
-  //   j = 4:    columns 4 8 12 16 in slots 5 10 15 14 (parities 1 0 1 0), flips 0 1 1 0               -> all four
-  //   j = 5:    columns 5 9 13 17 in slots 6 11 16 19 (parities 0 1 0 1), flips 0 1 1 0               -> all four
-  // (the row pitch, 1280 bytes, is a multiple of the bank row).  The V stores of a group are 128 contiguous bytes, as before.
+  // raw_slot(c) = S % 20; slots 6 and 13 of a row and those behind row 17 are padding), lane position q = t & 3 of the slot the pixel's
+  // piece q ^ (2 raw_flip(c)) -- fdw4::raw_request (wino4_layout.h).  PRODUCER, once per chunk, ONE pass RAW -> registers -> V that covers
+  // all 18 halo rows: an item is (halo row, channel pair = 32-bit word 0..7 of a chunk's 32 bytes, column third k = 0..2), 432 items, 54 in
+  // every wave (fdw4::item).  Lane k of a (row, word) group reads the halo columns 6 k .. 6 k + 5 straight from RAW (one base address, six
+  // immediates), applies silu(a x + d) -> fp16 (or the saturation) and the zero padding to the six words: every one of the 18 columns is
+  // activated ONCE.  The four tiles of the row need columns 0-5 (lane 0's own), 4-9, 8-13 and 12-17 (lane 2's own): lane 1 takes the
+  // activated columns 4, 5 from lane 0 and 12, 13 from lane 2 (four v_mov_b32 with a DPP row shift: the three lanes are adjacent and never
+  // straddle a 16-lane row) and transforms twice (tiles 1 and 2); the second transform's stores are masked off in lanes 0 and 2.  The
+  // (a, d) of a lane's two channels come from the affine table that the prologue stages in LDS (AFF: one ds_read_b128 per chunk, 8
+  // distinct 16-byte addresses per wave: a broadcast).
+  // Bank conflicts (ds_read_b32 / ds_write_b32: banks = (byte / 4) % 32, a 32-lane group at a time).  The 8 words of a (slot, chunk parity)
+  // are a quarter of the 128-byte bank row, quarter number 2 (slot & 1) + (parity ^ flip); the three lanes of a group need three
+  // different quarters for each read j: slots j, 7 + j, 14 + j (parities j, ~j, j) with flips 0, 0, 1.  A V store of a group goes to
+  // three of the four 32-byte tile cells of a 128-byte row.  So the lanes of ONE halo row never conflict; lanes 32..63 of a wave hold
+  // one row, lanes 0..31 one row and two groups of rows 16 / 17, whose six lanes are 2-way conflicts (wino4_layout.h; checked
+  // exhaustively on the host: tests/wino4_layout_check.cpp).
   // The K loop is bound by vector-instruction issue as soon as the per-chunk work costs more than a few hundred instructions per wave
   // (SQ counters, profiles/r04_wino4_*): everything a lane needs per chunk is computed ONCE here and kept in (packed) registers. -----
   auto opaque = [&](int v) { asm volatile("" : "+v"(v)); return v; };
@@ -185,26 +184,22 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   int hpix[RAW_PASSES];                    // (pixel offset inside the band) * 4 + source piece
 #pragma unroll
   for (int i = 0; i < RAW_PASSES; ++i) {   // request side: four adjacent lanes share a pixel's 64 bytes
-    const int sl = t + i * NTH;
-    const int slot = sl >> 2;
-    const int hr = slot / RROW, ps = slot - hr * RROW;
-    const int hc = (ps == 4 || ps == 9 || hr >= HH) ? -1 : ps == 14 ? 16 : ps == 19 ? 17 : ps - ps / 5;
-    const int gh = h0 - 1 + hr, gw = w0 - 1 + hc;
-    const bool ok = hc >= 0 && gh >= 0 && gh < H && gw >= 0 && gw < W;
-    hpix[i] = ((ok ? (gh - hb) * W + gw : 0) << 2) | ((sl & 3) ^ (ok ? 2 * raw_flip(hc) : 0));
+    const fdw4::Req rq = fdw4::raw_request(t + i * NTH);
+    const int gh = h0 - 1 + rq.row, gw = w0 - 1 + rq.col;
+    const bool ok = rq.col >= 0 && gh >= 0 && gh < H && gw >= 0 && gw < W;
+    hpix[i] = ((ok ? (gh - hb) * W + gw : 0) << 2) | (ok ? rq.piece : t & 3);
   }
-  // producer side: item (halo row t >> 5, tile wt, word).  Columns 4 wt + j, j = 0..3, are 64 bytes apart; j = 4 and 5 have their own
-  // offsets (the next group of four: another flip; columns 16, 17: the pad slots).  Rows 16, 17: wave 1 (rows 2, 3) + 14 rows.
-  int pA, pB, vbits;
+  // producer side: item (halo row, word, third k).  pA = RAW byte of column 6 k (chunk parity 0; columns 6 k + j are 64 bytes apart) |
+  // V offset of the first transform's tile << 16.  vbits: 1 = column 6 k is inside the image, 4 = column 6 k + 5 is, 2 = the row is,
+  // 8 = the lane has an item, 16 = it is the middle lane of its group.  Idle lanes (10 of 64) repeat the reads of a neighbour and store nothing.
+  int pA, vbits, pword;
   {
-    const int hrow = t >> 5, wt = (t >> 3) & 3, word = t & 7;
-    auto raw_at = [&](int c) { return hrow * RROW_BYTES + raw_slot(c) * 64 + raw_flip(c) * 32 + word * 4; };
-    const int tidx = hrow * 4 + wt;
-    const int vrel = tidx * 32 + (((word >> 2) ^ ((tidx >> 3) & 1)) * 16) + (word & 3) * 4;   // V plane: [18 rows][4 tiles][32 B], halves swizzled
-    pA = raw_at(4 * wt) | (vrel << 16);
-    pB = raw_at(4 * wt + 4) | (raw_at(4 * wt + 5) << 16);
-    const int gh = h0 - 1 + hrow, ghe = gh + 14;
-    vbits = (w0 - 1 + 4 * wt >= 0 ? 1 : 0) | (gh >= 0 && gh < H ? 2 : 0) | (w0 + 4 * wt + 4 < W ? 4 : 0) | (ghe >= 0 && ghe < H ? 8 : 0);
+    const fdw4::Item it = fdw4::item(t);
+    pA = fdw4::raw_addr(it.row, 6 * it.k, 0, it.word) | (fdw4::v_addr(it.row, fdw4::first_tile(it.k), it.word) << 16);
+    const int gh = h0 - 1 + it.row;
+    vbits = (it.k != 0 || w0 > 0 ? 1 : 0) | (gh >= 0 && gh < H ? 2 : 0) | (it.k != 2 || w0 + TW < W ? 4 : 0) | (it.active ? 8 : 0) |
+            (it.active && it.k == 1 ? 16 : 0);
+    pword = it.word;
   }
   // state of the chunk whose halo is in flight / being converted (wave-uniform)
   const bf16* nbase = sb0;
@@ -231,7 +226,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
     }
   };
   // affine table of image b = [C0 + C1] (a, d) pairs in concat order (fd_conv2d: aff_off = 0 / C0): chunk cc, word wd at cc * 128 + wd * 16
-  int affa = AFF_OFF + (t & 7) * 16;
+  int affa = AFF_OFF + pword * 16;
   auto load_affine = [&]() {
     if constexpr (ACT) {
       if (wave < AFF_BYTES / 1024) {       // 1 KiB per wave; lanes behind the table re-read its start
@@ -242,24 +237,20 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   };
 
   // ---- the producer pass of one item: RAW (bf16) -> [silu(a x + d)] -> fp16, zero padding AFTER the activation (an AND: no branch) ->
-  // packed-fp16 B^T -> V planes.  e = parity of the chunk inside its pair, affo = byte offset of its affine records behind affa
-  // (both compile-time).  Halo rows 0..15 = the sixteen 32-lane groups of the workgroup (rows 0..7 wave group 0, rows 8..15 wave
-  // group 1), rows 16, 17 = the two halves of wave 1 two steps later (`extra`).
-  auto produce = [&](const bool extra, const int e, const int vbuf, const int affo) {
+  // exchange inside the group -> packed-fp16 B^T (twice) -> V planes.  e = parity of the chunk inside its pair, affo = byte offset of
+  // its affine records behind affa (both compile-time).  Every wave runs it once per chunk: halo rows 2 w, 2 w + 1 and two (row 16 / 17,
+  // word) groups in wave w.
+  auto produce = [&](const int e, const int vbuf, const int affo) {
     // (opaque: hipcc otherwise hoists the unpacked addresses out of the K loop -- registers it does not have)
-    const int pa = opaque(pA), pb = opaque(pB), vbt = opaque(vbits);
-    const char* const rp = smem + RAW_OFF + (extra ? 14 * RROW_BYTES : 0);
-    const int a0 = (pa & 0xffff) ^ (e << 5), a4 = (pb & 0xffff) ^ (e << 5), a5 = (int)((unsigned)pb >> 16) ^ (e << 5);
-    const int vrel = (int)((unsigned)pa >> 16);
-    char* const vb = smem + V_OFF + vbuf * V_BYTES + (extra ? (vrel ^ 16) + 14 * 4 * 32 : vrel);   // (rows 16, 17: the other swizzle phase)
+    const int pa = opaque(pA), vbt = opaque(vbits);
+    const char* const rp = smem + RAW_OFF + ((pa & 0xffff) ^ (e << 5));
+    char* const vb = smem + V_OFF + vbuf * V_BYTES + (int)((unsigned)pa >> 16);
     unsigned w_[6];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) w_[j] = *reinterpret_cast<const unsigned*>(rp + a0 + j * 64);   // halo column 4 wt + j
-    w_[4] = *reinterpret_cast<const unsigned*>(rp + a4);
-    w_[5] = *reinterpret_cast<const unsigned*>(rp + a5);
+    for (int j = 0; j < 6; ++j) w_[j] = *reinterpret_cast<const unsigned*>(rp + j * 64);   // halo column 6 k + j
     f32x4 af = {0.f, 0.f, 0.f, 0.f};
     if constexpr (ACT) af = *reinterpret_cast<const f32x4*>(smem + opaque(affa) + affo);
-    const unsigned mrow = (unsigned)((int)((unsigned)vbt << (extra ? 28 : 30)) >> 31);
+    const unsigned mrow = (unsigned)((int)((unsigned)vbt << 30) >> 31);
     const unsigned m0 = mrow & (unsigned)((int)((unsigned)vbt << 31) >> 31), m5 = mrow & (unsigned)((int)((unsigned)vbt << 29) >> 31);
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
@@ -273,21 +264,34 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
         r = pack_f16(__builtin_amdgcn_fmed3f(x0, -RAW_MAX, RAW_MAX), __builtin_amdgcn_fmed3f(x1, -RAW_MAX, RAW_MAX));
       w_[j] = r & (j == 0 ? m0 : j == 5 ? m5 : mrow);
     }
+    // the middle lane's neighbours: columns 4, 5 (words 4, 5 of the lane below: row_shr:1) and 12, 13 (words 0, 1 of the lane above:
+    // row_shl:1).  Lanes 0 and 2 of a group receive words they do not use (or nothing, at the ends of a 16-lane row).
+    const unsigned l4 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w_[4], 0x111, 0xf, 0xf, true);
+    const unsigned l5 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w_[5], 0x111, 0xf, 0xf, true);
+    const unsigned r0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w_[0], 0x101, 0xf, 0xf, true);
+    const unsigned r1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w_[1], 0x101, 0xf, 0xf, true);
+    const bool mid = (vbt & 16) != 0;
     const f16x2 c4 = {(f16)4.f, (f16)4.f}, cm4 = {(f16)-4.f, (f16)-4.f}, cm5 = {(f16)-5.f, (f16)-5.f}, c2 = {(f16)2.f, (f16)2.f},
                 cm2 = {(f16)-2.f, (f16)-2.f};
-    const f16x2 z0 = h2(w_[0]), z1 = h2(w_[1]), z2 = h2(w_[2]), z3 = h2(w_[3]), z4 = h2(w_[4]), z5 = h2(w_[5]);
-    const f16x2 t1 = __builtin_elementwise_fma(z2, cm4, z4);   // z4 - 4 z2
-    const f16x2 t2 = __builtin_elementwise_fma(z1, cm4, z3);   // z3 - 4 z1
-    const f16x2 t3 = z4 - z2, t4 = z3 - z1;
-    // plane slots in the order xi = 0 1 2 | 5 3 4 (see the epilogue)
-    *reinterpret_cast<unsigned*>(vb + 0 * VXI) = u2(__builtin_elementwise_fma(z0, c4, __builtin_elementwise_fma(z2, cm5, z4)));   // xi = 0
-    *reinterpret_cast<unsigned*>(vb + 1 * VXI) = u2(t1 + t2);                                                                    // xi = 1
-    *reinterpret_cast<unsigned*>(vb + 2 * VXI) = u2(t1 - t2);                                                                    // xi = 2
-    *reinterpret_cast<unsigned*>(vb + 4 * VXI) = u2(__builtin_elementwise_fma(t4, c2, t3));                                       // xi = 3
-    *reinterpret_cast<unsigned*>(vb + 5 * VXI) = u2(__builtin_elementwise_fma(t4, cm2, t3));                                      // xi = 4
-    *reinterpret_cast<unsigned*>(vb + 3 * VXI) = u2(__builtin_elementwise_fma(z1, c4, __builtin_elementwise_fma(z3, cm5, z5)));   // xi = 5
+    auto transform = [&](char* const v, const unsigned d0, const unsigned d1, const unsigned d2, const unsigned d3, const unsigned d4, const unsigned d5) {
+      const f16x2 z0 = h2(d0), z1 = h2(d1), z2 = h2(d2), z3 = h2(d3), z4 = h2(d4), z5 = h2(d5);
+      const f16x2 t1 = __builtin_elementwise_fma(z2, cm4, z4);   // z4 - 4 z2
+      const f16x2 t2 = __builtin_elementwise_fma(z1, cm4, z3);   // z3 - 4 z1
+      const f16x2 t3 = z4 - z2, t4 = z3 - z1;
+      // plane slots in the order xi = 0 1 2 | 5 3 4 (see the epilogue)
+      *reinterpret_cast<unsigned*>(v + 0 * VXI) = u2(__builtin_elementwise_fma(z0, c4, __builtin_elementwise_fma(z2, cm5, z4)));   // xi = 0
+      *reinterpret_cast<unsigned*>(v + 1 * VXI) = u2(t1 + t2);                                                                    // xi = 1
+      *reinterpret_cast<unsigned*>(v + 2 * VXI) = u2(t1 - t2);                                                                    // xi = 2
+      *reinterpret_cast<unsigned*>(v + 4 * VXI) = u2(__builtin_elementwise_fma(t4, c2, t3));                                       // xi = 3
+      *reinterpret_cast<unsigned*>(v + 5 * VXI) = u2(__builtin_elementwise_fma(t4, cm2, t3));                                      // xi = 4
+      *reinterpret_cast<unsigned*>(v + 3 * VXI) = u2(__builtin_elementwise_fma(z1, c4, __builtin_elementwise_fma(z3, cm5, z5)));   // xi = 5
+    };
+    // tiles 0 and 3 = the own six columns of lanes 0 and 2; tile 1 = columns 4 .. 9 = (l4, l5, own 0 .. 3) of lane 1
+    if (vbt & 8)
+      transform(vb, mid ? l4 : w_[0], mid ? l5 : w_[1], mid ? w_[0] : w_[2], mid ? w_[1] : w_[3], mid ? w_[2] : w_[4], mid ? w_[3] : w_[5]);
+    // tile 2 = columns 8 .. 13 = (own 2 .. 5, r0, r1) of lane 1, the next 32 bytes of the V row
+    if (mid) transform(vb + 32, w_[2], w_[3], w_[4], w_[5], r0, r1);
   };
-  const bool extra_wave = wave == 1;
 
   // ---- weight stream: this wave's 2 KiB (cout blocks ct = 0, 1: two consecutive 1-KiB pieces) of its step f -> ring slot f % NRING.
   // packed layout: [chunk][xt][xi][dy][cq][ct][32 couts][32 B]; the wave's 9 steps of a chunk are 9 consecutive slabs.  The stream
@@ -349,8 +353,7 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   for (int k = 0; k < NRING; ++k) dma_step(k, k);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   barrier();                // every lane's halo slots and the affine table have landed
-  produce(false, 0, 0, 0);
-  if (extra_wave) produce(true, 0, 0, 0);
+  produce(0, 0, 0);
   next_chunk();             // (chunk 1: its halo arrived with chunk 0's)
   lds_wait();
   barrier();                // V[0] complete
@@ -360,16 +363,16 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
   // ---- K loop.  Chunk c multiplies V[c & 1]; meanwhile the halo of chunk c + 1 (in RAW) is activated and transformed into V[(c + 1) & 1]
   // by the producer pass, and (in the even chunks) the halo of the pair c + 2, c + 3 is requested.  LDS ordering, one barrier per chunk:
   //   V[(c + 1) & 1]: last read by the fragments of chunk c - 1, which every wave has before it passes the barrier of step 8 of chunk
-  //                   c - 1 (lds_wait in front of it); written in steps 0 .. 2 of chunk c; complete (lds_wait) at the barrier of step 8
+  //                   c - 1 (lds_wait in front of it); written in steps 0 and 1 of chunk c; complete (lds_wait) at the barrier of step 8
   //                   of chunk c; read from step 8 of chunk c on (the fragments of step 0 of chunk c + 1).
-  //   RAW (one buffer for a chunk PAIR): parity 1 is read in steps 0 .. 2 of the even chunk, parity 0 in steps 0 .. 2 of the odd chunk
+  //   RAW (one buffer for a chunk PAIR): parity 1 is read in steps 0 and 1 of the even chunk, parity 0 in steps 0 and 1 of the odd chunk
   //                   before it.  The barrier of step 3 of the EVEN chunks says "every producer pass over this pair is done": the request
   //                   for the next pair follows it, lands before the barrier of step 8 of the same chunk (every wave waits for its own
   //                   pieces first), and is read from step 0 of the odd chunk on.  The odd chunks have no barrier at step 3.
   //   AFF:            written once in the prologue, read only.
   // The two waves of a SIMD (groups xt = 0 / 1) do the producer's vector work in DIFFERENT steps:
-  //   group 0: halo rows 0..7 in step 0, rows 16, 17 in step 2 (wave 1)
-  //   group 1: halo rows 8..15 in step 1
+  //   group 0: its four passes (halo rows 0..7 and half of rows 16, 17) in step 0
+  //   group 1: its four passes (halo rows 8..15 and the other half of rows 16, 17) in step 1
   //   both:    the halo of the next chunk PAIR is requested in step 3 of the even chunks
   // A step starts with a counted wait for the weights of the NEXT step (its first fragments are requested right away); in flight on
   // this wave's vector-memory counter at that wait, oldest first: the weight pieces of steps s + 1 .. s + 5 (2 each) and, in the four
@@ -410,9 +413,8 @@ __global__ __launch_bounds__(NTH, 2) void conv_wino4_kernel(ConvArgs p) {
       mma(xl, 1, 1, A1, B1);
       __builtin_amdgcn_sched_barrier(0);
       // the chunk's vector work, while the quads A1 / B1 are dead: the NEXT chunk (the other parity) -> V[vn]
-      if (s == 0) { if (xg == 0) produce(false, half ^ 1, vn, 128 * (1 + half)); }
-      if (s == 1) { if (xg == 1) produce(false, half ^ 1, vn, 128 * (1 + half)); }
-      if (s == 2) { if (extra_wave) produce(true, half ^ 1, vn, 128 * (1 + half)); }
+      if (s == 0) { if (xg == 0) produce(half ^ 1, vn, 128 * (1 + half)); }
+      if (s == 1) { if (xg == 1) produce(half ^ 1, vn, 128 * (1 + half)); }
       __builtin_amdgcn_sched_barrier(0);
     }
     wp += 36 * SLAB;
