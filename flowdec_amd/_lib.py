@@ -96,6 +96,17 @@ SIGNATURES = {
     "fd_channel_sums_tiles": (c_int, [c_int, c_int]),
     "fd_channel_sums": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_gn_silu_apply": (c_int, [_P, _P, _P, c_int, c_ll, c_int, c_int, _P]),
+    "fd_op_pack_input": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "fd_op_combine": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_op_output_update": (c_int, [_P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_op_score_update": (c_int, [_P, _P, _P, c_float, _P, c_float, c_float, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_op_init_state": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "fd_op_caxpy": (c_int, [_P, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "fd_op_ode_lincomb": (c_int, [_P, c_float, c_float, C.POINTER(_P), C.POINTER(c_float), c_int, _P, c_ll, _P]),
+    "fd_op_ode_lincomb_clips": (c_int, [_P, c_float, _P, C.POINTER(_P), C.POINTER(c_float), c_int, _P, c_int, c_ll, _P]),
+    "fd_op_ode_scaled_sq": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int, c_ll, _P]),
+    "fd_op_ode_scaled_sq_clips": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, c_ll, _P]),
+    "fd_op_ode_commit_clips": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_ll, _P]),
     "fd_resblock_workspace_bytes": (c_size_t, [C.POINTER(FdResblockDesc), c_int, c_int, c_int, c_int]),
     "fd_resblock": (c_int, [C.POINTER(FdResblockDesc), _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "fd_attn_block_workspace_bytes": (c_size_t, [C.POINTER(FdAttnDesc), c_int, c_int, c_int, c_int]),

@@ -193,6 +193,124 @@ def temb_bias(temb, dense_w, dense_b, conv_bias):
     return out
 
 
+# ---- operator-level entry points of the solver and edge kernels (include/flowdec_hip.h "Operator-level: solver and edge kernels") ----
+# Complex planes are complex64 tensors; every output may be passed in (`out=` ...: a caller that prefilled it sees what the kernel wrote).
+def _plane(t, shape=None):
+    L.require_cuda(t)
+    if t.dtype != torch.complex64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError("expected a contiguous complex64 tensor" + ("" if shape is None else f" of shape {tuple(shape)}"))
+    return t
+
+
+def pack_input(x, y, dtype, out=None):
+    """x, y complex64 [B, H, W] -> [B, H, W, 8] in `dtype`: (x.re, x.im, y.re, y.im, 0, 0, 0, 0)."""
+    B, H, W = _plane(x).shape
+    _plane(y, x.shape)
+    out = torch.empty(B, H, W, 8, dtype=dtype, device=x.device) if out is None else out
+    L.check(L.load().fd_op_pack_input(L.ptr(x), L.ptr(y), L.ptr(out), B, H, W, L.dtype_id(dtype), L.stream()))
+    return out
+
+
+def combine(p4, w, bias, h, out=None, stats=None):
+    """conv1x1(p4[..., :4]) + bias + h on the packed pyramid p4 [B, H, W, 8]; w [Cout, 4], bias [Cout] float32; h [B, H, W, Cout].
+    Returns (out, stats [B, ceil(H W / 256), Cout, 2])."""
+    B, H, W, c8 = _nhwc(p4)
+    Cout = h.shape[3]
+    assert c8 == 8 and tuple(w.shape) == (Cout, 4) and w.dtype == torch.float32 and h.dtype == p4.dtype
+    out = torch.empty_like(h) if out is None else out
+    stats = torch.empty(B, -(-H * W // 256), Cout, 2, dtype=torch.float32, device=p4.device) if stats is None else stats
+    L.check(L.load().fd_op_combine(L.ptr(p4), L.ptr(w.contiguous()), L.ptr(bias), L.ptr(h), L.ptr(out), L.ptr(stats), B, H, W, Cout,
+                                   L.dtype_id(p4.dtype), L.stream()))
+    return out, stats
+
+
+def _output_ks(w):
+    if tuple(w.shape) not in ((2, 4), (2, 4, 1, 1), (2, 4, 3, 3)) or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError("output layer weight: contiguous float32 [2, 4] or [2, 4, 3, 3]")
+    return 3 if w.ndim == 4 and w.shape[2] == 3 else 1
+
+
+def output_update(pyr, w, coef, base=None, kold=None, dst=None, ksave=None, want_ksave=True):
+    """dst = base + coef * (output_layer(pyr) + kold), ksave = output_layer(pyr); pyr [B, H, W, 4].  Returns (dst, ksave)."""
+    B, H, W, c4 = _nhwc(pyr)
+    assert c4 == 4
+    dst = torch.empty(B, H, W, dtype=torch.complex64, device=pyr.device) if dst is None else dst
+    if ksave is None and want_ksave:
+        ksave = torch.empty(B, H, W, dtype=torch.complex64, device=pyr.device)
+    L.check(L.load().fd_op_output_update(L.ptr(pyr), L.ptr(w), L.ptr(base), L.ptr(kold), coef, L.ptr(dst), L.ptr(ksave), B, H, W, _output_ks(w),
+                                         L.dtype_id(pyr.dtype), L.stream()))
+    return dst, ksave
+
+
+def score_update(pyr, w, base, cb, Y, cy, cn, cz, z=None, seeds=None, draw=0, dst=None):
+    """dst = cb base + cy Y + cn output_layer(pyr) + cz z; z = a complex64 plane, or generated from `seeds` (uint64 [B]) and `draw`."""
+    B, H, W, c4 = _nhwc(pyr)
+    assert c4 == 4
+    dst = torch.empty(B, H, W, dtype=torch.complex64, device=pyr.device) if dst is None else dst
+    L.check(L.load().fd_op_score_update(L.ptr(pyr), L.ptr(w), L.ptr(base), cb, L.ptr(Y), cy, cn, L.ptr(z), L.ptr(seeds), draw, cz, L.ptr(dst),
+                                        B, H, W, _output_ks(w), L.dtype_id(pyr.dtype), L.stream()))
+    return dst
+
+
+def init_state(Y, sigma, sigma_fac, noise=None, seeds=None, frame0=None, draw=0, out=None):
+    """x0 = Y + sigma_fac * complex64(sigma[f] * z); Y complex64 [B, F, T], sigma float64 [1] or [F]; z = `noise` or the seeded plane."""
+    B, F, T = _plane(Y).shape
+    assert sigma.dtype == torch.float64
+    out = torch.empty_like(Y) if out is None else out
+    L.check(L.load().fd_op_init_state(L.ptr(Y), L.ptr(noise), L.ptr(seeds), L.ptr(frame0), draw, L.ptr(sigma), sigma.numel(), sigma_fac,
+                                      L.ptr(out), B, F, T, L.stream()))
+    return out
+
+
+def caxpy(a, cq, q=None, seeds=None, draw=0, out=None):
+    """a + cq * q; a complex64 [B, F, T]; q = a plane of the same shape, or generated from `seeds` and `draw`."""
+    B, F, T = _plane(a).shape
+    out = torch.empty_like(a) if out is None else out
+    L.check(L.load().fd_op_caxpy(L.ptr(a), L.ptr(q), L.ptr(seeds), draw, cq, L.ptr(out), B, F, T, L.stream()))
+    return out
+
+
+def _lincomb_tables(ks, cs):
+    import ctypes as C
+    assert len(ks) == len(cs)
+    kp = (C.c_void_p * max(len(ks), 1))(*[None if k is None else k.data_ptr() for k in ks])
+    cp = (C.c_float * max(len(cs), 1))(*[float(c) for c in cs])
+    return kp, cp
+
+
+def ode_lincomb(x, cx, dt, ks, cs, out):
+    """out = cx x + dt sum_j cs[j] ks[j] over complex64 tensors of one size (ks[j] may be None: skipped).  dt: a float (one step for
+    the whole state) or a float32 tensor [B] (per-clip steps of a [B, ...] state)."""
+    kp, cp = _lincomb_tables(ks, cs)
+    if torch.is_tensor(dt):
+        B = dt.numel()
+        L.check(L.load().fd_op_ode_lincomb_clips(L.ptr(x), cx, L.ptr(dt), kp, cp, len(ks), L.ptr(out), B, out.numel() // B, L.stream()))
+    else:
+        L.check(L.load().fd_op_ode_lincomb(L.ptr(x), cx, dt, kp, cp, len(ks), L.ptr(out), out.numel(), L.stream()))
+    return out
+
+
+def ode_scaled_sq(p, q, r, s, atol, rtol, nblocks=512, clips=None, out=None):
+    """Block partials (float64 [nblocks], or [clips, nblocks] per clip of a [clips, ...] state) of sum |p - q|^2 / (atol + rtol
+    max(|r|, |s|))^2; q may be None."""
+    if clips is None:
+        out = torch.empty(nblocks, dtype=torch.float64, device=p.device) if out is None else out
+        L.check(L.load().fd_op_ode_scaled_sq(L.ptr(p), L.ptr(q), L.ptr(r), L.ptr(s), atol, rtol, L.ptr(out), nblocks, p.numel(), L.stream()))
+    else:
+        out = torch.empty(clips, nblocks, dtype=torch.float64, device=p.device) if out is None else out
+        L.check(L.load().fd_op_ode_scaled_sq_clips(L.ptr(p), L.ptr(q), L.ptr(r), L.ptr(s), atol, rtol, L.ptr(out), nblocks, clips,
+                                                   p.numel() // clips, L.stream()))
+    return out
+
+
+def ode_commit_clips(accept, ckpt, x_new, k6, x, k0, traj=None):
+    """In place: clips b of the [B, ...] states with accept[b] != 0 take x <- x_new, k0 <- k6, traj[ckpt[b]][b] <- x_new (ckpt[b] > 0)."""
+    B = accept.numel()
+    assert accept.dtype == torch.int32 and ckpt.dtype == torch.int32
+    L.check(L.load().fd_op_ode_commit_clips(L.ptr(accept), L.ptr(ckpt), L.ptr(x_new), L.ptr(k6), L.ptr(x), L.ptr(k0), L.ptr(traj), B,
+                                            x.numel() // B, L.stream()))
+
+
 class _StftPlan:
     """Caller-owned fd_stft_plan (device-resident DFT matrices of one (n_fft, hop)); freed with the object."""
 

@@ -260,6 +260,70 @@ int fd_resblock(const fd_resblock_desc* d, const void* x0, const void* x1, void*
                 size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Operator-level: solver and edge kernels
+ * ----------------------------------------------------------------------------------------------
+ * The kernels between the network and the ODE / SDE solvers, one entry point each, for operator-level parity.  Every fd_op_* function
+ * checks its arguments (FD_EINVAL with a message, nothing launched) and then calls the launcher the model and the solvers themselves
+ * call: the same kernel, grid and block.  "complex" = complex64 as interleaved float pairs; all pointers are DEVICE memory unless marked
+ * HOST; dtype (FD_BF16 / FD_F32) = storage type of the NHWC tensors; float32 arithmetic throughout; one element per thread, grid-stride
+ * beyond 8192 blocks x 256 threads.  Formulas give the operations per component; a product-sum may be one fused multiply-add. */
+
+/* cat(x.re, x.im, y.re, y.im) -> out8 [B][H][W][8] (8-CHANNEL STRIDE: channels 0..3 = the values, rounded to dtype; 4..7 = 0, the
+ * padding the matrix-core convs need).  x, y: complex [B][H][W]. */
+int fd_op_pack_input(const float* x, const float* y, void* out8, int B, int H, int W, int dtype, void* stream);
+/* Combine 'sum' (layerspp.py:54-69): out[b][p][c] = ((((bias[c] + w[c][0] p4[0]) + w[c][1] p4[1]) + w[c][2] p4[2]) + w[c][3] p4[3]) +
+ * h[b][p][c], each product-sum one fma, stored as dtype.  p4 = [B][H][W][8] (the 4-channel pyramid in the 8-channel stride of
+ * fd_op_pack_input; channels 4..7 are not read), w = [Cout][4] float32, bias = [Cout] float32, h and out = [B][H][W][Cout].
+ * stats = [B][tiles][Cout][2] float32 with tiles = ceil(H W / 256): per-channel (sum, sum of squares) over the 256 consecutive pixels
+ * [256 tile, 256 tile + 256) of the image, taken from the values AS STORED (after rounding to dtype), the format fd_gn_finalize reads.
+ * Cout: a power of two in [8, 256]; 1 <= B <= 65535. */
+int fd_op_combine(const void* p4, const float* w, const float* bias, const void* h, void* out, float* stats, int B, int H, int W, int Cout,
+                  int dtype, void* stream);
+/* The output layer fused with a fixed-step solver's state update.  v = conv(pyr) as complex (channel 0 = re, 1 = im), no bias:
+ *   ks = 1: w = [2][4];        v[o] = fma(w[o][3], p[3], fma(w[o][2], p[2], fma(w[o][1], p[1], w[o][0] p[0])))
+ *   ks = 3: w = [2][4][3][3];  zero padding 'same' within each of the B images; taps ascending (dy, dx), input channels ascending per tap,
+ *           one fma each, from 0.
+ *   ksave = v (if non-NULL);  dst = base + coef * (v + kold)   (kold, base: NULL = that term is absent).
+ * pyr = [B][H][W][4] in dtype (4-CHANNEL STRIDE: the pyramid head's output); base, kold, dst, ksave: complex [B][H][W]. */
+int fd_op_output_update(const void* pyr, const float* w, const float* base, const float* kold, float coef, float* dst, float* ksave, int B,
+                        int H, int W, int ks, int dtype, void* stream);
+/* The output layer fused with a predictor / corrector update of the score sampler:
+ *   dst = fma(cz, z, fma(cy, Y, fma(cn, v, cb * base)))     (v, pyr, w, ks as above)
+ * The Y term is skipped when cy == 0 (Y is not read and may be NULL), the z term when cz == 0 (no noise is read or generated; z and seeds
+ * may both be NULL).  Otherwise exactly one of z (complex [B][H][W]) and seeds (uint64 [B]: z = the plane (seeds[b], draw) of "Seeded
+ * noise" below with F = H, T = W, generated in registers) must be given. */
+int fd_op_score_update(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn, const float* z,
+                       const unsigned long long* seeds, int draw, float cz, float* dst, int B, int H, int W, int ks, int dtype, void* stream);
+/* x0 = Y + sigma_fac * nx,  nx = (float)(sigma[f] * (double)z)   (sigma = float64 [sigma_n], sigma_n = 1: one value for every f, or F).
+ * Y, x0: complex [B][F][T].  Exactly one of noise (complex [B][F][T]) and seeds (uint64 [B]; z = plane (seeds[b], draw) at the absolute
+ * frames frame0[b] + t, frame0 = int32 [B] or NULL = zeros; frame0 needs seeds). */
+int fd_op_init_state(const float* Y, const float* noise, const unsigned long long* seeds, const int* frame0, int draw, const double* sigma,
+                     int sigma_n, float sigma_fac, float* x0, int B, int F, int T, void* stream);
+/* dst = fma(cq, q, a): a, dst complex [B][F][T]; exactly one of q (complex [B][F][T]) and seeds (uint64 [B], plane (seeds[b], draw)). */
+int fd_op_caxpy(const float* a, const float* q, const unsigned long long* seeds, int draw, float cq, float* dst, int B, int F, int T,
+                void* stream);
+/* Adaptive solvers.  n = complex elements of the state (fd_op_ode_lincomb, fd_op_ode_scaled_sq) or of ONE clip of a [B][n] state (the
+ * *_clips forms, 1 <= B <= 65535: one grid row per clip).
+ * dst = fma(cx, x, dt * s),  s = fma(c[m-1], k[m-1], ... fma(c[0], k[0], 0))  over the m terms kept: k, c = HOST arrays of nk <= 7 device
+ * pointers / coefficients, a term with k[j] == NULL or c[j] == 0 is dropped before the launch (its buffer is never read); with cx == 0,
+ * x is not read (may be NULL).  *_clips: clip b uses dt[b] (DEVICE float [B]) and equals fd_op_ode_lincomb on clip b alone, bit for bit. */
+int fd_op_ode_lincomb(const float* x, float cx, float dt, const float* const* k, const float* c, int nk, float* dst, long long n, void* stream);
+int fd_op_ode_lincomb_clips(const float* x, float cx, const float* dt, const float* const* k, const float* c, int nk, float* dst, int B,
+                            long long n, void* stream);
+/* Block partials of the Hairer error norm: partial[nblocks] (float64), their sum = sum_i |p_i - q_i|^2 / (atol + rtol max(|r_i|, |s_i|))^2
+ * (complex moduli; q may be NULL = 0).  Every term is formed in float32 and accumulated in float64; block j owns the elements i = j 256 +
+ * thread (mod nblocks 256); a block that owns no element writes 0.  *_clips: partial[B][nblocks], row b = the partials of
+ * fd_op_ode_scaled_sq on clip b alone, bit for bit.  nblocks >= 1 (the solvers use 512). */
+int fd_op_ode_scaled_sq(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks,
+                        long long n, void* stream);
+int fd_op_ode_scaled_sq_clips(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial,
+                              int nblocks, int B, long long n, void* stream);
+/* Masked commit of an attempted step: for every clip b with accept[b] != 0 (int32 [B]): x[b] = x_new[b], k0[b] = k6[b], and, where
+ * ckpt[b] > 0 (int32 [B]) and traj != NULL, traj[ckpt[b]][b] = x_new[b]   (traj = complex [ckpt][B][n]).  Nothing else is written. */
+int fd_op_ode_commit_clips(const int* accept, const int* ckpt, const float* x_new, const float* k6, float* x, float* k0, float* traj, int B,
+                           long long n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Front / back end
  * ---------------------------------------------------------------------------------------------- */
 
