@@ -107,6 +107,8 @@ SIGNATURES = {
     "fd_op_ode_scaled_sq": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int, c_ll, _P]),
     "fd_op_ode_scaled_sq_clips": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int, c_int, c_ll, _P]),
     "fd_op_ode_commit_clips": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_ll, _P]),
+    "fd_op_time_embedding": (c_int, [_P, c_float, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
+    "fd_op_temb_bias_jobs": (c_int, [_P, c_int, c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(c_int), c_int, _P]),
     "fd_resblock_workspace_bytes": (c_size_t, [C.POINTER(FdResblockDesc), c_int, c_int, c_int, c_int]),
     "fd_resblock": (c_int, [C.POINTER(FdResblockDesc), _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "fd_attn_block_workspace_bytes": (c_size_t, [C.POINTER(FdAttnDesc), c_int, c_int, c_int, c_int]),

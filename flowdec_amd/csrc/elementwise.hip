@@ -521,7 +521,8 @@ __global__ void fused_bias_act_kernel(const float* __restrict__ x, const float* 
 // =====================================================================================================
 // Time embedding (ncsnpp.py:263-274, layerspp.py:42-51) -- one block per t row.
 // =====================================================================================================
-// acc = init + sum_k w[k] * x[k], k ascending (one fma per term: the order the parity tests pin), n % 4 == 0.  The weight row is read
+// acc = init + sum_k w[k] * x[k], k ascending (one fma per term: the order the parity tests pin), n % 4 == 0 and w 16-byte aligned (the
+// public entry points refuse anything else: fd_check_time_embedding / fd_check_temb_bias, ops_api.hip).  The weight row is read
 // as 16-byte vectors with 16 of them in flight: these matrix-vector products are one dependent chain per thread and sit on the
 // critical path of every network evaluation.
 __device__ __forceinline__ float fd_row_dot(const float* __restrict__ w, const float* x, int n, float init) {
@@ -1216,7 +1217,8 @@ int fd_time_embedding_impl(const float* t, float t_imm, int nt, const float* gfp
 
 extern "C" int fd_time_embedding(const float* t, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,
                                  const float* w2, const float* b2, float* temb, void* stream) {
-  FD_REQUIRE(t && gfp_w && w1 && b1 && w2 && b2 && temb && nt > 0 && nf > 0, "fd_time_embedding: bad arguments");
+  FD_REQUIRE(t, "fd_time_embedding: null pointer (t)");
+  FD_TRY(fd_check_time_embedding("fd_time_embedding", nt, gfp_w, nf, w1, b1, w2, b2, temb));
   return fd_time_embedding_impl(t, 0.f, nt, gfp_w, nf, w1, b1, w2, b2, temb, fd_stream(stream));
 }
 
@@ -1228,7 +1230,8 @@ int fd_temb_bias_batched(const fd_temb_job* jobs_dev, int njobs, const float* te
 
 extern "C" int fd_temb_bias(const float* temb, int nt, int temb_dim, const float* dense_w, const float* dense_b,
                             const float* conv_bias, int Cout, float* out, void* stream) {
-  FD_REQUIRE(temb && dense_w && dense_b && out && nt > 0 && temb_dim > 0 && Cout > 0, "fd_temb_bias: bad arguments");
+  FD_TRY(fd_check_temb_bias("fd_temb_bias", temb, nt, temb_dim));
+  FD_TRY(fd_check_temb_job("fd_temb_bias", -1, dense_w, dense_b, out, Cout));
   fd_temb_job j{dense_w, dense_b, conv_bias, out, Cout};
   hipLaunchKernelGGL(temb_bias_single_kernel, dim3(nt), dim3(256), sizeof(float) * temb_dim, fd_stream(stream), j, temb, temb_dim);
   FD_LAUNCH_CHECK();

@@ -41,6 +41,12 @@ struct fd_edge_args {
 int fd_time_embedding_impl(const float* t, float t_imm, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,
                            const float* w2, const float* b2, float* temb, hipStream_t st);
 int fd_temb_bias_batched(const fd_temb_job* jobs_dev, int njobs, const float* temb, int nt, int temb_dim, hipStream_t st);
+// ops_api.hip: the argument checks of the public time-conditioning entry points (fd_time_embedding, fd_temb_bias and their fd_op_*
+// forms): FD_EINVAL with a message that names the argument, before any device call.  `who` = the entry point's name.
+int fd_check_time_embedding(const char* who, int nt, const float* gfp_w, int nf, const float* w1, const float* b1, const float* w2,
+                            const float* b2, const float* temb);
+int fd_check_temb_bias(const char* who, const float* temb, int nt, int temb_dim);
+int fd_check_temb_job(const char* who, int job, const float* dense_w, const float* dense_b, const float* out, int Cout);
 // which: 0 = pack_input, 2 = combine (1x1 4->Cout + h), 3 = output layer + state update,
 //        4 = output layer + score-sampler update, 5 = input convolution 3x3 4 -> Cout (x = packed input, w = [Cout][4][3][3] f32) with
 //        the GroupNorm partials of its output in `stats` ([B][(H / 16) * (W / 16)][Cout][2])

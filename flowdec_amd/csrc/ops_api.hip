@@ -1,8 +1,11 @@
-// ops_api.hip -- operator-level C ABI of the kernels between the network and the ODE / SDE solvers (include/flowdec_hip.h,
-// "Operator-level: solver and edge kernels").  Every entry point checks its arguments and then calls the launcher the model and the
-// solvers call (fd_edge_op, fd_init_state, fd_caxpy, fd_ode_*: internal.h).  No kernel and no launch configuration lives here, so a test
+// ops_api.hip -- operator-level C ABI of the kernels between the network and the ODE / SDE solvers and of the time-conditioning kernels
+// (include/flowdec_hip.h, "Operator-level: solver and edge kernels").  Every entry point checks its arguments and then calls the launcher
+// the model and the solvers call (fd_edge_op, fd_init_state, fd_caxpy, fd_ode_*, fd_time_embedding_impl, fd_temb_bias_batched: internal.h).  No kernel and no launch configuration lives here, so a test
 // of one of these functions is a test of the production launch.  A refused call launches nothing.
 #include <limits.h>
+#include <stdint.h>
+
+#include <vector>
 
 #include "common.h"
 #include "internal.h"
@@ -10,6 +13,14 @@
 namespace {
 
 constexpr int MAX_GRID_Y = 65535;
+constexpr int MAX_GRID_X_256 = (1 << 24) - 1;       // HIP: gridDim.x * blockDim.x < 2^32, with the 256-thread blocks of these kernels
+// Dynamic LDS one workgroup of the time-conditioning kernels may ask for.  A compile-time figure, so that the refusal needs no device:
+// the 64 KiB every CDNA device grants a workgroup (gfx950 itself has 160 KiB); nf <= 2730 and temb_dim <= 16384 are far beyond any model.
+constexpr long long MAX_DYN_LDS_BYTES = 64 * 1024;
+
+// fd_row_dot (elementwise.hip) reads a weight row as 16-byte vectors: with a row length that is a multiple of 4 floats every row is
+// aligned when the base pointer is
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // dtype, B >= 1 and an H x W image whose pixel count fits the kernels' int arithmetic
 int check_image(const char* who, int B, int H, int W, int dtype) {
@@ -45,6 +56,75 @@ int check_scaled_sq(const char* who, const float* p, const float* r, const float
 }
 
 }  // namespace
+
+// ---- time conditioning: the checks shared by fd_time_embedding / fd_temb_bias (elementwise.hip) and their fd_op_* forms ---------------
+int fd_check_time_embedding(const char* who, int nt, const float* gfp_w, int nf, const float* w1, const float* b1, const float* w2,
+                            const float* b2, const float* temb) {
+  FD_REQUIRE(gfp_w, "%s: null pointer (gfp_w)", who);
+  FD_REQUIRE(w1 && b1, "%s: null pointer (w1 / b1)", who);
+  FD_REQUIRE(w2 && b2, "%s: null pointer (w2 / b2)", who);
+  FD_REQUIRE(temb, "%s: null pointer (temb)", who);
+  FD_REQUIRE(nt >= 1 && nt <= MAX_GRID_X_256, "%s: nt must be in [1, %d] (got %d)", who, MAX_GRID_X_256, nt);
+  // rows of 2 nf and 4 nf floats are read as 4-float vectors
+  FD_REQUIRE(nf >= 2 && nf % 2 == 0, "%s: nf must be even and >= 2 (got %d)", who, nf);
+  FD_REQUIRE(6LL * nf * (long long)sizeof(float) <= MAX_DYN_LDS_BYTES, "%s: nf = %d needs %lld bytes of shared memory (6 nf floats), above the limit of %lld",
+             who, nf, 6LL * nf * (long long)sizeof(float), MAX_DYN_LDS_BYTES);
+  FD_REQUIRE(aligned16(w1), "%s: w1 is not 16-byte aligned", who);
+  FD_REQUIRE(aligned16(w2), "%s: w2 is not 16-byte aligned", who);
+  return FD_OK;
+}
+
+int fd_check_temb_bias(const char* who, const float* temb, int nt, int temb_dim) {
+  FD_REQUIRE(temb, "%s: null pointer (temb)", who);
+  FD_REQUIRE(nt >= 1 && nt <= MAX_GRID_X_256, "%s: nt must be in [1, %d] (got %d)", who, MAX_GRID_X_256, nt);
+  FD_REQUIRE(temb_dim >= 4 && temb_dim % 4 == 0, "%s: temb_dim must be a multiple of 4 and >= 4 (got %d)", who, temb_dim);
+  FD_REQUIRE((long long)temb_dim * (long long)sizeof(float) <= MAX_DYN_LDS_BYTES, "%s: temb_dim = %d needs %lld bytes of shared memory, above the limit of %lld",
+             who, temb_dim, (long long)temb_dim * (long long)sizeof(float), MAX_DYN_LDS_BYTES);
+  return FD_OK;
+}
+
+// job < 0: the single form (no job index in the message)
+int fd_check_temb_job(const char* who, int job, const float* dense_w, const float* dense_b, const float* out, int Cout) {
+  char where[32] = "";
+  if (job >= 0) snprintf(where, sizeof where, " of job %d", job);
+  FD_REQUIRE(dense_w && dense_b, "%s: null pointer (dense_w / dense_b%s)", who, where);
+  FD_REQUIRE(out, "%s: null pointer (out%s)", who, where);
+  FD_REQUIRE(Cout >= 1, "%s: Cout%s must be >= 1 (got %d)", who, where, Cout);
+  FD_REQUIRE(aligned16(dense_w), "%s: dense_w%s is not 16-byte aligned", who, where);
+  return FD_OK;
+}
+
+extern "C" int fd_op_time_embedding(const float* t, float t_imm, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,
+                                    const float* w2, const float* b2, float* temb, void* stream) {
+  FD_TRY(fd_check_time_embedding("fd_op_time_embedding", nt, gfp_w, nf, w1, b1, w2, b2, temb));
+  return fd_time_embedding_impl(t, t_imm, nt, gfp_w, nf, w1, b1, w2, b2, temb, fd_stream(stream));
+}
+
+extern "C" int fd_op_temb_bias_jobs(const float* temb, int nt, int temb_dim, const float* const* dense_w, const float* const* dense_b,
+                                    const float* const* conv_b, float* const* out, const int* cout, int njobs, void* stream) {
+  FD_TRY(fd_check_temb_bias("fd_op_temb_bias_jobs", temb, nt, temb_dim));
+  FD_REQUIRE(nt <= MAX_GRID_Y, "fd_op_temb_bias_jobs: nt must be in [1, 65535] (got %d)", nt);
+  FD_REQUIRE(njobs >= 1 && njobs <= MAX_GRID_X_256, "fd_op_temb_bias_jobs: njobs must be in [1, %d] (got %d)", MAX_GRID_X_256, njobs);
+  FD_REQUIRE(dense_w && dense_b && conv_b && out && cout, "fd_op_temb_bias_jobs: null pointer (job tables)");
+  std::vector<fd_temb_job> jobs((size_t)njobs);
+  for (int j = 0; j < njobs; ++j) {
+    FD_TRY(fd_check_temb_job("fd_op_temb_bias_jobs", j, dense_w[j], dense_b[j], out[j], cout[j]));
+    // the batched kernel reads conv_b unconditionally: only fd_temb_bias takes NULL as "no conv bias"
+    FD_REQUIRE(conv_b[j], "fd_op_temb_bias_jobs: null pointer (conv_b of job %d)", j);
+    jobs[j] = fd_temb_job{dense_w[j], dense_b[j], conv_b[j], out[j], cout[j]};
+  }
+  fd_temb_job* jobs_dev = nullptr;
+  FD_HIP(hipMalloc(&jobs_dev, sizeof(fd_temb_job) * jobs.size()));
+  int rc = FD_OK;
+  if (hipMemcpy(jobs_dev, jobs.data(), sizeof(fd_temb_job) * jobs.size(), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fd_set_error(FD_ERUNTIME, "fd_op_temb_bias_jobs: copying the job table failed");
+  if (rc == FD_OK) rc = fd_temb_bias_batched(jobs_dev, njobs, temb, nt, temb_dim, fd_stream(stream));
+  // the kernel reads the table: it is released only once the stream has finished with it (a synchronous entry point, for tests)
+  if (hipStreamSynchronize(fd_stream(stream)) != hipSuccess && rc == FD_OK)
+    rc = fd_set_error(FD_ERUNTIME, "fd_op_temb_bias_jobs: hipStreamSynchronize failed");
+  hipFree(jobs_dev);
+  return rc;
+}
 
 extern "C" int fd_op_pack_input(const float* x, const float* y, void* out8, int B, int H, int W, int dtype, void* stream) {
   FD_REQUIRE(x && y && out8, "fd_op_pack_input: null pointer");

@@ -185,12 +185,34 @@ def time_embedding(t, gfp_w, w1, b1, w2, b2):
     return out
 
 
-def temb_bias(temb, dense_w, dense_b, conv_bias):
+def temb_bias(temb, dense_w, dense_b, conv_bias, out=None):
     nt, D = temb.shape
     Cout = dense_w.shape[0]
-    out = torch.empty(nt, Cout, dtype=torch.float32, device=temb.device)
+    out = torch.empty(nt, Cout, dtype=torch.float32, device=temb.device) if out is None else out
     L.check(L.load().fd_temb_bias(L.ptr(temb), nt, D, L.ptr(dense_w), L.ptr(dense_b), L.ptr(conv_bias), Cout, L.ptr(out), L.stream()))
     return out
+
+
+def op_time_embedding(t, gfp_w, w1, b1, w2, b2, out=None):
+    """fd_op_time_embedding: t = a float32 tensor [nt], or a Python float (the scalar-time path: t == NULL, the time passed by value)."""
+    imm = not torch.is_tensor(t)
+    nt, nf = (1 if imm else t.numel()), gfp_w.numel()
+    out = torch.empty(nt, 4 * nf, dtype=torch.float32, device=gfp_w.device) if out is None else out
+    L.check(L.load().fd_op_time_embedding(None if imm else L.ptr(t), float(t) if imm else 0.0, nt, L.ptr(gfp_w), nf, L.ptr(w1), L.ptr(b1),
+                                          L.ptr(w2), L.ptr(b2), L.ptr(out), L.stream()))
+    return out
+
+
+def temb_bias_jobs(temb, jobs):
+    """fd_op_temb_bias_jobs: jobs = [(dense_w [Cout, D], dense_b [Cout], conv_b [Cout], out [nt, Cout])], all float32 GPU tensors; one launch
+    writes every out.  Synchronises the current stream."""
+    import ctypes as C
+    nt, D = temb.shape
+    n = len(jobs)
+    col = lambda i: (C.c_void_p * max(n, 1))(*[None if j[i] is None else j[i].data_ptr() for j in jobs])
+    couts = (C.c_int * max(n, 1))(*[int(j[0].shape[0]) for j in jobs])
+    L.check(L.load().fd_op_temb_bias_jobs(L.ptr(temb), nt, D, col(0), col(1), col(2), col(3), couts, n, L.stream()))
+    return [j[3] for j in jobs]
 
 
 # ---- operator-level entry points of the solver and edge kernels (include/flowdec_hip.h "Operator-level: solver and edge kernels") ----

@@ -231,10 +231,14 @@ enum { FD_CONV_KERNEL_DIRECT, FD_CONV_KERNEL_DIRECT_MIXED, FD_CONV_KERNEL_DIRECT
 int fd_conv_kernel_counts(long long* counts, int n);
 
 /* Time embedding: GaussianFourierProjection -> Linear -> SiLU -> Linear (ncsnpp.py:263-274,
- * layerspp.py:42-51); t [nt] float32 -> temb [nt][4*nf]. */
+ * layerspp.py:42-51); t [nt] float32 -> temb [nt][4*nf].  gfp_w [nf], w1 [4nf][2nf], w2 [4nf][4nf] row-major.  FD_EINVAL (nothing
+ * launched) for a null pointer, nt < 1, nf odd or < 2 (weight rows are read as 4-float vectors), 6 nf floats above the 64 KiB of shared
+ * memory the launch may ask for, and w1 / w2 not 16-byte aligned. */
 int fd_time_embedding(const float* t, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,
                       const float* w2, const float* b2, float* temb, void* stream);
-/* out[r][o] = conv_bias[o] + dense_b[o] + sum_k dense_w[o][k] * silu(temb[r][k])  (layerspp.py:272-273). */
+/* out[r][o] = conv_bias[o] + dense_b[o] + sum_k dense_w[o][k] * silu(temb[r][k])  (layerspp.py:272-273); conv_bias NULL = no conv
+ * bias.  FD_EINVAL (nothing launched) for a null pointer, nt < 1, Cout < 1, temb_dim < 4 or not a multiple of 4, temb_dim floats above
+ * 64 KiB of shared memory, and dense_w not 16-byte aligned. */
 int fd_temb_bias(const float* temb, int nt, int temb_dim, const float* dense_w, const float* dense_b,
                  const float* conv_bias, int Cout, float* out, void* stream);
 
@@ -322,6 +326,24 @@ int fd_op_ode_scaled_sq_clips(const float* p, const float* q, const float* r, co
  * ckpt[b] > 0 (int32 [B]) and traj != NULL, traj[ckpt[b]][b] = x_new[b]   (traj = complex [ckpt][B][n]).  Nothing else is written. */
 int fd_op_ode_commit_clips(const int* accept, const int* ckpt, const float* x_new, const float* k6, float* x, float* k0, float* traj, int B,
                            long long n, void* stream);
+
+/* Time conditioning (csrc/elementwise.hip: time_embedding_kernel, temb_bias_kernel), through the launchers fd_ncsnpp_forward calls.
+ * fd_op_time_embedding = fd_time_embedding with the scalar-time path of the fixed-step solvers: t == NULL takes the time of every row
+ * from t_imm (passed by value, no device read); with t != NULL, t_imm is ignored.  Row r:
+ *   xp = ((t[r] * gfp_w[j]) * 2) * pi_f32 (three float32 roundings), emb = (sinf(xp) [nf], cosf(xp) [nf]),
+ *   hid[o] = silu(fma chain over k ascending of w1[o][k] emb[k], from b1[o]),  temb[r][o] = the same chain of w2[o][k] hid[k] from b2[o].
+ * Refusals as fd_time_embedding (t may be NULL). */
+int fd_op_time_embedding(const float* t, float t_imm, int nt, const float* gfp_w, int nf, const float* w1, const float* b1, const float* w2,
+                         const float* b2, float* temb, void* stream);
+/* The batched table of every ResBlock's time bias in one launch (grid = jobs x rows), as the model runs it: for job j, row r
+ *   out[j][r][o] = (fma chain over k ascending of dense_w[j][o][k] * silu(temb[r][k]), from dense_b[j][o]) + conv_b[j][o],  o < cout[j],
+ * bit-identical to fd_temb_bias on job j alone.  dense_w, dense_b, conv_b, out, cout: HOST arrays of njobs device pointers / channel counts;
+ * out[j] = [nt][cout[j]].  The entry builds the device job table, launches and SYNCHRONISES the stream before it releases the table: a
+ * synchronous entry point for tests (the model keeps its table for its lifetime).  Refusals as fd_temb_bias per job, and: njobs < 1 or
+ * above 2^24 - 1 (grid x of 256-thread blocks), nt > 65535 (grid y), a NULL conv_b[j] (this kernel reads it unconditionally; only
+ * fd_temb_bias takes NULL as "no conv bias"). */
+int fd_op_temb_bias_jobs(const float* temb, int nt, int temb_dim, const float* const* dense_w, const float* const* dense_b,
+                         const float* const* conv_b, float* const* out, const int* cout, int njobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Front / back end

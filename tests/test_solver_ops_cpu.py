@@ -28,7 +28,8 @@ def test_symbols_are_declared_exported_and_bound():
         assert name in decl, f"{name} is not declared in include/flowdec_hip.h"
         assert name in L.SIGNATURES, f"{name} has no ctypes signature"
         assert getattr(lib, name).argtypes == L.SIGNATURES[name][1]
-    assert {n for n in decl if n.startswith("fd_op_")} == set(NAMES)
+    # the section also holds the two time-conditioning entries, which tests/test_temb_cpu.py checks
+    assert {n for n in decl if n.startswith("fd_op_")} == set(NAMES) | {"fd_op_time_embedding", "fd_op_temb_bias_jobs"}
     for helper in ("pack_input", "combine", "output_update", "score_update", "init_state", "caxpy", "ode_lincomb", "ode_scaled_sq", "ode_commit_clips"):
         assert callable(getattr(ops, helper))
     assert "ops_api.hip" in __import__("flowdec_amd.build", fromlist=["SOURCES"]).SOURCES
