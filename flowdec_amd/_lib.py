@@ -80,6 +80,7 @@ class FdStreamRow(C.Structure):
 
 PREDICTORS = {"reverse_diffusion": 0, "euler_maruyama": 1, "none": 2}
 CORRECTORS = {"ald": 0, "none": 1}
+STEP_CONTROL = {"batch": 0, "clip": 1}   # FD_STEP_CONTROL_* of the ODE sampler (fd_score_ode_solve / fd_score_ode_enhance)
 
 # name -> (restype, [argtypes]); must list every function declared in include/flowdec_hip.h
 _P = c_void_p
@@ -174,6 +175,13 @@ SIGNATURES = {
     "fd_score_enhance": (c_int, [_P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_enhance_ragged": (c_int, [_P, _P, _P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_eval": (c_int, [_P, _P, _P, c_float, C.POINTER(FdScoreConfig), c_int, _P, c_int, c_int, _P, c_size_t, _P]),
+    "fd_score_update_clips": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_score_ode_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "fd_score_ode_solve": (c_int, [_P, _P, _P, _P, C.POINTER(FdScoreConfig), c_float, c_float, c_int, _P, C.POINTER(c_int), C.POINTER(c_int),
+                                   C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
+    "fd_score_ode_enhance_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "fd_score_ode_enhance": (c_int, [_P, _P, _P, _P, _P, C.POINTER(FdScoreConfig), c_float, c_float, c_int, _P, C.POINTER(c_int), C.POINTER(c_int),
+                                     C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
     "fd_regression_enhance": (c_int, [_P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_regression_enhance_ragged": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_profile_enable": (c_int, [_P, c_int]),

@@ -867,6 +867,37 @@ __global__ void score_update_kernel(const T* __restrict__ pyr, const float* __re
   }
 }
 
+// score_update_kernel with one time per clip and without the noise term (the right-hand side of the ScoreDec ODE sampler under per-clip
+// step control):  dst[b] = cb_b * base[b] + cy_b * Y[b] + cn_b * v[b],  (cb_b, cy_b, cn_b) = ctab[b][0..2].  The clip is blockIdx.y, so the
+// three coefficients are one wave-uniform load per block and no element divides by the clip size; a block walks its clip's H * W elements
+// with the scalar kernel's one element per thread (consecutive lanes, consecutive 8 / 16-byte vectors).  Per element the arithmetic is
+// score_update_kernel's -- the same fmaf chain, the same skip at cy == 0 --, so clip b equals that kernel on the clip alone, bit for bit.
+template <typename T, int KS>
+__global__ void score_update_clips_kernel(const T* __restrict__ pyr, const float* __restrict__ wo, const float2* __restrict__ base,
+                                          const float2* __restrict__ Y, const float* __restrict__ ctab, float2* __restrict__ dst, long long nclip,
+                                          int H, int W) {
+  const float w0 = wo[0], w1 = wo[1], w2 = wo[2], w3 = wo[3], w4 = wo[4], w5 = wo[5], w6 = wo[6], w7 = wo[7];
+  const float cb = ctab[3 * blockIdx.y], cy = ctab[3 * blockIdx.y + 1], cn = ctab[3 * blockIdx.y + 2];
+  const long long first = (long long)blockIdx.y * nclip;
+  for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < nclip; j += (long long)gridDim.x * blockDim.x) {
+    const long long i = first + j;
+    float vx, vy;
+    if constexpr (KS == 3) {
+      const float2 v = output3x3<T>(pyr, wo, i, H, W);
+      vx = v.x; vy = v.y;
+    } else {
+      float p[4];
+      fd_load_vec<T, 4>(pyr + 4 * i, p);
+      vx = fmaf(w3, p[3], fmaf(w2, p[2], fmaf(w1, p[1], w0 * p[0])));
+      vy = fmaf(w7, p[3], fmaf(w6, p[2], fmaf(w5, p[1], w4 * p[0])));
+    }
+    const float2 b = base[i];
+    float2 o = {fmaf(cn, vx, cb * b.x), fmaf(cn, vy, cb * b.y)};
+    if (cy != 0.f) { const float2 yv = Y[i]; o.x = fmaf(cy, yv.x, o.x); o.y = fmaf(cy, yv.y, o.y); }
+    dst[i] = o;
+  }
+}
+
 // dst = a + cq * q  (prior sample x_T = Y + std(T) * z, sdes.py:197-202); q = a [B][F][T] plane of noise (buffer or seeds)
 template <bool SEEDED>
 __global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restrict__ q, const unsigned long long* __restrict__ seeds, int draw,
@@ -1261,7 +1292,16 @@ static int edge_launch(int which, const fd_edge_args& a, hipStream_t st) {
     }
     case 4: {  // output + score-sampler update
       const long long n = (long long)a.B * a.H * a.W;
-#define FD_SCORE_UPDATE(KS_, SEEDED_)                                                                                                          \
+      if (a.ctab) {   // one time per clip: the clip is the grid's y
+        const long long nclip = (long long)a.H * a.W;
+        const dim3 grid(grid_for(nclip, 256, 8192), a.B);
+        if (a.ks == 3)
+          hipLaunchKernelGGL((score_update_clips_kernel<T, 3>), grid, dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.y, a.ctab, (float2*)a.out, nclip, a.H, a.W);
+        else
+          hipLaunchKernelGGL((score_update_clips_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.y, a.ctab, (float2*)a.out, nclip, a.H, a.W);
+        break;
+      }
+#define FD_SCORE_UPDATE(KS_, SEEDED_)                                                                                                         \
   hipLaunchKernelGGL((score_update_kernel<T, KS_, SEEDED_>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, \
                      a.cb, (const float2*)a.y, a.cy, a.coef, (const float2*)a.z.ptr, a.z.seeds, a.z.draw, a.cz, (float2*)a.out, n, a.H, a.W)
       if (a.z.seeds) { if (a.ks == 3) FD_SCORE_UPDATE(3, true); else FD_SCORE_UPDATE(1, true); }

@@ -165,6 +165,57 @@ extern "C" int fd_score_enhance_ragged(fd_model* m, const float* y, const int* l
   return score_enhance_impl(m, "fd_score_enhance_ragged", y, lengths, src, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
 }
 
+// ---- the ODE sampler from waveform to waveform: enhance_common's front end and back end around score_ode_run (solve.hip), eagerly -- the
+// adaptive loop reads an error norm back per attempt, so there is nothing to capture.  Workspace: Y | X | normfac[B] | rest, rest = the
+// larger of the transform's and the adaptive driver's.
+namespace {
+bool score_ode_layout(const fd_model* m, int B, int L, bool per_clip, enhance_layout_t& s) {
+  if (!enhance_layout(m, B, L, s)) return false;
+  const size_t a = fd_stft_ws_bytes(B, L, m->cfg.n_fft, m->cfg.hop), b = score_ode_ws_bytes(m, B, s.Tp, per_clip);
+  s.total = s.rest + (a > b ? a : b) + 256;
+  return true;
+}
+}  // namespace
+
+extern "C" size_t fd_score_ode_enhance_workspace_bytes(const fd_model* m, int B, int L, int step_control) {
+  enhance_layout_t s;
+  if (step_control != FD_STEP_CONTROL_BATCH && step_control != FD_STEP_CONTROL_CLIP) return 0;
+  if (step_control == FD_STEP_CONTROL_CLIP && B > fd_model::MAX_NT) return 0;
+  return score_ode_layout(m, B, L, step_control == FD_STEP_CONTROL_CLIP, s) ? s.total : 0;
+}
+
+extern "C" int fd_score_ode_enhance(fd_model* m, const float* y, const int* lengths, const float* noise, const unsigned long long* seeds,
+                                    const fd_score_config* cfg, float rtol, float atol, int step_control, float* x_hat, int* nfe_out,
+                                    int* rejected_out, int* evals_out, int B, int L, void* ws, size_t ws_bytes, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_ode_enhance");
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(y && x_hat && ws && nfe_out, "fd_score_ode_enhance: null pointer");
+  FD_REQUIRE((noise != nullptr) != (seeds != nullptr), "fd_score_ode_enhance: give exactly one of noise and seeds");
+  FD_REQUIRE(B > 0 && L > m->cfg.n_fft / 2, "fd_score_ode_enhance: clips must be longer than %d samples", m->cfg.n_fft / 2);
+  FD_TRY(score_ode_check("fd_score_ode_enhance", cfg, rtol, atol, step_control, B));
+  const bool per_clip = step_control == FD_STEP_CONTROL_CLIP;
+  enhance_layout_t lay;
+  if (!score_ode_layout(m, B, L, per_clip, lay)) return FD_EINVAL;   // check_shape has left the message
+  if (ws_bytes < lay.total) return fd_set_error(FD_ENOMEM, "fd_score_ode_enhance: workspace %zu < required %zu bytes", ws_bytes, lay.total);
+  hipStream_t st = fd_stream(stream);
+  float* Y = (float*)ws;
+  float* X = (float*)((char*)ws + lay.state);
+  float* normfac = (float*)((char*)ws + lay.normfac);
+  char* rest = (char*)ws + lay.rest;
+  const size_t rest_bytes = ws_bytes - lay.rest;
+  const int n = per_clip ? B : 1;
+  std::vector<int> nfe(n), rejected(n);
+  int evals = 0;
+  FD_TRY(fd_stft_forward(m->stft, y, lengths, B, L, m->cfg.alpha, m->cfg.beta, m->normalize, normfac, Y, lay.Tp, rest, rest_bytes, st));
+  FD_TRY(score_ode_run(m, "fd_score_ode_enhance", Y, seeds ? fd_noise_src{nullptr, seeds, 0} : fd_noise_src{noise}, *cfg, rtol, atol, per_clip, X,
+                       nfe.data(), rejected.data(), &evals, B, lay.Tp, rest, rest_bytes, st));
+  FD_TRY(fd_stft_inverse(m->stft, X, lengths, B, lay.T, lay.Tp, m->cfg.alpha, m->cfg.beta, normfac, x_hat, L, rest, rest_bytes, st));
+  FD_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < n; ++b) { nfe_out[b] = nfe[b]; if (rejected_out) rejected_out[b] = rejected[b]; }
+  if (evals_out) *evals_out = evals;
+  return FD_OK;
+}
+
 static int regression_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
                                    int use_graph, void* stream) {
   GraphKey key; key.kind = 4;

@@ -33,6 +33,7 @@ struct fd_edge_args {
   float coef = 1.f;
   fd_noise_src z;              // score update: dst = cb*base + cy*y + coef*v + cz*z
   float cb = 1.f, cy = 0.f, cz = 0.f;
+  const float* ctab = nullptr; // score update, per-clip form: (cb, cy, coef) of clip b from ctab[b][0..2] (DEVICE [B][3]); no noise term
   int B = 0, H = 0, W = 0, Cout = 0;
   int ks = 1;                  // output layer (ops 3, 4): 1x1 or 3x3 (zero padding 'same'; w = [2][4][3][3])
 };

@@ -470,7 +470,7 @@ struct Fwd {
     if (!dry) {
       fd_edge_args a; a.x = ptr(pyramid.off); a.w = m->wo; a.base = os.base; a.kold = os.kold; a.coef = os.coef; a.out = os.dst; a.ksave = os.ksave;
       a.B = B; a.H = F; a.W = T; a.ks = m->arch.output_ksize;
-      if (os.score) { a.y = os.yv; a.z = os.z; a.cb = os.cb; a.cy = os.cy; a.cz = os.cz; }
+      if (os.score) { a.y = os.yv; a.z = os.z; a.cb = os.cb; a.cy = os.cy; a.cz = os.cz; a.ctab = os.ctab; }
       FD_TRY(fd_edge_op(os.score ? 4 : 3, a, dt, st));
     }
     tfree(pyramid);

@@ -131,6 +131,8 @@ struct OutSpec {           // what to do with v = NCSNpp(x, y, t):  dst = base +
   const float* yv = nullptr;
   fd_noise_src z;
   float cb = 1.f, cy = 0.f, cz = 0.f;
+  // per-clip score form (ctab given; no noise term): clip b reads (cb, cy, coef) from ctab[b][0..2] (DEVICE float [B][3])
+  const float* ctab = nullptr;
 };
 
 // model.hip
@@ -145,6 +147,11 @@ int ode_enqueue(fd_model* m, const float* Y, const fd_noise_src& noise, float si
                 size_t ws_bytes, hipStream_t st);
 int score_enqueue(fd_model* m, const float* Y, const fd_noise_src& noise, const fd_score_config& c, float* X, int B, int T, void* ws, size_t ws_bytes,
                   hipStream_t st);
+// the ScoreDec ODE sampler on features (fd_score_ode_solve / fd_score_ode_enhance): argument checks, workspace, the synchronous solve
+int score_ode_check(const char* who, const fd_score_config* c, float rtol, float atol, int step_control, int B);
+size_t score_ode_ws_bytes(const fd_model* m, int B, int T, bool per_clip);
+int score_ode_run(fd_model* m, const char* who, const float* Y, const fd_noise_src& noise, const fd_score_config& c, float rtol, float atol, bool per_clip,
+                  float* X, int* nfe, int* rejected, int* evals, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
 
 template <typename Fn>
 int run_maybe_graph(fd_model* m, const GraphKey& key, bool use_graph, hipStream_t st, Fn&& enqueue) {

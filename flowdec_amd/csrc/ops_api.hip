@@ -169,6 +169,18 @@ extern "C" int fd_op_score_update(const void* pyr, const float* w, const float* 
   return fd_edge_op(4, a, dtype, fd_stream(stream));
 }
 
+extern "C" int fd_score_update_clips(const void* pyr, const float* w, const float* base, const float* Y, const float* ctab, float* dst, int B, int H,
+                                        int W, int ks, int dtype, void* stream) {
+  // cy lives on the device, so Y is always required
+  FD_REQUIRE(pyr && w && base && Y && ctab && dst, "fd_score_update_clips: null pointer");
+  FD_TRY(check_image("fd_score_update_clips", B, H, W, dtype));
+  FD_REQUIRE(B <= MAX_GRID_Y, "fd_score_update_clips: B must be in [1, 65535] (got %d)", B);
+  FD_REQUIRE(ks == 1 || ks == 3, "fd_score_update_clips: ks must be 1 or 3 (got %d)", ks);
+  fd_edge_args a;
+  a.x = pyr; a.w = w; a.base = base; a.y = Y; a.ctab = ctab; a.out = dst; a.B = B; a.H = H; a.W = W; a.ks = ks;
+  return fd_edge_op(4, a, dtype, fd_stream(stream));
+}
+
 extern "C" int fd_op_init_state(const float* Y, const float* noise, const unsigned long long* seeds, const int* frame0, int draw,
                                 const double* sigma, int sigma_n, float sigma_fac, float* x0, int B, int F, int T, void* stream) {
   FD_REQUIRE(Y && sigma && x0, "fd_op_init_state: null pointer");

@@ -1,7 +1,8 @@
 // solve.hip -- everything that integrates the network (model.hip: forward_call) over time, host side: the fixed-step ODE loop
 // (model.py:503-515; torchdyn fixed-step semantics restated) behind fd_ode_solve with hipGraph capture, the ScoreDec
 // predictor-corrector sampler and fd_score_eval, and the adaptive dopri5 / tsit5 solvers: ONE host loop over step_ctl.h's controllers,
-// driven batch-globally (fd_ode_solve_adaptive*) or per clip (fd_ode_solve_adaptive_clips).
+// driven batch-globally (fd_ode_solve_adaptive*) or per clip (fd_ode_solve_adaptive_clips) -- and, on the ScoreDec probability-flow drift
+// under scipy RK45's step-size rule, the ODE sampler of the score model (fd_score_ode_solve; waveform form: enhance.hip).
 #include <math.h>
 #include <string.h>
 
@@ -77,6 +78,16 @@ float ouve_std(const fd_score_config& c, float t) {
 float ouve_diffusion(const fd_score_config& c, float t) {
   const float ls = logf(c.sigma_max / c.sigma_min);
   return c.sigma_min * powf(c.sigma_max / c.sigma_min, t) * sqrtf(2.f * ls);
+}
+// The epilogue coefficients of one fd_score_eval at time t, o = (cb, cy, cn):  out = cb x + cy Y + cn v
+void score_coefs(const fd_score_config& c, float t, int mode, float* o) {
+  const float std_t = ouve_std(c, t), g = ouve_diffusion(c, t);
+  if (mode == FD_SCORE_DENOISE) {   // x_mean = x - (theta (y - x) dt - G^2 score), G = g sqrt(dt), score = -net / std
+    const float dt = 1.f / (float)c.N, G = g * sqrtf(dt);
+    o[0] = 1.f + c.theta * dt; o[1] = -c.theta * dt; o[2] = -(G * G) / std_t;
+  } else {                          // drift = theta (y - x) - g^2 score * (0.5 | 1)
+    o[0] = -c.theta; o[1] = c.theta; o[2] = (mode == FD_SCORE_DRIFT_PF ? 0.5f : 1.f) * g * g / std_t;
+  }
 }
 int score_draws(const fd_score_config& c) {
   return 1 + c.N * ((c.corrector == FD_CORRECTOR_ALD ? c.corrector_steps : 0) + (c.predictor != FD_PREDICTOR_NONE ? 1 : 0));
@@ -157,33 +168,49 @@ extern "C" int fd_ode_solve_seeded(fd_model* m, const float* Y, const unsigned l
 // -- clip b of the batch then takes the steps, and gives the bits, of the batch-global call on that clip alone; a clip that has reached
 // t = 1 rides along with dt = 0 until the slowest clip is done.  What differs between the two modes is a policy (BatchPolicy,
 // ClipPolicy): how the state is combined, where the network's time comes from, how the error norm is taken, what reaches the device
-// before an attempt (publish) and how an accepted step is committed. ---------------------------------------------------------------
+// before an attempt (publish) and how an accepted step is committed.
+// The loop is also generic in the PROBLEM and in the step-size RULE: the flow model's field from t = 0 up to 1 under torchdyn's rule
+// (FlowCtl around StepCtl), or the ScoreDec probability-flow drift from t = 1 down to eps under scipy RK45's (ScipyCtl around Rk45Ctl;
+// fd_score_ode_solve).  The problem lives in AdaptiveCtx (the initial state and how one evaluation of the network becomes the right-hand
+// side), the rule in the controller objects the entry point hands over. -------------------------------------------------------------
 namespace {
 constexpr int DP_NORM_BLOCKS = 512;
 
 // per-clip control: the host table of one attempt, copied to the device in one piece.  Rows of B 32-bit words: dt, the six stage times
-// (row 1 doubles as the time of the two initial evaluations), and the commit of the PREVIOUS attempt (accept flag, checkpoint index)
-enum { TAB_DT = 0, TAB_T1 = 1, TAB_ACCEPT = 7, TAB_CKPT = 8, TAB_ROWS = 9 };
-size_t clips_tab_bytes(int B) { return fd_align(sizeof(float) * TAB_ROWS * (size_t)B); }
+// (row 1 doubles as the time of the two initial evaluations), and the commit of the PREVIOUS attempt (accept flag, checkpoint index);
+// the score problem appends the epilogue coefficients of the six evaluations ahead, [6][B][3] floats (cb, cy, cn at the clip's time)
+enum { TAB_DT = 0, TAB_T1 = 1, TAB_ACCEPT = 7, TAB_CKPT = 8, TAB_ROWS = 9, TAB_COEF = 9, TAB_ROWS_SCORE = TAB_ROWS + 6 * 3 };
+size_t clips_tab_bytes(int B, int rows = TAB_ROWS) { return fd_align(sizeof(float) * rows * (size_t)B); }
 size_t clips_partial_bytes(int B) { return fd_align(sizeof(double) * DP_NORM_BLOCKS * (size_t)B); }
+// the pinned host mirror (fd_model::pin_clips): the largest table, then the partials
+size_t pin_partial_offset() { return clips_tab_bytes(fd_model::MAX_NT, TAB_ROWS_SCORE); }
+int pin_clips_ready(fd_model* m) {
+  if (!m->pin_clips) FD_HIP(hipHostMalloc(&m->pin_clips, pin_partial_offset() + clips_partial_bytes(fd_model::MAX_NT), hipHostMallocDefault));
+  return FD_OK;
+}
 
 // The workspace of both modes (offsets): x | x_new | err | k[7] (ten states), the norm's partials, the per-clip table, forward scratch
 struct adaptive_layout_t { size_t state, partial, tab, fws, total; };
-adaptive_layout_t adaptive_layout(const fd_model* m, int B, int T, bool per_clip) {
+adaptive_layout_t adaptive_layout(const fd_model* m, int B, int T, bool per_clip, bool score = false) {
   adaptive_layout_t s;
   s.state = fd_align(sizeof(float) * 2 * (size_t)B * m->n_freq * T);
   s.partial = 10 * s.state;
   s.tab = s.partial + clips_partial_bytes(per_clip ? B : 1);
-  s.fws = s.tab + (per_clip ? clips_tab_bytes(B) : 0);
+  s.fws = s.tab + (per_clip ? clips_tab_bytes(B, score ? TAB_ROWS_SCORE : TAB_ROWS) : 0);
   s.total = s.fws + forward_ws_bytes(m, B, T);
   return s;
 }
 
-// What the two policies share: the problem and the carved workspace
+// What the two policies share: the problem and the carved workspace.  sc == nullptr: the flow model (x0 = Y + sigma_fac sigma_y z, the
+// right-hand side is the network's output); sc given: the ScoreDec probability-flow ODE (x_T = Y + std(1) z, the right-hand side is the
+// FD_SCORE_DRIFT_PF epilogue of fd_score_eval at the evaluation's time)
 struct AdaptiveCtx {
   fd_model* m; const float* Y; float* traj; int B, T; float atol, rtol; hipStream_t st;
   size_t nclip, nstate;   // complex elements of one clip, of the batch
   float *x, *x_new, *err, *k[7]; double* partial; float* tab_dev; void* fws; size_t fws_bytes;
+  const fd_score_config* sc = nullptr;
+  float sigma_fac = 1.f;
+  const char* who = "";
   AdaptiveCtx(fd_model* m_, const float* Y_, float* traj_, int B_, int T_, float atol_, float rtol_, hipStream_t st_, void* ws, size_t ws_bytes,
               const adaptive_layout_t& lay)
       : m(m_), Y(Y_), traj(traj_), B(B_), T(T_), atol(atol_), rtol(rtol_), st(st_), nclip((size_t)m_->n_freq * T_), nstate((size_t)B_ * nclip) {
@@ -193,8 +220,19 @@ struct AdaptiveCtx {
     partial = (double*)(base + lay.partial); tab_dev = (float*)(base + lay.tab);
     fws = base + lay.fws; fws_bytes = ws_bytes - lay.fws;
   }
-  int forward(const float* xin, const float* t, float t_imm, int nt, float* kout) const {
+  int tab_rows() const { return sc ? TAB_ROWS_SCORE : TAB_ROWS; }
+  int init_state(const fd_noise_src& noise) const {
+    if (sc) return fd_caxpy(Y, noise, ouve_std(*sc, 1.0f), x, B, m->n_freq, T, st);   // prior sample, sdes.py:197-202
+    return fd_init_state(Y, noise, m->sigma_dev, m->sigma_n, sigma_fac, x, B, m->n_freq, T, st);
+  }
+  // one right-hand side: the clips' times from the device (t, nt = B; the score problem's coefficients then from ctab, [B][3]) or t_imm
+  int forward(const float* xin, const float* t, float t_imm, int nt, const float* ctab, float* kout) const {
     OutSpec os; os.dst = kout; os.coef = 1.f;
+    if (sc) {
+      os.score = true; os.base = xin; os.yv = Y;
+      if (t) os.ctab = ctab;
+      else { float co[3]; score_coefs(*sc, t_imm, FD_SCORE_DRIFT_PF, co); os.cb = co[0]; os.cy = co[1]; os.coef = co[2]; }
+    }
     return forward_call(m, xin, Y, t, t_imm, nt, os, B, T, fws, fws_bytes, st);
   }
 };
@@ -207,7 +245,7 @@ struct BatchPolicy : AdaptiveCtx {
   int combine(float cx, const float* dt, const float* const* kk, const float* cc, int nk, float* dst) {
     return fd_ode_lincomb(x, cx, dt[0], kk, cc, nk, dst, (long long)nstate, st);
   }
-  int eval(const float* xin, int, const float* t, float* kout) { return forward(xin, nullptr, t[0], 1, kout); }
+  int eval(const float* xin, int, const float* t, float* kout) { return forward(xin, nullptr, t[0], 1, nullptr, kout); }
   // Hairer norm of (p - q) / (atol + rtol max(|r|, |s|)): sqrt(mean |.|^2) over the complex elements
   int norm(const float* p_, const float* q_, const float* r_, const float* s_, double* out) {
     FD_TRY(fd_ode_scaled_sq(p_, q_, r_, s_, atol, rtol, partial, DP_NORM_BLOCKS, (long long)nstate, st));
@@ -225,9 +263,8 @@ struct BatchPolicy : AdaptiveCtx {
     if (landed[0] && traj) FD_HIP(hipMemcpyAsync(traj + 2 * nstate * landed[0], x, sizeof(float) * 2 * nstate, hipMemcpyDeviceToDevice, st));
     return FD_OK;
   }
-  int step_limit(int, const StepCtl& c) const {
-    return fd_set_error(FD_ERUNTIME, "fd_ode_solve_adaptive: step limit reached (dt = %g at t = %g)", (double)c.dt, (double)c.t);
-  }
+  int step_limit(int, double dt, double t) const { return fd_set_error(FD_ERUNTIME, "%s: step limit reached (dt = %g at t = %g)", who, dt, t); }
+  int too_small(int, double dt, double t) const { return fd_set_error(FD_ERUNTIME, "%s: step size too small (dt = %g at t = %g)", who, dt, t); }
 };
 
 // One controller per clip: the device side reads the clips' step sizes, stage times and commit flags from the table (TAB_*).
@@ -242,7 +279,11 @@ struct ClipPolicy : AdaptiveCtx {
     memcpy(tab + (size_t)TAB_T1 * B, tq, sizeof(float) * 6 * B);
     memcpy(tab + (size_t)TAB_ACCEPT * B, accept, sizeof(int) * B);
     memcpy(tab + (size_t)TAB_CKPT * B, landed, sizeof(int) * B);
-    FD_HIP(hipMemcpyAsync(tab_dev, tab, sizeof(float) * TAB_ROWS * (size_t)B, hipMemcpyHostToDevice, st));
+    if (sc) {   // the coefficients fd_score_eval would derive from each clip's time, for the six evaluations ahead
+      float* co = (float*)(tab + (size_t)TAB_COEF * B);
+      for (size_t i = 0; i < 6 * (size_t)B; ++i) score_coefs(*sc, tq[i], FD_SCORE_DRIFT_PF, co + 3 * i);
+    }
+    FD_HIP(hipMemcpyAsync(tab_dev, tab, sizeof(float) * tab_rows() * (size_t)B, hipMemcpyHostToDevice, st));
     const int* accept_dev = (const int*)tab_dev + (size_t)TAB_ACCEPT * B;
     const int* ckpt_dev = (const int*)tab_dev + (size_t)TAB_CKPT * B;
     if (pending) FD_TRY(fd_ode_commit_clips(accept_dev, ckpt_dev, x_new, k[6], x, k[0], traj, B, (long long)nclip, st));
@@ -252,11 +293,11 @@ struct ClipPolicy : AdaptiveCtx {
     return fd_ode_lincomb_clips(x, cx, tab_dev + (size_t)TAB_DT * B, kk, cc, nk, dst, B, (long long)nclip, st);
   }
   int eval(const float* xin, int slot, const float*, float* kout) {   // clip b at time tab[TAB_T1 + slot][b]
-    return forward(xin, tab_dev + (size_t)(TAB_T1 + slot) * B, 0.f, B, kout);
+    return forward(xin, tab_dev + (size_t)(TAB_T1 + slot) * B, 0.f, B, tab_dev + (size_t)(TAB_COEF + 3 * slot) * B, kout);
   }
   // the Hairer norm of the one-clip call, clip by clip: the clip's DP_NORM_BLOCKS partials summed in index order
   int norm(const float* p_, const float* q_, const float* r_, const float* s_, double* out) {
-    const double* host_partial = (const double*)((char*)m->pin_clips + clips_tab_bytes(fd_model::MAX_NT));
+    const double* host_partial = (const double*)((char*)m->pin_clips + pin_partial_offset());
     FD_TRY(fd_ode_scaled_sq_clips(p_, q_, r_, s_, atol, rtol, partial, DP_NORM_BLOCKS, B, (long long)nclip, st));
     FD_HIP(hipMemcpyAsync((void*)host_partial, partial, sizeof(double) * DP_NORM_BLOCKS * (size_t)B, hipMemcpyDeviceToHost, st));
     FD_HIP(hipStreamSynchronize(st));
@@ -268,21 +309,52 @@ struct ClipPolicy : AdaptiveCtx {
     return FD_OK;
   }
   int commit(const int*, const int*) { return FD_OK; }   // deferred: the next publish carries the flags and runs fd_ode_commit_clips
-  int step_limit(int b, const StepCtl& c) const {
-    return fd_set_error(FD_ERUNTIME, "fd_ode_solve_adaptive_clips: step limit reached (clip %d: dt = %g at t = %g)", b, (double)c.dt, (double)c.t);
+  int step_limit(int b, double dt, double t) const {
+    return fd_set_error(FD_ERUNTIME, "%s: step limit reached (clip %d: dt = %g at t = %g)", who, b, dt, t);
   }
+  int too_small(int b, double dt, double t) const {
+    return fd_set_error(FD_ERUNTIME, "%s: step size too small (clip %d: dt = %g at t = %g)", who, b, dt, t);
+  }
+};
+
+// The two step-size rules behind the one face adaptive_solve drives; times and steps leave as the floats the device is given.
+struct FlowCtl {    // torchdyn's (StepCtl) over the checkpoints ts[0..N], forwards
+  const std::vector<float>* ts; int N; StepCtl c;
+  FlowCtl(const std::vector<float>* ts_, int N_) : ts(ts_), N(N_) { c.t = (*ts_)[0]; }
+  float time() const { return c.t; }
+  double probe_step(double d0, double d1) const { return StepCtl::probe_step(d0, d1); }
+  float probe_dt(double h0) const { return (float)h0; }
+  float probe_time(double h0) const { return c.probe_time(h0); }
+  void first_step(double h0, double d1, double d2) { c.first_step(h0, d1, d2); }   // d2: not yet divided by h0
+  bool active() const { return c.active(*ts, N); }
+  bool begin() { c.begin(*ts, N); return true; }
+  float dt() const { return c.dt; }
+  float stage_time(double cc) const { return c.stage_time(cc); }
+  bool end(double ratio, int* landed) { return c.end(ratio, *ts, N, landed); }
+};
+struct ScipyCtl {   // scipy RK45's (Rk45Ctl) from t0 down to t_bound: double inside, the network and the kernels get (float)t and (float)h
+  Rk45Ctl c;
+  ScipyCtl(double t0, double t_bound) { c.start(t0, t_bound); }
+  float time() const { return (float)c.t; }
+  double probe_step(double d0, double d1) const { return c.probe_step(d0, d1); }
+  float probe_dt(double h0) const { return (float)(h0 * Rk45Ctl::direction); }
+  float probe_time(double h0) const { return (float)c.probe_time(h0); }
+  void first_step(double h0, double d1, double d2) { c.first_step(h0, d1, d2 / h0); }
+  bool active() const { return c.active(); }
+  bool begin() { return c.begin(); }
+  float dt() const { return (float)c.h; }
+  float stage_time(double cc) const { return (float)c.stage_time(cc); }
+  bool end(double err, int* landed) { *landed = 0; return c.end(err); }
 };
 
 // The solve: x0, the initial-step probe, then attempts until every controller has reached the end of the span.  nfe / rejected: per
 // controller (2 + 6 per attempt it was active in); *evals: network evaluations enqueued.  Ends synchronised, the result in X_out.
-template <typename Policy>
-int adaptive_solve(Policy& p, const Tableau& tb, int N, const fd_noise_src& noise, float sigma_fac, float* X_out, int nctl, int* nfe, int* rejected,
-                   int* evals) {
+template <typename Policy, typename Ctl>
+int adaptive_solve(Policy& p, std::vector<Ctl>& c, const Tableau& tb, const fd_noise_src& noise, float* X_out, int* nfe, int* rejected, int* evals) {
+  const int nctl = (int)c.size();
   const size_t state_bytes = sizeof(float) * 2 * p.nstate;
-  FD_TRY(fd_init_state(p.Y, noise, p.m->sigma_dev, p.m->sigma_n, sigma_fac, p.x, p.B, p.m->n_freq, p.T, p.st));
+  FD_TRY(p.init_state(noise));
   if (p.traj) FD_HIP(hipMemcpyAsync(p.traj, p.x, state_bytes, hipMemcpyDeviceToDevice, p.st));
-  const std::vector<float> ts = t_span_linspace(N);
-  std::vector<StepCtl> c(nctl);
   std::vector<double> d0(nctl), d1(nctl), d2(nctl), h0(nctl), ratio(nctl);
   std::vector<float> dt(nctl, 0.f), tq(6 * (size_t)nctl, 0.f);   // per controller: the step, and the times of the (up to) six evaluations ahead
   std::vector<int> accept(nctl, 0), landed(nctl, 0);
@@ -290,14 +362,14 @@ int adaptive_solve(Policy& p, const Tableau& tb, int N, const fd_noise_src& nois
   *evals = 0;
   auto eval = [&](const float* xin, int slot, float* kout) { ++*evals; return p.eval(xin, slot, &tq[(size_t)slot * nctl], kout); };
   auto publish = [&](bool pending) { return p.publish(dt.data(), tq.data(), accept.data(), landed.data(), pending); };
-  for (int b = 0; b < nctl; ++b) { c[b].t = ts[0]; tq[b] = c[b].t; }
+  for (int b = 0; b < nctl; ++b) tq[b] = c[b].time();
   FD_TRY(publish(false));
   FD_TRY(eval(p.x, 0, p.k[0]));
   FD_TRY(p.norm(p.x, nullptr, p.x, p.x, d0.data()));
   FD_TRY(p.norm(p.k[0], nullptr, p.x, p.x, d1.data()));
   for (int b = 0; b < nctl; ++b) {
-    h0[b] = StepCtl::probe_step(d0[b], d1[b]);
-    dt[b] = (float)h0[b];
+    h0[b] = c[b].probe_step(d0[b], d1[b]);
+    dt[b] = c[b].probe_dt(h0[b]);
     tq[b] = c[b].probe_time(h0[b]);
   }
   FD_TRY(publish(false));
@@ -313,11 +385,11 @@ int adaptive_solve(Policy& p, const Tableau& tb, int N, const fd_noise_src& nois
   for (;;) {
     bool any = false;
     for (int b = 0; b < nctl; ++b) {
-      act[b] = c[b].active(ts, N);
+      act[b] = c[b].active();
       any = any || act[b];
-      if (act[b]) c[b].begin(ts, N);
-      dt[b] = act[b] ? c[b].dt : 0.f;                                // a finished clip: dt = 0, evaluated at its final time, never committed
-      for (int s = 1; s < 7; ++s) tq[(size_t)(s - 1) * nctl + b] = act[b] ? c[b].stage_time(tb.C[s]) : c[b].t;
+      if (act[b] && !c[b].begin()) return p.too_small(b, (double)c[b].dt(), (double)c[b].time());
+      dt[b] = act[b] ? c[b].dt() : 0.f;                              // a finished clip: dt = 0, evaluated at its final time, never committed
+      for (int s = 1; s < 7; ++s) tq[(size_t)(s - 1) * nctl + b] = act[b] ? c[b].stage_time(tb.C[s]) : c[b].time();
     }
     if (!any && !pending) break;
     FD_TRY(publish(pending));
@@ -325,7 +397,7 @@ int adaptive_solve(Policy& p, const Tableau& tb, int N, const fd_noise_src& nois
     if (++steps > ADAPTIVE_MAX_ATTEMPTS) {
       int b = 0;
       while (!act[b]) ++b;
-      return p.step_limit(b, c[b]);
+      return p.step_limit(b, (double)c[b].dt(), (double)c[b].time());
     }
     for (int s = 1; s < 7; ++s) {                                    // stages 2..7; stage 7 is evaluated at the 5th-order solution (FSAL)
       const float* kk[6]; float cc[6];
@@ -345,7 +417,7 @@ int adaptive_solve(Policy& p, const Tableau& tb, int N, const fd_noise_src& nois
       accept[b] = landed[b] = 0;
       if (!act[b]) continue;                                        // finished before this attempt
       nfe[b] += 6;
-      accept[b] = c[b].end(ratio[b], ts, N, &landed[b]) ? 1 : 0;
+      accept[b] = c[b].end(ratio[b], &landed[b]) ? 1 : 0;
       if (accept[b]) pending = true; else ++rejected[b];
     }
     FD_TRY(p.commit(accept.data(), landed.data()));
@@ -372,8 +444,11 @@ extern "C" int fd_ode_solve_adaptive_method(fd_model* m, const float* Y, const f
   const adaptive_layout_t lay = adaptive_layout(m, B, T_pad, false);
   if (ws_bytes < lay.total) return fd_set_error(FD_ENOMEM, "fd_ode_solve_adaptive: workspace %zu < required %zu bytes", ws_bytes, lay.total);
   BatchPolicy p(m, Y, traj, B, T_pad, atol, rtol, fd_stream(stream), ws, ws_bytes, lay);
+  p.sigma_fac = sigma_fac; p.who = "fd_ode_solve_adaptive";
+  const std::vector<float> ts = t_span_linspace(N);
+  std::vector<FlowCtl> ctl(1, FlowCtl(&ts, N));
   int nfe = 0, rejected = 0, evals = 0;
-  FD_TRY(adaptive_solve(p, adaptive_tableau(method), N, fd_noise_src{noise}, sigma_fac, X_out, 1, &nfe, &rejected, &evals));
+  FD_TRY(adaptive_solve(p, ctl, adaptive_tableau(method), fd_noise_src{noise}, X_out, &nfe, &rejected, &evals));
   if (nfe_out) *nfe_out = nfe;
   return FD_OK;
 }
@@ -401,13 +476,98 @@ extern "C" int fd_ode_solve_adaptive_clips(fd_model* m, const float* Y, const fl
   FD_TRY(check_shape(m, B, T_pad));
   const adaptive_layout_t lay = adaptive_layout(m, B, T_pad, true);
   if (ws_bytes < lay.total) return fd_set_error(FD_ENOMEM, "fd_ode_solve_adaptive_clips: workspace %zu < required %zu bytes", ws_bytes, lay.total);
-  if (!m->pin_clips) FD_HIP(hipHostMalloc(&m->pin_clips, clips_tab_bytes(fd_model::MAX_NT) + clips_partial_bytes(fd_model::MAX_NT), hipHostMallocDefault));
+  FD_TRY(pin_clips_ready(m));
   ClipPolicy p(m, Y, traj, B, T_pad, atol, rtol, fd_stream(stream), ws, ws_bytes, lay);
+  p.sigma_fac = sigma_fac; p.who = "fd_ode_solve_adaptive_clips";
+  const std::vector<float> ts = t_span_linspace(N);
+  std::vector<FlowCtl> ctl(B, FlowCtl(&ts, N));
   std::vector<int> nfe(B), rejected(B);
   int evals = 0;
-  FD_TRY(adaptive_solve(p, adaptive_tableau(method), N, seeds ? fd_noise_src{nullptr, seeds, 0} : fd_noise_src{noise}, sigma_fac, X_out, B, nfe.data(),
-                        rejected.data(), &evals));
+  FD_TRY(adaptive_solve(p, ctl, adaptive_tableau(method), seeds ? fd_noise_src{nullptr, seeds, 0} : fd_noise_src{noise}, X_out, nfe.data(), rejected.data(),
+                        &evals));
   for (int b = 0; b < B; ++b) { nfe_out[b] = nfe[b]; if (rejected_out) rejected_out[b] = rejected[b]; }
+  if (evals_out) *evals_out = evals;
+  return FD_OK;
+}
+
+// ---- the ScoreDec ODE sampler (sampling/__init__.py:75-146: scipy.integrate.solve_ivp, method RK45, over (sde.T = 1, eps)) on the
+// device: adaptive_solve on the probability-flow drift under scipy's step-size rule (Rk45Ctl, step_ctl.h).  step_control =
+// FD_STEP_CONTROL_BATCH: one controller on the norms of the flattened batch, which is what solve_ivp sees and the reference's meaning
+// of a batch; FD_STEP_CONTROL_CLIP: one per clip -- clip b takes the steps, and gives the bits, of the one-clip call.  The state planes
+// are float32 (scipy carries complex128).  Where scipy's solver gives up on a step below ten spacings of t and the reference goes on
+// with the last state, this returns FD_ERUNTIME ("step size too small"). ----------------------------------------------------------------
+namespace fdm {
+
+int score_ode_check(const char* who, const fd_score_config* c, float rtol, float atol, int step_control, int B) {
+  FD_REQUIRE(c, "%s: null pointer (cfg)", who);
+  FD_REQUIRE(c->sigma_min > 0.f && c->sigma_max > c->sigma_min && c->theta > 0.f, "%s: bad OUVE parameters", who);
+  FD_REQUIRE(c->t_eps > 0.f && c->t_eps < 1.f, "%s: t_eps must be in (0, 1)", who);
+  FD_REQUIRE(!c->denoise || c->N >= 1, "%s: the denoising step needs N >= 1", who);
+  FD_REQUIRE(atol > 0.f && rtol >= 0.f, "%s: need atol > 0, rtol >= 0", who);
+  FD_REQUIRE(step_control == FD_STEP_CONTROL_BATCH || step_control == FD_STEP_CONTROL_CLIP, "%s: unknown step_control %d", who, step_control);
+  FD_REQUIRE(step_control != FD_STEP_CONTROL_CLIP || B <= fd_model::MAX_NT, "%s: at most %d clips per call with per-clip step control (got %d)", who,
+             fd_model::MAX_NT, B);
+  return FD_OK;
+}
+
+size_t score_ode_ws_bytes(const fd_model* m, int B, int T, bool per_clip) { return adaptive_layout(m, B, T, per_clip, true).total; }
+
+// The solve on features: arguments checked by the caller (score_ode_check, check_shape, the workspace).  nfe / rejected: one entry
+// (batch) or B (per clip).  Ends synchronised.
+int score_ode_run(fd_model* m, const char* who, const float* Y, const fd_noise_src& noise, const fd_score_config& c, float rtol, float atol, bool per_clip,
+                  float* X, int* nfe, int* rejected, int* evals, int B, int T, void* ws, size_t ws_bytes, hipStream_t st) {
+  const adaptive_layout_t lay = adaptive_layout(m, B, T, per_clip, true);
+  const Tableau tb{DP_C, DP_A, DP_E};
+  std::vector<ScipyCtl> ctl(per_clip ? B : 1, ScipyCtl(1.0, (double)c.t_eps));
+  void* fws = nullptr; size_t fws_bytes = 0;
+  if (per_clip) {
+    FD_TRY(pin_clips_ready(m));
+    ClipPolicy p(m, Y, nullptr, B, T, atol, rtol, st, ws, ws_bytes, lay);
+    p.sc = &c; p.who = who;
+    FD_TRY(adaptive_solve(p, ctl, tb, noise, X, nfe, rejected, evals));
+    fws = p.fws; fws_bytes = p.fws_bytes;
+  } else {
+    BatchPolicy p(m, Y, nullptr, B, T, atol, rtol, st, ws, ws_bytes, lay);
+    p.sc = &c; p.who = who;
+    FD_TRY(adaptive_solve(p, ctl, tb, noise, X, nfe, rejected, evals));
+    fws = p.fws; fws_bytes = p.fws_bytes;
+  }
+  if (c.denoise) {   // one noise-free reverse-diffusion step at t = eps with dt = 1 / N (not counted in the NFE, as in the reference)
+    float co[3];
+    score_coefs(c, c.t_eps, FD_SCORE_DENOISE, co);
+    OutSpec os; os.score = true; os.base = X; os.yv = Y; os.dst = X; os.cb = co[0]; os.cy = co[1]; os.coef = co[2];
+    FD_TRY(forward_call(m, X, Y, nullptr, c.t_eps, 1, os, B, T, fws, fws_bytes, st));
+    FD_HIP(hipStreamSynchronize(st));
+  }
+  return FD_OK;
+}
+
+}  // namespace fdm
+
+extern "C" size_t fd_score_ode_workspace_bytes(const fd_model* m, int B, int T_pad, int step_control) {
+  if (!m || (step_control != FD_STEP_CONTROL_BATCH && step_control != FD_STEP_CONTROL_CLIP)) return 0;
+  if ((step_control == FD_STEP_CONTROL_CLIP && B > fd_model::MAX_NT) || check_shape(m, B, T_pad) != FD_OK) return 0;
+  return score_ode_ws_bytes(m, B, T_pad, step_control == FD_STEP_CONTROL_CLIP);
+}
+
+extern "C" int fd_score_ode_solve(fd_model* m, const float* Y, const float* noise, const unsigned long long* seeds, const fd_score_config* cfg, float rtol,
+                                  float atol, int step_control, float* X_out, int* nfe_out, int* rejected_out, int* evals_out, int B, int T_pad,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_ode_solve");
+  FD_TRY(check_ready(m));
+  FD_REQUIRE(Y && X_out && ws && nfe_out, "fd_score_ode_solve: null pointer");
+  FD_REQUIRE((noise != nullptr) != (seeds != nullptr), "fd_score_ode_solve: give exactly one of noise and seeds");
+  FD_TRY(score_ode_check("fd_score_ode_solve", cfg, rtol, atol, step_control, B));
+  FD_TRY(check_shape(m, B, T_pad));
+  const bool per_clip = step_control == FD_STEP_CONTROL_CLIP;
+  const size_t need = score_ode_ws_bytes(m, B, T_pad, per_clip);
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_score_ode_solve: workspace %zu < required %zu bytes", ws_bytes, need);
+  const int n = per_clip ? B : 1;
+  std::vector<int> nfe(n), rejected(n);
+  int evals = 0;
+  FD_TRY(score_ode_run(m, "fd_score_ode_solve", Y, seeds ? fd_noise_src{nullptr, seeds, 0} : fd_noise_src{noise}, *cfg, rtol, atol, per_clip, X_out,
+                       nfe.data(), rejected.data(), &evals, B, T_pad, ws, ws_bytes, fd_stream(stream)));
+  for (int b = 0; b < n; ++b) { nfe_out[b] = nfe[b]; if (rejected_out) rejected_out[b] = rejected[b]; }
   if (evals_out) *evals_out = evals;
   return FD_OK;
 }
@@ -431,13 +591,8 @@ extern "C" int fd_score_eval(fd_model* m, const float* x, const float* Y, float 
   FD_TRY(check_shape(m, B, T_pad));
   const size_t need = forward_ws_bytes(m, B, T_pad);
   if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_score_eval: workspace %zu < required %zu bytes", ws_bytes, need);
-  const float std_t = ouve_std(*c, t), g = ouve_diffusion(*c, t);
-  OutSpec os; os.score = true; os.base = x; os.yv = Y; os.dst = out;
-  if (mode == FD_SCORE_DENOISE) {   // x_mean = x - (theta (y - x) dt - G^2 score), G = g sqrt(dt), score = -net / std
-    const float dt = 1.f / (float)c->N, G = g * sqrtf(dt);
-    os.cb = 1.f + c->theta * dt; os.cy = -c->theta * dt; os.coef = -(G * G) / std_t;
-  } else {                          // drift = theta (y - x) - g^2 score * (0.5 | 1)
-    os.cb = -c->theta; os.cy = c->theta; os.coef = (mode == FD_SCORE_DRIFT_PF ? 0.5f : 1.f) * g * g / std_t;
-  }
+  float co[3];
+  score_coefs(*c, t, mode, co);
+  OutSpec os; os.score = true; os.base = x; os.yv = Y; os.dst = out; os.cb = co[0]; os.cy = co[1]; os.coef = co[2];
   return forward_call(m, x, Y, nullptr, t, 1, os, B, T_pad, ws, ws_bytes, fd_stream(stream));
 }

@@ -1,6 +1,7 @@
 // step_ctl.h -- the host arithmetic of the solvers (solve.hip): the time grids, the fixed-step NFE count, the two embedded Runge-Kutta
-// tableaux and the adaptive step-size controller.  Host-only: no HIP, so that a plain C++ compiler builds it alone
-// (tests/c/step_ctl_check.cpp); StepCtl decides accept / reject on exactly these roundings.
+// tableaux and the two adaptive step-size controllers (StepCtl: torchdyn's rule, the flow model's dopri5 / tsit5; Rk45Ctl: scipy RK45's rule,
+// the ScoreDec ODE sampler).  Host-only: no HIP, so that a plain C++ compiler builds it alone (tests/c/step_ctl_check.cpp,
+// tests/c/rk45_ctl_check.cpp); the controllers decide accept / reject on exactly these roundings.
 #pragma once
 #include <math.h>
 
@@ -104,6 +105,61 @@ struct StepCtl {
       dt = (float)((double)dt * fmin(10.0, fmax(0.9 / pow(ratio, 1.0 / 5.0), minf)));
     }
     return accept;
+  }
+};
+// The step-size controller of scipy.integrate.RK45 (scipy/integrate/_ivp/rk.py: RungeKutta._step_impl, common.py: select_initial_step)
+// restated for ONE solve backwards in time, from t0 down to t_bound (direction -1: the ScoreDec probability-flow ODE over (sde.T, eps)):
+// double precision and scipy's order of operations, so that every t, h and accept flag is scipy's.  What differs from StepCtl: the
+// initial step takes the estimator's order 4 (exponent 1/5, not 1/6) and is bounded by the span, a step is accepted on err < 1
+// (strictly), the growth factor is capped at 1 once an attempt of the step was rejected, there are no checkpoints, and a step below ten
+// spacings of t is an error (begin() -> false; scipy's TOO_SMALL_STEP).  Tableau: DP_C / DP_A / DP_E (scipy's E is -DP_E: the norm does
+// not see the sign).  Time is a double here; the network is given (float)t.
+struct Rk45Ctl {
+  static constexpr double direction = -1.0;
+  double t = 0.0, t_bound = 0.0, t_new = 0.0;
+  double h = 0.0, h_abs = 0.0, min_step = 0.0;   // the signed step of the attempt, the controller's step size, ten spacings of t
+  bool fresh = true, rejected = false;           // the next attempt opens a new step; an attempt of this step was rejected
+  void start(double t0, double tb) { t = t0; t_bound = tb; fresh = true; }
+  // select_initial_step: h0, then one explicit Euler probe x + direction h0 f0 at t + direction h0, d2 = |f1 - f0| / h0
+  double probe_step(double d0, double d1) const {
+    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    return fmin(h0, fabs(t_bound - t));
+  }
+  double probe_time(double h0) const { return t + h0 * direction; }
+  void first_step(double h0, double d1, double d2) {   // d2 already divided by h0
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
+    h_abs = fmin(fmin(100.0 * h0, h1), fabs(t_bound - t));
+  }
+  bool active() const { return direction * (t - t_bound) < 0.0; }
+  // the attempt to make (left in h, t_new): -> false when the step size has fallen below min_step
+  bool begin() {
+    if (fresh) {
+      min_step = 10.0 * fabs(nextafter(t, direction * INFINITY) - t);
+      if (h_abs < min_step) h_abs = min_step;
+      fresh = rejected = false;
+    }
+    if (h_abs < min_step) return false;
+    t_new = t + h_abs * direction;
+    if (direction * (t_new - t_bound) > 0.0) t_new = t_bound;
+    h = t_new - t;
+    h_abs = fabs(h);
+    return true;
+  }
+  double stage_time(double c) const { return t + c * h; }
+  // after the attempt: accept iff err < 1, then the next step size (a NaN norm rejects and shrinks by 0.2, like Python's max(0.2, nan))
+  bool end(double err) {
+    if (err < 1.0) {
+      double factor = err == 0.0 ? 10.0 : fmin(10.0, 0.9 * pow(err, -1.0 / 5.0));
+      if (rejected) factor = fmin(1.0, factor);
+      h_abs *= factor;
+      t = t_new;
+      fresh = true;
+      return true;
+    }
+    const double shrink = 0.9 * pow(err, -1.0 / 5.0);
+    h_abs *= shrink > 0.2 ? shrink : 0.2;
+    rejected = true;
+    return false;
   }
 };
 constexpr int ADAPTIVE_MAX_ATTEMPTS = 100000;

@@ -35,6 +35,12 @@ Adaptive solvers: `--solver dopri5` / `tsit5` accept or reject a step on one err
 (`FlowModel.enhance_batch(step_control='clip')` -> fd_ode_solve_adaptive_clips): the files are bucketed and batched like everything
 else, and every file's waveform is still the one-file result, bit for bit.
 
+ODE sampler of a score model: `--sampler ode` (`--ode-rtol`, `--ode-atol`, default 1e-5) integrates the probability-flow ODE on the
+device under scipy RK45's step-size rule instead of running the predictor-corrector sampler: the buckets go through
+`ScoreModel.enhance_ode_batch` (one step controller per file, so a file's waveform does not depend on its batch), `--predictor`,
+`--corrector` and `--snr` are ignored with one printed line, and every file's NFE is printed (`rtfs.csv` has no column for it).
+`--sampler pc` (the default) changes nothing.
+
 Length limit: the reference skips files longer than 30 s; so does this driver by default, in every precision.  `--max-seconds S`
 moves that limit: the kernels address images of any length that fits in device memory (a 180 s clip in bf16 is one call), and
 what remains is the device memory itself.  A file whose workspace (`fd_enhance_workspace_bytes`) does not fit in the free device
@@ -119,6 +125,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--predictor", type=str, default="reverse_diffusion", choices=["reverse_diffusion", "euler_maruyama"])   # score model only
     p.add_argument("--corrector", type=str, default="ald", choices=["ald", "none"])
     p.add_argument("--snr", type=float, default=0.5)
+    p.add_argument("--sampler", type=str, default="pc", choices=["pc", "ode"],
+                   help="score model only.  pc: the predictor-corrector sampler (--predictor, --corrector, --snr).  ode: the probability-flow ODE "
+                        "under scipy RK45's step-size rule on the device (ScoreModel.enhance_ode_batch: one step controller per file, so every "
+                        "file's waveform does not depend on its batch); --predictor, --corrector and --snr are then ignored")
+    p.add_argument("--ode-rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance of the adaptive solve")
+    p.add_argument("--ode-atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance of the adaptive solve")
     p.add_argument("--solver", type=str, default="midpoint")   # flow model only
     p.add_argument("--step-control", type=str, default="batch", choices=["batch", "clip"],
                    help="adaptive --solver (dopri5, tsit5) of a flow model: batch = one step controller per native call, so files run one per "
@@ -312,7 +324,10 @@ def noise_kwargs(model: FlowModel, args, indices: List[int], batch: bool) -> dic
 
 def enhance_kwargs(model, args) -> dict:
     """The sampler / solver arguments of `enhance` and `enhance_batch` for the model's class: a FlowModel takes --N and --solver, a ScoreModel
-    --N, --predictor, --corrector and --snr, a RegressionModel none (one network evaluation)."""
+    --N, --predictor, --corrector and --snr, a RegressionModel none (one network evaluation).  With --sampler ode a ScoreModel's are those of
+    `enhance_ode_batch`: --N (the denoising step's dt = 1 / N), --ode-rtol, --ode-atol."""
+    if ode_sampler(model, args):
+        return dict(N=args.N, rtol=args.ode_rtol, atol=args.ode_atol)
     if isinstance(model, ScoreModel):
         return dict(N=args.N, predictor=args.predictor, corrector=args.corrector, snr=args.snr)
     if isinstance(model, RegressionModel):
@@ -320,6 +335,21 @@ def enhance_kwargs(model, args) -> dict:
     if per_clip_control(args):
         return dict(N=args.N, solver=args.solver, step_control="clip")
     return dict(N=args.N, solver=args.solver)
+
+
+def ode_sampler(model, args) -> bool:
+    """--sampler ode on a score model: the files run through `ScoreModel.enhance_ode_batch`."""
+    return isinstance(model, ScoreModel) and getattr(args, "sampler", "pc") == "ode"
+
+
+def enhance_ode_files(model, clips, jobs: List[FileJob], args):
+    """--sampler ode: the files `jobs` (waveforms `clips`, one T_pad bucket) as ONE `enhance_ode_batch` call, one step controller per file;
+    prints every file's NFE (rtfs.csv has no column for it).  -> the enhanced waveforms."""
+    outs, nfe = model.enhance_ode_batch(clips, return_nfe=True, **enhance_kwargs(model, args),
+                                        **noise_kwargs(model, args, [job.index for job in jobs], batch=True))
+    for job, n in zip(jobs, nfe):
+        print(f"NFE {n}: {job.dst}")
+    return outs
 
 
 def per_clip_control(args) -> bool:
@@ -405,7 +435,10 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
     # not by the host's launches (profiles/r02_graph_cost.txt: eager 18.06 ms, replay 18.10 ms; capture + instantiate 2.4 ms)
     try:
         with GpuTimer(args.rtf) as timer:
-            x_hat = model.enhance(y, use_graph=False, **enhance_kwargs(model, args), **noise_kwargs(model, args, [job.index], batch=False))
+            if ode_sampler(model, args):   # a batch of one: the same per-file controller, so the file's waveform is its batched one
+                x_hat = enhance_ode_files(model, [y], [job], args)[0]
+            else:
+                x_hat = model.enhance(y, use_graph=False, **enhance_kwargs(model, args), **noise_kwargs(model, args, [job.index], batch=False))
     except WorkspaceTooLarge as err:
         skip_over_memory(job, res, err)
         return
@@ -446,7 +479,10 @@ def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLo
     noise = noise_kwargs(model, args, [job.index for job, _ in loaded], batch=True)
     try:
         with GpuTimer(args.rtf) as timer:
-            outs = model.enhance_batch([y for _, y in loaded], **enhance_kwargs(model, args), **noise)
+            if ode_sampler(model, args):
+                outs = enhance_ode_files(model, [y for _, y in loaded], [job for job, _ in loaded], args)
+            else:
+                outs = model.enhance_batch([y for _, y in loaded], **enhance_kwargs(model, args), **noise)
     except WorkspaceTooLarge:   # the batch does not fit: one call per file (each result is the same, bit for bit)
         for job, y in loaded:
             enhance_file(model, job, args, log, res, max_seconds, y=y)
@@ -699,6 +735,12 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
         print("Done loading model.")
     if args.chunk_seconds is not None and not isinstance(model, FlowModel):
         parser.error("--chunk-seconds needs a flow checkpoint (this one is a %s)" % type(model).__name__)
+    if args.sampler == "ode":
+        if not isinstance(model, ScoreModel):
+            parser.error("--sampler ode needs a score model (this one is a %s)" % type(model).__name__)
+        if not args.ode_atol > 0 or not args.ode_rtol >= 0:
+            parser.error("--sampler ode needs --ode-atol > 0 and --ode-rtol >= 0")
+        print("flowdec_amd: --sampler ode: --predictor, --corrector and --snr are ignored")
     max_seconds = min(args.max_seconds, PRECISION_MAX_SECONDS.get(args.precision, args.max_seconds))
     settings = ", ".join(f"{k}={v}" for k, v in enhance_kwargs(model, args).items()) or "one network evaluation"
     print(f"flowdec_amd: model={type(model).__name__}, precision={args.precision} ({PRECISION_NOTE[args.precision]}), {settings}, "

@@ -1205,8 +1205,8 @@ class ScoreModel(_WaveModel):
         BIT-IDENTICAL to `self.enhance(clip)` with the same noise.  `noise` = one [n_draws, 1, 1, F, T_pad] complex tensor per clip
         (n_draws = self.num_draws(...)), or `generator` = one torch.Generator (drawn clip by clip) or a list of one per clip -- clip b's
         planes are then one draw of that shape, exactly what `enhance(clip_b, generator=g_b)` draws --, or `seeds` = one 64-bit seed
-        per clip: clip i equals `self.enhance(clip_i, seed=[seeds[i]])`.  Only the predictor-corrector sampler runs in batches (the ODE
-        sampler is driven from the host, clip by clip)."""
+        per clip: clip i equals `self.enhance(clip_i, seed=[seeds[i]])`.  Only the predictor-corrector sampler runs here; the ODE sampler
+        has its own batch entry point, `enhance_ode_batch` (one step controller per clip)."""
         fd_noise.exclusive(seeds=seeds, noise=noise, generator=generator)
         sampler_type = kwargs.get("sampler_type", "pc")
         if sampler_type != "pc":
@@ -1220,13 +1220,87 @@ class ScoreModel(_WaveModel):
                                                 L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
         return self._ragged_call(clips, n_draws, noise, generator, seeds, launch)
 
+    def _ode_config(self, N, denoise, eps, rtol, atol, who):
+        """-> (fd_score_config of the ODE sampler, rtol, atol); the tolerances are checked here, before the device is touched."""
+        rtol, atol = float(rtol), float(atol)
+        if not atol > 0.0 or not rtol >= 0.0:
+            raise ValueError(f"{who}: need atol > 0 and rtol >= 0 (got atol={atol}, rtol={rtol})")
+        N = self.sde.N if N is None else int(N)
+        t_eps = float(self.t_eps if eps is None else eps)
+        return L.FdScoreConfig(self.sde.theta, self.sde.sigma_min, self.sde.sigma_max, t_eps, 0.0, N, 0, 1, 0, int(bool(denoise))), rtol, atol
+
+    def _ode_launch(self, sc, rtol, atol, per_clip, seeded, ragged, stats):
+        """The `launch` closure of the device-driven ODE sampler: ONE fd_score_ode_enhance call on the staged rows (its own workspace: the
+        adaptive driver's ten state planes do not fit the enhance calls').  Leaves nfe / rejected (lists) and evals in `stats`."""
+        def launch(lib, h, io, B, Lrow, _):
+            ctl = L.STEP_CONTROL["clip" if per_clip else "batch"]
+            need = lib.fd_score_ode_enhance_workspace_bytes(h, B, Lrow, ctl)
+            if need == 0:
+                raise RuntimeError(f"flowdec_hip: the ODE sampler takes at most 256 clips of a valid shape per call with per-clip step control "
+                                   f"(got B={B}, L={Lrow})")
+            ws = self.backbone.workspace(("score_ode", B, Lrow), need, io["y"].device)
+            n = B if per_clip else 1
+            nfe, rej, evals = (C.c_int * n)(), (C.c_int * n)(), C.c_int(0)
+            L.check(lib.fd_score_ode_enhance(h, L.ptr(io["y"]), L.ptr(io["lens"]) if ragged else None,
+                                             None if seeded else L.ptr(torch.view_as_real(io["noise"])), L.ptr(io["seeds"]) if seeded else None,
+                                             C.byref(sc), rtol, atol, ctl, L.ptr(io["out"]), nfe, rej, C.byref(evals), B, Lrow, L.ptr(ws), ws.numel(),
+                                             L.stream()))
+            stats.update(nfe=list(nfe), rejected=list(rej), evals=int(evals.value))
+            self.last_nfe, self.last_evals = max(stats["nfe"]), stats["evals"]
+            self.last_nfe_per_clip = torch.tensor(stats["nfe"], dtype=torch.int64) if per_clip else None
+            self.last_rejected_per_clip = torch.tensor(stats["rejected"], dtype=torch.int64) if per_clip else None
+            if ragged:
+                return None
+            off = lib.fd_enhance_normfac_offset(h, B, Lrow)   # the layout's head (Y | X | normfac) is the enhance calls'
+            return io["out"].reshape(B, 1, Lrow).clone(), ws[off:off + 4 * B].view(torch.float32).clone()
+        return launch
+
+    def _enhance_ode_device(self, y, N, denoise, noise, generator, seed, rtol, atol, method, eps, return_nfe, return_preprocess_info, extra):
+        """sampler_type='ode', driver='device': the whole sampler as ONE native call (fd_score_ode_enhance) -- STFT, the prior sample, the
+        Dormand-Prince 5(4) solve of the probability-flow ODE under scipy RK45's own step-size rule with ONE controller for the batch
+        (what solve_ivp sees in the host driver: the reference's meaning of a batch), the denoising step, iSTFT.  The state stays on the
+        device in float32 planes (scipy carries complex128 on the host); NFE is scipy's count.  A step below ten spacings of t raises
+        ("step size too small") where scipy stops with a failure status and the reference goes on with the last state."""
+        if method != "RK45":
+            raise ValueError(f"enhance(sampler_type='ode', driver='device'): method='RK45' only (got {method!r}); other scipy methods run with driver='host'")
+        if extra:
+            raise ValueError(f"enhance(sampler_type='ode', driver='device'): unsupported solve_ivp option(s) {sorted(extra)}; they run with driver='host'")
+        sc, rtol, atol = self._ode_config(N, denoise, eps, rtol, atol, "enhance(sampler_type='ode', driver='device')")
+        stats = {}
+        res = self._wave_call(y, 1, noise, generator, self._ode_launch(sc, rtol, atol, False, seed is not None, False, stats),
+                              return_preprocess_info, seed=seed)
+        if return_preprocess_info:
+            return res
+        return (res, stats["nfe"][0]) if return_nfe else res
+
+    @torch.no_grad()
+    def enhance_ode_batch(self, clips, N=30, rtol=1e-5, atol=1e-5, denoise=True, eps=None, noise=None, generator=None, seeds=None,
+                          return_nfe: bool = False):
+        """The ODE sampler on clips of DIFFERENT lengths whose spectrograms pad to one T_pad (the bucket rule of `enhance_batch`), as ONE
+        native call with ONE step-size controller PER CLIP: clip b takes the steps of, and is BIT-IDENTICAL to,
+        `self.enhance(clip_b, sampler_type='ode', driver='device', ...)` with the same noise or seed, in any batch and in any order; a clip
+        that has reached t_eps rides along (dt = 0) until the slowest one is done.  `noise` = one [1, 1, F, T_pad] complex tensor per clip,
+        `generator` = one torch.Generator (drawn clip by clip) or one per clip, `seeds` = one 64-bit seed per clip (clip i equals
+        `enhance(clip_i, ..., seed=[seeds[i]])`).  At most 256 clips per call.  -> list of waveforms; with return_nfe also the per-clip NFE
+        (list of int).  `last_nfe_per_clip`, `last_rejected_per_clip`, `last_evals` as in FlowModel.enhance."""
+        fd_noise.exclusive(seeds=seeds, noise=noise, generator=generator)
+        sc, rtol, atol = self._ode_config(N, denoise, eps, rtol, atol, "enhance_ode_batch")
+        stats = {}
+        outs = self._ragged_call(clips, 1, noise, generator, seeds, self._ode_launch(sc, rtol, atol, True, seeds is not None, True, stats))
+        return (outs, stats.get("nfe", [])) if return_nfe else outs
+
     @_serialized
     def _enhance_ode(self, y, N=None, denoise=True, noise=None, generator=None, seed=None, rtol=1e-5, atol=1e-5, method="RK45", eps=None,
-                     return_nfe: bool = False, return_preprocess_info: bool = False, **ignored):
+                     return_nfe: bool = False, return_preprocess_info: bool = False, driver: str = "host", **ignored):
         """sampler_type='ode' (sampling/__init__.py:75-146): the probability-flow ODE integrated by scipy.integrate.solve_ivp
         on the host, exactly like the reference; every drift evaluation is one fd_score_eval (backbone + fused update) on
         the GPU, the STFT / iSTFT run in libflowdec_hip.so.  Host-driven and slow by construction (the state crosses PCIe
-        twice per evaluation) -- it exists for API parity with ScoreModel.enhance."""
+        twice per evaluation) -- it exists for API parity with ScoreModel.enhance.  driver='device' (`_enhance_ode_device`) runs the
+        same sampler, method 'RK45', entirely on the GPU."""
+        if driver == "device":
+            return self._enhance_ode_device(y, N, denoise, noise, generator, seed, rtol, atol, method, eps, return_nfe, return_preprocess_info, ignored)
+        if driver != "host":
+            raise ValueError(f"enhance(sampler_type='ode'): driver must be 'host' or 'device' (got {driver!r})")
         from scipy import integrate
         dev = self._gpu()
         orig_device = y.device

@@ -274,6 +274,17 @@ def score_update(pyr, w, base, cb, Y, cy, cn, cz, z=None, seeds=None, draw=0, ds
     return dst
 
 
+def score_update_clips(pyr, w, base, Y, ctab, dst=None):
+    """dst[b] = cb_b base[b] + cy_b Y[b] + cn_b output_layer(pyr[b]) with (cb_b, cy_b, cn_b) = ctab[b] (float32 [B, 3] on the GPU): the
+    per-clip form of `score_update` without its noise term."""
+    B, H, W, c4 = _nhwc(pyr)
+    assert c4 == 4 and ctab.dtype == torch.float32 and tuple(ctab.shape) == (B, 3) and ctab.is_contiguous()
+    dst = torch.empty(B, H, W, dtype=torch.complex64, device=pyr.device) if dst is None else dst
+    L.check(L.load().fd_score_update_clips(L.ptr(pyr), L.ptr(w), L.ptr(base), L.ptr(Y), L.ptr(ctab), L.ptr(dst), B, H, W, _output_ks(w),
+                                           L.dtype_id(pyr.dtype), L.stream()))
+    return dst
+
+
 def init_state(Y, sigma, sigma_fac, noise=None, seeds=None, frame0=None, draw=0, out=None):
     """x0 = Y + sigma_fac * complex64(sigma[f] * z); Y complex64 [B, F, T], sigma float64 [1] or [F]; z = `noise` or the seeded plane."""
     B, F, T = _plane(Y).shape

@@ -298,6 +298,12 @@ int fd_op_output_update(const void* pyr, const float* w, const float* base, cons
  * noise" below with F = H, T = W, generated in registers) must be given. */
 int fd_op_score_update(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn, const float* z,
                        const unsigned long long* seeds, int draw, float cz, float* dst, int B, int H, int W, int ks, int dtype, void* stream);
+/* fd_op_score_update with one time per clip and no noise term (the right-hand side of fd_score_ode_solve under per-clip step control):
+ *   dst[b] = fma(cy_b, Y[b], fma(cn_b, v[b], cb_b * base[b])),  (cb_b, cy_b, cn_b) = ctab[b][0..2]   (ctab: DEVICE float [B][3])
+ * The Y term of a clip is skipped when its cy_b == 0; cy lives on the device, so Y is always required.  Image b equals
+ * fd_op_score_update(cb_b, cy_b, cn_b, cz = 0) on that image alone, bit for bit.  B <= 65535. */
+int fd_score_update_clips(const void* pyr, const float* w, const float* base, const float* Y, const float* ctab, float* dst, int B, int H,
+                             int W, int ks, int dtype, void* stream);
 /* x0 = Y + sigma_fac * nx,  nx = (float)(sigma[f] * (double)z)   (sigma = float64 [sigma_n], sigma_n = 1: one value for every f, or F).
  * Y, x0: complex [B][F][T].  Exactly one of noise (complex [B][F][T]) and seeds (uint64 [B]; z = plane (seeds[b], draw) at the absolute
  * frames frame0[b] + t, frame0 = int32 [B] or NULL = zeros; frame0 needs seeds). */
@@ -666,6 +672,37 @@ int fd_score_enhance_ragged(fd_model* m, const float* y, const int* lengths, con
 #define FD_SCORE_DENOISE 2
 int fd_score_eval(fd_model* m, const float* x, const float* Y, float t, const fd_score_config* cfg, int mode, float* out, int B,
                   int T_pad, void* ws, size_t ws_bytes, void* stream);
+/* The ODE sampler itself on the device (ScoreModel.enhance(sampler_type="ode"), sampling/__init__.py:75-146): the probability-flow ODE
+ * integrated from t = 1 down to cfg->t_eps by Dormand-Prince 5(4) under the step-size rule of scipy.integrate.RK45 -- its
+ * select_initial_step, its strict acceptance err < 1, its growth and shrink factors, its clamp to the end of the span --, restated in
+ * double precision (Rk45Ctl, csrc/step_ctl.h); the network is given (float)t like the host-driven sampler gives it.  The state and the
+ * stages are float32 planes on the device (scipy carries complex128), the error norm is a float64 sum; one synchronisation per attempted
+ * step, no hipGraph.  Of *cfg only theta, sigma_min, sigma_max, t_eps, N and denoise are read; with denoise one FD_SCORE_DENOISE
+ * evaluation at t_eps (dt = 1 / N) follows the solve.
+ *   step_control = FD_STEP_CONTROL_BATCH: ONE controller on the norms over the whole batch -- what solve_ivp sees, and the reference's
+ *     meaning of a batch; nfe_out / rejected_out have one entry.
+ *   step_control = FD_STEP_CONTROL_CLIP: one controller per clip (B <= 256): clip b takes the steps, and gives the bits, of the B = 1 call
+ *     on it; a clip that has reached t_eps rides along with dt = 0 until the slowest is done.  nfe_out / rejected_out have B entries.
+ * Exactly one of noise (complex64 [B][n_freq][T_pad]: the prior sample is Y + std(1) noise) and seeds (DEVICE uint64 [B]: draw 0 of "Seeded
+ * noise") is non-NULL.  nfe_out (required): 2 + 6 per attempt, the count scipy reports (the denoising evaluation is not counted);
+ * rejected_out, evals_out (optional): rejected attempts, and the network evaluations of the whole batch that ran.
+ * FD_EINVAL before any launch for null pointers, bad OUVE parameters, t_eps outside (0, 1), atol <= 0, rtol < 0, an unknown step_control
+ * and B > 256 with FD_STEP_CONTROL_CLIP; FD_ENOMEM for a short workspace.  FD_ERUNTIME "step size too small" when a step falls below ten
+ * spacings of t (a NaN input ends there after some twenty attempts): scipy's solver stops with a failure status at that point and the
+ * reference carries on with the last state without a word -- this library reports it. */
+#define FD_STEP_CONTROL_BATCH 0
+#define FD_STEP_CONTROL_CLIP 1
+size_t fd_score_ode_workspace_bytes(const fd_model* m, int B, int T_pad, int step_control);
+int fd_score_ode_solve(fd_model* m, const float* Y, const float* noise, const unsigned long long* seeds, const fd_score_config* cfg, float rtol,
+                       float atol, int step_control, float* X_out, int* nfe_out, int* rejected_out, int* evals_out, int B, int T_pad, void* ws,
+                       size_t ws_bytes, void* stream);
+/* The same from waveform to waveform, with the front end and the back end of fd_score_enhance_ragged: y / x_hat are [B][L] rows, lengths
+ * (DEVICE int32 [B]) the clips' own sample counts of ONE T_pad bucket, or NULL when every clip is L samples long.  With
+ * FD_STEP_CONTROL_CLIP clip b is bit-identical to the B = 1 call on that clip alone with its noise plane or its seed.  Synchronous. */
+size_t fd_score_ode_enhance_workspace_bytes(const fd_model* m, int B, int L, int step_control);
+int fd_score_ode_enhance(fd_model* m, const float* y, const int* lengths, const float* noise, const unsigned long long* seeds,
+                         const fd_score_config* cfg, float rtol, float atol, int step_control, float* x_hat, int* nfe_out, int* rejected_out,
+                         int* evals_out, int B, int L, void* ws, size_t ws_bytes, void* stream);
 /* RegressionModel.enhance (model.py:566-578): x_hat = iSTFT(backbone(Y, Y, t = 0)). */
 int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph,
                           void* stream);
