@@ -40,6 +40,11 @@ int fd_set_error(int code, const char* fmt, ...);
 static inline hipStream_t fd_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int fd_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t fd_dtype_size(int dtype) { return dtype == FD_BF16 ? 2 : 4; }
+// workgroups of a grid-stride launch over n items: ceil(n / per_block), at least 1 and at most cap
+inline int grid_for(long long n, int per_block = 256, int cap = 1 << 20) {
+  long long g = (n + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 
 // ---- device helpers ---------------------------------------------------------------------------
 // x * sigmoid(x) with the hardware reciprocal (1 ulp) instead of an IEEE division (10 VALU instructions)

@@ -35,10 +35,10 @@ struct fd_edge_args {
   float cb = 1.f, cy = 0.f, cz = 0.f;
   const float* ctab = nullptr; // score update, per-clip form: (cb, cy, coef) of clip b from ctab[b][0..2] (DEVICE [B][3]); no noise term
   int B = 0, H = 0, W = 0, Cout = 0;
-  int ks = 1;                  // output layer (ops 3, 4): 1x1 or 3x3 (zero padding 'same'; w = [2][4][3][3])
+  int ks = 1;                  // output layer (output_update, score_update): 1x1 or 3x3 (zero padding 'same'; w = [2][4][3][3])
 };
 
-// elementwise.hip
+// net_edges.hip
 int fd_time_embedding_impl(const float* t, float t_imm, int nt, const float* gfp_w, int nf, const float* w1, const float* b1,
                            const float* w2, const float* b2, float* temb, hipStream_t st);
 int fd_temb_bias_batched(const fd_temb_job* jobs_dev, int njobs, const float* temb, int nt, int temb_dim, hipStream_t st);
@@ -48,13 +48,18 @@ int fd_check_time_embedding(const char* who, int nt, const float* gfp_w, int nf,
                             const float* b2, const float* temb);
 int fd_check_temb_bias(const char* who, const float* temb, int nt, int temb_dim);
 int fd_check_temb_job(const char* who, int job, const float* dense_w, const float* dense_b, const float* out, int Cout);
-// which: 0 = pack_input, 2 = combine (1x1 4->Cout + h), 3 = output layer + state update,
-//        4 = output layer + score-sampler update, 5 = input convolution 3x3 4 -> Cout (x = packed input, w = [Cout][4][3][3] f32) with
-//        the GroupNorm partials of its output in `stats` ([B][(H / 16) * (W / 16)][Cout][2])
-int fd_edge_op(int which, const fd_edge_args& a, int dtype, hipStream_t st);
+// net_edges.hip: the edge ops, each on the fields of fd_edge_args it names there -- pack_input; combine (1x1 4->Cout + h); output layer +
+// state update; output layer + score-sampler update (per clip when a.ctab is set); input convolution 3x3 4 -> Cout (x = packed input,
+// w = [Cout][4][3][3] f32) with the GroupNorm partials of its output in `stats` ([B][(H / 16) * (W / 16)][Cout][2])
+int fd_edge_pack_input(const fd_edge_args& a, int dtype, hipStream_t st);
+int fd_edge_combine(const fd_edge_args& a, int dtype, hipStream_t st);
+int fd_edge_output_update(const fd_edge_args& a, int dtype, hipStream_t st);
+int fd_edge_score_update(const fd_edge_args& a, int dtype, hipStream_t st);
+int fd_edge_conv_in(const fd_edge_args& a, int dtype, hipStream_t st);
+int fd_combine_tiles(int H, int W);
+// solver_ops.hip
 int fd_init_state(const float* Y, const fd_noise_src& noise, const double* sigma_dev, int sigma_n, float sigma_fac, float* x0, int B,
                   int F, int T, hipStream_t st);
-int fd_combine_tiles(int H, int W);
 // adaptive solver helpers: dst = cx * x + dt * sum c[i] k[i];  partial[b] = sum |p - q|^2 / (atol + rtol max(|r|, |s|))^2
 int fd_ode_lincomb(const float* x, float cx, float dt, const float* const* k, const float* c, int nk, float* dst, long long n, hipStream_t st);
 int fd_ode_scaled_sq(const float* p, const float* q, const float* r, const float* s, float atol, float rtol, double* partial, int nblocks,

@@ -364,7 +364,7 @@ struct Fwd {
     }
     size_t mi = 3;
     Tens in4 = talloc(8, F, T);   // 4 real channels + 4 zero channels (MFMA conv needs Cin % 8 == 0)
-    if (!dry) { fd_edge_args a; a.x = x; a.y = y; a.out = ptr(in4.off); a.B = B; a.H = F; a.W = T; FD_TRY(fd_edge_op(0, a, dt, st)); }
+    if (!dry) { fd_edge_args a; a.x = x; a.y = y; a.out = ptr(in4.off); a.B = B; a.H = F; a.W = T; FD_TRY(fd_edge_pack_input(a, dt, st)); }
     std::vector<Tens> hs;
     {
       const Mod& md = mods[mi++];
@@ -377,7 +377,7 @@ struct Fwd {
         h0.tiles = (F / 16) * (T / 16); h0.stride = md.cout;
         h0.sums = arena.alloc(sizeof(float) * 2 * (size_t)B * h0.tiles * h0.stride);
         if (!dry) { fd_edge_args a; a.x = ptr(in4.off); a.w = md.w_f32; a.bias = md.b_f32; a.out = ptr(h0.off); a.stats = (float*)ptr(h0.sums);
-                    a.B = B; a.H = F; a.W = T; a.Cout = md.cout; FD_TRY(fd_edge_op(5, a, dt, st)); }
+                    a.B = B; a.H = F; a.W = T; a.Cout = md.cout; FD_TRY(fd_edge_conv_in(a, dt, st)); }
       } else {
         FD_TRY(conv(in4, nullptr, (size_t)-1, nullptr, nullptr, md.conv0, md.b_f32, 1, nullptr, 1.f, h0, true));
         if (!dry && m->profiling) {   // the 4 padding channels are not algorithmic work
@@ -407,7 +407,7 @@ struct Fwd {
         hc.tiles = fd_combine_tiles(hd.H, hd.W); hc.stride = md.cout;     // the combine kernel emits the GroupNorm partials of hc
         hc.sums = arena.alloc(sizeof(float) * 2 * (size_t)B * hc.tiles * hc.stride);
         if (!dry) { fd_edge_args a; a.x = ptr(pyr_in.off); a.y = ptr(hd.off); a.w = md.w_f32; a.bias = md.b_f32; a.out = ptr(hc.off);
-                    a.stats = (float*)ptr(hc.sums); a.B = B; a.H = hd.H; a.W = hd.W; a.Cout = md.cout; FD_TRY(fd_edge_op(2, a, dt, st)); }
+                    a.stats = (float*)ptr(hc.sums); a.B = B; a.H = hd.H; a.W = hd.W; a.Cout = md.cout; FD_TRY(fd_edge_combine(a, dt, st)); }
         tfree(hd);
         hs.push_back(hc);
       }
@@ -471,7 +471,7 @@ struct Fwd {
       fd_edge_args a; a.x = ptr(pyramid.off); a.w = m->wo; a.base = os.base; a.kold = os.kold; a.coef = os.coef; a.out = os.dst; a.ksave = os.ksave;
       a.B = B; a.H = F; a.W = T; a.ks = m->arch.output_ksize;
       if (os.score) { a.y = os.yv; a.z = os.z; a.cb = os.cb; a.cy = os.cy; a.cz = os.cz; a.ctab = os.ctab; }
-      FD_TRY(fd_edge_op(os.score ? 4 : 3, a, dt, st));
+      FD_TRY(os.score ? fd_edge_score_update(a, dt, st) : fd_edge_output_update(a, dt, st));
     }
     tfree(pyramid);
     return FD_OK;

@@ -48,7 +48,7 @@ struct Epi { int b, co0, tpos[2]; bool ok[2]; };   // ([2]: NT <= 2)
 
 // 8 rows of a tile at a time; the residual values of the NEXT 8 rows are requested before the current rows are stored.  FULL (every
 // column of the wave's tile is a real output): the stores are unconditional -- loads and stores return in order through one counter
-// (vmcnt), and with control flow between them hipcc has to wait as if no store were in flight, i.e. for all of them (elementwise.hip,
+// (vmcnt), and with control flow between them hipcc has to wait as if no store were in flight, i.e. for all of them (fir.hip,
 // fir_raw).
 template <int MT, int NT, bool RES, bool OUT, bool ACT, bool FULL>
 __device__ __forceinline__ void epilogue(const MArgs& a, const Epi& ep, f32x16 (&acc)[MT][NT]) {

@@ -38,3 +38,21 @@ __device__ __forceinline__ float2 fd_noise_from_bits(uint2 b) {
 __device__ __forceinline__ float2 fd_noise_at(unsigned long long seed, int draw, int f, int t) {
   return fd_noise_from_bits(fd_noise_bits_at(seed, draw, f, t));
 }
+
+// Element i of a [B][F][T] plane of Gaussian noise: read from the caller's buffer, or (SEEDED) generated in registers from the clip's
+// seed.  A thread recomputes the Philox call it shares with the neighbouring frame instead of handling a frame pair: the consumers
+// (init_state / caxpy in solver_ops.hip, score_update in net_edges.hip) stay one element per thread like their unseeded forms (one grid,
+// one index map), and the ~150 integer / float operations per element hide behind the 24-40 bytes each of them moves (they replace an
+// 8-byte load).
+// frame0 (int32 [B], may be null = zeros): the absolute frame of every row's first column (rows that are chunks of longer recordings).
+template <bool SEEDED>
+__device__ __forceinline__ float2 noise_elem(const float2* __restrict__ z, const unsigned long long* __restrict__ seeds, int draw, long long i,
+                                             int F, int T, const int* __restrict__ frame0 = nullptr) {
+  if constexpr (SEEDED) {
+    const long long row = i / T;
+    const long long b = row / F;
+    return fd_noise_at(seeds[b], draw, (int)(row % F), (frame0 ? frame0[b] : 0) + (int)(i - row * T));
+  } else {
+    return z[i];
+  }
+}

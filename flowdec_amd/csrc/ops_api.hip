@@ -1,6 +1,6 @@
 // ops_api.hip -- operator-level C ABI of the kernels between the network and the ODE / SDE solvers and of the time-conditioning kernels
 // (include/flowdec_hip.h, "Operator-level: solver and edge kernels").  Every entry point checks its arguments and then calls the launcher
-// the model and the solvers call (fd_edge_op, fd_init_state, fd_caxpy, fd_ode_*, fd_time_embedding_impl, fd_temb_bias_batched: internal.h).  No kernel and no launch configuration lives here, so a test
+// the model and the solvers call (fd_edge_*, fd_init_state, fd_caxpy, fd_ode_*, fd_time_embedding_impl, fd_temb_bias_batched: internal.h).  No kernel and no launch configuration lives here, so a test
 // of one of these functions is a test of the production launch.  A refused call launches nothing.
 #include <limits.h>
 #include <stdint.h>
@@ -18,7 +18,7 @@ constexpr int MAX_GRID_X_256 = (1 << 24) - 1;       // HIP: gridDim.x * blockDim
 // the 64 KiB every CDNA device grants a workgroup (gfx950 itself has 160 KiB); nf <= 2730 and temb_dim <= 16384 are far beyond any model.
 constexpr long long MAX_DYN_LDS_BYTES = 64 * 1024;
 
-// fd_row_dot (elementwise.hip) reads a weight row as 16-byte vectors: with a row length that is a multiple of 4 floats every row is
+// fd_row_dot (net_edges.hip) reads a weight row as 16-byte vectors: with a row length that is a multiple of 4 floats every row is
 // aligned when the base pointer is
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -57,7 +57,7 @@ int check_scaled_sq(const char* who, const float* p, const float* r, const float
 
 }  // namespace
 
-// ---- time conditioning: the checks shared by fd_time_embedding / fd_temb_bias (elementwise.hip) and their fd_op_* forms ---------------
+// ---- time conditioning: the checks shared by fd_time_embedding / fd_temb_bias (net_edges.hip) and their fd_op_* forms ---------------
 int fd_check_time_embedding(const char* who, int nt, const float* gfp_w, int nf, const float* w1, const float* b1, const float* w2,
                             const float* b2, const float* temb) {
   FD_REQUIRE(gfp_w, "%s: null pointer (gfp_w)", who);
@@ -131,7 +131,7 @@ extern "C" int fd_op_pack_input(const float* x, const float* y, void* out8, int 
   FD_TRY(check_image("fd_op_pack_input", B, H, W, dtype));
   fd_edge_args a;
   a.x = x; a.y = y; a.out = out8; a.B = B; a.H = H; a.W = W;
-  return fd_edge_op(0, a, dtype, fd_stream(stream));
+  return fd_edge_pack_input(a, dtype, fd_stream(stream));
 }
 
 extern "C" int fd_op_combine(const void* p4, const float* w, const float* bias, const void* h, void* out, float* stats, int B, int H, int W,
@@ -142,7 +142,7 @@ extern "C" int fd_op_combine(const void* p4, const float* w, const float* bias, 
   FD_REQUIRE(Cout >= 8 && Cout <= 256 && (Cout & (Cout - 1)) == 0, "fd_op_combine: Cout must be a power of two in [8, 256] (got %d)", Cout);
   fd_edge_args a;
   a.x = p4; a.w = w; a.bias = bias; a.y = h; a.out = out; a.stats = stats; a.B = B; a.H = H; a.W = W; a.Cout = Cout;
-  return fd_edge_op(2, a, dtype, fd_stream(stream));
+  return fd_edge_combine(a, dtype, fd_stream(stream));
 }
 
 extern "C" int fd_op_output_update(const void* pyr, const float* w, const float* base, const float* kold, float coef, float* dst, float* ksave,
@@ -152,7 +152,7 @@ extern "C" int fd_op_output_update(const void* pyr, const float* w, const float*
   FD_REQUIRE(ks == 1 || ks == 3, "fd_op_output_update: ks must be 1 or 3 (got %d)", ks);
   fd_edge_args a;
   a.x = pyr; a.w = w; a.base = base; a.kold = kold; a.coef = coef; a.out = dst; a.ksave = ksave; a.B = B; a.H = H; a.W = W; a.ks = ks;
-  return fd_edge_op(3, a, dtype, fd_stream(stream));
+  return fd_edge_output_update(a, dtype, fd_stream(stream));
 }
 
 extern "C" int fd_op_score_update(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn,
@@ -166,7 +166,7 @@ extern "C" int fd_op_score_update(const void* pyr, const float* w, const float* 
   fd_edge_args a;
   a.x = pyr; a.w = w; a.base = base; a.cb = cb; a.y = Y; a.cy = cy; a.coef = cn; a.z.ptr = z; a.z.seeds = seeds; a.z.draw = draw; a.cz = cz;
   a.out = dst; a.B = B; a.H = H; a.W = W; a.ks = ks;
-  return fd_edge_op(4, a, dtype, fd_stream(stream));
+  return fd_edge_score_update(a, dtype, fd_stream(stream));
 }
 
 extern "C" int fd_score_update_clips(const void* pyr, const float* w, const float* base, const float* Y, const float* ctab, float* dst, int B, int H,
@@ -178,7 +178,7 @@ extern "C" int fd_score_update_clips(const void* pyr, const float* w, const floa
   FD_REQUIRE(ks == 1 || ks == 3, "fd_score_update_clips: ks must be 1 or 3 (got %d)", ks);
   fd_edge_args a;
   a.x = pyr; a.w = w; a.base = base; a.y = Y; a.ctab = ctab; a.out = dst; a.B = B; a.H = H; a.W = W; a.ks = ks;
-  return fd_edge_op(4, a, dtype, fd_stream(stream));
+  return fd_edge_score_update(a, dtype, fd_stream(stream));
 }
 
 extern "C" int fd_op_init_state(const float* Y, const float* noise, const unsigned long long* seeds, const int* frame0, int draw,

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(1024) void stream_gather_kernel(const fd_stream_row
 // is READ and the new one WRITTEN in the same launch by different threads: the caller gives two distinct buffers (row parity).
 __global__ __launch_bounds__(256) void stream_emit_kernel(const fd_stream_row* __restrict__ table, const float* __restrict__ x_hat, int Lrow,
                                                           const float* __restrict__ weights, int xfade) {
-#pragma clang fp contract(off)   // a + w * (b - a) in three roundings, as stitch_kernel (elementwise.hip): no fma
+#pragma clang fp contract(off)   // a + w * (b - a) in three roundings, as stitch_kernel (solver_ops.hip): no fma
   const int b = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= Lrow) return;

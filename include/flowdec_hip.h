@@ -333,7 +333,7 @@ int fd_op_ode_scaled_sq_clips(const float* p, const float* q, const float* r, co
 int fd_op_ode_commit_clips(const int* accept, const int* ckpt, const float* x_new, const float* k6, float* x, float* k0, float* traj, int B,
                            long long n, void* stream);
 
-/* Time conditioning (csrc/elementwise.hip: time_embedding_kernel, temb_bias_kernel), through the launchers fd_ncsnpp_forward calls.
+/* Time conditioning (csrc/net_edges.hip: time_embedding_kernel, temb_bias_kernel), through the launchers fd_ncsnpp_forward calls.
  * fd_op_time_embedding = fd_time_embedding with the scalar-time path of the fixed-step solvers: t == NULL takes the time of every row
  * from t_imm (passed by value, no device read); with t != NULL, t_imm is ignored.  Row r:
  *   xp = ((t[r] * gfp_w[j]) * 2) * pi_f32 (three float32 roundings), emb = (sinf(xp) [nf], cosf(xp) [nf]),

@@ -1,6 +1,6 @@
 """References, data and error bounds of the operator-level tests of the time-conditioning kernels (tests/test_hip_temb.py on the GPU,
 tests/test_temb_cpu.py without one; include/flowdec_hip.h fd_time_embedding, fd_temb_bias, fd_op_time_embedding, fd_op_temb_bias_jobs;
-csrc/elementwise.hip time_embedding_kernel, temb_bias_kernel, temb_bias_single_kernel).
+csrc/net_edges.hip time_embedding_kernel, temb_bias_kernel, temb_bias_single_kernel).
 
 The reference is NumPy float64 TAKEN FROM THE FLOAT32 ANGLE: xp = fl(fl(fl(t W) 2) pi32) in the kernel's three float32 roundings (the
 doubling is exact), then sin / cos, both Linear layers, the SiLU and the bias sums in float64.  With W ~ 16 N(0, 1) the angles reach

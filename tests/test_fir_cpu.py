@@ -26,7 +26,7 @@ def ops():
 # ---------------------------------------------------------------------------------------------------------
 # the selection rule
 # ---------------------------------------------------------------------------------------------------------
-ENOUGH, FILL = 512, 768      # workgroups of 256 threads (fir_select in csrc/elementwise.hip)
+ENOUGH, FILL = 512, 768      # workgroups of 256 threads (fir_select in csrc/fir.hip)
 
 
 def mirror(B, H, W, C, direction, prec, affine, want_raw, want_act):

@@ -1,4 +1,4 @@
-"""Every kernel variant of the FIR [1,3,3,1] x2 resampling (csrc/elementwise.hip: fir_up_kernel, fir_down_kernel, fir_down_march_kernel)
+"""Every kernel variant of the FIR [1,3,3,1] x2 resampling (csrc/fir.hip: fir_up_kernel, fir_down_kernel, fir_down_march_kernel)
 against an independent reference, on whole images -- borders, ragged last strips and column blocks included.
 
 Raw output, EXACT.  The taps are 1/8, 3/8 per axis (down) and 1/4, 3/4 (up).  On integer input with |x| <= 2 every product and every

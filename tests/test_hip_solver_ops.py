@@ -1,5 +1,5 @@
 """The kernels between the network and the ODE / SDE solvers, one at a time, on the GPU (include/flowdec_hip.h "Operator-level: solver and
-edge kernels"; csrc/elementwise.hip through csrc/ops_api.hip, whose wrappers call the launchers the model and the solvers call).
+edge kernels"; csrc/net_edges.hip and csrc/solver_ops.hip through csrc/ops_api.hip, whose wrappers call the launchers the model and the solvers call).
 
 Every reference is NumPy float64 computed from the stored inputs, every bound is derived from the kernel's operation count
 (tests/solver_ops_ref.py; tests/test_solver_ops_cpu.py shows that the float32 arithmetic itself meets them, fused or not), every output is

@@ -1,6 +1,6 @@
 """The time-conditioning kernels at model widths, one at a time, on the GPU: time_embedding_kernel (Fourier features -> Linear -> SiLU ->
 Linear), temb_bias_kernel (the batched jobs x rows table of every ResBlock's Conv_0.bias + Dense_0(silu(temb))) and its one-job form
-temb_bias_single_kernel (csrc/elementwise.hip), through fd_time_embedding, fd_temb_bias and the operator-level entries
+temb_bias_single_kernel (csrc/net_edges.hip), through fd_time_embedding, fd_temb_bias and the operator-level entries
 fd_op_time_embedding and fd_op_temb_bias_jobs (csrc/ops_api.hip), which call the launchers the model calls.
 
 Every reference is NumPy float64 taken from the float32 angle, every bound is counted from the operations (tests/temb_ref.py;

@@ -35,6 +35,15 @@ def test_symbols_are_declared_exported_and_bound():
     assert "ops_api.hip" in __import__("flowdec_amd.build", fromlist=["SOURCES"]).SOURCES
 
 
+def test_build_sources_are_exactly_the_hip_files():
+    """Every .hip file under csrc is linked into the library and every listed source exists: a new file cannot be left out, a deleted one
+    cannot be left in."""
+    from flowdec_amd import build
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith(".hip")}
+    assert len(build.SOURCES) == len(set(build.SOURCES)), sorted(build.SOURCES)
+    assert set(build.SOURCES) == on_disk, sorted(set(build.SOURCES) ^ on_disk)
+
+
 def test_every_argument_check_refuses_before_the_device():
     from flowdec_amd import _lib as L
     lib = L.load()
