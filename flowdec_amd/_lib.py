@@ -211,6 +211,8 @@ SIGNATURES = {
     "fd_rvq_encode": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "fd_rvq_from_codes": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
     "fd_ndac_decode": (c_int, [_P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "fd_ndac_decode_ragged": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "fd_ndac_decode_halo": (c_int, [_P, C.POINTER(c_int), C.POINTER(c_int)]),
     "fd_stft_plan_profile": (c_int, [_P, c_int]),
     "fd_stft_plan_profile_read": (c_int, [_P, C.POINTER(C.c_double * 6), C.POINTER(c_int * 2)]),
     "fd_metrics_workspace_bytes": (c_size_t, [c_int] * 4),

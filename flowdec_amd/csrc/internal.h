@@ -97,8 +97,11 @@ void fd_resample_plan_dims(const fd_resample_plan* p, int* o, int* n, int* width
 bool fd_ndac_mfma_supported(int Ci, int Co, int K, int stride, int dil, int transposed);
 // (fd_ndac_mfma_packed_bytes: public, include/flowdec_hip.h)
 void fd_ndac_mfma_pack(const float* w_ci_k_co, int Ci, int Co, int K, int stride, int transposed, void* dst);
+// Ragged decode (fd_ndac_decode_ragged): clip b of a layer's input is frames[b] * mul + add positions long (frames: device int32 [B], the
+// clips' LATENT frame counts; every decoder layer's length rule is affine in them).  frames == nullptr: every clip fills the row.
+struct fd_ndac_lens { const int* frames = nullptr; int mul = 1, add = 0; };
 int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
-                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st);
+                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st, fd_ndac_lens lens = {});
 // ndac.hip: PyTorch weight layout ([Co][Ci][K] conv, [Ci][Co][K] transposed) -> the codec's own [Ci][K][Co] (host memory)
 void fd_ndac_weight_ci_k_co(const float* w, int Ci, int Co, int K, int transposed, float* dst);
 // attn.hip: the bottleneck attention block (x -> out, GroupNorm affine given); qkv = f32 workspace of fd_attn_qkv_bytes; stats (optional) =

@@ -20,6 +20,9 @@
 //   rvq_step_kernel     one residual quantiser: in_proj with f64 accumulation, nearest neighbour with the float32 operation order the
 //                       oracle defines (code indices BIT-EXACT; ties -> lowest index), straight-through value, out_proj, residual update
 //   rvq_from_codes_kernel   codes -> sum_i out_proj_i(codebook_i[code])
+// Ragged decode (fd_ndac_decode_ragged): every convolution kernel reads input positions at and behind T as the zero padding; under a frame
+// table (fd_ndac_lens) that bound is the CLIP's own length at the layer, so a clip in a batch of longer rows sees exactly the padding it
+// sees alone -- the same bits -- and nothing behind it is read as data.  No table (every dense call): the bound is T.
 #include <math.h>
 #include <string.h>
 
@@ -52,7 +55,12 @@ struct Conv1dArgs {
                                             // computed once by the producer instead of once per consuming workgroup (24x at 768 channels)
   int B, Ci, T, Co, K, To, stride, pad, dil, tanh_out;
   int wt;   // weight layout: 0 = [Co][Ci][K] (nn.Conv1d, the operator-level ABI), 1 = [Ci][K][Co] (the codec's own copy: coalesced staging)
+  fd_ndac_lens lens;   // ragged decode: clip b is lens.frames[b] * lens.mul + lens.add positions long (T stays the row pitch); null = T
 };
+
+// The clip's own input length: positions at and behind it read as the zero padding, whatever the row holds there.
+template <typename Args>
+__device__ __forceinline__ int clip_len(const Args& a, int b) { return a.lens.frames ? a.lens.frames[b] * a.lens.mul + a.lens.add : a.T; }
 
 // weights are read as [Co][Ci][K] (PyTorch layout) and staged as [ci][k][co] so that a thread's 4 output channels are one b128 read
 __global__ __launch_bounds__(256) void conv1d_kernel(Conv1dArgs a) {
@@ -66,13 +74,14 @@ __global__ __launch_bounds__(256) void conv1d_kernel(Conv1dArgs a) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j][0] = acc[j][1] = f32x2{0.f, 0.f};
   const long long in0 = (long long)t0 * a.stride - a.pad;   // input position of xs[.][0]
+  const int Tb = clip_len(a, b);
   for (int c0 = 0; c0 < a.Ci; c0 += CIC) {
     __syncthreads();
     for (int i = tid; i < CIC * span; i += 256) {
       const int ci = i / span, p = i - ci * span;
       const long long tin = in0 + p;
       float v = 0.f;
-      if (c0 + ci < a.Ci && tin >= 0 && tin < a.T) {
+      if (c0 + ci < a.Ci && tin >= 0 && tin < Tb) {
         v = a.x[((size_t)b * a.Ci + c0 + ci) * a.T + tin];
         if (a.alpha) v = snake_f(v, a.alpha[c0 + ci]);      // zero padding applies to the ACTIVATED signal (Snake, then Conv1d(padding=..))
       }
@@ -144,13 +153,14 @@ __global__ __launch_bounds__(256) void conv1d_s1_kernel(Conv1dArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[g][i][0] = acc[g][i][1] = f32x2{0.f, 0.f};
   const long long in0 = (long long)t0 - a.pad;
+  const int Tb = clip_len(a, b);
   for (int c0 = 0; c0 < a.Ci; c0 += CIC) {
     __syncthreads();
     for (int i = tid; i < CIC * SPAN; i += 256) {
       const int ci = i / SPAN, p = i - ci * SPAN;
       const long long tin = in0 + p;
       float v = 0.f;
-      if (c0 + ci < a.Ci && tin >= 0 && tin < a.T) {
+      if (c0 + ci < a.Ci && tin >= 0 && tin < Tb) {
         v = a.x[((size_t)b * a.Ci + c0 + ci) * a.T + tin];
         if (a.alpha) v = snake_f(v, a.alpha[c0 + ci]);
       }
@@ -218,11 +228,12 @@ __global__ __launch_bounds__(256) void conv1d_s1_kernel(Conv1dArgs a) {
 __global__ __launch_bounds__(256) void conv1d_ci1_kernel(Conv1dArgs a) {   // Ci == 1, stride 1, K <= 8, no input activation
   const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
   if (t >= a.To) return;
+  const int Tb = clip_len(a, b);
   float xv[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const long long tin = (long long)t - a.pad + (long long)k * a.dil;
-    xv[k] = k < a.K && tin >= 0 && tin < a.T ? a.x[(size_t)b * a.T + tin] : 0.f;
+    xv[k] = k < a.K && tin >= 0 && tin < Tb ? a.x[(size_t)b * a.T + tin] : 0.f;
   }
   for (int co = 0; co < a.Co; ++co) {
     float acc = 0.f;
@@ -244,6 +255,7 @@ __global__ __launch_bounds__(256) void conv1d_co1_kernel(Conv1dArgs a) {   // Co
   const int span = 256 + (a.K - 1) * a.dil;
   const int b = blockIdx.y, t0 = blockIdx.x * 256, tid = threadIdx.x;
   const long long in0 = (long long)t0 - a.pad;
+  const int Tb = clip_len(a, b);
   float acc = 0.f;
   for (int c0 = 0; c0 < a.Ci; c0 += C1C) {
     __syncthreads();
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(256) void conv1d_co1_kernel(Conv1dArgs a) {   // Co
       const int ci = i / span, p = i - ci * span;
       const long long tin = in0 + p;
       float v = 0.f;
-      if (c0 + ci < a.Ci && tin >= 0 && tin < a.T) {
+      if (c0 + ci < a.Ci && tin >= 0 && tin < Tb) {
         v = a.x[((size_t)b * a.Ci + c0 + ci) * a.T + tin];
         if (a.alpha) v = snake_f(v, a.alpha[c0 + ci]);
       }
@@ -280,6 +292,7 @@ struct ConvTr1dArgs {
   float* out_act; const float* alpha_out;
   int B, Ci, T, Co, K, To, stride, pad;
   int wt;   // 0 = [Ci][Co][K] (nn.ConvTranspose1d), 1 = [Ci][K][Co]
+  fd_ndac_lens lens;
 };
 
 // out[b][co][n] = bias[co] + sum_ci sum_{k = (n + p) mod s, += s, < K} act(x)[b][ci][(n + p - k) / s] * w[ci][co][k]   (w: [Ci][Co][K])
@@ -293,6 +306,7 @@ __global__ __launch_bounds__(256) void convtr1d_kernel(ConvTr1dArgs a) {
   const int b = blockIdx.z, co0 = blockIdx.y * CT, n0 = blockIdx.x * TT;
   const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
   const int tbase = (n0 + a.pad) / a.stride - (ntap - 1);   // input position of xs[.][0] (may be negative)
+  const int Tb = clip_len(a, b);
   float acc[4][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -310,7 +324,7 @@ __global__ __launch_bounds__(256) void convtr1d_kernel(ConvTr1dArgs a) {
     for (int i = tid; i < CIC * tspan; i += 256) {
       const int ci = i / tspan, p = i - ci * tspan, tin = tbase + p;
       float v = 0.f;
-      if (c0 + ci < a.Ci && tin >= 0 && tin < a.T) {
+      if (c0 + ci < a.Ci && tin >= 0 && tin < Tb) {
         v = a.x[((size_t)b * a.Ci + c0 + ci) * a.T + tin];
         if (a.alpha) v = snake_f(v, a.alpha[c0 + ci]);
       }
@@ -495,13 +509,14 @@ size_t conv1d_lds(int K, int stride, int dil) { return sizeof(float) * (size_t)(
 size_t convtr_lds(int K, int stride) { return sizeof(float) * (size_t)(CIC * (TT / stride + (K + stride - 1) / stride + 1) + CIC * K * CTP); }
 
 int launch_conv1d(const float* x, const float* w, const float* bias, const float* alpha, const float* res, float* out, int B, int Ci, int T, int Co,
-                  int K, int stride, int pad, int dil, int tanh_out, hipStream_t st, int wt = 0, float* out_act = nullptr, const float* alpha_out = nullptr) {
+                  int K, int stride, int pad, int dil, int tanh_out, hipStream_t st, int wt = 0, float* out_act = nullptr, const float* alpha_out = nullptr,
+                  fd_ndac_lens lens = {}) {
   FD_REQUIRE(B > 0 && Ci > 0 && T > 0 && Co > 0 && K > 0 && stride > 0 && dil > 0 && pad >= 0, "fd_conv1d: bad shape");
   const long long To = ((long long)T + 2 * pad - (long long)dil * (K - 1) - 1) / stride + 1;
   FD_REQUIRE(To > 0 && To < (1ll << 31), "fd_conv1d: empty output");
   const size_t lds = conv1d_lds(K, stride, dil);
   FD_REQUIRE(lds <= 64 * 1024, "fd_conv1d: kernel %d / stride %d / dilation %d needs %zu bytes of LDS (limit 64 KiB)", K, stride, dil, lds);
-  Conv1dArgs a{x, w, bias, alpha, res, out, out_act, alpha_out, B, Ci, T, Co, K, (int)To, stride, pad, dil, tanh_out, wt};
+  Conv1dArgs a{x, w, bias, alpha, res, out, out_act, alpha_out, B, Ci, T, Co, K, (int)To, stride, pad, dil, tanh_out, wt, lens};
   // the accumulation order per output is the same in both kernels (input channels ascending, taps ascending, one fma each): identical bits
   if (stride == 1 && Ci == 1 && K <= 8 && !alpha) {
     hipLaunchKernelGGL(conv1d_ci1_kernel, dim3(fd_cdiv(To, 256), B), dim3(256), 0, st, a);
@@ -528,13 +543,13 @@ int launch_conv1d(const float* x, const float* w, const float* bias, const float
 }
 
 int launch_convtr1d(const float* x, const float* w, const float* bias, const float* alpha, float* out, int B, int Ci, int T, int Co, int K, int stride,
-                    int pad, hipStream_t st, int wt = 0, float* out_act = nullptr, const float* alpha_out = nullptr) {
+                    int pad, hipStream_t st, int wt = 0, float* out_act = nullptr, const float* alpha_out = nullptr, fd_ndac_lens lens = {}) {
   FD_REQUIRE(B > 0 && Ci > 0 && T > 0 && Co > 0 && K > 0 && stride > 0 && pad >= 0, "fd_conv_transpose1d: bad shape");
   const long long To = ((long long)T - 1) * stride - 2 * pad + K;
   FD_REQUIRE(To > 0 && To < (1ll << 31), "fd_conv_transpose1d: empty output");
   const size_t lds = convtr_lds(K, stride);
   FD_REQUIRE(lds <= 64 * 1024, "fd_conv_transpose1d: kernel %d needs %zu bytes of LDS (limit 64 KiB)", K, lds);
-  ConvTr1dArgs a{x, w, bias, alpha, out, out_act, alpha_out, B, Ci, T, Co, K, (int)To, stride, pad, wt};
+  ConvTr1dArgs a{x, w, bias, alpha, out, out_act, alpha_out, B, Ci, T, Co, K, (int)To, stride, pad, wt, lens};
   hipLaunchKernelGGL(convtr1d_kernel, dim3(fd_cdiv(To, TT), fd_cdiv(Co, CT), B), dim3(256), lds, st, a);
   FD_LAUNCH_CHECK();
   return FD_OK;
@@ -604,6 +619,7 @@ void build_params(fd_ndac* m) {
 // (sinf + a division per element).  Same function on the same float32 values: bit-identical to activating at the consumer.
 struct Run {
   fd_ndac* m; hipStream_t st; int B; bool mfma;
+  fd_ndac_lens lens;   // ragged decode: the clips' lengths at the CURRENT layer's input (the decode loop advances it with T)
   const float* P(const std::string& n) const { return m->dev.at(n); }
   const void* packed(const std::string& n) const {
     if (!mfma) return nullptr;
@@ -615,8 +631,9 @@ struct Run {
   int conv(const float* x, const std::string& n, const float* res, float* out, float* out_act, const float* alpha_next, int Ci, int T, int Co, int K,
            int stride, int pad, int dil, int tanh_out = 0) const {
     if (const void* wp = packed(n); wp && !tanh_out)
-      return fd_ndac_mfma_conv(x, wp, P(n + ".bias"), res, out, out_act, alpha_next, B, Ci, T, Co, K, stride, pad, dil, 0, st);
-    return launch_conv1d(x, P(n + ".weight"), P(n + ".bias"), nullptr, res, out, B, Ci, T, Co, K, stride, pad, dil, tanh_out, st, /*wt*/ 1, out_act, alpha_next);
+      return fd_ndac_mfma_conv(x, wp, P(n + ".bias"), res, out, out_act, alpha_next, B, Ci, T, Co, K, stride, pad, dil, 0, st, lens);
+    return launch_conv1d(x, P(n + ".weight"), P(n + ".bias"), nullptr, res, out, B, Ci, T, Co, K, stride, pad, dil, tanh_out, st, /*wt*/ 1, out_act, alpha_next,
+                         lens);
   }
   // ResidualUnit on (x_raw, x_act = snake(x, block.0.alpha)): y = x + conv1(snake(conv7_dil(x_act))); -> y_raw (may be null), snake(y, alpha_next)
   int res_unit(const float* x_raw, const float* x_act, const std::string& n, int dim, int T, int dil, float* tmp_act, float* y_raw, float* y_act,
@@ -926,16 +943,25 @@ extern "C" int fd_ndac_encode(fd_ndac* m, const float* x, int B, int L, int n_qu
   return rvq_run(m, zbuf, B, T, nq, z_q, codes, latents, st);
 }
 
-extern "C" int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream) {
-  FD_TRY(check_ready(m, "fd_ndac_decode"));
-  FD_REQUIRE(z && audio && ws && B > 0 && T > 0, "fd_ndac_decode: bad arguments");
+namespace {
+
+// Ragged decode: row b of the audio behind its clip's own decoded length is zero, whatever the last convolution computed there.
+__global__ __launch_bounds__(256) void ndac_zero_tail_kernel(float* audio, fd_ndac_lens lens, int L) {
+  const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  if (t < L && t >= lens.frames[b] * lens.mul + lens.add) audio[(size_t)b * L + t] = 0.f;
+}
+
+// The decoder walk of fd_ndac_decode / fd_ndac_decode_ragged.  frames (device int32 [B], validated by the caller) or nullptr.  Every layer
+// is computed over the whole row; under a frame table each kernel bounds its INPUT reads by the clip's own length at that layer, so what a
+// layer wrote behind a clip is never read as data, and the clip sees exactly the zero padding it sees alone.
+int decode_walk(fd_ndac* m, const char* who, const float* z, const int* frames, int B, int T, float* audio, void* ws, size_t ws_bytes, hipStream_t st) {
   const fd_ndac_config& c = m->cfg;
   const size_t slot = fd_align(sizeof(float) * (size_t)B * dec_max_elems(c, T));
-  if (ws_bytes < 5 * slot) return fd_set_error(FD_ENOMEM, "fd_ndac_decode: workspace %zu < required %zu bytes", ws_bytes, 5 * slot);
-  hipStream_t st = fd_stream(stream);
+  if (ws_bytes < 5 * slot) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, 5 * slot);
   float* buf[5];
   for (int i = 0; i < 5; ++i) buf[i] = (float*)((char*)ws + i * slot);
   Run r{m, st, B, (m->precision & FD_NDAC_MFMA_DECODER) != 0};
+  r.lens.frames = frames;
   float *cur_raw = buf[0], *cur_act = buf[1], *nxt_raw = buf[2], *nxt_act = buf[3], *tmp = buf[4];
   auto alpha_of = [&](const std::string& n) { return r.P(n + ".alpha"); };
   // model.0: WNConv1d(latent, D, 7); DecoderBlock 1 starts with a Snake: only the activated output is needed
@@ -947,12 +973,13 @@ extern "C" int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* a
     const std::string p = "decoder.model." + std::to_string(i + 1);
     if (const void* wp = r.packed(p + ".block.1"))
       FD_TRY(fd_ndac_mfma_conv(cur_act, wp, r.P(p + ".block.1.bias"), nullptr, nxt_raw, nxt_act, alpha_of(p + ".block.2.block.0"), B, idim, T, od, 2 * s, s,
-                               ceil_half(s), 1, 1, st));
+                               ceil_half(s), 1, 1, st, r.lens));
     else
       FD_TRY(launch_convtr1d(cur_act, r.P(p + ".block.1.weight"), r.P(p + ".block.1.bias"), nullptr, nxt_raw, B, idim, T, od, 2 * s, s, ceil_half(s), st, /*wt*/ 1,
-                             nxt_act, alpha_of(p + ".block.2.block.0")));
+                             nxt_act, alpha_of(p + ".block.2.block.0"), r.lens));
     std::swap(cur_raw, nxt_raw); std::swap(cur_act, nxt_act);
     T = (T - 1) * s - 2 * ceil_half(s) + 2 * s;
+    r.lens.mul *= s; r.lens.add = r.lens.add * s + s - 2 * ceil_half(s);   // the same rule on a clip's own length: (n - 1) s - 2 p + 2 s
     const int dil[3] = {1, 3, 9};
     for (int j = 0; j < 3; ++j) {
       const bool last_unit = j == 2;
@@ -964,5 +991,60 @@ extern "C" int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* a
     }
   }
   const std::string last = "decoder.model." + std::to_string(c.n_decoder_rates + 2);
-  return r.conv(cur_act, last, nullptr, audio, nullptr, nullptr, od, T, 1, 7, 1, 3, 1, /*tanh*/ 1);
+  FD_TRY(r.conv(cur_act, last, nullptr, audio, nullptr, nullptr, od, T, 1, 7, 1, 3, 1, /*tanh*/ 1));
+  if (frames) {
+    hipLaunchKernelGGL(ndac_zero_tail_kernel, dim3(fd_cdiv(T, 256), B), dim3(256), 0, st, audio, r.lens, T);
+    FD_LAUNCH_CHECK();
+  }
+  return FD_OK;
+}
+
+int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+}  // namespace
+
+extern "C" int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream) {
+  FD_TRY(check_ready(m, "fd_ndac_decode"));
+  FD_REQUIRE(z && audio && ws && B > 0 && T > 0, "fd_ndac_decode: bad arguments");
+  return decode_walk(m, "fd_ndac_decode", z, nullptr, B, T, audio, ws, ws_bytes, fd_stream(stream));
+}
+
+extern "C" int fd_ndac_decode_ragged(fd_ndac* m, const float* z, const int* frames, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream) {
+  FD_TRY(check_ready(m, "fd_ndac_decode_ragged"));
+  FD_REQUIRE(z && frames && audio && ws && B > 0 && T > 0, "fd_ndac_decode_ragged: bad arguments");
+  hipStream_t st = fd_stream(stream);
+  std::vector<int> h(B);   // the bounds the kernels index with are checked before anything is launched (B ints: one small copy)
+  FD_HIP(hipMemcpyAsync(h.data(), frames, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+  FD_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b)
+    FD_REQUIRE(h[b] >= 1 && h[b] <= T, "fd_ndac_decode_ragged: frames[%d] = %d is outside [1, %d]", b, h[b], T);
+  return decode_walk(m, "fd_ndac_decode_ragged", z, frames, B, T, audio, ws, ws_bytes, st);
+}
+
+// Latent frames before / after a frame that can reach that frame's hop output samples: the sample interval of each output sample walked
+// backwards through the decoder (final conv +-3; per block the three residual units +-3 d, d = 9, 3, 1, then the transposed convolution
+// K = 2 s, p = ceil(s / 2): output n reads inputs floor((n + p) / s) - 1 .. floor((n + p) / s); first conv +-3), maximum over the frame.
+extern "C" int fd_ndac_decode_halo(const fd_ndac* m, int* left, int* right) {
+  FD_REQUIRE(m && left && right, "fd_ndac_decode_halo: null pointer");
+  const fd_ndac_config& c = m->cfg;
+  int up = 1;
+  for (int i = 0; i < c.n_decoder_rates; ++i) {
+    FD_REQUIRE(c.decoder_rates[i] % 2 == 0, "fd_ndac_decode_halo: decoder rate %d is odd (the decoded length is not frames * hop: no window arithmetic)",
+               c.decoder_rates[i]);
+    up *= c.decoder_rates[i];
+  }
+  int hl = 0, hr = 0;
+  for (int n = 0; n < up; ++n) {   // frame 0's samples; negative positions are real arithmetic here, not padding
+    int lo = n - 3, hi = n + 3;
+    for (int i = c.n_decoder_rates - 1; i >= 0; --i) {
+      const int s = c.decoder_rates[i], p = ceil_half(s);
+      lo -= 3 * (9 + 3 + 1); hi += 3 * (9 + 3 + 1);
+      lo = floor_div(lo + p, s) - 1; hi = floor_div(hi + p, s);
+    }
+    lo -= 3; hi += 3;
+    if (-lo > hl) hl = -lo;
+    if (hi > hr) hr = hi;
+  }
+  *left = hl; *right = hr;
+  return FD_OK;
 }

@@ -37,6 +37,7 @@ struct MArgs {
   int ostride, ooff;         // output position of column n, phase r = n * ostride + r + ooff
   int nchunk;                // K-loop chunks of 32 GEMM-K elements
   int pad;                   // strided form: input position of (row m, residue r) = S m + r - pad
+  fd_ndac_lens lens;         // ragged decode: clip b's own input length (T stays the row pitch); null = T
 };
 
 __device__ __forceinline__ float snake_fast(float v, float alpha, float inv) {
@@ -144,6 +145,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_kernel(MArgs a) {
 
   const float* const xb = a.x + (size_t)b * a.Ci * a.T;
   const long long pos0 = (long long)n0 + a.xlo;
+  const int Tb = a.lens.frames ? a.lens.frames[b] * a.lens.mul + a.lens.add : a.T;   // staging reads at and behind it are the zero padding
   const int col = wave * 32 * NT + (lane & 31);
   const int koff = (lane >> 5) * 16;
 
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_kernel(MArgs a) {
         for (int p = tid; p < a.rows; p += 256) {
           const long long tp = pos0 + p;
           float v[16];
-          if (tp >= 0 && tp < a.T) {
+          if (tp >= 0 && tp < Tb) {
             const float* q = src + tp;
 #pragma unroll
             for (int j = 0; j < 16; ++j) { v[j] = *q; q += a.T; }
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_kernel(MArgs a) {
 #pragma unroll
         for (int r = 0; r < S; ++r) {
           const long long q = q0 + r;
-          v[r] = ci < a.Ci && q >= 0 && q < a.T ? src[q] : 0.f;
+          v[r] = ci < a.Ci && q >= 0 && q < Tb ? src[q] : 0.f;
         }
         unsigned char* const dh = xh + p * ROWB + 2 * c * S;
         unsigned char* const dl = xl + p * ROWB + 2 * c * S;
@@ -408,14 +410,14 @@ int plan_conv(int B, int Ci, int T, int Co, int K, int stride, int pad, int dil,
 }  // namespace
 
 int fd_ndac_mfma_conv(const float* x, const void* wp, const float* bias, const float* res, float* out, float* out_act, const float* alpha_out, int B,
-                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st) {
+                      int Ci, int T, int Co, int K, int stride, int pad, int dil, int transposed, hipStream_t st, fd_ndac_lens lens) {
   Plan p;
   FD_TRY(plan_conv(B, Ci, T, Co, K, stride, pad, dil, transposed, &p));
   FD_REQUIRE(x && wp && bias && (out || out_act) && (!out_act || alpha_out), "ndac mfma conv: null argument");
   // every epilogue with a residual also writes the activated output (epilogue_dispatch has no <RES, OUT, !ACT> instance)
   FD_REQUIRE(!res || out_act, "ndac mfma conv: a residual needs the activated output out_act");
   MArgs& a = p.a;
-  a.x = x; a.wp = static_cast<const uint4*>(wp); a.bias = bias; a.res = res; a.out = out; a.out_act = out_act; a.alpha_out = alpha_out;
+  a.x = x; a.wp = static_cast<const uint4*>(wp); a.bias = bias; a.res = res; a.out = out; a.out_act = out_act; a.alpha_out = alpha_out; a.lens = lens;
   if (p.nt == 2) return p.mt == 3 ? launch<3, 2>(a, p.S, p.grid, p.lds, st) : launch<2, 2>(a, p.S, p.grid, p.lds, st);
   return p.mt == 3 ? launch<3, 1>(a, p.S, p.grid, p.lds, st) : launch<2, 1>(a, p.S, p.grid, p.lds, st);
 }

@@ -13,6 +13,9 @@ The module tree (`encoder.block.*`, `quantizer.quantizers.*`, `decoder.model.*`)
 `load_state_dict` of a DAC checkpoint works unchanged; the modules are parameter containers only -- every forward runs in the
 HIP library (there is no PyTorch / CPU compute path: a codec on the CPU raises).
 
+Beyond that surface: `decode_ragged` / `decode_batch` (clips of different lengths in one native call, each the bits of its own decode),
+`decode_long` (any length in fixed memory) and `decode_halo`; streaming sessions are `flowdec_amd.ndac_stream.DecodeStream`.
+
 The arithmetic is third party and absent from /root/reference: restated from the published algorithm, PARITY UNPINNED
 (oracle/ndac_oracle.py lists the upstream definitions).
 """
@@ -26,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import ndac_stream
 
 
 def _wn(module):
@@ -309,6 +313,77 @@ class DAC(nn.Module):
             ws = torch.empty(lib.fd_ndac_workspace_bytes(h, B, max(Lo, T * self.hop_length)), dtype=torch.uint8, device=z.device)
             L.check(lib.fd_ndac_decode(h, L.ptr(zz), B, T, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()))
         return out
+
+    # ---- ragged / long / streaming decode (flowdec_amd/ndac_stream.py) ------------------------------------------------------------
+    def decode_halo(self):
+        """-> (left, right): latent frames before / after a frame that can reach that frame's hop output samples (fd_ndac_decode_halo).
+        Raises for odd decoder rates (the decoded length is then not T * hop)."""
+        sig = self.decoder_rates
+        if getattr(self, "_halo_sig", None) != sig:
+            left, right = C.c_int(), C.c_int()
+            with self._lock:
+                L.check(L.load().fd_ndac_decode_halo(self.handle(), C.byref(left), C.byref(right)))
+            self._halo, self._halo_sig = (left.value, right.value), sig
+        return self._halo
+
+    def decode_workspace(self, B, T):
+        """The workspace of a (ragged) decode of B rows of T frames, as a uint8 device tensor."""
+        lib = L.load()
+        with self._lock, torch.cuda.device(self.device):
+            h = self.handle()
+            return torch.empty(lib.fd_ndac_workspace_bytes(h, int(B), max(lib.fd_ndac_decoded_length(h, int(T)), int(T) * self.hop_length)), dtype=torch.uint8,
+                               device=self.device)
+
+    @torch.no_grad()
+    def decode_ragged(self, z, frames, ws=None):
+        """z [B, latent_dim, T] rows holding left-aligned clips of `frames` [B] (ints or an int32 device tensor) latent frames -> audio
+        [B, 1, L']: row b up to the decoded length of frames[b] is `decode(z[b:b+1, :, :frames[b]])` bit for bit, the rest 0.  `ws`: a
+        `decode_workspace` at least this large (default: allocated here)."""
+        L.require_cuda(z)
+        if z.ndim != 3 or z.shape[1] != self.latent_dim:
+            raise RuntimeError(f"decode_ragged expects [B, {self.latent_dim}, T] latents (got {tuple(z.shape)})")
+        B, _, T = z.shape
+        zz = z.float().contiguous()
+        fr = torch.as_tensor(frames, dtype=torch.int32).to(z.device).contiguous()
+        if fr.shape != (B,):
+            raise RuntimeError(f"decode_ragged: {B} rows but frames has shape {tuple(fr.shape)}")
+        lib = L.load()
+        with self._lock, torch.cuda.device(z.device):
+            h = self.handle()
+            self._apply_precision(h)
+            Lo = lib.fd_ndac_decoded_length(h, T)
+            out = torch.empty(B, 1, Lo, dtype=torch.float32, device=z.device)
+            if ws is None:
+                ws = self.decode_workspace(B, T)
+            L.check(lib.fd_ndac_decode_ragged(h, L.ptr(zz), L.ptr(fr), B, T, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()))
+        return out
+
+    @torch.no_grad()
+    def decode_batch(self, zs, batch: int = 8):
+        """zs: a list of [latent_dim, T_i] latents -> a list of [1, L_i] waveforms in the caller's order, each `decode(z_i[None])[0]` bit
+        for bit; run as ragged calls of up to `batch` clips of neighbouring lengths."""
+        if int(batch) < 1:
+            raise ValueError(f"decode_batch: batch must be >= 1 (got {batch})")
+        for z in zs:
+            if z.ndim != 2 or z.shape[0] != self.latent_dim or z.shape[1] < 1:
+                raise RuntimeError(f"decode_batch expects [{self.latent_dim}, T >= 1] latents (got {tuple(z.shape)})")
+        order = sorted(range(len(zs)), key=lambda i: (zs[i].shape[1], i))
+        outs = [None] * len(zs)
+        lib = L.load()
+        for g in range(0, len(order), int(batch)):
+            idx = order[g:g + int(batch)]
+            T = zs[idx[-1]].shape[1]
+            rows = torch.zeros(len(idx), self.latent_dim, T, dtype=torch.float32, device=self.device)
+            for b, i in enumerate(idx):
+                rows[b, :, :zs[i].shape[1]] = zs[i]
+            y = self.decode_ragged(rows, [zs[i].shape[1] for i in idx])
+            for b, i in enumerate(idx):
+                outs[i] = y[b, :, :lib.fd_ndac_decoded_length(self.handle(), zs[i].shape[1])].clone()
+        return outs
+
+    def decode_long(self, codes, window_frames: int = 1024, rows_per_call: int = 4):
+        """`decode(quantizer.from_codes(codes)[0])` bit for bit in fixed memory: see `ndac_stream.decode_long`."""
+        return ndac_stream.decode_long(self, codes, window_frames, rows_per_call)
 
     def forward(self, audio_data, sample_rate=None, n_quantizers: Optional[int] = None):
         """dac.DAC.forward (inference part): preprocess -> encode -> decode, trimmed to the input length."""

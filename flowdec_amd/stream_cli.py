@@ -11,7 +11,16 @@ xfade / 2 further samples have arrived, plus one row's compute time.
 --in-rate / --out-rate (default: the model's rate) resample the stream on the device on its way in and out (flowdec_amd.resample:
 torchaudio's sinc resampler at lowpass_filter_width 64, stateful, independent of the cut into blocks): the float32 output is then
 resample_device(enhance_long(resample_device(input, IN, model rate)), model rate, OUT) bit for bit.  Each resampler adds width + o
-samples of delay at its own input rate; the line on stderr reports the three delays."""
+samples of delay at its own input rate; the line on stderr reports the three delays.
+
+    python -m flowdec_amd.stream_cli --codes --codec WEIGHTS.pth [--n-quantizers Q] [--decode-block-frames 8] --ckpt C ... --format f32le
+
+--codes: the input is a headerless stream of NDAC code indices instead of PCM -- little-endian int16, frame-major, Q values per frame
+(Q = --n-quantizers, default: all of the codec's codebooks); a pipe may cut a frame in two.  The frames go through
+`ndac_stream.DecodeStream` on the codec `DAC.load(WEIGHTS.pth)` and from there into the enhancer; the codec's sampling rate takes the
+place of --in-rate, and --format names the output only.  The float32 output equals this program fed the one-shot decoded PCM
+(`dac.decode(dac.quantizer.from_codes(codes)[0])`) as f32le, byte for byte.  The decoder adds (block_frames + halo_right - 1) * hop samples
+of delay at the codec's rate, reported on stderr with the others."""
 import argparse
 import sys
 from typing import List, Optional
@@ -20,6 +29,8 @@ import numpy as np
 import torch
 
 from .checkpoint import load_from_checkpoint
+from .ndac import DAC
+from .ndac_stream import DecodeStream
 from .stream import EnhanceStream
 
 FORMATS = {"s16le": np.dtype("<i2"), "f32le": np.dtype("<f4")}
@@ -53,6 +64,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--block-samples", type=int, default=4800, help="samples read per push")
     p.add_argument("--in-rate", type=int, default=None, help="sampling rate of the input in Hz (default: the model's rate)")
     p.add_argument("--out-rate", type=int, default=None, help="sampling rate of the output in Hz (default: the model's rate)")
+    p.add_argument("--codes", action="store_true", help="the input is int16 NDAC code indices (frame-major, Q per frame), decoded by --codec")
+    p.add_argument("--codec", type=str, default=None, help="NDAC weights.pth (DAC.load) that decodes the --codes stream")
+    p.add_argument("--n-quantizers", type=int, default=None, help="code indices per frame (default: all of the codec's codebooks)")
+    p.add_argument("--decode-block-frames", type=int, default=8, help="frames the streaming decoder emits at a time")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--ema", type=lambda s: str(s).lower() not in ("0", "false", "no"), default=True)
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
@@ -69,7 +84,40 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     for name in ("in_rate", "out_rate"):
         if getattr(args, name) is not None and getattr(args, name) < 1:
             p.error(f"--{name.replace('_', '-')} must be >= 1")
+    if args.codes and not args.codec:
+        p.error("--codes needs --codec WEIGHTS.pth (the NDAC codec that decodes the stream)")
+    if args.codec and not args.codes:
+        p.error("--codec is the decoder of a --codes stream; without --codes the input is PCM")
+    if args.n_quantizers is not None and not args.codes:
+        p.error("--n-quantizers belongs to --codes")
+    if args.n_quantizers is not None and args.n_quantizers < 1:
+        p.error("--n-quantizers must be >= 1")
+    if args.decode_block_frames < 1:
+        p.error("--decode-block-frames must be >= 1")
     return args
+
+
+class CodeFrames:
+    """Bytes of a --codes stream -> whole frames.  `feed(buf)` returns the frames the bytes so far complete as an int64 array [nq, n]
+    (possibly n = 0) and carries a cut frame over to the next call; a code outside [0, codebook_size) goes to `error` (the parser's:
+    exits) with the index of its frame in the stream."""
+
+    def __init__(self, nq: int, codebook_size: int, error):
+        self.nq, self.codebook_size, self.error = int(nq), int(codebook_size), error
+        self.rest, self.frames = b"", 0
+
+    def feed(self, buf: bytes) -> np.ndarray:
+        buf = self.rest + buf
+        k = len(buf) // (2 * self.nq) * (2 * self.nq)
+        buf, self.rest = buf[:k], buf[k:]
+        a = np.frombuffer(buf, dtype="<i2").astype(np.int64).reshape(-1, self.nq)
+        bad = np.nonzero(((a < 0) | (a >= self.codebook_size)).any(axis=1))[0]
+        if bad.size:
+            f = int(bad[0])
+            self.error(f"--codes: frame {self.frames + f} holds the code {int(a[f][(a[f] < 0) | (a[f] >= self.codebook_size)][0])}, outside "
+                       f"[0, {self.codebook_size})")
+        self.frames += a.shape[0]
+        return np.ascontiguousarray(a.T)
 
 
 def encode(x: torch.Tensor, fmt: str) -> bytes:
@@ -85,6 +133,19 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
     args = parse_args(argv)
     if model is None:
         model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model="flow")
+    dec = split = None
+    if args.codes:
+        error = build_parser().error
+        dac = DAC.load(args.codec).to(model.device)
+        nq = dac.n_codebooks if args.n_quantizers is None else args.n_quantizers
+        if nq > dac.n_codebooks:
+            error(f"--n-quantizers {nq}: the codec has {dac.n_codebooks} codebooks")
+        if args.in_rate is not None and args.in_rate != dac.sample_rate:
+            error(f"--in-rate {args.in_rate}: a --codes stream decodes to the codec's rate, {dac.sample_rate} Hz")
+        if dac.sample_rate != model.sampling_rate:
+            args.in_rate = int(dac.sample_rate)
+        dec = DecodeStream(dac, n_quantizers=nq, block_frames=args.decode_block_frames)
+        split = CodeFrames(nq, dac.codebook_size, error)
     st = EnhanceStream(model, seed=args.seed, N=args.N, solver=args.solver, row_frames=args.row_frames, halo_frames=args.halo_frames,
                        normfac=args.normfac, in_rate=args.in_rate, out_rate=args.out_rate)
     dt = FORMATS[args.format]
@@ -92,12 +153,23 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
     fout = sys.stdout.buffer if args.out == "-" else open(args.out, "wb")
     written = 0
     try:
-        want = args.block_samples * dt.itemsize
+        want = args.block_samples * (2 if split else dt.itemsize)
         rest = b""
         while True:
             buf = fin.read(want)
             if not buf:
                 break
+            if split:          # code frames -> decoded PCM -> the enhancer
+                frames = split.feed(buf)
+                x = dec.push(torch.from_numpy(frames)) if frames.shape[1] else None
+                if x is None or not x.numel():
+                    continue
+                y = st.push(x)
+                if y.numel():
+                    fout.write(encode(y, args.format))
+                    fout.flush()
+                    written += y.numel()
+                continue
             buf = rest + buf
             k = len(buf) // dt.itemsize * dt.itemsize            # a pipe may cut a sample in two
             buf, rest = buf[:k], buf[k:]
@@ -107,6 +179,14 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
             if y.numel():
                 fout.write(encode(y, args.format))
                 fout.flush()
+                written += y.numel()
+        if split:
+            if split.rest:
+                print(f"stream_cli: {len(split.rest)} trailing bytes are not a whole frame of {split.nq} codes: dropped", file=sys.stderr)
+            x = dec.flush()
+            if x.numel():
+                y = st.push(x)
+                fout.write(encode(y, args.format))
                 written += y.numel()
         y = st.flush()
         fout.write(encode(y, args.format))
@@ -121,7 +201,8 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
     d_in, d_pool, d_out = st.delays
     print(f"stream_cli: {written} samples written (delay {st.delay_samples} samples; resampler in {d_in} samples at {st.in_rate} Hz = "
           f"{1e3 * d_in / st.in_rate:.2f} ms, pool {d_pool} samples at {sr} Hz = {1e3 * d_pool / sr:.2f} ms, resampler out {d_out} samples at {sr} Hz = "
-          f"{1e3 * d_out / sr:.2f} ms)", file=sys.stderr)
+          f"{1e3 * d_out / sr:.2f} ms" + (f", decoder {dec.delay_samples} samples at {dec.dac.sample_rate} Hz = "
+                                           f"{1e3 * dec.delay_samples / dec.dac.sample_rate:.2f} ms" if dec else "") + ")", file=sys.stderr)
     return written
 
 

@@ -806,6 +806,19 @@ int fd_rvq_encode(fd_ndac* m, const float* z, int B, int T, int n_quantizers, fl
 int fd_rvq_from_codes(fd_ndac* m, const int* codes, int B, int n_quantizers, int T, float* z_q, void* stream);
 /* dac.DAC.decode: z [B][latent][T] -> audio [B][fd_ndac_decoded_length(T)] in (-1, 1) */
 int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream);
+/* Decode of a RAGGED batch: z [B][latent][T], frames = DEVICE int32 [B] (like the lengths of fd_enhance_ragged), clip b = the first
+ * frames[b] frames of its row, 1 <= frames[b] <= T (checked on the host before anything is launched: one B-int copy and a stream
+ * synchronisation; FD_EINVAL leaves audio untouched).  audio [B][fd_ndac_decoded_length(T)]: samples [0, fd_ndac_decoded_length(
+ * frames[b])) of row b are BIT-IDENTICAL to fd_ndac_decode of that clip alone (B = 1, T = frames[b]) in the same precision mode, the
+ * rest of the row is 0.  Every kernel bounds its input reads by the clip's own length at that layer (an affine function of
+ * frames[b], odd rates included), so what lies behind a clip in the workspace is never read as data.  Workspace: as fd_ndac_decode. */
+int fd_ndac_decode_ragged(fd_ndac* m, const float* z, const int* frames, int B, int T, float* audio, void* ws, size_t ws_bytes,
+                          void* stream);
+/* Latent frames before (left) and after (right) a frame that can influence that frame's hop output samples -- the receptive field
+ * of the decoder in frames, from the configuration alone (host only).  A window of frames with this much real context on both sides
+ * (or a true edge of the signal) decodes its interior to the bits of the one-shot decode (flowdec_amd/ndac_stream.py).
+ * FD_EINVAL, naming the rate, when a decoder rate is odd: the decoded length is then not frames * hop. */
+int fd_ndac_decode_halo(const fd_ndac* m, int* left, int* right);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics: the two metrics of the reference's evaluation (flowdec/eval/metrics.py) that need no outside model, over ragged
