@@ -210,6 +210,10 @@ SIGNATURES = {
     "fd_ndac_encode": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "fd_rvq_encode": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "fd_rvq_from_codes": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "fd_rvq_chain_supported": (c_int, [c_int, c_int]),
+    "fd_rvq_encode_chain": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "fd_ndac_encode_ragged": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "fd_ndac_encode_halo": (c_int, [_P, C.POINTER(c_int), C.POINTER(c_int)]),
     "fd_ndac_decode": (c_int, [_P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_ndac_decode_ragged": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_ndac_decode_halo": (c_int, [_P, C.POINTER(c_int), C.POINTER(c_int)]),

@@ -19,10 +19,13 @@
 //   convtr1d_kernel     transposed convolution as a gather: output n takes taps k = (n + p) mod s, + s, ... of inputs (n + p - k) / s
 //   rvq_step_kernel     one residual quantiser: in_proj with f64 accumulation, nearest neighbour with the float32 operation order the
 //                       oracle defines (code indices BIT-EXACT; ties -> lowest index), straight-through value, out_proj, residual update
+//   rvq_chain_kernel    the whole chain of quantisers in ONE launch: the residual tile stays in LDS, z_q in registers; the same phase
+//                       functions as rvq_step_kernel, the same bits (fd_rvq_encode_chain; the quantiser of fd_ndac_encode_ragged)
 //   rvq_from_codes_kernel   codes -> sum_i out_proj_i(codebook_i[code])
 // Ragged decode (fd_ndac_decode_ragged): every convolution kernel reads input positions at and behind T as the zero padding; under a frame
 // table (fd_ndac_lens) that bound is the CLIP's own length at the layer, so a clip in a batch of longer rows sees exactly the padding it
 // sees alone -- the same bits -- and nothing behind it is read as data.  No table (every dense call): the bound is T.
+// Ragged encode (fd_ndac_encode_ragged) is the same table on the way down: a clip of f frames is f * hop / (the strides so far) positions.
 #include <math.h>
 #include <string.h>
 
@@ -370,111 +373,227 @@ __global__ __launch_bounds__(256) void convtr1d_kernel(ConvTr1dArgs a) {
 
 // ---- residual vector quantiser -------------------------------------------------------------------------------------------
 constexpr int RT = 8;    // time steps per workgroup
+constexpr int NP = 256 / RT;       // codebook slices / output-channel lanes per time step
+static_assert(NP == 32, "the in_proj split below is 8 dims x 4 channel quarters");
+
+struct RvqQuant {         // one quantiser's parameters (device pointers)
+  const float* win; const float* bin;     // [cd][D], [cd]
+  const float* wout; const float* bout;   // [D][cd], [D]
+  const float* cb;        // [J][cd] raw codebook
+  const float* cbn;       // [J][cd] L2-normalised rows (host, the oracle's float32 operation order)
+  const float* c2;        // [J] sum of squares of the normalised rows
+};
 
 struct RvqArgs {
   float* residual;        // [B][D][T] in / out
   float* zq;              // [B][D][T] accumulated
   int* codes;             // [B][nq][T], this quantiser writes row q
   float* latents;         // [B][nq * cd][T] or null
-  const float* win; const float* bin;     // [cd][D], [cd]
-  const float* wout; const float* bout;   // [D][cd], [D]
-  const float* cb;        // [J][cd] raw codebook
-  const float* cbn;       // [J][cd] L2-normalised rows (host, the oracle's float32 operation order)
-  const float* c2;        // [J] sum of squares of the normalised rows
+  RvqQuant p;
+  const int* frames;      // device int32 [B] or null: clip b is its row's first frames[b] steps; steps behind it are never read and get code 0 / latents 0
   int B, D, T, J, cd, q, nq;
 };
 
-// The float32 operation order of oracle/ndac_oracle.py `vq_nearest` / `l2_normalize_rows_f32` (no fused multiply-add anywhere).
-// 8 time steps per workgroup (a 2 s clip has 150 frames: small tiles are what fills the chip); the 256 threads are
+struct RvqTile {                     // the small per-tile arrays of one quantiser step (LDS)
+  double pz[4][RT][8];
+  float ze[RT][9];                   // in_proj output per time step (cd <= 8: fd_ndac_create), +1 pad
+  float en[RT][9];
+  float e2s[RT];
+  float bestd[NP][RT];
+  int besti[NP][RT];
+  float stv[RT][9];                  // straight-through value z_e + (c - z_e)
+  int code[RT];
+};
+
+constexpr int RVQ_PF = 16;           // operand loads in flight per thread in the in_proj sum (a channel quarter of D = 64 is 16 long)
+
+// One slice [j0, j1) of the normalised codebook scanned in ascending order with a strict '<' (ties -> lowest index): dot product
+// sequential over the dimensions, dist = (e2 - 2 dot) + c2[j].  CD: the codebook dimension at compile time, 0 = cd at run time.
+template <int CD>
+__device__ __forceinline__ void rvq_scan_slice(const float* e, float e2, const float* cbn, const float* c2, int cd, int j0, int j1, float& bd, int& bi) {
+#pragma clang fp contract(off)
+  const int n = CD ? CD : cd;
+#pragma unroll 4
+  for (int j = j0; j < j1; ++j) {
+    const float* c = cbn + (size_t)j * n;
+    float dot = 0.f;
+#pragma unroll
+    for (int d = 0; d < n; ++d) dot = dot + e[d] * c[d];
+    const float dist = (e2 - 2.0f * dot) + c2[j];
+    if (dist < bd) { bd = dist; bi = j; }
+  }
+}
+
+// Phases (1)-(3) of one quantiser on one tile of 8 time steps, stated once for rvq_step_kernel and rvq_chain_kernel: the float32 /
+// float64 operation order of oracle/ndac_oracle.py `pointwise_f64` / `vq_nearest` / `l2_normalize_rows_f32` (no fused multiply-add
+// anywhere).  The 256 threads (tt = tid % 8, part = tid / 8) are
 //   (1) 8 steps x 8 codebook dims x 4 quarters of the latent channels (f64 partial sums, combined in a fixed order),
 //   (3) 8 steps x 32 slices of the codebook, each scanned in ascending order with a strict '<', slices merged in ascending order
-//       (ties -> lowest index), (4) 8 steps x 32 output-channel lanes.
-__global__ __launch_bounds__(256) void rvq_step_kernel(RvqArgs a) {
+//       (ties -> lowest index).
+// rp: this thread's time step of the residual, channel c at rp[c * rstride] (global memory, stride T / the chain's LDS tile, stride RT).
+// tv: the step holds data (else z_e = 0 and nothing of it is written by the caller).  Every thread of the workgroup calls it; on return
+// (behind a barrier) s.ze, s.stv and s.code hold the step's in_proj output, straight-through value and code index.
+__device__ __forceinline__ void rvq_tile_quantise(RvqTile& s, const RvqQuant& p, const float* rp, size_t rstride, bool tv, int D, int J, int cd, int tt,
+                                                  int part) {
 #pragma clang fp contract(off)
-  constexpr int NP = 256 / RT;       // codebook slices / output-channel lanes per time step
-  static_assert(NP == 32, "the in_proj split below is 8 dims x 4 channel quarters");
-  __shared__ double pz[4][RT][8];
-  __shared__ float ze[RT][9];        // in_proj output per time step (cd <= 8: fd_ndac_create), +1 pad
-  __shared__ float en[RT][9];
-  __shared__ float e2s[RT];
-  __shared__ float bestd[NP][RT];
-  __shared__ int besti[NP][RT];
-  __shared__ float stv[RT][9];       // straight-through value z_e + (c - z_e)
-  const int b = blockIdx.y, t0 = blockIdx.x * RT, tid = threadIdx.x;
-  const int tt = tid % RT, part = tid / RT;
-  const int t = t0 + tt;
-  const bool tv = t < a.T;
   // (1) z_e[d] = sum_c win[d][c] * residual[c] + bin[d]: exact f32 products accumulated in f64, rounded to f32 once
   {
     const int d = part & 7, qd = part >> 3;   // NP = 32: 8 dims x 4 channel quarters
     double acc = 0.0;
-    if (tv && d < a.cd) {
-      const int c0 = (int)((long long)a.D * qd / 4), c1 = (int)((long long)a.D * (qd + 1) / 4);
-      const float* rp = a.residual + (size_t)b * a.D * a.T + t;
-      const float* wp = a.win + (size_t)d * a.D;
-      for (int c = c0; c < c1; ++c) acc += (double)wp[c] * (double)rp[(size_t)c * a.T];
+    if (tv && d < cd) {
+      const int c0 = (int)((long long)D * qd / 4), c1 = (int)((long long)D * (qd + 1) / 4);
+      const float* wp = p.win + (size_t)d * D;
+      int c = c0;
+      for (; c + RVQ_PF <= c1; c += RVQ_PF) {   // RVQ_PF loads of each operand in flight, then the same sequential sum: the loop is latency-bound
+        float w[RVQ_PF], r[RVQ_PF];
+#pragma unroll
+        for (int i = 0; i < RVQ_PF; ++i) { w[i] = wp[c + i]; r[i] = rp[(size_t)(c + i) * rstride]; }
+#pragma unroll
+        for (int i = 0; i < RVQ_PF; ++i) acc += (double)w[i] * (double)r[i];
+      }
+      for (; c < c1; ++c) acc += (double)wp[c] * (double)rp[(size_t)c * rstride];
     }
-    pz[qd][tt][d] = acc;
+    s.pz[qd][tt][d] = acc;
   }
   __syncthreads();
   if (part < 8) {
     const int d = part;
-    ze[tt][d] = d < a.cd && tv ? (float)((((pz[0][tt][d] + pz[1][tt][d]) + pz[2][tt][d]) + pz[3][tt][d]) + (double)a.bin[d]) : 0.f;
+    s.ze[tt][d] = d < cd && tv ? (float)((((s.pz[0][tt][d] + s.pz[1][tt][d]) + s.pz[2][tt][d]) + s.pz[3][tt][d]) + (double)p.bin[d]) : 0.f;
   }
   __syncthreads();
   // (2) normalise: s = sum x^2 (sequential), n = sqrt(s), x / max(n, 1e-12); e2 = sum en^2
   if (part == 0) {
-    float s = 0.f;
-    for (int d = 0; d < a.cd; ++d) s = s + ze[tt][d] * ze[tt][d];
-    const float n = fmaxf(sqrtf(s), 1e-12f);
+    float sq = 0.f;
+    for (int d = 0; d < cd; ++d) sq = sq + s.ze[tt][d] * s.ze[tt][d];
+    const float n = fmaxf(sqrtf(sq), 1e-12f);
     float e2 = 0.f;
-    for (int d = 0; d < a.cd; ++d) {
-      const float v = ze[tt][d] / n;
-      en[tt][d] = v;
+    for (int d = 0; d < cd; ++d) {
+      const float v = s.ze[tt][d] / n;
+      s.en[tt][d] = v;
       e2 = e2 + v * v;
     }
-    e2s[tt] = e2;
+    s.e2s[tt] = e2;
   }
   __syncthreads();
   // (3) nearest neighbour
   {
     float e[8];
-    for (int d = 0; d < 8; ++d) e[d] = d < a.cd ? en[tt][d] : 0.f;
-    const float e2 = e2s[tt];
-    const int j0 = (int)((long long)a.J * part / NP), j1 = (int)((long long)a.J * (part + 1) / NP);
+    for (int d = 0; d < 8; ++d) e[d] = d < cd ? s.en[tt][d] : 0.f;
+    const float e2 = s.e2s[tt];
+    const int j0 = (int)((long long)J * part / NP), j1 = (int)((long long)J * (part + 1) / NP);
     float bd = INFINITY; int bi = j0;
-    for (int j = j0; j < j1; ++j) {
-      const float* c = a.cbn + (size_t)j * a.cd;
-      float dot = 0.f;
-      for (int d = 0; d < a.cd; ++d) dot = dot + e[d] * c[d];
-      const float dist = (e2 - 2.0f * dot) + a.c2[j];
-      if (dist < bd) { bd = dist; bi = j; }
-    }
-    bestd[part][tt] = bd; besti[part][tt] = bi;
+    if (cd == 8) rvq_scan_slice<8>(e, e2, p.cbn, p.c2, cd, j0, j1, bd, bi);   // DAC's codebook dimension: the row as two wide loads
+    else rvq_scan_slice<0>(e, e2, p.cbn, p.c2, cd, j0, j1, bd, bi);
+    s.bestd[part][tt] = bd; s.besti[part][tt] = bi;
   }
   __syncthreads();
   if (part == 0) {
-    float bd = bestd[0][tt]; int bi = besti[0][tt];
-    for (int p = 1; p < NP; ++p)
-      if (bestd[p][tt] < bd) { bd = bestd[p][tt]; bi = besti[p][tt]; }
-    if (tv) a.codes[((size_t)b * a.nq + a.q) * a.T + t] = bi;
-    for (int d = 0; d < a.cd; ++d) {
-      const float z = ze[tt][d];
-      stv[tt][d] = z + (a.cb[(size_t)bi * a.cd + d] - z);     // z_e + (z_q - z_e).detach()
-      if (tv && a.latents) a.latents[((size_t)b * a.nq * a.cd + (size_t)a.q * a.cd + d) * a.T + t] = z;
+    float bd = s.bestd[0][tt]; int bi = s.besti[0][tt];
+    for (int q = 1; q < NP; ++q)
+      if (s.bestd[q][tt] < bd) { bd = s.bestd[q][tt]; bi = s.besti[q][tt]; }
+    s.code[tt] = bi;
+    for (int d = 0; d < cd; ++d) {
+      const float z = s.ze[tt][d];
+      s.stv[tt][d] = z + (p.cb[(size_t)bi * cd + d] - z);     // z_e + (z_q - z_e).detach()
     }
   }
   __syncthreads();
-  // (4) z_q_i[c] = sum_d wout[c][d] * st[d] + bout[c] (f64, rounded once);  zq += z_q_i;  residual -= z_q_i
+}
+
+// (4) z_q_i[c] = sum_d wout[c][d] * st[d] + bout[c] (f64, rounded once)
+__device__ __forceinline__ float rvq_out_proj(const RvqQuant& p, const float* st, int cd, int c) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  const float* wp = p.wout + (size_t)c * cd;
+  for (int d = 0; d < cd; ++d) acc += (double)wp[d] * (double)st[d];
+  return (float)(acc + (double)p.bout[c]);
+}
+
+// codes / latents of one step: the values where the step holds data, 0 behind a clip (tv false, t < T only under a frame table)
+__device__ __forceinline__ void rvq_write_step(const RvqTile& s, int* codes, float* latents, bool tv, int b, int t, int tt, int T, int cd, int q, int nq) {
+  if (t >= T) return;
+  codes[((size_t)b * nq + q) * T + t] = tv ? s.code[tt] : 0;
+  if (latents)
+    for (int d = 0; d < cd; ++d) latents[((size_t)b * nq * cd + (size_t)q * cd + d) * T + t] = tv ? s.ze[tt][d] : 0.f;
+}
+
+// One residual quantiser per launch, 8 time steps per workgroup (a 2 s clip has 150 frames: small tiles are what fills the chip);
+// (4) runs as 8 steps x 32 output-channel lanes: zq += z_q_i; residual -= z_q_i, both through global memory.
+__global__ __launch_bounds__(256) void rvq_step_kernel(RvqArgs a) {
+#pragma clang fp contract(off)
+  __shared__ RvqTile s;
+  const int b = blockIdx.y, t0 = blockIdx.x * RT, tid = threadIdx.x;
+  const int tt = tid % RT, part = tid / RT;
+  const int t = t0 + tt;
+  const bool tv = t < (a.frames ? a.frames[b] : a.T);
+  rvq_tile_quantise(s, a.p, a.residual + (size_t)b * a.D * a.T + t, (size_t)a.T, tv, a.D, a.J, a.cd, tt, part);
+  if (part == 0) rvq_write_step(s, a.codes, a.latents, tv, b, t, tt, a.T, a.cd, a.q, a.nq);
   if (tv) {
     for (int c = part; c < a.D; c += NP) {
-      double acc = 0.0;
-      const float* wp = a.wout + (size_t)c * a.cd;
-      for (int d = 0; d < a.cd; ++d) acc += (double)wp[d] * (double)stv[tt][d];
-      const float zi = (float)(acc + (double)a.bout[c]);
+      const float zi = rvq_out_proj(a.p, s.stv[tt], a.cd, c);
       const size_t o = ((size_t)b * a.D + c) * a.T + t;
       a.zq[o] = a.zq[o] + zi;
       a.residual[o] = a.residual[o] - zi;
+    }
+  }
+}
+
+// All n_quantizers quantisers in ONE launch, same tiling.  The [D][RT] residual tile is loaded once and lives in LDS across the
+// quantisers (never written back; z is read-only), a thread's z_q values (channels part, part + 32, ...: NI of them) accumulate in
+// registers from 0 in quantiser order and are stored once.  Same arithmetic per value as the chain of rvq_step_kernel launches (the
+// phases are the functions above): the same bits.  LDS: in (1) a wave reads ONE channel row of the tile per step -- 8 consecutive
+// words, each broadcast to the wave's 8 codebook dims -- and in (4) 64 consecutive words: conflict-free.
+// Under a frame table, steps at and behind frames[b] are not read; they get code 0, z_q 0, latents 0.
+struct RvqChainArgs {
+  const float* z; float* zq; int* codes; float* latents;
+  const RvqQuant* quant;  // [n_codebooks] (device)
+  const int* frames;
+  int B, D, T, J, cd, nq;
+};
+
+template <int NI>
+__global__ __launch_bounds__(256) void rvq_chain_kernel(RvqChainArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ float rs[];      // [D][RT] residual tile
+  __shared__ RvqTile s;
+  const int b = blockIdx.y, t0 = blockIdx.x * RT, tid = threadIdx.x;
+  const int tt = tid % RT, part = tid / RT;
+  const int t = t0 + tt;
+  const bool tv = t < (a.frames ? a.frames[b] : a.T);
+  float zq[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = part + NP * i;
+    zq[i] = 0.f;
+    if (c < a.D) rs[c * RT + tt] = tv ? a.z[((size_t)b * a.D + c) * a.T + t] : 0.f;
+  }
+  __syncthreads();
+  if (t0 < (a.frames ? a.frames[b] : a.T)) {      // (uniform per workgroup; a tile wholly behind its clip only writes the zeros below)
+    for (int q = 0; q < a.nq; ++q) {
+      const RvqQuant p = a.quant[q];
+      rvq_tile_quantise(s, p, rs + tt, (size_t)RT, tv, a.D, a.J, a.cd, tt, part);
+      if (part == 0) rvq_write_step(s, a.codes, a.latents, tv, b, t, tt, a.T, a.cd, q, a.nq);
+      if (tv) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const int c = part + NP * i;
+          if (c < a.D) {
+            const float zi = rvq_out_proj(p, s.stv[tt], a.cd, c);
+            zq[i] = zq[i] + zi;
+            rs[c * RT + tt] = rs[c * RT + tt] - zi;
+          }
+        }
+      }
+      __syncthreads();               // the tile's next in_proj reads what (4) wrote; s is reused
+    }
+  } else if (part == 0) {
+    for (int q = 0; q < a.nq; ++q) rvq_write_step(s, a.codes, a.latents, false, b, t, tt, a.T, a.cd, q, a.nq);
+  }
+  if (t < a.T) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int c = part + NP * i;
+      if (c < a.D) a.zq[((size_t)b * a.D + c) * a.T + t] = zq[i];
     }
   }
 }
@@ -572,7 +691,9 @@ struct fd_ndac {
   // per-codebook device pointer tables for rvq_from_codes_kernel
   const float** d_wout = nullptr; const float** d_bout = nullptr; const float** d_cb = nullptr;
   std::vector<float*> cbn, c2;
-  std::map<std::string, void*> packed;   // "<layer>.weight" -> split-bf16 A-operand copy for ndac_mfma.hip (the layers it supports)
+  std::vector<RvqQuant> quant;           // per codebook: the pointers the RVQ kernels take
+  const RvqQuant* d_quant = nullptr;     // the same table on the device (rvq_chain_kernel walks it)
+  std::map<std::string, void*> packed;  // "<layer>.weight" -> split-bf16 A-operand copy for ndac_mfma.hip (the layers it supports)
   int precision = FD_NDAC_MFMA_DECODER;
   bool finalized = false;
 };
@@ -678,16 +799,45 @@ int check_ready(const fd_ndac* m, const char* who) {
   return FD_OK;
 }
 
-int rvq_run(fd_ndac* m, float* residual /* in: z, destroyed */, int B, int T, int nq, float* zq, int* codes, float* latents, hipStream_t st) {
+// The chain of rvq_step_kernel launches.  frames (device int32 [B]) or nullptr: under a table a step at or behind frames[b] is never read
+// and gets code 0, z_q 0, latents 0.
+int rvq_run(fd_ndac* m, float* residual /* in: z, destroyed */, const int* frames, int B, int T, int nq, float* zq, int* codes, float* latents,
+            hipStream_t st) {
   const fd_ndac_config& c = m->cfg;
   FD_HIP(hipMemsetAsync(zq, 0, sizeof(float) * (size_t)B * c.latent_dim * T, st));
   for (int q = 0; q < nq; ++q) {
-    const std::string n = "quantizer.quantizers." + std::to_string(q);
-    RvqArgs a{residual, zq, codes, latents, m->dev.at(n + ".in_proj.weight"), m->dev.at(n + ".in_proj.bias"), m->dev.at(n + ".out_proj.weight"),
-              m->dev.at(n + ".out_proj.bias"), m->dev.at(n + ".codebook.weight"), m->cbn[q], m->c2[q], B, c.latent_dim, T, c.codebook_size, c.codebook_dim, q, nq};
+    RvqArgs a{residual, zq, codes, latents, m->quant[q], frames, B, c.latent_dim, T, c.codebook_size, c.codebook_dim, q, nq};
     hipLaunchKernelGGL(rvq_step_kernel, dim3(fd_cdiv(T, RT), B), dim3(256), 0, st, a);
   }
   FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+constexpr int RVQ_CHAIN_MAX_NI = 32;   // z_q values a thread of rvq_chain_kernel keeps in registers: channels part + 32 i
+
+// One launch for the whole chain (rvq_chain_kernel); the caller has checked fd_rvq_chain_supported.  z is read-only.
+int rvq_run_chain(fd_ndac* m, const float* z, const int* frames, int B, int T, int nq, float* zq, int* codes, float* latents, hipStream_t st) {
+  const fd_ndac_config& c = m->cfg;
+  RvqChainArgs a{z, zq, codes, latents, m->d_quant, frames, B, c.latent_dim, T, c.codebook_size, c.codebook_dim, nq};
+  const dim3 grid(fd_cdiv(T, RT), B);
+  const size_t lds = sizeof(float) * (size_t)c.latent_dim * RT;
+  const int ni = fd_cdiv(c.latent_dim, NP);
+  if (ni <= 4) hipLaunchKernelGGL(rvq_chain_kernel<4>, grid, dim3(256), lds, st, a);
+  else if (ni <= 8) hipLaunchKernelGGL(rvq_chain_kernel<8>, grid, dim3(256), lds, st, a);
+  else if (ni <= 16) hipLaunchKernelGGL(rvq_chain_kernel<16>, grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL(rvq_chain_kernel<RVQ_CHAIN_MAX_NI>, grid, dim3(256), lds, st, a);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+int resolve_nq(const fd_ndac* m, int n_quantizers) { return n_quantizers <= 0 || n_quantizers > m->cfg.n_codebooks ? m->cfg.n_codebooks : n_quantizers; }
+
+// The frame table of a ragged call, checked on the host before anything is launched (B ints: one small copy and a synchronisation).
+int check_frames(const char* who, const int* frames, int B, int T, hipStream_t st) {
+  std::vector<int> h(B);
+  FD_HIP(hipMemcpyAsync(h.data(), frames, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+  FD_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) FD_REQUIRE(h[b] >= 1 && h[b] <= T, "%s: frames[%d] = %d is outside [1, %d]", who, b, h[b], T);
   return FD_OK;
 }
 
@@ -836,6 +986,8 @@ extern "C" int fd_ndac_finalize(fd_ndac* m, void* stream) {
     FD_TRY(upload(cn, &dcn)); FD_TRY(upload(c2, &dc2));
     FD_HIP(hipStreamSynchronize(st));   // cn / c2 are locals
     m->cbn.push_back(dcn); m->c2.push_back(dc2);
+    m->quant.push_back(RvqQuant{m->dev.at(n + ".in_proj.weight"), m->dev.at(n + ".in_proj.bias"), m->dev.at(n + ".out_proj.weight"), m->dev.at(n + ".out_proj.bias"),
+                                m->dev.at(n + ".codebook.weight"), dcn, dc2});
     hw.push_back(m->dev.at(n + ".out_proj.weight")); hb.push_back(m->dev.at(n + ".out_proj.bias")); hc.push_back(m->dev.at(n + ".codebook.weight"));
   }
   auto upload_ptrs = [&](const std::vector<const float*>& h, const float*** out) -> int {
@@ -847,6 +999,13 @@ extern "C" int fd_ndac_finalize(fd_ndac* m, void* stream) {
     return FD_OK;
   };
   FD_TRY(upload_ptrs(hw, &m->d_wout)); FD_TRY(upload_ptrs(hb, &m->d_bout)); FD_TRY(upload_ptrs(hc, &m->d_cb));
+  {
+    RvqQuant* dq = nullptr;
+    FD_HIP(hipMalloc(&dq, sizeof(RvqQuant) * m->quant.size()));
+    m->allocs.push_back((void*)dq);
+    FD_HIP(hipMemcpy((void*)dq, m->quant.data(), sizeof(RvqQuant) * m->quant.size(), hipMemcpyHostToDevice));
+    m->d_quant = dq;
+  }
   FD_HIP(hipStreamSynchronize(st));
   m->host.clear();
   m->finalized = true;
@@ -883,12 +1042,27 @@ extern "C" int fd_rvq_encode(fd_ndac* m, const float* z, int B, int T, int n_qua
                              void* stream) {
   FD_TRY(check_ready(m, "fd_rvq_encode"));
   FD_REQUIRE(z && z_q && codes && ws && B > 0 && T > 0, "fd_rvq_encode: bad arguments");
-  const int nq = n_quantizers <= 0 || n_quantizers > m->cfg.n_codebooks ? m->cfg.n_codebooks : n_quantizers;
+  const int nq = resolve_nq(m, n_quantizers);
   const size_t need = sizeof(float) * (size_t)B * m->cfg.latent_dim * T;
   if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_rvq_encode: workspace %zu < required %zu bytes", ws_bytes, need);
   hipStream_t st = fd_stream(stream);
   FD_HIP(hipMemcpyAsync(ws, z, need, hipMemcpyDeviceToDevice, st));   // the residual chain works in place on a copy
-  return rvq_run(m, (float*)ws, B, T, nq, z_q, codes, latents, st);
+  return rvq_run(m, (float*)ws, nullptr, B, T, nq, z_q, codes, latents, st);
+}
+
+extern "C" int fd_rvq_chain_supported(int D, int cd) {   // host only: the [D][8] float32 tile beside the small arrays within LDS, D / 32 z_q registers per thread
+  return D >= 1 && cd >= 1 && cd <= 8 && fd_cdiv(D, NP) <= RVQ_CHAIN_MAX_NI && sizeof(float) * (size_t)D * RT + sizeof(RvqTile) <= 64 * 1024;
+}
+
+extern "C" int fd_rvq_encode_chain(fd_ndac* m, const float* z, const int* frames, int B, int T, int n_quantizers, float* z_q, int* codes, float* latents,
+                                   void* stream) {
+  FD_TRY(check_ready(m, "fd_rvq_encode_chain"));
+  FD_REQUIRE(z && z_q && codes && B > 0 && T > 0, "fd_rvq_encode_chain: bad arguments");
+  FD_REQUIRE(fd_rvq_chain_supported(m->cfg.latent_dim, m->cfg.codebook_dim), "fd_rvq_encode_chain: latent_dim %d is beyond the one-launch kernel (at most %d)",
+             m->cfg.latent_dim, NP * RVQ_CHAIN_MAX_NI);
+  hipStream_t st = fd_stream(stream);
+  if (frames) FD_TRY(check_frames("fd_rvq_encode_chain", frames, B, T, st));
+  return rvq_run_chain(m, z, frames, B, T, resolve_nq(m, n_quantizers), z_q, codes, latents, st);
 }
 
 extern "C" int fd_rvq_from_codes(fd_ndac* m, const int* codes, int B, int n_quantizers, int T, float* z_q, void* stream) {
@@ -901,19 +1075,35 @@ extern "C" int fd_rvq_from_codes(fd_ndac* m, const int* codes, int B, int n_quan
   return FD_OK;
 }
 
-extern "C" int fd_ndac_encode(fd_ndac* m, const float* x, int B, int L, int n_quantizers, float* z_q, int* codes, float* latents, void* ws,
-                              size_t ws_bytes, void* stream) {
-  FD_TRY(check_ready(m, "fd_ndac_encode"));
-  FD_REQUIRE(x && z_q && codes && ws && B > 0 && L > 0, "fd_ndac_encode: bad arguments");
-  FD_REQUIRE(L % m->hop == 0, "fd_ndac_encode: pad the waveform to a multiple of the hop length %d first (DAC.preprocess); got %d samples", m->hop, L);
+namespace {
+
+// Frame tables and windows count in whole frames: n hops of samples must be n frames, and n hops / (the strides so far) positions at every
+// layer.  A strided convolution (K = 2 s, padding ceil(s / 2)) maps a length n s to n for every s >= 2, even or odd; a rate of 1 maps n to
+// n + 1 (a later stride can absorb that in the frame count, but not at the layers in between).
+int check_whole_frames(const fd_ndac* m, const char* who) {
+  for (int i = 0; i < m->cfg.n_encoder_rates; ++i)
+    FD_REQUIRE(m->cfg.encoder_rates[i] >= 2, "%s: encoder rate %d is a rate of 1 (a layer that makes n + 1 positions of n: no whole-frame arithmetic)", who, i);
+  for (int n = 1; n <= 3; ++n)
+    FD_REQUIRE(fd_ndac_latent_frames(m, n * m->hop) == n, "%s: the encoder rates give %d frames for %d hops of samples", who, fd_ndac_latent_frames(m, n * m->hop), n);
+  return FD_OK;
+}
+
+// The encoder walk and the quantiser of fd_ndac_encode / fd_ndac_encode_ragged.  frames (device int32 [B], validated by the caller) or
+// nullptr.  Every layer is computed over the whole row; under a frame table each kernel bounds its INPUT reads by the clip's own length at
+// that layer -- frames[b] * hop / (the strides so far): a strided convolution (K = 2 s, padding ceil(s / 2), s >= 2) maps a length n s to n
+// -- so what a layer wrote behind a clip is never read as data, and the clip sees exactly the zero padding it sees alone.  The quantiser
+// then runs as ONE launch under the table (rvq_chain_kernel; the step kernels where fd_rvq_chain_supported says no), as the chain of step
+// launches without one.
+int encode_walk(fd_ndac* m, const char* who, const float* x, const int* frames, int B, int L, int n_quantizers, float* z_q, int* codes, float* latents,
+                void* ws, size_t ws_bytes, hipStream_t st) {
   const size_t need = fd_ndac_workspace_bytes(m, B, L);
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_ndac_encode: workspace %zu < required %zu bytes", ws_bytes, need);
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
   const fd_ndac_config& c = m->cfg;
-  hipStream_t st = fd_stream(stream);
   const size_t slot = (need - 256) / 5;
   float* buf[5];
   for (int i = 0; i < 5; ++i) buf[i] = (float*)((char*)ws + i * slot);
   Run r{m, st, B, (m->precision & FD_NDAC_MFMA_ENCODER) != 0};
+  r.lens.frames = frames; r.lens.mul = m->hop;
   int T = L, d = c.encoder_dim;
   float *cur_raw = buf[0], *cur_act = buf[1], *nxt_raw = buf[2], *nxt_act = buf[3], *tmp = buf[4];
   auto alpha_of = [&](const std::string& n) { return r.P(n + ".alpha"); };
@@ -934,13 +1124,56 @@ extern "C" int fd_ndac_encode(fd_ndac* m, const float* x, int B, int L, int n_qu
     FD_TRY(r.conv(cur_act, p + ".block.4", nullptr, last ? nullptr : nxt_raw, nxt_act, an, d, T, 2 * d, 2 * s, s, ceil_half(s), 1));
     std::swap(cur_raw, nxt_raw); std::swap(cur_act, nxt_act);
     T = (T + 2 * ceil_half(s) - 2 * s) / s + 1;
+    r.lens.mul /= s;
     d *= 2;
   }
   const std::string last = "encoder.block." + std::to_string(c.n_encoder_rates + 2);
   FD_TRY(r.conv(cur_act, last, nullptr, nxt_raw, nullptr, nullptr, d, T, c.latent_dim, 3, 1, 1, 1));
   float* const zbuf = nxt_raw;
-  const int nq = n_quantizers <= 0 || n_quantizers > c.n_codebooks ? c.n_codebooks : n_quantizers;
-  return rvq_run(m, zbuf, B, T, nq, z_q, codes, latents, st);
+  const int nq = resolve_nq(m, n_quantizers);
+  if (frames && fd_rvq_chain_supported(c.latent_dim, c.codebook_dim)) return rvq_run_chain(m, zbuf, frames, B, T, nq, z_q, codes, latents, st);
+  return rvq_run(m, zbuf, frames, B, T, nq, z_q, codes, latents, st);
+}
+
+}  // namespace
+
+extern "C" int fd_ndac_encode(fd_ndac* m, const float* x, int B, int L, int n_quantizers, float* z_q, int* codes, float* latents, void* ws,
+                              size_t ws_bytes, void* stream) {
+  FD_TRY(check_ready(m, "fd_ndac_encode"));
+  FD_REQUIRE(x && z_q && codes && ws && B > 0 && L > 0, "fd_ndac_encode: bad arguments");
+  FD_REQUIRE(L % m->hop == 0, "fd_ndac_encode: pad the waveform to a multiple of the hop length %d first (DAC.preprocess); got %d samples", m->hop, L);
+  return encode_walk(m, "fd_ndac_encode", x, nullptr, B, L, n_quantizers, z_q, codes, latents, ws, ws_bytes, fd_stream(stream));
+}
+
+extern "C" int fd_ndac_encode_ragged(fd_ndac* m, const float* x, const int* frames, int B, int L, int n_quantizers, float* z_q, int* codes, float* latents,
+                                     void* ws, size_t ws_bytes, void* stream) {
+  FD_TRY(check_ready(m, "fd_ndac_encode_ragged"));
+  FD_REQUIRE(x && frames && z_q && codes && ws && B > 0 && L > 0, "fd_ndac_encode_ragged: bad arguments");
+  FD_REQUIRE(L % m->hop == 0, "fd_ndac_encode_ragged: the row length must be a multiple of the hop length %d; got %d samples", m->hop, L);
+  FD_TRY(check_whole_frames(m, "fd_ndac_encode_ragged"));
+  hipStream_t st = fd_stream(stream);
+  FD_TRY(check_frames("fd_ndac_encode_ragged", frames, B, L / m->hop, st));
+  return encode_walk(m, "fd_ndac_encode_ragged", x, frames, B, L, n_quantizers, z_q, codes, latents, ws, ws_bytes, st);
+}
+
+// Latent frames before / after a frame whose samples can reach that frame: the interval [t - 1, t + 1] of the final K = 3 convolution walked
+// backwards through the encoder (per block the strided convolution K = 2 s, p = ceil(s / 2): outputs [lo, hi] read inputs [lo s - p,
+// hi s - p + 2 s - 1]; then the three residual units +-3 d, d = 9, 3, 1; first conv +-3), in whole hops of samples around frame 0.
+extern "C" int fd_ndac_encode_halo(const fd_ndac* m, int* left, int* right) {
+  FD_REQUIRE(m && left && right, "fd_ndac_encode_halo: null pointer");
+  const fd_ndac_config& c = m->cfg;
+  FD_TRY(check_whole_frames(m, "fd_ndac_encode_halo"));
+  long long lo = -1, hi = 1;
+  for (int i = c.n_encoder_rates - 1; i >= 0; --i) {
+    const int s = c.encoder_rates[i], p = ceil_half(s);
+    lo = lo * s - p; hi = hi * s - p + 2 * s - 1;
+    lo -= 3 * (9 + 3 + 1); hi += 3 * (9 + 3 + 1);
+  }
+  lo -= 3; hi += 3;
+  const long long hop = m->hop;
+  *left = (int)((-lo + hop - 1) / hop);
+  *right = (int)((hi - (hop - 1) + hop - 1) / hop);
+  return FD_OK;
 }
 
 namespace {
@@ -1013,11 +1246,7 @@ extern "C" int fd_ndac_decode_ragged(fd_ndac* m, const float* z, const int* fram
   FD_TRY(check_ready(m, "fd_ndac_decode_ragged"));
   FD_REQUIRE(z && frames && audio && ws && B > 0 && T > 0, "fd_ndac_decode_ragged: bad arguments");
   hipStream_t st = fd_stream(stream);
-  std::vector<int> h(B);   // the bounds the kernels index with are checked before anything is launched (B ints: one small copy)
-  FD_HIP(hipMemcpyAsync(h.data(), frames, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
-  FD_HIP(hipStreamSynchronize(st));
-  for (int b = 0; b < B; ++b)
-    FD_REQUIRE(h[b] >= 1 && h[b] <= T, "fd_ndac_decode_ragged: frames[%d] = %d is outside [1, %d]", b, h[b], T);
+  FD_TRY(check_frames("fd_ndac_decode_ragged", frames, B, T, st));   // the bounds the kernels index with are checked before anything is launched
   return decode_walk(m, "fd_ndac_decode_ragged", z, frames, B, T, audio, ws, ws_bytes, st);
 }
 

@@ -14,7 +14,8 @@ The module tree (`encoder.block.*`, `quantizer.quantizers.*`, `decoder.model.*`)
 HIP library (there is no PyTorch / CPU compute path: a codec on the CPU raises).
 
 Beyond that surface: `decode_ragged` / `decode_batch` (clips of different lengths in one native call, each the bits of its own decode),
-`decode_long` (any length in fixed memory) and `decode_halo`; streaming sessions are `flowdec_amd.ndac_stream.DecodeStream`.
+`decode_long` (any length in fixed memory) and `decode_halo`; the same for encode (`encode_ragged` / `encode_batch` / `encode_long` /
+`encode_halo`); streaming sessions are `flowdec_amd.ndac_stream.DecodeStream` and `EncodeStream`.
 
 The arithmetic is third party and absent from /root/reference: restated from the published algorithm, PARITY UNPINNED
 (oracle/ndac_oracle.py lists the upstream definitions).
@@ -100,6 +101,30 @@ class ResidualVectorQuantize(nn.Module):
             ws = torch.empty(z.numel() * 4, dtype=torch.uint8, device=z.device)
             L.check(L.load().fd_rvq_encode(h, L.ptr(z), B, T, nq, L.ptr(zq), L.ptr(codes), L.ptr(lat), L.ptr(ws), ws.numel(), L.stream()))
         return zq, codes.long(), lat, None, None
+
+    def encode_chain(self, z, n_quantizers: Optional[int] = None, frames=None, latents: bool = True):
+        """`forward` as ONE launch (fd_rvq_encode_chain) -> (z_q, codes int64, latents or None), bit for bit `forward`'s.  `frames` [B]
+        (ints or an int32 device tensor): clip b is the first frames[b] frames of its row; what lies behind is never read and comes
+        back as code 0, z_q 0, latents 0."""
+        dac = self._owner[0]
+        L.require_cuda(z)
+        z = z.float().contiguous()
+        B, D, T = z.shape
+        if D != dac.latent_dim:
+            raise RuntimeError(f"encode_chain expects [B, {dac.latent_dim}, T] latents (got {tuple(z.shape)})")
+        nq = self.n_codebooks if n_quantizers is None else max(1, min(int(n_quantizers), self.n_codebooks))
+        fr = None
+        if frames is not None:
+            fr = torch.as_tensor(frames, dtype=torch.int32).to(z.device).contiguous()
+            if fr.shape != (B,):
+                raise RuntimeError(f"encode_chain: {B} rows but frames has shape {tuple(fr.shape)}")
+        with dac._lock, torch.cuda.device(z.device):
+            h = dac.handle()
+            zq = torch.empty_like(z)
+            codes = torch.empty(B, nq, T, dtype=torch.int32, device=z.device)
+            lat = torch.empty(B, nq * self.codebook_dim, T, dtype=torch.float32, device=z.device) if latents else None
+            L.check(L.load().fd_rvq_encode_chain(h, L.ptr(z), L.ptr(fr), B, T, nq, L.ptr(zq), L.ptr(codes), L.ptr(lat), L.stream()))
+        return zq, codes.long(), lat
 
     def from_codes(self, codes):
         """-> (z_q [B, D, T], z_p [B, nq * codebook_dim, T], codes)."""
@@ -384,6 +409,82 @@ class DAC(nn.Module):
     def decode_long(self, codes, window_frames: int = 1024, rows_per_call: int = 4):
         """`decode(quantizer.from_codes(codes)[0])` bit for bit in fixed memory: see `ndac_stream.decode_long`."""
         return ndac_stream.decode_long(self, codes, window_frames, rows_per_call)
+
+    # ---- ragged / long / streaming encode (flowdec_amd/ndac_stream.py) ------------------------------------------------------------
+    def encode_halo(self):
+        """-> (left, right): latent frames before / after a frame whose samples can reach that frame (fd_ndac_encode_halo).  Raises for
+        a rate of 1 (n hops of samples are then not n frames)."""
+        sig = self.encoder_rates
+        if getattr(self, "_enc_halo_sig", None) != sig:
+            left, right = C.c_int(), C.c_int()
+            with self._lock:
+                L.check(L.load().fd_ndac_encode_halo(self.handle(), C.byref(left), C.byref(right)))
+            self._enc_halo, self._enc_halo_sig = (left.value, right.value), sig
+        return self._enc_halo
+
+    def encode_workspace(self, B, L_samples):
+        """The workspace of a (ragged) encode of B rows of L_samples samples, as a uint8 device tensor."""
+        lib = L.load()
+        with self._lock, torch.cuda.device(self.device):
+            return torch.empty(lib.fd_ndac_workspace_bytes(self.handle(), int(B), int(L_samples)), dtype=torch.uint8, device=self.device)
+
+    @torch.no_grad()
+    def encode_ragged(self, audio_data, frames, n_quantizers: Optional[int] = None, ws=None):
+        """audio_data [B, 1, L] (L % hop_length == 0) rows holding left-aligned clips of `frames` [B] (ints or an int32 device tensor)
+        hops of samples -> (z [B, latent_dim, T], codes [B, nq, T] int64, latents [B, nq * codebook_dim, T]), T = L / hop_length: columns
+        t < frames[b] of row b are `encode(audio_data[b:b+1, :, :frames[b] * hop_length])` bit for bit, the rest 0.  `ws`: an
+        `encode_workspace` at least this large (default: allocated here)."""
+        L.require_cuda(audio_data)
+        if audio_data.ndim != 3 or audio_data.shape[1] != 1:
+            raise RuntimeError(f"encode_ragged expects [B, 1, L] audio (got {tuple(audio_data.shape)})")
+        B, _, Lw = audio_data.shape
+        if Lw % self.hop_length or Lw < self.hop_length:
+            raise RuntimeError(f"encode_ragged: length {Lw} is not a positive multiple of the hop length {self.hop_length}")
+        nq = self.n_codebooks if n_quantizers is None else max(1, min(int(n_quantizers), self.n_codebooks))
+        x = audio_data.float().contiguous()
+        fr = torch.as_tensor(frames, dtype=torch.int32).to(x.device).contiguous()
+        if fr.shape != (B,):
+            raise RuntimeError(f"encode_ragged: {B} rows but frames has shape {tuple(fr.shape)}")
+        lib = L.load()
+        with self._lock, torch.cuda.device(x.device):
+            h = self.handle()
+            self._apply_precision(h)
+            T = Lw // self.hop_length
+            z = torch.empty(B, self.latent_dim, T, dtype=torch.float32, device=x.device)
+            codes = torch.empty(B, nq, T, dtype=torch.int32, device=x.device)
+            lat = torch.empty(B, nq * self.codebook_dim, T, dtype=torch.float32, device=x.device)
+            if ws is None:
+                ws = self.encode_workspace(B, Lw)
+            L.check(lib.fd_ndac_encode_ragged(h, L.ptr(x), L.ptr(fr), B, Lw, nq, L.ptr(z), L.ptr(codes), L.ptr(lat), L.ptr(ws), ws.numel(), L.stream()))
+        return z, codes.long(), lat
+
+    @torch.no_grad()
+    def encode_batch(self, waves, n_quantizers: Optional[int] = None, batch: int = 8):
+        """waves: a list of [1, L_i] waveforms -> a list of [nq, T_i] int64 codes in the caller's order, each
+        `encode(preprocess(w_i[None]), n_quantizers)[1][0]` bit for bit; run as ragged calls of up to `batch` clips of neighbouring
+        lengths (each clip zero-padded to whole hops, as `preprocess` pads it)."""
+        if int(batch) < 1:
+            raise ValueError(f"encode_batch: batch must be >= 1 (got {batch})")
+        for w in waves:
+            if w.ndim != 2 or w.shape[0] != 1 or w.shape[1] < 1:
+                raise RuntimeError(f"encode_batch expects [1, L >= 1] waveforms (got {tuple(w.shape)})")
+        hop = self.hop_length
+        nfr = [-(-int(w.shape[1]) // hop) for w in waves]
+        order = sorted(range(len(waves)), key=lambda i: (nfr[i], i))
+        outs = [None] * len(waves)
+        for g in range(0, len(order), int(batch)):
+            idx = order[g:g + int(batch)]
+            rows = torch.zeros(len(idx), 1, nfr[idx[-1]] * hop, dtype=torch.float32, device=self.device)
+            for b, i in enumerate(idx):
+                rows[b, 0, :waves[i].shape[1]] = waves[i][0]
+            codes = self.encode_ragged(rows, [nfr[i] for i in idx], n_quantizers)[1]
+            for b, i in enumerate(idx):
+                outs[i] = codes[b, :, :nfr[i]].clone()
+        return outs
+
+    def encode_long(self, audio_data, n_quantizers: Optional[int] = None, window_frames: int = 1024, rows_per_call: int = 4):
+        """`encode(audio_data, n_quantizers)` bit for bit through one fixed workspace: see `ndac_stream.encode_long`."""
+        return ndac_stream.encode_long(self, audio_data, n_quantizers, window_frames, rows_per_call)
 
     def forward(self, audio_data, sample_rate=None, n_quantizers: Optional[int] = None):
         """dac.DAC.forward (inference part): preprocess -> encode -> decode, trimmed to the input length."""

@@ -10,6 +10,9 @@ section 2 "Streaming decode").
 `DecodePlanner` (host only) decides which frames can leave and which window decodes them; `DecodeStream` is the push / flush session
 on a `flowdec_amd.ndac.DAC`; `decode_long` runs the same jobs over a finished recording through one fixed workspace.  Cost: every
 emitted block of b frames decodes b + left + right frames, a recompute share of (b + left + right) / b.
+
+The other direction -- samples in, codes out, bit for bit `dac.encode(dac.preprocess(all samples))[1]` -- is `EncodeStream` and
+`encode_long` at the end of this file, on the same planner with `DAC.encode_halo()` (DESIGN.md section 2 "Streaming encode").
 """
 from typing import List, Optional, Tuple
 
@@ -213,3 +216,134 @@ def decode_long(dac, codes, window_frames: int = 1024, rows_per_call: int = 4) -
         for (_, _, e0, e1), y in zip(grp, ys):
             out[0, 0, e0 * hop:e1 * hop] = y
     return out
+
+
+# ---- streaming and long-form ENCODE: samples in, codes out -----------------------------------------------------------------------------
+# The same premise on the other side of the codec: every encoder layer has a finite receptive field and a per-output operation order that
+# does not depend on position (a strided convolution's phase is kept by a shift of whole frames, odd strides included), so a window of whole
+# hops with `DAC.encode_halo()` = (left, right) frames of real samples on both sides -- or a true edge of the signal -- reproduces the
+# one-shot encoder output on its interior frames bit for bit, and the quantiser works per frame.  DecodePlanner is reused unchanged with
+# frames received = complete hops of samples.
+
+
+def _run_encode_jobs(dac, windows: List[torch.Tensor], jobs: List[Job], nq: Optional[int], rows_per_call: int, ws=None):
+    """windows[i]: the (win_end - win_start) * hop device samples of jobs[i], 1-D -> per job (z [D, k], codes [nq, k], latents [nq * cd, k])
+    of its final frames.  `rows_per_call` jobs share one ragged encode; a lone job is a ragged call of one row (the same bits as the
+    plain encode of its window -- a ragged row IS its one-clip encode -- with the quantiser as one launch instead of one per codebook)."""
+    hop, outs = dac.hop_length, []
+    for g in range(0, len(jobs), rows_per_call):
+        grp, wx = jobs[g:g + rows_per_call], windows[g:g + rows_per_call]
+        rows = torch.zeros(len(grp), 1, max(x.numel() for x in wx), dtype=torch.float32, device=wx[0].device)
+        for b, x in enumerate(wx):
+            rows[b, 0, :x.numel()] = x
+        z, codes, lat = dac.encode_ragged(rows, [x.numel() // hop for x in wx], nq, ws=ws)
+        for b, (w0, _, e0, e1) in enumerate(grp):
+            outs.append((z[b, :, e0 - w0:e1 - w0], codes[b, :, e0 - w0:e1 - w0], lat[b, :, e0 - w0:e1 - w0]))
+    return outs
+
+
+class EncodeStream:
+    """One streaming encode session on a `DAC` (on the GPU).
+
+        st = EncodeStream(dac, n_quantizers=4, block_frames=8)
+        for chunk in chunks: out.append(st.push(chunk))     # float32 samples, 1-D, any length >= 0, host or device
+        out.append(st.flush())    # torch.cat(out, 1) == dac.encode(dac.preprocess(cat(chunks)[None, None]), 4)[1][0], bit for bit
+
+    however the samples were cut into pushes, for every block_frames >= 1 and in both precisions.  `push` returns the [nq, k] int64 codes
+    that became final (possibly k = 0); `flush` zero-pads a trailing partial frame, as `preprocess` does, and ends the session.  Only
+    codes leave: `from_codes(codes)` is not bitwise the encoder's straight-through z.  A push that finishes several blocks encodes them as
+    rows of ragged calls, `rows_per_call` at a time.  `delay_samples`: a frame's codes leave once that many further samples have arrived,
+    plus one window's compute time."""
+
+    def __init__(self, dac, n_quantizers: Optional[int] = None, block_frames: int = 8, rows_per_call: int = 4):
+        if int(rows_per_call) < 1:
+            raise ValueError(f"EncodeStream: rows_per_call must be >= 1 (got {rows_per_call})")
+        if n_quantizers is not None and not 1 <= int(n_quantizers) <= dac.n_codebooks:
+            raise RuntimeError(f"EncodeStream: {n_quantizers} code rows but the model has {dac.n_codebooks} codebooks")
+        self.dac, self.rows_per_call = dac, int(rows_per_call)
+        self.nq = dac.n_codebooks if n_quantizers is None else int(n_quantizers)
+        left, right = dac.encode_halo()
+        self.planner = DecodePlanner(left, right, block_frames)
+        self.hop = int(dac.hop_length)
+        self.delay_samples = self.planner.latency_frames * self.hop
+        self._x = torch.empty(0, dtype=torch.float32, device=dac.device)   # buffered samples, element 0 = absolute sample self._base
+        self._base = 0
+        self.samples_received = 0
+        self.windows_run = self.frames_encoded = 0
+
+    @property
+    def buffered_samples(self) -> int:
+        return int(self._x.numel())
+
+    def _run(self, jobs: List[Job]) -> torch.Tensor:
+        hop = self.hop
+        if jobs:
+            wx = [self._x[w0 * hop - self._base:w1 * hop - self._base] for w0, w1, _, _ in jobs]
+            outs = _run_encode_jobs(self.dac, wx, jobs, self.nq, self.rows_per_call)
+            self.windows_run += len(jobs)
+            self.frames_encoded += sum(w1 - w0 for w0, w1, _, _ in jobs)
+            y = torch.cat([o[1] for o in outs], dim=1)
+        else:
+            y = torch.empty(self.nq, 0, dtype=torch.int64, device=self.dac.device)
+        keep = self.planner.keep_from * hop          # only the samples the planner can still ask for stay
+        if keep > self._base:
+            self._x = self._x[keep - self._base:].clone()
+            self._base = keep
+        return y
+
+    def push(self, samples) -> torch.Tensor:
+        """-> the [nq, k] int64 codes that became final (on the codec's device; possibly k = 0)."""
+        if self.planner.closed:
+            raise RuntimeError("EncodeStream: push after flush")
+        x = torch.as_tensor(samples)
+        if x.ndim != 1 or x.dtype != torch.float32:
+            raise TypeError(f"EncodeStream.push: samples must be 1-D float32 (got {x.dtype}, shape {tuple(x.shape)})")
+        self._x = torch.cat([self._x, x.to(self.dac.device)])
+        self.samples_received += int(x.numel())
+        return self._run(self.planner.push(self.samples_received // self.hop - self.planner.received))
+
+    def flush(self) -> torch.Tensor:
+        """-> the codes of the rest of the stream; ends the session."""
+        if self.planner.closed:
+            raise RuntimeError("EncodeStream: flush after flush")
+        jobs, part = [], self.samples_received % self.hop
+        if part:                                      # the trailing partial frame, zero-padded as DAC.preprocess pads it
+            self._x = torch.cat([self._x, torch.zeros(self.hop - part, dtype=torch.float32, device=self.dac.device)])
+            jobs = self.planner.push(1)
+        y = self._run(jobs + self.planner.flush())
+        self._x = self._x[:0]
+        return y
+
+
+def encode_long(dac, audio, n_quantizers: Optional[int] = None, window_frames: int = 1024, rows_per_call: int = 4):
+    """audio [1, 1, L] (L % hop == 0: `preprocess` pads) -> (z, codes, latents, None, None), bit for bit `dac.encode(audio, n_quantizers)`,
+    through windows of at most `window_frames` frames, `rows_per_call` of them per ragged call, in ONE workspace sized for (rows_per_call,
+    window_frames * hop) whatever L.  A recording that fits one window is one plain encode call."""
+    if not isinstance(audio, torch.Tensor) or audio.ndim != 3 or audio.shape[0] != 1 or audio.shape[1] != 1:
+        raise RuntimeError(f"encode_long expects [1, 1, L] audio (got {tuple(getattr(audio, 'shape', ()))})")
+    if int(rows_per_call) < 1:
+        raise ValueError(f"encode_long: rows_per_call must be >= 1 (got {rows_per_call})")
+    hop, Lw = int(dac.hop_length), int(audio.shape[-1])
+    if Lw % hop or Lw < hop:
+        raise RuntimeError(f"encode_long: length {Lw} is not a positive multiple of the hop length {hop}; call preprocess() first")
+    window_frames, rows_per_call, T = int(window_frames), int(rows_per_call), Lw // hop
+    if T <= window_frames:
+        return dac.encode(audio, n_quantizers)
+    left, right = dac.encode_halo()
+    if window_frames <= left + right:
+        raise ValueError(f"encode_long: window_frames must exceed the encoder's halos {left} + {right} (got {window_frames})")
+    x = audio.to(dac.device, torch.float32)[0, 0]
+    planner = DecodePlanner(left, right, window_frames - left - right)
+    jobs = planner.push(T) + planner.flush()
+    ws = dac.encode_workspace(rows_per_call, window_frames * hop)
+    z = codes = lat = None
+    for g in range(0, len(jobs), rows_per_call):
+        grp = jobs[g:g + rows_per_call]
+        outs = _run_encode_jobs(dac, [x[w0 * hop:w1 * hop] for w0, w1, _, _ in grp], grp, n_quantizers, rows_per_call, ws=ws)
+        for (_, _, e0, e1), (zj, cj, lj) in zip(grp, outs):
+            if z is None:
+                z = torch.empty(1, zj.shape[0], T, dtype=zj.dtype, device=zj.device)
+                codes = torch.empty(1, cj.shape[0], T, dtype=cj.dtype, device=cj.device)
+                lat = torch.empty(1, lj.shape[0], T, dtype=lj.dtype, device=lj.device)
+            z[0, :, e0:e1], codes[0, :, e0:e1], lat[0, :, e0:e1] = zj, cj, lj
+    return z, codes, lat, None, None

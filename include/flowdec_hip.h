@@ -804,6 +804,30 @@ int fd_ndac_encode(fd_ndac* m, const float* x, int B, int L, int n_quantizers, f
 int fd_rvq_encode(fd_ndac* m, const float* z, int B, int T, int n_quantizers, float* z_q, int* codes, float* latents, void* ws,
                   size_t ws_bytes, void* stream);
 int fd_rvq_from_codes(fd_ndac* m, const int* codes, int B, int n_quantizers, int T, float* z_q, void* stream);
+/* fd_rvq_encode as ONE launch (rvq_chain_kernel: the residual tile stays in LDS across the quantisers, z_q accumulates in registers): z is
+ * read-only and no workspace is needed.  codes, z_q and latents are BIT-IDENTICAL to fd_rvq_encode on the same z.  frames: DEVICE int32
+ * [B] or NULL; under a table clip b is the first frames[b] frames of its row, 1 <= frames[b] <= T (checked on the host as
+ * fd_ndac_decode_ragged does: FD_EINVAL leaves the outputs untouched); frames at and behind frames[b] are never read, and get code 0,
+ * z_q 0 and latents 0.  fd_rvq_chain_supported(latent_dim, codebook_dim) (host only) says whether the kernel takes the shape: the
+ * [latent_dim][8] float32 tile within LDS and latent_dim / 32 <= 32 accumulators per thread, i.e. latent_dim <= 1024; FD_EINVAL otherwise. */
+int fd_rvq_chain_supported(int latent_dim, int codebook_dim);
+int fd_rvq_encode_chain(fd_ndac* m, const float* z, const int* frames, int B, int T, int n_quantizers, float* z_q, int* codes,
+                        float* latents, void* stream);
+/* Encode of a RAGGED batch: x [B][L] (L % hop == 0), frames = DEVICE int32 [B], clip b = the first frames[b] * hop samples of its row,
+ * 1 <= frames[b] <= L / hop (checked on the host before anything is launched: one B-int copy and a stream synchronisation; FD_EINVAL
+ * leaves every output untouched).  Columns t < frames[b] of row b of z_q / codes / latents are BIT-IDENTICAL to fd_ndac_encode of that clip
+ * alone (B = 1, L = frames[b] * hop) in the same precision mode; the columns behind are 0.  Every kernel bounds its input reads by the
+ * clip's own length at that layer (frames[b] * hop / the strides so far), so what lies behind a clip -- in x or in the workspace -- is
+ * never read as data.  The quantiser runs as one launch (fd_rvq_encode_chain; the per-quantiser kernels under the same table where
+ * fd_rvq_chain_supported says no).  Workspace: fd_ndac_workspace_bytes(m, B, L), as fd_ndac_encode. */
+int fd_ndac_encode_ragged(fd_ndac* m, const float* x, const int* frames, int B, int L, int n_quantizers, float* z_q, int* codes,
+                          float* latents, void* ws, size_t ws_bytes, void* stream);
+/* Latent frames before (left) and after (right) a frame whose samples can reach that frame -- the receptive field of the encoder in
+ * frames, from the configuration alone (host only): rates (2,4,8,10) give (7, 7), (2,4,8,8) give (8, 8).  A window of whole hops with
+ * this much real context on both sides (or a true edge of the signal) encodes its interior frames to the bits of the one-shot encode
+ * (flowdec_amd/ndac_stream.py); odd rates are fine here (a shift by whole frames keeps every layer's phase).  FD_EINVAL when the rates
+ * do not give n frames for n hops of samples (a rate of 1). */
+int fd_ndac_encode_halo(const fd_ndac* m, int* left, int* right);
 /* dac.DAC.decode: z [B][latent][T] -> audio [B][fd_ndac_decoded_length(T)] in (-1, 1) */
 int fd_ndac_decode(fd_ndac* m, const float* z, int B, int T, float* audio, void* ws, size_t ws_bytes, void* stream);
 /* Decode of a RAGGED batch: z [B][latent][T], frames = DEVICE int32 [B] (like the lengths of fd_enhance_ragged), clip b = the first
