@@ -78,6 +78,12 @@ class FdStreamRow(C.Structure):
                 ("emit_count", c_int), ("tail_lo", c_int), ("tail_in", c_void_p), ("tail_out", c_void_p), ("out", c_void_p)]
 
 
+class FdNdacPoolRow(C.Structure):
+    """fd_ndac_pool_row: one entry per row of a codec pool step (include/flowdec_hip.h "Codec pools"); 48 bytes."""
+    _fields_ = [("ring", c_void_p), ("start", c_ll), ("ring_cap", c_int), ("frames", c_int), ("nq", c_int), ("emit_lo", c_int), ("emit_count", c_int),
+                ("out", c_void_p)]
+
+
 PREDICTORS = {"reverse_diffusion": 0, "euler_maruyama": 1, "none": 2}
 CORRECTORS = {"ald": 0, "none": 1}
 STEP_CONTROL = {"batch": 0, "clip": 1}   # FD_STEP_CONTROL_* of the ODE sampler (fd_score_ode_solve / fd_score_ode_enhance)
@@ -217,6 +223,9 @@ SIGNATURES = {
     "fd_ndac_decode": (c_int, [_P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_ndac_decode_ragged": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "fd_ndac_decode_halo": (c_int, [_P, C.POINTER(c_int), C.POINTER(c_int)]),
+    "fd_ndac_pool_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "fd_ndac_pool_decode": (c_int, [_P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
+    "fd_ndac_pool_encode": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_stft_plan_profile": (c_int, [_P, c_int]),
     "fd_stft_plan_profile_read": (c_int, [_P, C.POINTER(C.c_double * 6), C.POINTER(c_int * 2)]),
     "fd_metrics_workspace_bytes": (c_size_t, [c_int] * 4),

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "ndac_internal.h"
 
 namespace {
 
@@ -611,15 +612,7 @@ __global__ __launch_bounds__(256) void rvq_from_codes_kernel(FromCodesArgs a) {
     const int c = (int)((i / a.T) % a.D);
     const int b = (int)(i / ((long long)a.T * a.D));
     float z = 0.f;
-    for (int q = 0; q < a.nq; ++q) {
-      int code = a.codes[((size_t)b * a.nq + q) * a.T + t];
-      code = code < 0 ? 0 : (code >= a.J ? a.J - 1 : code);
-      const float* e = a.cb[q] + (size_t)code * a.cd;
-      const float* wp = a.wout[q] + (size_t)c * a.cd;
-      double acc = 0.0;
-      for (int d = 0; d < a.cd; ++d) acc += (double)wp[d] * (double)e[d];
-      z = z + (float)(acc + (double)a.bout[q][c]);
-    }
+    for (int q = 0; q < a.nq; ++q) z = z + fd_rvq_code_term(a.cb[q], a.wout[q], a.bout[q], a.codes[((size_t)b * a.nq + q) * a.T + t], a.J, a.cd, c);
     a.zq[i] = z;
   }
 }
@@ -696,6 +689,7 @@ struct fd_ndac {
   std::map<std::string, void*> packed;  // "<layer>.weight" -> split-bf16 A-operand copy for ndac_mfma.hip (the layers it supports)
   int precision = FD_NDAC_MFMA_DECODER;
   bool finalized = false;
+  void* pool_state = nullptr;            // ndac_pool.hip's graph cache (fd_ndac_pool_state)
 };
 
 namespace {
@@ -881,6 +875,7 @@ extern "C" int fd_ndac_create(const fd_ndac_config* cfg, fd_ndac** out) {
 
 extern "C" void fd_ndac_destroy(fd_ndac* m) {
   if (!m) return;
+  fd_ndac_pool_state_free(m->pool_state);
   for (void* p : m->allocs) (void)hipFree(p);
   delete m;
 }
@@ -1277,3 +1272,19 @@ extern "C" int fd_ndac_decode_halo(const fd_ndac* m, int* left, int* right) {
   *left = hl; *right = hr;
   return FD_OK;
 }
+
+// ---- for ndac_pool.hip (ndac_internal.h) -------------------------------------------------------------------------------------------
+fd_ndac_view fd_ndac_get_view(const fd_ndac* m) {
+  const fd_ndac_config& c = m->cfg;
+  return fd_ndac_view{m->d_wout, m->d_bout, m->d_cb, c.latent_dim, c.codebook_size, c.codebook_dim, c.n_codebooks, m->hop, m->precision};
+}
+int fd_ndac_check_ready(const fd_ndac* m, const char* who) { return check_ready(m, who); }
+int fd_ndac_decode_walk(fd_ndac* m, const char* who, const float* z, const int* frames, int B, int T, float* audio, void* ws, size_t ws_bytes, hipStream_t st) {
+  return decode_walk(m, who, z, frames, B, T, audio, ws, ws_bytes, st);
+}
+int fd_ndac_encode_walk(fd_ndac* m, const char* who, const float* x, const int* frames, int B, int L, int n_quantizers, float* z_q, int* codes,
+                        float* latents, void* ws, size_t ws_bytes, hipStream_t st) {
+  FD_TRY(check_whole_frames(m, who));
+  return encode_walk(m, who, x, frames, B, L, n_quantizers, z_q, codes, latents, ws, ws_bytes, st);
+}
+void** fd_ndac_pool_state(fd_ndac* m) { return &m->pool_state; }

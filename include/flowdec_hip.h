@@ -843,6 +843,40 @@ int fd_ndac_decode_ragged(fd_ndac* m, const float* z, const int* frames, int B, 
  * (or a true edge of the signal) decodes its interior to the bits of the one-shot decode (flowdec_amd/ndac_stream.py).
  * FD_EINVAL, naming the rate, when a decoder rate is odd: the decoded length is then not frames * hop. */
 int fd_ndac_decode_halo(const fd_ndac* m, int* left, int* right);
+/* ---- Codec pools: many streaming sessions through one native call per step (session layer: flowdec_amd/ndac_pool.py) -----------------
+ * A session's output is, bit for bit, the one-shot decode / encode of everything it was given, however that was cut into pushes and
+ * whichever other sessions shared its native calls (the windows are ndac_stream.DecodePlanner's; a ragged row is its one-clip result).
+ * One step = one table upload and ONE call, whose launch count does not depend on the number of rows:
+ *   decode: gather (code rings -> z_q, from_codes fused in, per-row nq; the device frame table) -> the decoder layers of
+ *           fd_ndac_decode_ragged under that table -> emit (the final samples of every row -> out)
+ *   encode: gather (sample rings -> x; the frame table) -> the encoder layers and the quantiser of fd_ndac_encode_ragged with the call's
+ *           n_quantizers -> emit (the first nq code rows of the final frames -> out)
+ * Both read ONE DEVICE table, an entry per row of the call; a session may have several rows in a call (rows are independent).  The call
+ * checks the caller's HOST copy of the same table -- every rule below, before anything is launched: FD_EINVAL leaves every output
+ * untouched -- so there is no copy back to the host and no stream synchronisation; no atomics.  What lies outside a row's window, in a
+ * ring or in the workspace, is never read as data. */
+typedef struct fd_ndac_pool_row {
+  const void* ring;     /* decode: int32 codes [n_codebooks][ring_cap], frame i of code row q at ring[q * ring_cap + i % ring_cap]
+                         * encode: float32 samples [ring_cap], absolute sample i at ring[i % ring_cap] */
+  long long start;      /* absolute first frame (decode) / first sample (encode) of the window, >= 0; the window may wrap the ring */
+  int ring_cap;         /* >= frames (decode) / frames * hop (encode) */
+  int frames;           /* window length in frames, 1 .. T */
+  int nq;               /* code rows of this session, 1 .. n_codebooks (decode: summed as fd_rvq_from_codes sums them) / 1 .. n_quantizers
+                         * (encode: rows emitted; quantiser i does not depend on the later ones, so these are the session's own encode) */
+  int emit_lo, emit_count;   /* window-local frames that are final: emit_lo >= 0, emit_count >= 0, emit_lo + emit_count <= frames */
+  void* out;            /* decode: float32 [emit_count * samples per frame]; encode: int32 [nq][emit_count] */
+} fd_ndac_pool_row;
+/* Bytes of a step of B rows of at most T frames, either direction (0 for a bad B or T). */
+size_t fd_ndac_pool_workspace_bytes(const fd_ndac* m, int B, int T);
+/* use_graph != 0: the step is one linear chain, so after one eager call with the same (B, T, n_quantizers, precision, table_dev, ws) it is
+ * captured once as a hipGraph and replayed -- the table's content is read at run time and is not part of the graph, so upload it before
+ * the call; the same bits either way.  Capture is illegal on the legacy default stream.  fd_ndac_pool_decode refuses odd decoder rates
+ * (fd_ndac_decode_halo's message), fd_ndac_pool_encode an encoder rate of 1 (fd_ndac_encode_halo's).  The precision mode is the codec's
+ * (fd_ndac_set_precision). */
+int fd_ndac_pool_decode(fd_ndac* m, const fd_ndac_pool_row* table_dev, const fd_ndac_pool_row* table_host, int B, int T, void* ws,
+                        size_t ws_bytes, int use_graph, void* stream);
+int fd_ndac_pool_encode(fd_ndac* m, const fd_ndac_pool_row* table_dev, const fd_ndac_pool_row* table_host, int B, int T, int n_quantizers,
+                        void* ws, size_t ws_bytes, int use_graph, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics: the two metrics of the reference's evaluation (flowdec/eval/metrics.py) that need no outside model, over ragged
