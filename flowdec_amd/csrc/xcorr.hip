@@ -30,6 +30,10 @@
 //
 // Kernel variant kept: the f64 matrix instruction.  The plain v_fma_f64 form of the same partition (8 lags per thread as ascending fma
 // chains over a register window of b) gives the same bits on integer data and is 12 % slower (MEASUREMENTS.md "Alignment").
+//
+// fd_xcorr_lags_frac (eval_cli --align-frac / --align-polarity, the --align of estimate_cli and loss_cli) runs the same slice kernel, a
+// finalise variant that picks on |c| when polarity is asked for, and one workgroup per clip that interpolates the peak on a grid of 1 / Q
+// samples from the host's table of windowed sincs (align.py frac_bank, refine_lag): see xcorr_refine_kernel.
 #include <limits.h>
 #include <math.h>
 
@@ -165,6 +169,83 @@ __global__ __launch_bounds__(256) void xcorr_pick_kernel(const double* __restric
   if (threadIdx.x == 0) lags[b] = l;
 }
 
+// ---- fd_xcorr_lags_frac: the peak on a grid of 1 / Q samples, with polarity (align.py refine_lag) -----------------------------------------
+// xcorr_finalise_kernel with the best picked on |c| when `polarity` is set; the finished c is the same either way
+__global__ __launch_bounds__(256) void xcorr_finalise_pol_kernel(double* __restrict__ part, const int* __restrict__ lens_a, int La, int M, int slices, int blocks,
+                                                                 int polarity, double* __restrict__ c, double* __restrict__ best_v, int* __restrict__ best_l) {
+  __shared__ double sv[256];
+  __shared__ int sl[256];
+  const int b = blockIdx.y, t = threadIdx.x;
+  const long long W = 2LL * M + 1;
+  const long long idx = (long long)blockIdx.x * PICK + t;
+  const int ns = slices_of(clip_len(lens_a, b, La));
+  double v = -HUGE_VAL;
+  int l = INT_MAX;
+  if (idx < W) {
+    double* __restrict__ p = part + (size_t)b * slices * (size_t)W + idx;
+    double s = 0.0;
+    for (int j = 0; j < ns; ++j) s += p[(size_t)j * W];
+    p[0] = s;
+    if (c) c[(size_t)b * W + idx] = s;
+    const double m = polarity ? fabs(s) : s;
+    v = m != m ? -HUGE_VAL : m;
+    l = (int)(idx - M);
+  }
+  block_best(v, l, sv, sl);
+  if (t == 0) { best_v[(size_t)b * blocks + blockIdx.x] = v; best_l[(size_t)b * blocks + blockIdx.x] = l; }
+}
+
+// One workgroup per clip: l0 from the workgroups' winners (xcorr_pick_kernel's reduction), the sign of c[l0], then the 2 Q - 1 candidates
+// q of refine_lag from the finished c (part[b][0][.]) and the bank [Q][2 taps]: r(q) = sum_k (sign c[l0 + floor(q / Q) + k]) H[q mod Q][k],
+// k ascending, every product and sum rounded on its own (no contraction), indices outside [-M, M] left out, NaN as -inf; the best by
+// `better` (a total order on (r, q): any grouping finds the same q).  A candidate is one thread's own chain, so nothing depends on B.
+__global__ __launch_bounds__(256) void xcorr_refine_kernel(const double* __restrict__ part, const double* __restrict__ best_v, const int* __restrict__ best_l,
+                                                           int slices, int blocks, int M, const double* __restrict__ bank, int Q, int taps, int polarity,
+                                                           long long* __restrict__ lag_q, int* __restrict__ sign) {
+#pragma clang fp contract(off)
+  __shared__ double sv[256];
+  __shared__ int sl[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  double v = -HUGE_VAL;
+  int l0 = INT_MAX;
+  for (int i = t; i < blocks; i += 256) {
+    const double vi = best_v[(size_t)b * blocks + i];
+    const int li = best_l[(size_t)b * blocks + i];
+    if (better(vi, li, v, l0)) { v = vi; l0 = li; }
+  }
+  block_best(v, l0, sv, sl);
+  __syncthreads();                                              // sv[0] / sl[0] have been read by every thread
+  l0 = l0 < -M ? -M : (l0 > M ? M : l0);                        // (always inside; clamped so that no table can lead outside the row)
+  const long long W = 2LL * M + 1;
+  const double* __restrict__ c = part + (size_t)b * slices * (size_t)W + M;      // c[l], l in [-M, M]
+  const double sg = (polarity && c[l0] < 0.0) ? -1.0 : 1.0;
+  const long long edge = (long long)M * Q;
+  double rv = -HUGE_VAL;
+  int rq = INT_MAX;                                             // loses every tie against a real candidate
+  for (int i = t; i < 2 * Q - 1; i += 256) {
+    const int q = i - (Q - 1);
+    const long long lq = (long long)l0 * Q + q;
+    if (lq > edge || lq < -edge) continue;                      // |l0 + q / Q| > M
+    const int fl = q < 0 ? -1 : 0, j = q - fl * Q;              // floor(q / Q), q mod Q
+    const double* __restrict__ h = bank + (size_t)j * (2 * taps);
+    double r = 0.0;
+    for (int k = 0; k < 2 * taps; ++k) {
+      const long long l = (long long)l0 + fl + k - taps + 1;
+      if (l >= -M && l <= M) {
+        const double p = (sg * c[l]) * h[k];
+        r = r + p;
+      }
+    }
+    if (r != r) r = -HUGE_VAL;
+    if (better(r, q, rv, rq)) { rv = r; rq = q; }
+  }
+  block_best(rv, rq, sv, sl);
+  if (t == 0) {
+    lag_q[b] = (long long)l0 * Q + (rq == INT_MAX ? 0 : rq);
+    sign[b] = sg < 0.0 ? -1 : 1;
+  }
+}
+
 struct xcorr_layout { size_t part, best_v, best_l, total; int slices, tiles, blocks; };
 
 inline bool args_ok(int B, int La, int Lb, int max_lag) {
@@ -210,6 +291,34 @@ extern "C" int fd_xcorr_lags(const float* a, const float* b, const int* lens_a, 
   hipLaunchKernelGGL(xcorr_slice_kernel, dim3(s.slices, s.tiles, B), dim3(256), 0, st, a, b, lens_a, lens_b, La, Lb, max_lag, s.slices, part);
   hipLaunchKernelGGL(xcorr_finalise_kernel, dim3(s.blocks, B), dim3(256), 0, st, part, lens_a, La, max_lag, s.slices, s.blocks, c, best_v, best_l);
   hipLaunchKernelGGL(xcorr_pick_kernel, dim3(B), dim3(256), 0, st, best_v, best_l, s.blocks, lags);
+  FD_LAUNCH_CHECK();
+  return FD_OK;
+}
+
+extern "C" size_t fd_xcorr_frac_workspace_bytes(int B, int La, int Lb, int max_lag) { return fd_xcorr_workspace_bytes(B, La, Lb, max_lag); }
+
+extern "C" int fd_xcorr_lags_frac(const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag,
+                                  const double* bank, int Q, int W, int polarity, double* c, long long* lag_q, int* sign, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  FD_REQUIRE(a && b && lens_a && lens_b && lag_q && sign && ws, "fd_xcorr_lags_frac: null pointer");
+  FD_REQUIRE(bank, "fd_xcorr_lags_frac: null bank (DEVICE double [Q][2 W], align.frac_bank)");
+  FD_REQUIRE(B > 0 && B <= 65535, "fd_xcorr_lags_frac: bad batch B %d (1 <= B <= 65535)", B);
+  FD_REQUIRE(max_lag >= 1 && max_lag <= MAX_LAG_CAP, "fd_xcorr_lags_frac: bad max_lag %d (1 <= max_lag <= %d)", max_lag, MAX_LAG_CAP);
+  FD_REQUIRE(La > 0 && La <= MAX_ROW && Lb > 0 && Lb <= MAX_ROW, "fd_xcorr_lags_frac: bad row lengths La %d Lb %d (1 <= La, Lb <= %d)", La, Lb, MAX_ROW);
+  FD_REQUIRE(Q >= 2 && Q <= 1024, "fd_xcorr_lags_frac: bad grid Q %d (2 <= Q <= 1024 steps per sample)", Q);
+  FD_REQUIRE(W >= 1 && W <= 256, "fd_xcorr_lags_frac: bad half width W %d (1 <= W <= 256: 2 W taps)", W);
+  const xcorr_layout s = layout(B, La, max_lag);
+  const size_t need = s.total + 256;
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_xcorr_lags_frac: workspace %zu < required %zu bytes (fd_xcorr_frac_workspace_bytes)", ws_bytes, need);
+  hipStream_t st = fd_stream(stream);
+  char* base = aligned(ws);
+  double* part = reinterpret_cast<double*>(base);
+  double* best_v = reinterpret_cast<double*>(base + s.part);
+  int* best_l = reinterpret_cast<int*>(base + s.part + s.best_v);
+  hipLaunchKernelGGL(xcorr_slice_kernel, dim3(s.slices, s.tiles, B), dim3(256), 0, st, a, b, lens_a, lens_b, La, Lb, max_lag, s.slices, part);
+  hipLaunchKernelGGL(xcorr_finalise_pol_kernel, dim3(s.blocks, B), dim3(256), 0, st, part, lens_a, La, max_lag, s.slices, s.blocks, polarity ? 1 : 0, c, best_v,
+                     best_l);
+  hipLaunchKernelGGL(xcorr_refine_kernel, dim3(B), dim3(256), 0, st, part, best_v, best_l, s.slices, s.blocks, max_lag, bank, Q, W, polarity ? 1 : 0, lag_q, sign);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

@@ -73,7 +73,9 @@ written -- after the merge in the launcher of a --gpus N run -- with `flowdec_am
 LogSpecMSE per triple into `metrics{suffix}.csv` beside the list.  The files are scored as they were written to disk, as the reference's
 evaluation scores them (flowdec/eval/metrics.py).  `--eval-estoi` (with --eval) passes `--estoi` on: a fifth column, ESTOI;
 `--eval-spectral` passes `--spectral` on: two last columns, the multi-scale STFT and mel distances; `--eval-align MS` passes `--align MS` on:
-the triples are aligned in time within +-MS milliseconds before they are scored, two last columns `lag_x_hat` and `lag_y`.
+the triples are aligned in time within +-MS milliseconds before they are scored, two last columns `lag_x_hat` and `lag_y`;
+`--eval-align-frac` and `--eval-align-polarity` (with --eval-align MS) pass `--align-frac` and `--align-polarity` on: sub-sample delays,
+and an inverted polarity undone with two further last columns `pol_x_hat` and `pol_y`.
 """
 import argparse
 import collections
@@ -174,6 +176,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-align", type=float, default=None, metavar="MS",
                    help="with --eval: align every triple in time within +-MS milliseconds before scoring (eval_cli --align MS), two last columns "
                         "`lag_x_hat` and `lag_y`")
+    p.add_argument("--eval-align-frac", action="store_true",
+                   help="with --eval-align MS: sub-sample delays (eval_cli --align-frac); `lag_x_hat` and `lag_y` then hold fractions of a sample")
+    p.add_argument("--eval-align-polarity", action="store_true",
+                   help="with --eval-align MS: undo an inverted polarity before scoring (eval_cli --align-polarity), two further last columns "
+                        "`pol_x_hat` and `pol_y`")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -638,7 +645,9 @@ def evaluate_triples(args, suffix: str) -> None:
         eval_cli.run(["--triples", os.path.join(args.outdir, f"triples_list{suffix}.txt"), "--out", os.path.join(args.outdir, f"metrics{suffix}.csv"),
                       "--batch-files", str(max(args.batch_files, 1))] + (["--estoi"] if getattr(args, "eval_estoi", False) else [])
                      + (["--spectral"] if getattr(args, "eval_spectral", False) else [])
-                     + (["--align", repr(float(args.eval_align))] if getattr(args, "eval_align", None) is not None else []))
+                     + (["--align", repr(float(args.eval_align))] if getattr(args, "eval_align", None) is not None else [])
+                     + (["--align-frac"] if getattr(args, "eval_align_frac", False) else [])
+                     + (["--align-polarity"] if getattr(args, "eval_align_polarity", False) else []))
 
 
 def run_launcher(args, parser, argv: List[str]) -> RunResult:
@@ -709,6 +718,8 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
             parser.error("--chunk-seconds needs a flow model (got --model %s)" % args.model)
         if args.solver not in ("euler", "midpoint", "heun2", "heun2_eulerlast"):
             parser.error("--chunk-seconds needs a fixed-step --solver (euler, midpoint, heun2, heun2_eulerlast)")
+    if (args.eval_align_frac or args.eval_align_polarity) and args.eval_align is None:
+        parser.error("--eval-align-frac and --eval-align-polarity need --eval-align MS")
     worker = args.worker_rank is not None
     if args.gpus < 1:
         parser.error("--gpus must be at least 1")

@@ -2,6 +2,7 @@
 
     python -m flowdec_amd.estimate_cli --pairs-file pairs.txt --alpha 0.3 --nfft 1534 --hop 384 [--per-band] [--n-samples 2500]
                                        [--seed 302] [--qx 0.997] [--qrmse 0.997] [--outfile-suffix S] [--overwrite] [--compare-ckpt CKPT]
+                                       [--align MS [--align-frac] [--align-polarity]]
 
 Input: lines `clean ---> coded` (--delim).  --n-samples of them are drawn without replacement and each pair is cropped at a random
 position (or zero-padded) to --sample-duration seconds, with the script's own sequence of NumPy draws (flowdec_amd/estimate.py:
@@ -13,7 +14,16 @@ beside the pairs file, with the `=== Results ===` lines that are also printed; w
 with `.txt` replaced by `sigy_perband.npy` (so it ends in `_perbandsigy_perband.npy`, as the script's does).  If the text file exists
 and --overwrite is not given, its contents are printed and nothing is computed.
 
---compare-ckpt CKPT then prints the checkpoint's beta and sigma_y beside the estimates (see `compare_with_ckpt`)."""
+--compare-ckpt CKPT then prints the checkpoint's beta and sigma_y beside the estimates (see `compare_with_ckpt`).
+
+--align MS [--align-frac] [--align-polarity] [--align-q 64] [--align-taps 32] (off by default; without --align nothing changes) is for
+pairs from a codec that is not this chain's own and brings a delay -- a whole number of samples, a fraction of one where a resampler sits
+in its path -- or an inverted polarity: a delay of tau samples puts 2 sin(omega tau / 2) of every component's own magnitude into the
+difference the sigma_y curve measures.  Right after loading and before the crop / pad rule, every coded file is aligned against its clean
+file within +-MS milliseconds and both are cut to their common support, on the GPU in batches of --batch-pairs (flowdec_amd/align.py:
+align_pairs; eval_cli's --align switches with the same meaning).  What is printed on stdout and the results file keep their text (the Args
+line names the new switches); one alignment summary line (the smallest and the largest lag, the count of non-zero lags and of inverted
+pairs) and the warnings for a lag at the edge of the search and an empty support go to stderr."""
 import argparse
 import contextlib
 import os
@@ -24,6 +34,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from . import align
 from . import estimate as E
 from .audio import RESAMPLE_HELP, load_mono
 from .checkpoint import _cfg_get, _to_plain
@@ -129,13 +140,24 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch-pairs", type=int, default=64, help="pairs per native call")
     p.add_argument("--compare-ckpt", type=str, default=None, help="a checkpoint whose beta and sigma_y are printed beside the estimates")
     p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
+    align.add_pair_arguments(p)
     return p
 
 
 def run(argv=None, out=None) -> Optional[E.EstimateResult]:
     """-> the estimate, or None where an existing results file was printed instead."""
     out = out or sys.stdout
-    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    parser = build_parser()
+    args = parser.parse_args(list(sys.argv[1:] if argv is None else argv))
+    aligner = None
+    if args.align is not None or args.align_frac or args.align_polarity:
+        try:
+            aligner = align.PairAligner(args, args.sr, args.batch_pairs, device=args.device)
+        except ValueError as err:
+            parser.error(str(err))
+    else:                       # the Args line of a run without alignment keeps its text
+        for name in ("align", "align_frac", "align_polarity", "align_q", "align_taps"):
+            delattr(args, name)
     print(args, file=sys.stderr)
     txt, curve_path = outfile_paths(args)
     if os.path.isfile(txt) and not args.overwrite:
@@ -151,11 +173,19 @@ def run(argv=None, out=None) -> Optional[E.EstimateResult]:
     target = int(args.sample_duration * args.sr)
     xs, ys = [], []
     with (torch.cuda.device(args.device) if args.resample == "device" else contextlib.nullcontext()):
-        for fx, fy in pairs:
-            x, y, _ = E.crop_or_pad_pair(load_mono(fx, args.sr, args.resample), load_mono(fy, args.sr, args.resample), target,
-                                         name=f"{fx}{args.delim}{fy}")
-            xs.append(x)
-            ys.append(y)
+        step = max(args.batch_pairs, 1) if aligner else 1
+        for k in range(0, len(pairs), step):
+            group = pairs[k:k + step]
+            names = [f"{fx}{args.delim}{fy}" for fx, fy in group]
+            gx, gy = [load_mono(fx, args.sr, args.resample) for fx, _ in group], [load_mono(fy, args.sr, args.resample) for _, fy in group]
+            if aligner:        # right after loading, before the crop / pad rule (which draws in the list's order either way)
+                gx, gy = aligner(gx, gy, names)
+            for x, y, name in zip(gx, gy, names):
+                x, y, _ = E.crop_or_pad_pair(x, y, target, name=name)
+                xs.append(x)
+                ys.append(y)
+    if aligner:
+        print(aligner.summary(), file=sys.stderr)
     res = E.estimate_params(xs, ys, alpha=args.alpha, n_fft=args.nfft, hop=args.hop, qx=args.qx, qrmse=args.qrmse, per_band=args.per_band,
                             batch_pairs=args.batch_pairs, device=f"cuda:{args.device}")
     if args.per_band:

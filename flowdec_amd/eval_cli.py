@@ -2,7 +2,8 @@
 flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for those of its metrics that need no outside model or program.
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
-                                   [--sr 48000] [--estoi] [--spectral] [--align MS]
+                                   [--sr 48000] [--estoi] [--spectral] [--align MS [--align-frac] [--align-polarity] [--align-q 64]
+                                   [--align-taps 32]]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -45,7 +46,17 @@ pick_lag; ties go to the smallest |l| and to +l), found on the GPU for all tripl
 scored as above.  Two last CSV columns, `lag_x_hat` and `lag_y` (after `mel` / `estoi` when those are on): integers in samples at --sr,
 positive = late; two summary lines with the minimum, the maximum and the count of non-zero lags.  A lag equal to +-M gets a warning (the
 peak sits at the edge of the search; the triple is still scored); a triple whose common support is empty gets NaN in every metric and a
-warning.  No fractional delays, no drift, no polarity or gain matching.
+warning.
+
+--align-frac and --align-polarity (each needs --align MS; without them every byte of the output is what --align MS alone writes) are for a
+codec with a resampler in its path, whose delay is no whole number of samples, and for one that inverts the polarity.  --align-frac finds
+each delay on a grid of 1 / Q samples (--align-q, default 64): the peak of the correlation interpolated by a Hann-windowed sinc of 2 W
+taps (--align-taps W, default 32) around its integer peak (align.refine_lag; csrc/xcorr.hip fd_xcorr_lags_frac), and reads x_hat and y
+that much later through the same interpolator (align.frac_shift; csrc/fracshift.hip), cut to the samples for which no tap leaves the file
+(align.support_frac).  `lag_x_hat` and `lag_y` then print lag_q / Q in full (an exact binary fraction for the default Q).  A signal whose
+delay is a whole number of samples is cut as --align cuts it, so such a triple scores the same bits.  --align-polarity picks the peak of
+|c| and multiplies a signal whose peak is negative by -1 before it is scored: two further last columns `pol_x_hat`, `pol_y` (1 or -1)
+and a summary line with the count of inverted signals.  No drift, no gain matching.
 
 The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
 (DESIGN section 9).
@@ -68,7 +79,8 @@ METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
 ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), the last column without --spectral
 SPECTRAL_NAMES = specdist.NAMES     # the optional metrics of --spectral (msstft, mel), always the last two columns
-LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two
+LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two (before POL_NAMES)
+POL_NAMES = ("pol_x_hat", "pol_y")  # the optional columns of --align-polarity, always the last two
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -116,12 +128,16 @@ def min_spectral_samples(sr: int) -> int:
 class Scorer:
     """si_sxr(x_hats, xs, ys, batch) -> [n, 3] (si_sdr, si_sir, si_sar); logspec(x_hats, xs, sr, batch) -> [n]; estoi(x_hats, xs, sr,
     batch) -> [n] (optional: only --estoi calls it); spectral(x_hats, xs, sr, batch) -> [n, 2] (msstft, mel) (optional: only --spectral
-    calls it); align(as_, bs, max_lag, batch) -> int64 [n], the lag of each b against its a (optional: only --align calls it)."""
+    calls it); align(as_, bs, max_lag, batch) -> int64 [n], the lag of each b against its a (optional: only --align calls it);
+    align_frac(as_, bs, max_lag, Q, W, polarity, batch) -> (lag_q int64 [n], sign int32 [n]) and shift(signals, lag_q, sign, windows, Q, W,
+    batch) -> float32 tensors (optional: only --align-frac / --align-polarity call them)."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
     spectral: Optional[Callable] = None
     align: Optional[Callable] = None
+    align_frac: Optional[Callable] = None
+    shift: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -157,9 +173,9 @@ def _host_spectral(x_hats, xs, sr, batch):
 
 
 # ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/xcorr.hip)
-GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch)
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch, align.lags_batch_frac, align.shift_batch)
 # the host functions of metrics.py, specdist.py and align.py, one triple at a time: the yardstick
-HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags)
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags, align.host_lags_frac, align.host_shift)
 
 
 def metric_columns(estoi: bool = False, spectral: bool = False) -> tuple:
@@ -228,13 +244,16 @@ def _columns_of(values: np.ndarray, columns) -> tuple:
     return tuple(columns)
 
 
-def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None) -> None:
-    """lags (--align): int [n, 2], written as the two last columns LAG_NAMES."""
+def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None, lag_q=None, Q: int = 1, pols=None) -> None:
+    """lags (--align): int [n, 2], written as the two last columns LAG_NAMES.  lag_q (--align-frac) instead: int [n, 2] in units of 1 / Q
+    sample, written as lag_q / Q.  pols (--align-polarity): int [n, 2] of 1 / -1, written behind them as POL_NAMES."""
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LAG_NAMES if lags is not None else ()))
+        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LAG_NAMES if lags is not None or lag_q is not None else ())
+                   + (POL_NAMES if pols is not None else ()))
         for i, (t, row) in enumerate(zip(triples, values)):
-            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([str(int(l)) for l in lags[i]] if lags is not None else []))
+            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([str(int(l)) for l in lags[i]] if lags is not None else [])
+                       + ([align.lag_text(l, Q) for l in lag_q[i]] if lag_q is not None else []) + ([str(int(g)) for g in pols[i]] if pols is not None else []))
 
 
 def summary(values: np.ndarray, columns=None):
@@ -256,6 +275,7 @@ class EvalResult:
     means: list = field(default_factory=list)
     csv_path: Optional[str] = None
     lags: list = field(default_factory=list)   # --align: [(column, min, max, count of non-zero lags)], empty without it
+    inverted: list = field(default_factory=list)   # --align-polarity: [(column, count of inverted signals)], empty without it
 
     @property
     def exit_code(self) -> int:
@@ -280,7 +300,23 @@ def build_parser() -> argparse.ArgumentParser:
                    help="before scoring, find the delay of x_hat and of y against x within +-MS milliseconds (peak of the cross-correlation, on "
                         "the GPU) and cut the three signals to their common support: two last CSV columns `lag_x_hat` and `lag_y` in samples "
                         "at --sr (positive = late)")
+    p.add_argument("--align-frac", action="store_true",
+                   help="with --align MS: find the delays on a grid of 1 / Q samples and read x_hat and y through a windowed-sinc interpolator "
+                        "(on the GPU); `lag_x_hat` and `lag_y` then print fractions of a sample")
+    p.add_argument("--align-polarity", action="store_true",
+                   help="with --align MS: pick the peak of |c| and undo an inverted polarity before scoring: two further last CSV columns "
+                        "`pol_x_hat` and `pol_y` (1 or -1)")
+    p.add_argument("--align-q", type=int, default=align.FRAC_Q, metavar="Q", help="--align-frac: grid steps per sample (2 to 1024)")
+    p.add_argument("--align-taps", type=int, default=align.FRAC_W, metavar="W", help="--align-frac: the interpolator has 2 W taps (W from 1 to 256)")
     return p
+
+
+def check_align_args(parser, args) -> None:
+    """--align-frac / --align-polarity need --align MS; --align-q and --align-taps stay inside what the kernels take."""
+    if (args.align_frac or args.align_polarity) and args.align is None:
+        parser.error("--align-frac and --align-polarity need --align MS")
+    if not 2 <= args.align_q <= align.MAX_Q or not 1 <= args.align_taps <= align.MAX_W:
+        parser.error(f"--align-q takes 2 to {align.MAX_Q} and --align-taps 1 to {align.MAX_W}")
 
 
 def align_max_lag(ms: float, sr: int) -> int:
@@ -319,6 +355,40 @@ def align_signals(loaded, M: int, batch: int, scorer: Scorer, names: Optional[Li
     return out, lags
 
 
+def align_signals_frac(loaded, M: int, batch: int, scorer: Scorer, frac: bool, polarity: bool, Q: int, W: int, names: Optional[List[str]] = None):
+    """align_signals for --align-frac / --align-polarity -> (the triples on their common support, lag_q int64 [n, 2] in units of 1 / Q
+    sample, sign int32 [n, 2]).  All lags come from ONE call of scorer.align_frac (or scorer.align, for whole samples with polarity), all
+    signals that are not cut as views from ONE call of scorer.shift."""
+    if scorer.align is None or scorer.align_frac is None or scorer.shift is None:
+        raise ValueError("align_signals_frac: --align-frac / --align-polarity need a Scorer with align, align_frac and shift functions")
+    n = len(loaded)
+    xs = [x for _, x, _ in loaded]
+    got_q, got_s = align.find_lags(xs + xs, [h for h, _, _ in loaded] + [y for _, _, y in loaded], M, frac, polarity, Q, W, batch, scorer.align,
+                                   scorer.align_frac)
+    lag_q, sign = np.stack([got_q[:n], got_q[n:]], axis=1).reshape(n, 2), np.stack([got_s[:n], got_s[n:]], axis=1).reshape(n, 2)
+    windows = []
+    for i, (h, x, y) in enumerate(loaded):
+        who = names[i] if names else "triple %d" % i
+        for k, col in enumerate(LAG_NAMES):
+            if abs(int(lag_q[i, k])) == M * Q:
+                print(f"warning: {who}: {col} = {align.lag_text(lag_q[i, k], Q)} is at the edge of the search (+-{M} samples): the true delay may "
+                      f"lie outside it (a larger --align)", file=sys.stderr)
+        n0, n1 = align.common_support_frac(x.shape[-1], (h.shape[-1], y.shape[-1]), lag_q[i], Q, W)
+        if n1 <= n0:
+            print(f"warning: {who}: the common support of the aligned signals is empty (lag_x_hat {align.lag_text(lag_q[i, 0], Q)}, lag_y "
+                  f"{align.lag_text(lag_q[i, 1], Q)}; x_hat {h.shape[-1]}, x {x.shape[-1]}, y {y.shape[-1]} samples): NaN for every metric", file=sys.stderr)
+        windows.append((n0, max(n1, n0)))
+    cut = align.cut_frac([h for h, _, _ in loaded] + [y for _, _, y in loaded], np.concatenate([lag_q[:, 0], lag_q[:, 1]]),
+                         np.concatenate([sign[:, 0], sign[:, 1]]), windows + windows, Q, W, scorer.shift, batch)
+    return [(cut[i], x[..., n0:n1], cut[n + i]) for i, ((_, x, _), (n0, n1)) in enumerate(zip(loaded, windows))], lag_q, sign
+
+
+def lag_summary_frac(lag_q: np.ndarray, Q: int):
+    """lag_summary of lag_q / Q: the minimum and the maximum as the text the CSV holds."""
+    return [(name, align.lag_text(lag_q[:, k].min(), Q) if len(lag_q) else "0", align.lag_text(lag_q[:, k].max(), Q) if len(lag_q) else "0",
+             int(np.count_nonzero(lag_q[:, k]))) for k, name in enumerate(LAG_NAMES)]
+
+
 def lag_summary(lags: np.ndarray):
     """-> [(column, min, max, count of non-zero lags)] of int [n, 2] lags; 0, 0, 0 for no rows."""
     return [(name, int(lags[:, k].min()) if len(lags) else 0, int(lags[:, k].max()) if len(lags) else 0, int(np.count_nonzero(lags[:, k])))
@@ -334,6 +404,7 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
             max_lag = align_max_lag(args.align, args.sr)
         except ValueError as err:
             parser.error(str(err))
+    check_align_args(parser, args)
     triples = read_triples(args.triples)
     res = EvalResult(n_triples=len(triples), csv_path=args.out)
     kept, signals = [], []
@@ -346,14 +417,22 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
             continue
         kept.append(t)
         signals.append((x_hat, x, y))
-    names, lags = [t.name for t in kept], None
-    if max_lag is not None:
+    names, lags, lag_q, sign = [t.name for t in kept], None, None, None
+    if max_lag is not None and (args.align_frac or args.align_polarity):
+        signals, lag_q, sign = align_signals_frac(signals, max_lag, args.batch_files, scorer, args.align_frac, args.align_polarity, args.align_q,
+                                                  args.align_taps, names=names)
+    elif max_lag is not None:
         signals, lags = align_signals(signals, max_lag, args.batch_files, scorer, names=names)
     signals = [crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat) for x_hat, x, y in signals]
     values = score(signals, args.sr, args.batch_files, scorer, names=names, estoi=args.estoi, spectral=args.spectral)
     columns = metric_columns(args.estoi, args.spectral)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if lags is None:
+    if lag_q is not None:
+        pols = sign if args.align_polarity else None
+        write_csv(args.out, kept, values, columns=columns, lag_q=lag_q, Q=args.align_q, pols=pols)
+        res.lags = lag_summary_frac(lag_q, args.align_q)
+        res.inverted = [(name, int(np.count_nonzero(sign[:, k] < 0))) for k, name in enumerate(POL_NAMES)] if pols is not None else []
+    elif lags is None:
         write_csv(args.out, kept, values, columns=columns)
     else:
         write_csv(args.out, kept, values, columns=columns, lags=lags)
@@ -364,6 +443,8 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
     for name, lo, hi, nonzero in res.lags:
         print(f"  {name:12s} min = {lo}  max = {hi}  non-zero in {nonzero} of {res.n_scored} rows")
+    for name, count in res.inverted:
+        print(f"  {name:12s} inverted in {count} of {res.n_scored} rows")
     return res
 
 

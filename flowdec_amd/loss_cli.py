@@ -3,6 +3,7 @@
 
     python -m flowdec_amd.loss_cli --ckpt C --pairs-file P [--target-duration 2] [--no-crop] [--batch 8] [--seed 0]
                                    [--precision bf16|fp32|mixed|bf16x3] [--resample host|device] [--out losses.csv]
+                                   [--align MS [--align-frac] [--align-polarity]]
 
 Input: the pair lines of enhance_cli (`clean ---> coded` or `clean,coded`; audio.read_list).  Every file is loaded like eval_cli's:
 mean of the channels, resampled to the model's rate when its rate differs.  Each pair then gets the validation set's rule
@@ -12,7 +13,14 @@ mean of the channels, resampled to the model's rate when its rate differs.  Each
 
 The class the checkpoint names runs (checkpoint.model_from_checkpoint).  Pair i of the list is seeded
 flowdec_amd.noise.clip_seed(--seed, i): its noise, its time t and therefore its loss do not depend on --batch or on how the pairs were
-bucketed.  Prints `valid_loss = ...` (the class's own reduction over all pairs) and, with --out, writes `name,t,loss` per pair."""
+bucketed.  Prints `valid_loss = ...` (the class's own reduction over all pairs) and, with --out, writes `name,t,loss` per pair.
+
+--align MS [--align-frac] [--align-polarity] [--align-q 64] [--align-taps 32] (off by default; without --align nothing changes): right
+after loading and before the length and crop rules, every coded file is aligned against its clean file within +-MS milliseconds -- in
+whole samples, with --align-frac on a grid of 1 / Q samples through a windowed-sinc interpolator, with --align-polarity undoing an
+inverted polarity -- and both are cut to their common support, on the GPU in batches of --batch (flowdec_amd/align.py: align_pairs; the
+switches of eval_cli and estimate_cli).  stdout keeps its text; one alignment summary line and the warnings for a lag at the edge of the
+search and an empty support go to stderr."""
 import argparse
 import contextlib
 import os
@@ -23,6 +31,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import align
 from . import loss as fd_loss
 from .audio import RESAMPLE_HELP, load_mono, read_list
 from .checkpoint import load_from_checkpoint
@@ -75,22 +84,29 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32", "mixed", "bf16x3"])
     p.add_argument("--resample", type=str, default="host", choices=["host", "device"], help=RESAMPLE_HELP)
     p.add_argument("--out", type=str, default=None, help="CSV of name,t,loss per pair")
+    align.add_pair_arguments(p)
     return p
 
 
-def load_pairs(args, sr: int):
-    """-> (names, xs, ys): the list's pairs, loaded, brought to `sr` and cropped / padded by the validation set's rule."""
+def load_pairs(args, sr: int, aligner=None):
+    """-> (names, xs, ys): the list's pairs, loaded, brought to `sr`, aligned in batches of --batch by `aligner` (--align; None: as they
+    are) and cropped / padded by the validation set's rule."""
     fl = read_list(args.pairs_file)
     if not fl.from_pairs or not fl.inputs:
         raise ValueError(f"{args.pairs_file}: no `clean ---> coded` pair lines")
     target = int(args.target_duration * sr)
+    files = [(fx.strip(), fy.strip()) for fx, fy in zip(fl.clean, fl.inputs)]
+    step = max(args.batch, 1) if aligner else 1
     names, xs, ys = [], [], []
-    for fx, fy in zip(fl.clean, fl.inputs):
-        fx, fy = fx.strip(), fy.strip()
-        x, y = load_mono(fx, sr, args.resample), load_mono(fy, sr, args.resample)
-        name = f"{fx} ---> {fy}"
-        x, y = truncate_pair(x, y, name) if args.no_crop else crop_or_pad_valid(x, y, target, name)
-        names.append(os.path.basename(fy)); xs.append(x); ys.append(y)
+    for k in range(0, len(files), step):
+        group = files[k:k + step]
+        full = [f"{fx} ---> {fy}" for fx, fy in group]
+        gx, gy = [load_mono(fx, sr, args.resample) for fx, _ in group], [load_mono(fy, sr, args.resample) for _, fy in group]
+        if aligner:
+            gx, gy = aligner(gx, gy, full)
+        for (_, fy), x, y, name in zip(group, gx, gy, full):
+            x, y = truncate_pair(x, y, name) if args.no_crop else crop_or_pad_valid(x, y, target, name)
+            names.append(os.path.basename(fy)); xs.append(x); ys.append(y)
     return names, xs, ys
 
 
@@ -105,12 +121,23 @@ def write_csv(path: str, res: LossResult) -> None:
 def run(argv=None, model=None, out=None) -> LossResult:
     """`model`: an already built model (tests); otherwise the checkpoint's."""
     out = out or sys.stdout
-    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    parser = build_parser()
+    args = parser.parse_args(list(sys.argv[1:] if argv is None else argv))
+    if (args.align_frac or args.align_polarity) and args.align is None:
+        parser.error("--align-frac and --align-polarity need --align MS")
     if model is None:
         model = load_from_checkpoint(args.ckpt, map_location="cuda", precision=args.precision)
     kind = model_kind_of(model)
+    aligner = None
+    if args.align is not None:
+        try:
+            aligner = align.PairAligner(args, int(model.sampling_rate), args.batch, device=model.device)
+        except ValueError as err:
+            parser.error(str(err))
     with (torch.cuda.device(model.device) if args.resample == "device" else contextlib.nullcontext()):
-        names, xs, ys = load_pairs(args, int(model.sampling_rate))
+        names, xs, ys = load_pairs(args, int(model.sampling_rate), aligner)
+    if aligner:
+        print(aligner.summary(), file=sys.stderr)
     kw = {} if kind == "regression" else dict(seeds=int(args.seed), return_t=True)
     got = model.valid_loss_batch(xs, ys, reduce="none", max_batch=args.batch, **kw)
     values, t = got if kind != "regression" else (got, None)

@@ -931,6 +931,36 @@ size_t fd_xcorr_workspace_bytes(int B, int La, int Lb, int max_lag);
 int fd_xcorr_lags(const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag, double* c, int* lags,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* The same peak on a grid of 1 / Q samples, with polarity (align.py refine_lag; eval_cli --align-frac / --align-polarity and the --align
+ * of estimate_cli and loss_cli).  bank DEVICE double [Q][2 W]: the host's table of Hann-windowed sinc interpolators (align.frac_bank: row
+ * j, column t is the tap k = t - W + 1 of the delay j / Q; row 0 the unit impulse) -- the device only reads it and evaluates no
+ * transcendental.  c is fd_xcorr_lags' c, bit for bit (the same slice kernel and the same order of the slice sums).  l0 is picked by the
+ * rule above on |c| when polarity != 0, else on c; sign = -1 when polarity != 0 and c[l0] < 0, else +1.  Then one workgroup per clip
+ * evaluates, for q in [-(Q - 1), Q - 1] with |l0 Q + q| <= max_lag Q,
+ *     r(q) = sum_{k = -W + 1 .. W} (sign c[l0 + floor(q / Q) + k]) bank[q mod Q][k + W - 1]
+ * k ascending, every product and sum rounded to float64 on its own (no fused multiply-add), indices outside [-M, M] left out, a NaN r
+ * counting as -inf, and picks the largest r; ties go to the smallest |q|, then to +q (all -inf: q = 0).
+ * lag_q DEVICE int64 [B] = l0 Q + q (the lag is lag_q / Q samples); sign DEVICE int32 [B]; c DEVICE double [B][2 M + 1] or NULL.
+ * The promises of fd_xcorr_lags hold: asynchronous on `stream`, no allocation, no atomics, a clip's c, lag_q and sign have the same bits
+ * alone and in any batch, nothing launched on a refusal: FD_EINVAL with a message for a NULL pointer (c alone may be NULL; a NULL bank
+ * is named), B, max_lag and the row lengths as above, Q outside [2, 1024], W outside [1, 256]; FD_ENOMEM for a workspace smaller than
+ * fd_xcorr_frac_workspace_bytes (0 for a bad argument). */
+size_t fd_xcorr_frac_workspace_bytes(int B, int La, int Lb, int max_lag);
+int fd_xcorr_lags_frac(const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag, const double* bank,
+                       int Q, int W, int polarity, double* c, long long* lag_q, int* sign, void* ws, size_t ws_bytes, void* stream);
+
+/* fd_frac_shift (csrc/fracshift.hip; align.py frac_shift): a ragged batch of signals moved by base + j / Q samples and multiplied by sign.
+ * s DEVICE float [B][Ls], lens DEVICE int32 [B] (clamped into the row); per clip base DEVICE int32 [B], its tap row taps DEVICE double
+ * [B][2 W] (bank[j]), sign DEVICE int32 [B] (negative: -1, else +1) and the output window n0, n1 DEVICE int32 [B]:
+ *     out[b][i] = f32(sign_b * sum_{k = -W + 1 .. W} f64(s_b[n0_b + i + base_b + k]) * taps_b[k + W - 1]),   0 <= i < n1_b - n0_b
+ * k ascending, products and sums separately rounded float64, one rounding to float32; samples outside [0, len) are zeros and are never
+ * loaded; out DEVICE float [B][Lo], zeros behind the window (a window longer than Lo is cut to it).  Every index is clamped: a wrong
+ * table gives wrong samples, never an access outside a row.  Asynchronous, no allocation, no workspace, no atomics; a clip's samples
+ * have the same bits alone and in any batch.  FD_EINVAL with a message (nothing launched) for a NULL pointer, B outside [1, 65535], a
+ * row length outside [1, 0x7fffffff - 1024] and W outside [1, 256]. */
+int fd_frac_shift(const float* s, const int* lens, int B, int Ls, const int* base, const double* taps, int W, const int* sign, const int* n0,
+                  const int* n1, float* out, int Lo, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Parameter estimation: the statistics behind a FlowDec model's beta and sigma_y (the reference's scripts/estimate_flowdec_params.py;
  * flowdec_amd/estimate.py, flowdec_amd/estimate_cli.py).  Both calls are asynchronous on `stream`, allocate nothing, keep no state and
