@@ -18,12 +18,17 @@
 
 namespace {
 
+struct PoolCodebooks {   // what the decode gather takes of the codec
+  const float* const* wout; const float* const* bout; const float* const* cb;   // DEVICE arrays [n_codebooks] of device pointers (rvq_from_codes_kernel's)
+  int latent_dim, codebook_size, codebook_dim, n_codebooks;
+};
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // grid (x, B), grid-stride over the row's latent_dim * T elements.  z_q[b][c][t] = sum_{q < nq_b} term_q(code ring of row b at frame
 // start_b + t), q ascending, f32 adds: the arithmetic of rvq_from_codes_kernel on the row alone.  Columns at and behind frames_b are 0
 // (the walk never reads them).  Frame i of code row q lives at ring[q * ring_cap + i % ring_cap]: the window may wrap.
-__global__ __launch_bounds__(256) void pool_decode_gather_kernel(const fd_ndac_pool_row* __restrict__ table, fd_ndac_view v, float* __restrict__ zq,
+__global__ __launch_bounds__(256) void pool_decode_gather_kernel(const fd_ndac_pool_row* __restrict__ table, PoolCodebooks v, float* __restrict__ zq,
                                                                  int* __restrict__ frames_out, int T) {
 #pragma clang fp contract(off)
   const int b = blockIdx.y;
@@ -110,9 +115,8 @@ struct PoolState {
 template <typename Fn>
 int run_step(fd_ndac* m, const PoolKey& key, bool use_graph, hipStream_t st, Fn&& enqueue) {
   if (!use_graph) return enqueue();
-  void** slot = fd_ndac_pool_state(m);
-  if (!*slot) *slot = new PoolState();
-  PoolState& ps = *static_cast<PoolState*>(*slot);
+  if (!m->pool_state) m->pool_state = new PoolState();
+  PoolState& ps = *static_cast<PoolState*>(m->pool_state);
   auto it = ps.graphs.find(key);
   if (it == ps.graphs.end()) {
     if (!ps.seen.count(key)) {
@@ -145,15 +149,16 @@ struct PoolLayout {
   size_t frames, zq, io, codes, walk, walk_bytes, total;   // byte offsets: frame table | z_q | audio (decode) / x (encode) | codes | the walk's own
   int Lo;                                                  // decoded samples of T frames
 };
-PoolLayout layout(const fd_ndac* m, const fd_ndac_view& v, int B, int T) {
+PoolLayout layout(const fd_ndac* m, int B, int T) {
+  const fd_ndac_config& c = m->plan.cfg;
   PoolLayout p{};
   p.Lo = fd_ndac_decoded_length(m, T);
-  const long long Lmax = (long long)T * v.hop > p.Lo ? (long long)T * v.hop : p.Lo;
+  const long long Lmax = (long long)T * m->plan.hop > p.Lo ? (long long)T * m->plan.hop : p.Lo;
   p.frames = 0;
   p.zq = fd_align(sizeof(int) * (size_t)B);
-  p.io = p.zq + fd_align(sizeof(float) * (size_t)B * v.latent_dim * T);
+  p.io = p.zq + fd_align(sizeof(float) * (size_t)B * c.latent_dim * T);
   p.codes = p.io + fd_align(sizeof(float) * (size_t)B * Lmax);
-  p.walk = p.codes + fd_align(sizeof(int) * (size_t)B * v.n_codebooks * T);
+  p.walk = p.codes + fd_align(sizeof(int) * (size_t)B * c.n_codebooks * T);
   p.walk_bytes = fd_ndac_workspace_bytes(m, B, (int)Lmax);
   p.total = p.walk + p.walk_bytes;
   return p;
@@ -187,9 +192,8 @@ void fd_ndac_pool_state_free(void* state) {
 
 extern "C" size_t fd_ndac_pool_workspace_bytes(const fd_ndac* m, int B, int T) {
   if (!m || B <= 0 || T <= 0 || fd_ndac_check_ready(m, "fd_ndac_pool_workspace_bytes") != FD_OK) return 0;
-  const fd_ndac_view v = fd_ndac_get_view(m);
-  if ((long long)T * v.hop >= (1ll << 31) / 4 || (long long)v.latent_dim * T >= (1ll << 31)) return 0;
-  return layout(m, v, B, T).total;
+  if ((long long)T * m->plan.hop >= (1ll << 31) / 4 || (long long)m->plan.cfg.latent_dim * T >= (1ll << 31)) return 0;
+  return layout(m, B, T).total;
 }
 
 extern "C" int fd_ndac_pool_decode(fd_ndac* m, const fd_ndac_pool_row* table_dev, const fd_ndac_pool_row* table_host, int B, int T, void* ws,
@@ -199,12 +203,13 @@ extern "C" int fd_ndac_pool_decode(fd_ndac* m, const fd_ndac_pool_row* table_dev
   FD_REQUIRE(table_dev && table_host && ws && B > 0 && B <= 65535 && T > 0, "%s: bad arguments", who);
   int hl = 0, hr = 0;
   FD_TRY(fd_ndac_decode_halo(m, &hl, &hr));   // refuses odd decoder rates: the decoded length is then not frames * up
-  const fd_ndac_view v = fd_ndac_get_view(m);
+  const fd_ndac_config& c = m->plan.cfg;
+  const PoolCodebooks v{m->d_wout, m->d_bout, m->d_cb, c.latent_dim, c.codebook_size, c.codebook_dim, c.n_codebooks};
   const size_t need = fd_ndac_pool_workspace_bytes(m, B, T);
   FD_REQUIRE(need, "%s: %d rows of %d frames are beyond the 32-bit indices of a step", who, B, T);
   if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
-  FD_TRY(check_table(who, table_host, B, T, 1, v.n_codebooks));
-  const PoolLayout p = layout(m, v, B, T);
+  FD_TRY(check_table(who, table_host, B, T, 1, c.n_codebooks));
+  const PoolLayout p = layout(m, B, T);
   const int up = p.Lo / T;
   FD_REQUIRE(up * T == p.Lo, "%s: the decoder makes %d samples of %d frames: no whole samples per frame", who, p.Lo, T);
   hipStream_t st = fd_stream(stream);
@@ -212,9 +217,9 @@ extern "C" int fd_ndac_pool_decode(fd_ndac* m, const fd_ndac_pool_row* table_dev
   int* frames = (int*)(base + p.frames);
   float* zq = (float*)(base + p.zq);
   float* audio = (float*)(base + p.io);
-  PoolKey key; key.dir = 0; key.B = B; key.T = T; key.precision = v.precision; key.table = table_dev; key.ws = ws;
+  PoolKey key; key.dir = 0; key.B = B; key.T = T; key.precision = m->precision; key.table = table_dev; key.ws = ws;
   return run_step(m, key, use_graph != 0, st, [&]() -> int {
-    hipLaunchKernelGGL(pool_decode_gather_kernel, dim3(grid_x((long long)v.latent_dim * T), B), dim3(256), 0, st, table_dev, v, zq, frames, T);
+    hipLaunchKernelGGL(pool_decode_gather_kernel, dim3(grid_x((long long)c.latent_dim * T), B), dim3(256), 0, st, table_dev, v, zq, frames, T);
     FD_LAUNCH_CHECK();
     FD_TRY(fd_ndac_decode_walk(m, who, zq, frames, B, T, audio, base + p.walk, p.walk_bytes, st));
     hipLaunchKernelGGL(pool_decode_emit_kernel, dim3(grid_x(p.Lo), B), dim3(256), 0, st, table_dev, audio, p.Lo, up);
@@ -230,23 +235,23 @@ extern "C" int fd_ndac_pool_encode(fd_ndac* m, const fd_ndac_pool_row* table_dev
   FD_REQUIRE(table_dev && table_host && ws && B > 0 && B <= 65535 && T > 0, "%s: bad arguments", who);
   int hl = 0, hr = 0;
   FD_TRY(fd_ndac_encode_halo(m, &hl, &hr));   // refuses a rate of 1: n hops of samples are then not n frames
-  const fd_ndac_view v = fd_ndac_get_view(m);
-  FD_REQUIRE(n_quantizers >= 1 && n_quantizers <= v.n_codebooks, "%s: n_quantizers = %d but the model has %d codebooks", who, n_quantizers, v.n_codebooks);
+  const int hop = m->plan.hop, ncb = m->plan.cfg.n_codebooks;
+  FD_REQUIRE(n_quantizers >= 1 && n_quantizers <= ncb, "%s: n_quantizers = %d but the model has %d codebooks", who, n_quantizers, ncb);
   const size_t need = fd_ndac_pool_workspace_bytes(m, B, T);
   FD_REQUIRE(need, "%s: %d rows of %d frames are beyond the 32-bit indices of a step", who, B, T);
   if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
-  FD_TRY(check_table(who, table_host, B, T, v.hop, n_quantizers));
-  const PoolLayout p = layout(m, v, B, T);
+  FD_TRY(check_table(who, table_host, B, T, hop, n_quantizers));
+  const PoolLayout p = layout(m, B, T);
   hipStream_t st = fd_stream(stream);
   char* base = (char*)ws;
   int* frames = (int*)(base + p.frames);
   float* zq = (float*)(base + p.zq);
   float* x = (float*)(base + p.io);
   int* codes = (int*)(base + p.codes);
-  const int L = T * v.hop;
-  PoolKey key; key.dir = 1; key.B = B; key.T = T; key.nq = n_quantizers; key.precision = v.precision; key.table = table_dev; key.ws = ws;
+  const int L = T * hop;
+  PoolKey key; key.dir = 1; key.B = B; key.T = T; key.nq = n_quantizers; key.precision = m->precision; key.table = table_dev; key.ws = ws;
   return run_step(m, key, use_graph != 0, st, [&]() -> int {
-    hipLaunchKernelGGL(pool_encode_gather_kernel, dim3(grid_x(L), B), dim3(256), 0, st, table_dev, x, frames, T, v.hop);
+    hipLaunchKernelGGL(pool_encode_gather_kernel, dim3(grid_x(L), B), dim3(256), 0, st, table_dev, x, frames, T, hop);
     FD_LAUNCH_CHECK();
     FD_TRY(fd_ndac_encode_walk(m, who, x, frames, B, L, n_quantizers, zq, codes, nullptr, base + p.walk, p.walk_bytes, st));
     hipLaunchKernelGGL(pool_encode_emit_kernel, dim3(grid_x((long long)n_quantizers * T), B), dim3(256), 0, st, table_dev, codes, n_quantizers, T);

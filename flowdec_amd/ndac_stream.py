@@ -1,7 +1,7 @@
 """Streaming and long-form NDAC decode: codes in, PCM out, bit for bit `dac.decode(dac.quantizer.from_codes(all codes)[0])`.
 
 Every decoder layer has a finite receptive field, and every kernel accumulates an output in an order that does not depend on the
-output's position (csrc/ndac.hip: input channels ascending, taps ascending, then the bias; the transposed convolution's tap phase is
+output's position (csrc/ndac_conv1d.hip: input channels ascending, taps ascending, then the bias; the transposed convolution's tap phase is
 (n + p) mod s, which a shift by whole frames leaves alone; csrc/ndac_mfma.hip: the K order of an output is the same in every tile
 variant).  So a WINDOW of frames with `DAC.decode_halo()` = (left, right) frames of real context on both sides -- or a true edge of the
 signal, where the window's zero padding IS the signal's -- reproduces the bits of the one-shot decode on its interior (DESIGN.md

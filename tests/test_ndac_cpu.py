@@ -29,6 +29,34 @@ def scaled_sd(cfg, seed, gain):
     return {k: (v * np.float32(gain)).astype(np.float32) if k.endswith("weight_g") else v for k, v in sd.items()}
 
 
+def native_codec(lib, cfg):
+    """fd_ndac_create for a DAC keyword dict (latent_dim as DAC defaults it) -> handle.  Host only: no weights, no GPU; the caller destroys it."""
+    import ctypes as C
+    from flowdec_amd import _lib as L
+    c = L.FdNdacConfig()
+    er, dr = cfg["encoder_rates"], cfg["decoder_rates"]
+    c.encoder_dim, c.n_encoder_rates, c.latent_dim = cfg["encoder_dim"], len(er), cfg.get("latent_dim") or cfg["encoder_dim"] * 2 ** len(er)
+    c.decoder_dim, c.n_decoder_rates = cfg["decoder_dim"], len(dr)
+    for i, s in enumerate(er):
+        c.encoder_rates[i] = s
+    for i, s in enumerate(dr):
+        c.decoder_rates[i] = s
+    c.n_codebooks, c.codebook_size, c.codebook_dim = cfg["n_codebooks"], cfg["codebook_size"], cfg["codebook_dim"]
+    h = C.c_void_p()
+    assert lib.fd_ndac_create(C.byref(c), C.byref(h)) == 0, lib.fd_last_error()
+    return h
+
+
+def native_halo(lib, cfg, which):
+    """(return code, (left, right)) of fd_ndac_encode_halo / fd_ndac_decode_halo (`which` = "encode" | "decode") for a DAC keyword dict."""
+    import ctypes as C
+    h = native_codec(lib, cfg)
+    left, right = C.c_int(-1), C.c_int(-1)
+    rc = getattr(lib, f"fd_ndac_{which}_halo")(h, C.byref(left), C.byref(right))
+    lib.fd_ndac_destroy(h)
+    return rc, (left.value, right.value)
+
+
 def test_oracle_primitives_against_torch():
     rng = np.random.default_rng(0)
     x = rng.standard_normal((2, 6, 50)).astype(np.float32)

@@ -1,8 +1,7 @@
-"""Streaming NDAC encode, host side: the encoder's halo rule (csrc/ndac.hip fd_ndac_encode_halo, restated here) against the oracle's
-actual receptive field, `EncodeStream`'s bookkeeping (flowdec_amd/ndac_stream.py) over random cuts in samples on a stand-in codec
-whose encode IS the oracle, the host-only rules of the C ABI (fd_ndac_encode_halo, fd_rvq_chain_supported) and the `codec_cli`
+"""Streaming NDAC encode, host side: the encoder's halo rule (fd_ndac_encode_halo, computed by csrc/ndac_plan.h from the layer records;
+called through the library, which needs no GPU for it) against recorded values and the oracle's actual receptive field, `EncodeStream`'s
+bookkeeping (flowdec_amd/ndac_stream.py) over random cuts in samples on a stand-in codec whose encode IS the oracle, the host-only rules of the C ABI (fd_ndac_encode_halo, fd_rvq_chain_supported) and the `codec_cli`
 pieces that need no GPU (the parser's refusals, the sample reader, the frame-major int16 writer)."""
-import ctypes as C
 import math
 import random
 
@@ -11,24 +10,7 @@ import pytest
 import torch
 
 from oracle import ndac_oracle as N
-from test_ndac_cpu import NDAC75_LIKE, SMALL, scaled_sd
-
-
-def encode_halo_mirror(encoder_rates):
-    """fd_ndac_encode_halo: the interval [t - 1, t + 1] of the final K = 3 convolution (t = 0) walked backwards through the encoder."""
-    hop = int(np.prod(encoder_rates))
-    lo, hi = -1, 1
-    for s in reversed(encoder_rates):
-        p = math.ceil(s / 2)
-        lo, hi = lo * s - p, hi * s - p + 2 * s - 1             # strided conv K = 2 s: output n reads inputs n s - p .. n s - p + 2 s - 1
-        lo, hi = lo - 3 * (9 + 3 + 1), hi + 3 * (9 + 3 + 1)     # three residual units, K = 7 at dilation 9, 3, 1, at the block's input rate
-    lo, hi = lo - 3, hi + 3                                     # first conv, K = 7
-    return math.ceil(-lo / hop), math.ceil((hi - (hop - 1)) / hop)
-
-
-@pytest.mark.parametrize("rates,want", [((2, 4, 8, 10), (7, 7)), ((2, 4, 8, 8), (8, 8)), ((2, 4, 5), (13, 13))])
-def test_encode_halo_mirror(rates, want):
-    assert encode_halo_mirror(rates) == want
+from test_ndac_cpu import NDAC75_LIKE, SMALL, native_halo, scaled_sd
 
 
 @pytest.fixture(scope="module")
@@ -40,24 +22,24 @@ def lib():
 
 
 def _native_halo(lib, rates):
-    from flowdec_amd import _lib as L
-    cfg = L.FdNdacConfig()
-    cfg.encoder_dim, cfg.n_encoder_rates, cfg.latent_dim, cfg.decoder_dim, cfg.n_decoder_rates = 8, len(rates), 64, 64, 1
-    for i, s in enumerate(rates):
-        cfg.encoder_rates[i] = s
-    cfg.decoder_rates[0] = 2
-    cfg.n_codebooks, cfg.codebook_size, cfg.codebook_dim = 2, 32, 8
-    h = C.c_void_p()
-    assert lib.fd_ndac_create(C.byref(cfg), C.byref(h)) == 0, lib.fd_last_error()
-    left, right = C.c_int(-1), C.c_int(-1)
-    rc = lib.fd_ndac_encode_halo(h, C.byref(left), C.byref(right))      # host only: the configuration alone, no weights, no GPU
-    lib.fd_ndac_destroy(h)
-    return rc, (left.value, right.value)
+    """fd_ndac_encode_halo (host only: the configuration alone, no weights, no GPU) -> (return code, (left, right))"""
+    return native_halo(lib, dict(SMALL, encoder_rates=tuple(rates)), "encode")
+
+
+@pytest.mark.parametrize("rates,want", [((2, 4, 8, 10), (7, 7)), ((2, 4, 8, 8), (8, 8)), ((2, 4, 5), (13, 13))])
+def test_encode_halo_mirror(lib, rates, want):
+    """The three halos DESIGN.md quotes (they were once asserted of a Python restatement of the rule; now of the rule itself)."""
+    assert _native_halo(lib, rates) == (0, want)
+
+
+# what the rule gave when it was written out by hand (commit e828d71: [t - 1, t + 1] walked back through strided conv, +-3 (9 + 3 + 1), +-3)
+HALO_AT_E828D71 = {(2, 4, 8, 10): (7, 7), (2, 4, 8, 8): (8, 8), (2, 4, 5): (13, 13), (3,): (16, 16), (16, 2): (23, 23), (5, 3, 7): (10, 10)}
 
 
 @pytest.mark.parametrize("rates", [(2, 4, 8, 10), (2, 4, 8, 8), (2, 4, 5), (3,), (16, 2), (5, 3, 7)])
 def test_native_halo_equals_the_mirror(lib, rates):
-    assert _native_halo(lib, rates) == (0, encode_halo_mirror(rates))
+    """The rule derived from the layer records gives what the hand-written rule (and its Python mirror) gave, odd and single rates included."""
+    assert _native_halo(lib, rates) == (0, HALO_AT_E828D71[rates])
 
 
 def test_native_halo_refuses_a_rate_of_one(lib):
@@ -73,9 +55,9 @@ def test_rvq_chain_supported_rule(lib):
 
 
 @pytest.mark.parametrize("cfg,want", [(NDAC75_LIKE, (7, 7)), (SMALL, (13, 13))], ids=["ndac75_like", "small"])
-def test_encode_halo_rule_against_the_oracle(cfg, want):
-    hl, hr = encode_halo_mirror(cfg["encoder_rates"])
-    assert (hl, hr) == want
+def test_encode_halo_rule_against_the_oracle(lib, cfg, want):
+    rc, (hl, hr) = _native_halo(lib, cfg["encoder_rates"])
+    assert rc == 0 and (hl, hr) == want
     T, f = 40, 20
     assert f - hr >= 1 and f + hl <= T - 2        # the affected range lies inside the signal, with an unaffected frame on each side
     o = N.DACOracle(scaled_sd(cfg, 3, 0.7), **cfg)
@@ -106,7 +88,8 @@ def test_encode_halo_rule_against_the_oracle(cfg, want):
 class OracleCodec:
     """Stands in for `flowdec_amd.ndac.DAC` under EncodeStream: `encode` / `encode_ragged` are the oracle, row by row, on the host."""
 
-    def __init__(self, cfg, seed=3, gain=0.7):
+    def __init__(self, lib, cfg, seed=3, gain=0.7):
+        self.lib = lib
         self.o = N.DACOracle(scaled_sd(cfg, seed, gain), **cfg)
         self.hop_length, self.n_codebooks, self.sample_rate = self.o.hop_length, cfg["n_codebooks"], cfg["sample_rate"]
         self.encoder_rates = cfg["encoder_rates"]
@@ -114,7 +97,9 @@ class OracleCodec:
         self.calls = []
 
     def encode_halo(self):
-        return encode_halo_mirror(self.encoder_rates)
+        rc, halo = _native_halo(self.lib, self.encoder_rates)      # the code that ships, not a restatement of it
+        assert rc == 0
+        return halo
 
     def encode(self, audio, n_quantizers=None):
         z, codes, lat, _, _ = self.o.encode(audio.numpy(), n_quantizers)
@@ -144,9 +129,9 @@ def _cut_samples(rng, total):
 
 
 @pytest.mark.parametrize("block", [1, 8])
-def test_encode_stream_bookkeeping_over_random_cuts(block):
+def test_encode_stream_bookkeeping_over_random_cuts(lib, block):
     from flowdec_amd.ndac_stream import EncodeStream
-    dac = OracleCodec(SMALL)
+    dac = OracleCodec(lib, SMALL)
     hop = dac.hop_length
     assert hop == 40 and dac.encode_halo() == (13, 13)
     rng = random.Random(block)
@@ -186,10 +171,10 @@ def test_encode_stream_bookkeeping_over_random_cuts(block):
         EncodeStream(dac, rows_per_call=0)
 
 
-def test_encode_long_windows_on_the_oracle():
+def test_encode_long_windows_on_the_oracle(lib):
     """encode_long's jobs tile the recording: z, codes and latents equal the one-shot encode; one workspace request, sized for the window."""
     from flowdec_amd.ndac_stream import encode_long
-    dac = OracleCodec(SMALL)
+    dac = OracleCodec(lib, SMALL)
     asked = []
     dac.encode_workspace = lambda B, Ls: asked.append((B, Ls))
     hop = dac.hop_length

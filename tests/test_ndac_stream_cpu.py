@@ -1,33 +1,44 @@
-"""Streaming NDAC decode, host side: the decoder's halo rule (csrc/ndac.hip fd_ndac_decode_halo, restated here) against the oracle's
-actual receptive field, the window planner (flowdec_amd/ndac_stream.py DecodePlanner) over random cuts, and the `stream_cli --codes`
-pieces that need no GPU (the byte-to-frame splitter, the parser's refusals)."""
-import math
+"""Streaming NDAC decode, host side: the decoder's halo rule (fd_ndac_decode_halo, computed by csrc/ndac_plan.h from the layer records;
+called here through the library, which needs no GPU for it) against the oracle's actual receptive field and against recorded values, the
+window planner (flowdec_amd/ndac_stream.py DecodePlanner) over random cuts, and the `stream_cli --codes` pieces that need no GPU (the byte-to-frame splitter, the parser's refusals)."""
 import random
 
 import numpy as np
 import pytest
 
 from oracle import ndac_oracle as N
-from test_ndac_cpu import NDAC75_LIKE, SMALL, scaled_sd
+from test_ndac_cpu import NDAC75_LIKE, SMALL, native_halo, scaled_sd
 
 
-def halo_mirror(decoder_rates):
-    """fd_ndac_decode_halo: the sample interval of every output sample of frame 0 walked backwards through the decoder."""
-    up = int(np.prod(decoder_rates))
-    left = right = 0
-    for n in range(up):
-        lo, hi = n - 3, n + 3                                  # final conv, K = 7
-        for s in reversed(decoder_rates):
-            p = math.ceil(s / 2)
-            lo, hi = lo - 3 * (9 + 3 + 1), hi + 3 * (9 + 3 + 1)     # three residual units, K = 7 at dilation 9, 3, 1
-            lo, hi = (lo + p) // s - 1, (hi + p) // s           # transposed conv K = 2 s: output n reads floor((n + p) / s) - 1 and floor((n + p) / s)
-        left, right = max(left, -(lo - 3)), max(right, hi + 3)     # first conv, K = 7
-    return left, right
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from flowdec_amd import _lib
+    return _lib.load()
+
+
+def decode_halo(lib, decoder_rates):
+    """fd_ndac_decode_halo (host only: the configuration alone, no weights, no GPU) -> (return code, (left, right))"""
+    return native_halo(lib, dict(SMALL, decoder_rates=tuple(decoder_rates)), "decode")
+
+
+# what the rule gave when it was written out by hand (commit e828d71: per block +-3 (9 + 3 + 1), floor((n + p) / s) - 1 .. floor((n + p) / s))
+@pytest.mark.parametrize("rates,want", [((2,), (25, 25)), ((4, 2), (19, 19)), ((10, 8, 4, 2), (9, 9)), ((4, 2, 2), (21, 21))])
+def test_native_decode_halo_values(lib, rates, want):
+    assert decode_halo(lib, rates) == (0, want)
+
+
+def test_native_decode_halo_refuses_an_odd_rate(lib):
+    """(5, 4, 2): the decoded length is not frames * hop.  (The rule itself gives (15, 15) there: tests/test_model_host_cpu.py.)"""
+    rc, _ = decode_halo(lib, (5, 4, 2))
+    assert rc != 0 and b"decoder rate 5 is odd" in lib.fd_last_error()
 
 
 @pytest.mark.parametrize("cfg,want", [(NDAC75_LIKE, (9, 9)), (dict(SMALL, decoder_rates=(4, 2, 2)), None)], ids=["ndac75_like", "small_422"])
-def test_halo_rule_against_the_oracle(cfg, want):
-    hl, hr = halo_mirror(cfg["decoder_rates"])
+def test_halo_rule_against_the_oracle(lib, cfg, want):
+    rc, (hl, hr) = decode_halo(lib, cfg["decoder_rates"])
+    assert rc == 0
     if want is not None:
         assert (hl, hr) == want
     T, f = 48, 24
