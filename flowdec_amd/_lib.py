@@ -107,8 +107,10 @@ SIGNATURES = {
     "fd_op_combine": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_op_output_update": (c_int, [_P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_op_score_update": (c_int, [_P, _P, _P, c_float, _P, c_float, c_float, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "fd_score_update_at": (c_int, [_P, _P, _P, c_float, _P, c_float, c_float, _P, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_op_init_state": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
     "fd_op_caxpy": (c_int, [_P, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "fd_caxpy_at": (c_int, [_P, _P, _P, _P, c_int, c_float, _P, c_int, c_int, c_int, _P]),
     "fd_op_ode_lincomb": (c_int, [_P, c_float, c_float, C.POINTER(_P), C.POINTER(c_float), c_int, _P, c_ll, _P]),
     "fd_op_ode_lincomb_clips": (c_int, [_P, c_float, _P, C.POINTER(_P), C.POINTER(c_float), c_int, _P, c_int, c_ll, _P]),
     "fd_op_ode_scaled_sq": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int, c_ll, _P]),
@@ -180,6 +182,7 @@ SIGNATURES = {
     "fd_score_num_draws": (c_int, [C.POINTER(FdScoreConfig)]),
     "fd_score_enhance": (c_int, [_P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_enhance_ragged": (c_int, [_P, _P, _P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),
+    "fd_score_enhance_chunks": (c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(FdScoreConfig), _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_score_eval": (c_int, [_P, _P, _P, c_float, C.POINTER(FdScoreConfig), c_int, _P, c_int, c_int, _P, c_size_t, _P]),
     "fd_score_update_clips": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "fd_score_ode_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
@@ -190,6 +193,7 @@ SIGNATURES = {
                                      C.POINTER(c_int), c_int, c_int, _P, c_size_t, _P]),
     "fd_regression_enhance": (c_int, [_P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_regression_enhance_ragged": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
+    "fd_regression_enhance_chunks": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, c_int, _P]),
     "fd_profile_enable": (c_int, [_P, c_int]),
     "fd_profile_read_executed": (c_int, [_P, C.POINTER(C.c_double)]),
     "fd_profile_read": (c_int, [_P, C.POINTER(C.c_double), C.POINTER(c_ll), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -119,7 +119,7 @@ extern "C" int fd_enhance_chunks(fd_model* m, const float* y, const int* lengths
 }
 
 static int score_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, const fd_noise_src& noise, const fd_score_config* c,
-                              float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+                              float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream, const float* normfac_in = nullptr) {
   FD_REQUIRE(c && (noise.ptr || noise.seeds), "%s: null pointer", who);
   FD_REQUIRE(c->N >= 1, "%s: N must be >= 1", who);
   FD_REQUIRE(c->predictor >= FD_PREDICTOR_REVERSE_DIFFUSION && c->predictor <= FD_PREDICTOR_NONE, "%s: unknown predictor id %d", who, c->predictor);
@@ -127,12 +127,12 @@ static int score_enhance_impl(fd_model* m, const char* who, const float* y, cons
   FD_REQUIRE(c->corrector_steps >= 0 && c->corrector_steps <= 64, "%s: corrector_steps out of range", who);
   FD_REQUIRE(c->sigma_min > 0.f && c->sigma_max > c->sigma_min && c->theta > 0.f, "%s: bad OUVE parameters", who);
   FD_REQUIRE(c->t_eps > 0.f && c->t_eps < 1.f, "%s: t_eps must be in (0, 1)", who);
-  GraphKey key; key.noise = noise.ptr; key.seeds = noise.seeds; key.kind = 3; key.score = *c;
+  GraphKey key; key.noise = noise.ptr; key.seeds = noise.seeds; key.frame0 = noise.frame0; key.kind = 3; key.score = *c;
   const fd_score_config cfg = *c;
   return enhance_common(m, who, y, lens, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
                         [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
                           return score_enqueue(m, Y, noise, cfg, X, B, Tp, rest, rest_bytes, st);
-                        });
+                        }, normfac_in);
 }
 
 extern "C" int fd_score_enhance(fd_model* m, const float* y, const float* noise, const fd_score_config* c, float* x_hat, int B, int L, void* ws,
@@ -163,6 +163,22 @@ extern "C" int fd_score_enhance_ragged(fd_model* m, const float* y, const int* l
   FD_REQUIRE(B > 0, "fd_score_enhance_ragged: B must be positive (got %d)", B);
   const fd_noise_src src = noise ? fd_noise_src{noise} : fd_noise_src{nullptr, seeds, 0};
   return score_enhance_impl(m, "fd_score_enhance_ragged", y, lengths, src, c, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// Long-form for the score sampler: fd_score_enhance_ragged on seeds plus the two optional device arrays of fd_enhance_chunks.  frame0 (int32
+// [B]) makes EVERY one of the fd_score_num_draws planes the recording's -- z(seed, draw, f, frame0[b] + t): the prior and each predictor /
+// corrector step of two overlapping rows see bit-identical noise where they overlap; normfac_in (float [B]) replaces the per-row maximum in
+// the front and back end.  Both NULL = fd_score_enhance_ragged(seeds), bit for bit.  A captured graph is keyed on the POINTERS lengths, seeds,
+// frame0 and normfac_in and on the values of *c.
+extern "C" int fd_score_enhance_chunks(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, const int* frame0,
+                                       const float* normfac_in, const fd_score_config* c, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                                       int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_score_enhance_chunks");
+  FD_REQUIRE(lengths, "fd_score_enhance_chunks: null lengths");
+  FD_REQUIRE(seeds, "fd_score_enhance_chunks: null seeds");
+  FD_REQUIRE(B > 0, "fd_score_enhance_chunks: B must be positive (got %d)", B);
+  return score_enhance_impl(m, "fd_score_enhance_chunks", y, lengths, fd_noise_src{nullptr, seeds, 0, frame0}, c, x_hat, B, L, ws, ws_bytes, use_graph,
+                            stream, normfac_in);
 }
 
 // ---- the ODE sampler from waveform to waveform: enhance_common's front end and back end around score_ode_run (solve.hip), eagerly -- the
@@ -217,13 +233,13 @@ extern "C" int fd_score_ode_enhance(fd_model* m, const float* y, const int* leng
 }
 
 static int regression_enhance_impl(fd_model* m, const char* who, const float* y, const int* lens, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
-                                   int use_graph, void* stream) {
+                                   int use_graph, void* stream, const float* normfac_in = nullptr) {
   GraphKey key; key.kind = 4;
   return enhance_common(m, who, y, lens, x_hat, B, L, ws, ws_bytes, key, use_graph, stream,
                         [&](float* Y, float* X, int Tp, void* rest, size_t rest_bytes, hipStream_t st) {
                           OutSpec os; os.dst = X; os.coef = 1.f;                                 // X_hat = backbone(Y, Y, t = 0), model.py:566-578
                           return forward_call(m, Y, Y, nullptr, 0.f, 1, os, B, Tp, rest, rest_bytes, st);
-                        });
+                        }, normfac_in);
 }
 
 extern "C" int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph,
@@ -241,6 +257,17 @@ extern "C" int fd_regression_enhance_ragged(fd_model* m, const float* y, const i
   FD_REQUIRE(lengths, "fd_regression_enhance_ragged: null lengths");
   FD_REQUIRE(B > 0, "fd_regression_enhance_ragged: B must be positive (got %d)", B);
   return regression_enhance_impl(m, "fd_regression_enhance_ragged", y, lengths, x_hat, B, L, ws, ws_bytes, use_graph, stream);
+}
+
+// Long-form for the regression model: fd_regression_enhance_ragged plus normfac_in (device float [B], may be NULL) in place of the per-row
+// maximum, as in fd_enhance_chunks (there is no noise, so no frame0).  NULL = fd_regression_enhance_ragged, bit for bit.  A captured graph is
+// keyed on the POINTERS lengths and normfac_in.
+extern "C" int fd_regression_enhance_chunks(fd_model* m, const float* y, const int* lengths, const float* normfac_in, float* x_hat, int B, int L,
+                                            void* ws, size_t ws_bytes, int use_graph, void* stream) {
+  FD_MODEL_ENTER(m, "fd_regression_enhance_chunks");
+  FD_REQUIRE(lengths, "fd_regression_enhance_chunks: null lengths");
+  FD_REQUIRE(B > 0, "fd_regression_enhance_chunks: B must be positive (got %d)", B);
+  return regression_enhance_impl(m, "fd_regression_enhance_chunks", y, lengths, x_hat, B, L, ws, ws_bytes, use_graph, stream, normfac_in);
 }
 
 // ---- validation loss (include/flowdec_hip.h "Validation loss"; kernels: loss.hip) ---------------------------------------------------

@@ -11,8 +11,8 @@ struct fd_temb_job {
 };
 
 // Where a [B][F][T] plane of sampler noise comes from: a caller-filled buffer (`ptr`), or the clips' seeds (DEVICE uint64 [B]) and the
-// index of the draw -- then the consuming kernel generates the plane in registers (noise.h).  frame0 (DEVICE int32 [B], seeded initial
-// state only; nullptr = zeros): the absolute frame of every row's first column -- the rows are chunks of longer recordings
+// index of the draw -- then the consuming kernel generates the plane in registers (noise.h).  frame0 (DEVICE int32 [B], with seeds
+// only; nullptr = zeros): the absolute frame of every row's first column -- the rows are chunks of longer recordings
 struct fd_noise_src {
   const float* ptr = nullptr;
   const unsigned long long* seeds = nullptr;

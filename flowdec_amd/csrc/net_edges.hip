@@ -323,17 +323,19 @@ __global__ void output_update_kernel(const T* __restrict__ pyr, const float* __r
 // Predictor / corrector update of the ScoreDec sampler (sampling/predictors.py:48-71, correctors.py:52-66) fused with the
 // output layer:  dst = cb * base + cy * Y + cn * v + cz * z   (v = output_layer(pyr) as complex; every coefficient is a
 // real scalar that the host derives from the OUVE closed forms, sdes.py:168-192).  SEEDED: z comes from the clips' seeds (draw index
-// `draw`) instead of a buffer, and is not generated at all when cz == 0.
-template <typename T, int KS, bool SEEDED>
+// `draw`) instead of a buffer, at the absolute frames frame0[b] + t (frame0: int32 [B], may be null = zeros; noise.h), and is not
+// generated at all when cz == 0: then neither seeds nor frame0 is read.  AT = false: frame0 is not looked at (the instantiation of the entry
+// points that have none: the code it was before frame0 existed).
+template <typename T, int KS, bool SEEDED, bool AT>
 __global__ void score_update_kernel(const T* __restrict__ pyr, const float* __restrict__ wo, const float2* __restrict__ base, float cb,
                                     const float2* __restrict__ Y, float cy, float cn, const float2* __restrict__ z,
-                                    const unsigned long long* __restrict__ seeds, int draw, float cz, float2* __restrict__ dst, long long n,
-                                    int H, int W) {
+                                    const unsigned long long* __restrict__ seeds, const int* __restrict__ frame0, int draw, float cz,
+                                    float2* __restrict__ dst, long long n, int H, int W) {
   const out_w1x1 k1(wo);
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const float2 v = output_layer<T, KS>(pyr, wo, k1, i, H, W);
     float2 o = score_combine(v, base, cb, Y, cy, cn, i);
-    if (cz != 0.f) { const float2 zv = noise_elem<SEEDED>(z, seeds, draw, i, H, W); o.x = fmaf(cz, zv.x, o.x); o.y = fmaf(cz, zv.y, o.y); }
+    if (cz != 0.f) { const float2 zv = noise_elem<SEEDED>(z, seeds, draw, i, H, W, AT ? frame0 : nullptr); o.x = fmaf(cz, zv.x, o.x); o.y = fmaf(cz, zv.y, o.y); }
     dst[i] = o;
   }
 }
@@ -437,11 +439,12 @@ static int launch_score_update(const fd_edge_args& a, hipStream_t st) {
     else
       hipLaunchKernelGGL((score_update_clips_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, (const float2*)a.y, a.ctab, (float2*)a.out, nclip, a.H, a.W);
   } else {
-#define FD_SCORE_UPDATE(KS_, SEEDED_)                                                                                                         \
-  hipLaunchKernelGGL((score_update_kernel<T, KS_, SEEDED_>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, \
-                     a.cb, (const float2*)a.y, a.cy, a.coef, (const float2*)a.z.ptr, a.z.seeds, a.z.draw, a.cz, (float2*)a.out, n, a.H, a.W)
-    if (a.z.seeds) { if (a.ks == 3) FD_SCORE_UPDATE(3, true); else FD_SCORE_UPDATE(1, true); }
-    else { if (a.ks == 3) FD_SCORE_UPDATE(3, false); else FD_SCORE_UPDATE(1, false); }
+#define FD_SCORE_UPDATE(KS_, SEEDED_, AT_)                                                                                                       \
+  hipLaunchKernelGGL((score_update_kernel<T, KS_, SEEDED_, AT_>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const T*)a.x, a.w, (const float2*)a.base, \
+                     a.cb, (const float2*)a.y, a.cy, a.coef, (const float2*)a.z.ptr, a.z.seeds, a.z.frame0, a.z.draw, a.cz, (float2*)a.out, n, a.H, a.W)
+    if (a.z.seeds && a.z.frame0) { if (a.ks == 3) FD_SCORE_UPDATE(3, true, true); else FD_SCORE_UPDATE(1, true, true); }
+    else if (a.z.seeds) { if (a.ks == 3) FD_SCORE_UPDATE(3, true, false); else FD_SCORE_UPDATE(1, true, false); }
+    else { if (a.ks == 3) FD_SCORE_UPDATE(3, false, false); else FD_SCORE_UPDATE(1, false, false); }
 #undef FD_SCORE_UPDATE
   }
   FD_LAUNCH_CHECK();

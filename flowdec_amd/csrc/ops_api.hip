@@ -155,18 +155,33 @@ extern "C" int fd_op_output_update(const void* pyr, const float* w, const float*
   return fd_edge_output_update(a, dtype, fd_stream(stream));
 }
 
+static int op_score_update(const char* who, const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn,
+                           const float* z, const unsigned long long* seeds, const int* frame0, int draw, float cz, float* dst, int B, int H, int W,
+                           int ks, int dtype, void* stream) {
+  FD_REQUIRE(pyr && w && base && dst, "%s: null pointer", who);
+  FD_REQUIRE(Y || cy == 0.f, "%s: null pointer (Y with cy != 0)", who);
+  FD_TRY(check_image(who, B, H, W, dtype));
+  FD_REQUIRE(ks == 1 || ks == 3, "%s: ks must be 1 or 3 (got %d)", who, ks);
+  if (cz != 0.f || z || seeds) FD_TRY(check_noise(who, z, seeds, draw));   // cz == 0: the plane is never read, none is needed
+  FD_REQUIRE(!frame0 || seeds, "%s: frame0 needs seeds", who);
+  fd_edge_args a;
+  a.x = pyr; a.w = w; a.base = base; a.cb = cb; a.y = Y; a.cy = cy; a.coef = cn; a.z.ptr = z; a.z.seeds = seeds; a.z.draw = draw; a.z.frame0 = frame0;
+  a.cz = cz; a.out = dst; a.B = B; a.H = H; a.W = W; a.ks = ks;
+  return fd_edge_score_update(a, dtype, fd_stream(stream));
+}
+
 extern "C" int fd_op_score_update(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn,
                                   const float* z, const unsigned long long* seeds, int draw, float cz, float* dst, int B, int H, int W, int ks,
                                   int dtype, void* stream) {
-  FD_REQUIRE(pyr && w && base && dst, "fd_op_score_update: null pointer");
-  FD_REQUIRE(Y || cy == 0.f, "fd_op_score_update: null pointer (Y with cy != 0)");
-  FD_TRY(check_image("fd_op_score_update", B, H, W, dtype));
-  FD_REQUIRE(ks == 1 || ks == 3, "fd_op_score_update: ks must be 1 or 3 (got %d)", ks);
-  if (cz != 0.f || z || seeds) FD_TRY(check_noise("fd_op_score_update", z, seeds, draw));   // cz == 0: the plane is never read, none is needed
-  fd_edge_args a;
-  a.x = pyr; a.w = w; a.base = base; a.cb = cb; a.y = Y; a.cy = cy; a.coef = cn; a.z.ptr = z; a.z.seeds = seeds; a.z.draw = draw; a.cz = cz;
-  a.out = dst; a.B = B; a.H = H; a.W = W; a.ks = ks;
-  return fd_edge_score_update(a, dtype, fd_stream(stream));
+  return op_score_update("fd_op_score_update", pyr, w, base, cb, Y, cy, cn, z, seeds, nullptr, draw, cz, dst, B, H, W, ks, dtype, stream);
+}
+
+// fd_op_score_update with the seeded plane at absolute frames: column t of image b is frame frame0[b] + t (DEVICE int32 [B]; NULL = zeros =
+// fd_op_score_update, bit for bit; frame0 needs seeds)
+extern "C" int fd_score_update_at(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn,
+                                     const float* z, const unsigned long long* seeds, const int* frame0, int draw, float cz, float* dst, int B,
+                                     int H, int W, int ks, int dtype, void* stream) {
+  return op_score_update("fd_score_update_at", pyr, w, base, cb, Y, cy, cn, z, seeds, frame0, draw, cz, dst, B, H, W, ks, dtype, stream);
 }
 
 extern "C" int fd_score_update_clips(const void* pyr, const float* w, const float* base, const float* Y, const float* ctab, float* dst, int B, int H,
@@ -193,14 +208,26 @@ extern "C" int fd_op_init_state(const float* Y, const float* noise, const unsign
   return fd_init_state(Y, src, sigma, sigma_n, sigma_fac, x0, B, F, T, fd_stream(stream));
 }
 
+static int op_caxpy(const char* who, const float* a, const float* q, const unsigned long long* seeds, const int* frame0, int draw, float cq,
+                    float* dst, int B, int F, int T, void* stream) {
+  FD_REQUIRE(a && dst, "%s: null pointer", who);
+  FD_REQUIRE(B >= 1 && F >= 1 && T >= 1, "%s: bad shape (B=%d F=%d T=%d)", who, B, F, T);
+  FD_TRY(check_noise(who, q, seeds, draw));
+  FD_REQUIRE(!frame0 || seeds, "%s: frame0 needs seeds", who);
+  fd_noise_src src;
+  src.ptr = q; src.seeds = seeds; src.draw = draw; src.frame0 = frame0;
+  return fd_caxpy(a, src, cq, dst, B, F, T, fd_stream(stream));
+}
+
 extern "C" int fd_op_caxpy(const float* a, const float* q, const unsigned long long* seeds, int draw, float cq, float* dst, int B, int F, int T,
                            void* stream) {
-  FD_REQUIRE(a && dst, "fd_op_caxpy: null pointer");
-  FD_REQUIRE(B >= 1 && F >= 1 && T >= 1, "fd_op_caxpy: bad shape (B=%d F=%d T=%d)", B, F, T);
-  FD_TRY(check_noise("fd_op_caxpy", q, seeds, draw));
-  fd_noise_src src;
-  src.ptr = q; src.seeds = seeds; src.draw = draw;
-  return fd_caxpy(a, src, cq, dst, B, F, T, fd_stream(stream));
+  return op_caxpy("fd_op_caxpy", a, q, seeds, nullptr, draw, cq, dst, B, F, T, stream);
+}
+
+// fd_op_caxpy with the seeded plane at absolute frames frame0[b] + t (DEVICE int32 [B]; NULL = fd_op_caxpy, bit for bit; frame0 needs seeds)
+extern "C" int fd_caxpy_at(const float* a, const float* q, const unsigned long long* seeds, const int* frame0, int draw, float cq, float* dst,
+                              int B, int F, int T, void* stream) {
+  return op_caxpy("fd_caxpy_at", a, q, seeds, frame0, draw, cq, dst, B, F, T, stream);
 }
 
 extern "C" int fd_op_ode_lincomb(const float* x, float cx, float dt, const float* const* k, const float* c, int nk, float* dst, long long n,

@@ -97,7 +97,8 @@ int score_draws(const fd_score_config& c) {
 namespace fdm {
 
 // sampling/__init__.py:57-70.  noise = [draws][B][F][T] complex64 (or the clips' seeds: draw indices 0, 1, ...), consumed in the reference's
-// order of randn_like calls -- a draw whose coefficient is zero (the last predictor step under `denoise`) still takes its index.
+// order of randn_like calls -- a draw whose coefficient is zero (the last predictor step under `denoise`) still takes its index.  Every draw
+// carries the source's frame0 (fd_score_enhance_chunks): all fd_score_num_draws planes are the recording's, at the absolute frame.
 int score_enqueue(fd_model* m, const float* Y, const fd_noise_src& noise, const fd_score_config& c, float* X, int B, int T, void* ws, size_t ws_bytes,
                   hipStream_t st) {
   const size_t nstate = (size_t)B * m->n_freq * T;

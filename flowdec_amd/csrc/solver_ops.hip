@@ -25,12 +25,15 @@ __global__ void init_state_kernel(const float2* __restrict__ Y, const float2* __
   }
 }
 
-// dst = a + cq * q  (prior sample x_T = Y + std(T) * z, sdes.py:197-202); q = a [B][F][T] plane of noise (buffer or seeds)
-template <bool SEEDED>
-__global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restrict__ q, const unsigned long long* __restrict__ seeds, int draw,
-                             float cq, float2* __restrict__ dst, int F, int T, long long n) {
+// dst = a + cq * q  (prior sample x_T = Y + std(T) * z, sdes.py:197-202); q = a [B][F][T] plane of noise (buffer or seeds; SEEDED with
+// frame0 as in init_state_kernel: the plane's columns are the absolute frames frame0[b] + t).  AT = false: frame0 is not looked at -- the
+// instantiation of the entry points that have none, whose code is what it was before frame0 existed (MEASUREMENTS.md "Baselines: long-form
+// and streaming": the one kernel for both cost them 0.03 %)
+template <bool SEEDED, bool AT>
+__global__ void caxpy_kernel(const float2* __restrict__ a, const float2* __restrict__ q, const unsigned long long* __restrict__ seeds,
+                             const int* __restrict__ frame0, int draw, float cq, float2* __restrict__ dst, int F, int T, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float2 av = a[i], qv = noise_elem<SEEDED>(q, seeds, draw, i, F, T);
+    const float2 av = a[i], qv = noise_elem<SEEDED>(q, seeds, draw, i, F, T, AT ? frame0 : nullptr);
     float2 o = {fmaf(cq, qv.x, av.x), fmaf(cq, qv.y, av.y)};
     dst[i] = o;
   }
@@ -164,12 +167,15 @@ int fd_init_state(const float* Y, const fd_noise_src& noise, const double* sigma
 
 int fd_caxpy(const float* a, const fd_noise_src& q, float cq, float* dst, int B, int F, int T, hipStream_t st) {
   const long long n = (long long)B * F * T;
-  if (q.seeds)
-    hipLaunchKernelGGL(caxpy_kernel<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)nullptr, q.seeds, q.draw, cq,
-                       (float2*)dst, F, T, n);
+  if (q.seeds && q.frame0)
+    hipLaunchKernelGGL((caxpy_kernel<true, true>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)nullptr, q.seeds, q.frame0,
+                       q.draw, cq, (float2*)dst, F, T, n);
+  else if (q.seeds)
+    hipLaunchKernelGGL((caxpy_kernel<true, false>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)nullptr, q.seeds,
+                       (const int*)nullptr, q.draw, cq, (float2*)dst, F, T, n);
   else
-    hipLaunchKernelGGL(caxpy_kernel<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)q.ptr,
-                       (const unsigned long long*)nullptr, 0, cq, (float2*)dst, F, T, n);
+    hipLaunchKernelGGL((caxpy_kernel<false, false>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, (const float2*)a, (const float2*)q.ptr,
+                       (const unsigned long long*)nullptr, (const int*)nullptr, 0, cq, (float2*)dst, F, T, n);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

@@ -749,6 +749,179 @@ class _WaveModel(nn.Module):
             res.append(outs[b].reshape(c.shape).to(c.device))
         return res
 
+    # -- long-form: a recording of any length as overlapping rows of one bucket (flowdec_amd/longform.py; include/flowdec_hip.h "Long-form").
+    # The machinery is the same for the three classes; a class adds `_chunks_call`, the hook around its native chunks entry point.  The
+    # streaming pools (flowdec_amd/stream.py) issue the same hook between fd_stream_gather and fd_stream_emit.
+    _draws_noise = True   # RegressionModel: False -- it takes no seed, and its rows no frame0
+
+    def _chunks_call(self, who: str = "enhance_long", **sampler):
+        """The long-form hook: checks the class's sampler arguments (the refusals need no GPU) and returns
+        call(lib, h, y, lens, seeds, frame0, normfac, out, B, Lrow, ws, use_graph), which issues the class's native chunks call on the
+        current stream -- y / out [B, Lrow] float32, lens int32 [B], seeds uint64 [B], frame0 int32 [B], normfac float32 [B] or None:
+        device pointers (ctypes), ws the workspace tensor.  All rows of a call share the one sampler configuration."""
+        raise NotImplementedError(f"{type(self).__name__} has no long-form entry point")
+
+    def _long_buffers(self, B, Lrow, dev):
+        """The device arrays of the long-form native calls.  They live as long as the shape does: a captured graph is keyed on their
+        addresses, so every group of rows of every file of that shape replays one graph.  Not an entry of `_io`: a caller that alternates
+        `enhance` and `enhance_long` keeps both shapes, and both graphs, resident."""
+        key = (B, Lrow, str(dev))
+        if getattr(self, "_io_long_key", None) != key:
+            self._io_long = dict(y=torch.zeros(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
+                                 lens=torch.empty(B, dtype=torch.int32, device=dev), seeds=torch.empty(B, dtype=torch.int64, device=dev),
+                                 frame0=torch.empty(B, dtype=torch.int32, device=dev), normfac=torch.empty(B, dtype=torch.float32, device=dev))
+            self._io_long_key = key
+        return self._io_long
+
+    @torch.no_grad()
+    @_serialized
+    def _enhance_long(self, y, call, seed=None, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None,
+                      rows_per_call: int = 8, use_graph: bool = True, normfac=None):
+        """`FlowModel.enhance_long` for any of the three classes: `call` = self._chunks_call(<the class's sampler arguments>).  y, seed (a
+        model that draws no noise ignores it), the geometry and `normfac` as documented there.  A recording of one row equals the class's
+        `enhance(y, seed=seed)` bit for bit, a longer one is the float32 stitch of its rows, and the result depends neither on
+        `rows_per_call` nor on graph or eager execution."""
+        if not self._draws_noise:
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        plan = self._long_plan(y, seed, row_frames, halo_frames, xfade, rows_per_call, normfac)
+        with self._long_stream(plan) as (lib, h, y_dev):
+            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs, call, rows_per_call, use_graph)
+            x_hat = self._long_stitch_rows(lib, plan, row_out)
+        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
+        return x_hat.reshape(y.shape).to(y.device)
+
+    @torch.no_grad()
+    @_serialized
+    def _enhance_long_rows(self, y, call, jobs: Optional[Tuple[int, int]] = None, seed=None, row_frames: int = 3712, halo_frames: int = 256,
+                           xfade: Optional[int] = None, rows_per_call: int = 8, use_graph: bool = True, normfac=None):
+        """`FlowModel.enhance_long_rows` for any of the three classes (`call` as in `_enhance_long`)."""
+        if not self._draws_noise:
+            seed = 0
+        elif seed is None:
+            raise ValueError("enhance_long_rows: pass the recording's seed (the calls that share a recording must share it)")
+        plan = self._long_plan(y, seed, row_frames, halo_frames, xfade, rows_per_call, normfac)
+        lo, hi = (0, len(plan.jobs)) if jobs is None else (int(jobs[0]), int(jobs[1]))
+        if not 0 <= lo <= hi <= len(plan.jobs):
+            raise ValueError(f"enhance_long_rows: jobs {(lo, hi)} outside the recording's {len(plan.jobs)} (channel, row) jobs")
+        with self._long_stream(plan) as (lib, h, y_dev):
+            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs[lo:hi], call, rows_per_call, use_graph)
+        row_out.record_stream(torch.cuda.current_stream(plan.dev))
+        return row_out
+
+    @torch.no_grad()
+    @_serialized
+    def _enhance_long_stitch(self, y, row_out, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None):
+        plan = self._long_plan(y, 0, row_frames, halo_frames, xfade, 1)
+        if tuple(row_out.shape) != (len(plan.jobs), plan.Lrow) or row_out.dtype != torch.float32:
+            raise ValueError(f"enhance_long_stitch: expected float32 row outputs {(len(plan.jobs), plan.Lrow)} (got {row_out.dtype} {tuple(row_out.shape)})")
+        row_out = row_out.to(plan.dev).contiguous()
+        with self._long_stream(plan, upload=False) as (lib, h, _):
+            x_hat = self._long_stitch_rows(lib, plan, row_out)
+        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
+        return x_hat.reshape(y.shape).to(y.device)
+
+    def _enhance_long_jobs(self, y, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None) -> int:
+        return len(self._long_plan(y, 0, row_frames, halo_frames, xfade, 1).jobs)
+
+    def _long_plan(self, y, seed, row_frames, halo_frames, xfade, rows_per_call, normfac=None):
+        """Argument checks and the host-side geometry of a long-form call: rows, bucket, the (channel, row) job pool, per-channel seeds."""
+        from types import SimpleNamespace
+        if int(rows_per_call) < 1:
+            raise ValueError(f"enhance_long: rows_per_call must be >= 1 (got {rows_per_call})")
+        dev = self._gpu()
+        y3, _ = _to_3d(y, "enhance_long expects", rows="C")
+        lib = L.load()
+        cfg = self.feature_extractor._cfg()
+        hop = cfg["hop"]
+        C_, n = y3.shape[0], y3.shape[-1]
+        rows = longform.plan_rows(n, hop, row_frames, halo_frames, xfade)
+        xfade = 2 * hop if xfade is None else int(xfade)
+        Tp = int(lib.fd_padded_frames(lib.fd_num_frames(rows[0].length, hop)))
+        Lrow = hop * Tp - 1
+        ops.check_ragged_lengths([r.length for r in rows], Lrow, cfg["n_fft"], hop)
+        if n // hop + Tp >= 2 ** 31:
+            raise RuntimeError(f"enhance_long: {n} samples exceed the 2^31 absolute frames of the noise contract")
+        normalize = self.normalize_mode == "noisy"
+        if normfac is not None:
+            if not normalize:
+                raise ValueError("enhance_long: normfac needs normalize_mode='noisy' (a 'none' model does not normalise)")
+            if isinstance(normfac, str):
+                if normfac != "causal":
+                    raise ValueError(f"enhance_long: normfac is None, a float, a per-channel tensor or 'causal' (got {normfac!r})")
+            else:
+                normfac = torch.as_tensor(normfac, dtype=torch.float32).reshape(-1)
+                if normfac.numel() not in (1, C_) or not bool((torch.isfinite(normfac) & (normfac > 0)).all()):
+                    raise ValueError(f"enhance_long: normfac must be one positive finite factor, or one per channel ({C_})")
+                normfac = normfac.expand(C_)
+        jobs = [(c, r) for c in range(C_) for r in rows]          # every channel's rows, one pool: a row's result depends on nothing else
+        return SimpleNamespace(dev=dev, y3=y3, C=C_, n=n, rows=rows, R=len(rows), xfade=xfade, Tp=Tp, Lrow=Lrow, jobs=jobs,
+                               file_seeds=fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist(), normalize=normalize, normfac=normfac)
+
+    @contextlib.contextmanager
+    def _long_stream(self, plan, upload: bool = True):
+        """The long-form native calls run on the side stream, after the upload of the recording.  -> (lib, handle, the recording [C, n] on
+        the device, or None without `upload`)."""
+        lib = L.load()
+        h = self._sync_native()
+        with torch.cuda.device(plan.dev):
+            y_dev = plan.y3.reshape(plan.C, plan.n).to(plan.dev, torch.float32).contiguous() if upload else None
+            with self._on_side_stream(plan.dev):
+                yield lib, h, y_dev
+
+    def _long_run_jobs(self, lib, h, plan, y_dev, jobs, call, rows_per_call, use_graph):
+        """`jobs` (a slice of plan.jobs) through the class's chunks call in balanced groups of at most `rows_per_call` -> [len(jobs), Lrow]."""
+        dev, Lrow, normalize = plan.dev, plan.Lrow, plan.normalize
+        row_out = torch.empty(len(jobs), Lrow, dtype=torch.float32, device=dev)
+        if not jobs:
+            return row_out
+        n_calls = -(-len(jobs) // int(rows_per_call))
+        B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
+        io = self._long_buffers(B, Lrow, dev)
+        file_normfac = row_index = None                           # [C], or [C, R] with normfac="causal"
+        if normalize and plan.normfac is None:                    # the WHOLE recording's factor, whichever of its jobs run here
+            file_normfac = torch.empty(plan.C, dtype=torch.float32, device=dev)
+            L.check(lib.fd_normfac(L.ptr(y_dev), None, plan.C, plan.n, L.ptr(file_normfac), L.stream()))
+        elif normalize and isinstance(plan.normfac, str):         # "causal": the peak of [0, row end) -- one prefix pass per row that runs here
+            file_normfac = torch.ones(plan.C, plan.R, dtype=torch.float32, device=dev)
+            row_index = {r.start: j for j, r in enumerate(plan.rows)}
+            for c, r in sorted(set((c, r) for c, r in jobs)):
+                L.check(lib.fd_normfac(L.ptr(y_dev[c]), None, 1, r.start + r.length, L.ptr(file_normfac[c, row_index[r.start]:]), L.stream()))
+            file_normfac = file_normfac.reshape(-1)
+        elif normalize:
+            file_normfac = plan.normfac.to(dev)
+        ws = self._enhance_workspace(lib, h, B, Lrow, dev)
+        for g0 in range(0, len(jobs), B):
+            group = jobs[g0:g0 + B]
+            group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
+            for b, (c, r) in enumerate(group):
+                io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
+                io["y"][b, r.length:].zero_()
+            chans = torch.tensor([c if row_index is None else c * plan.R + row_index[r.start] for c, r in group], dtype=torch.int64)
+            io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
+            io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
+            io["seeds"].copy_(torch.tensor([plan.file_seeds[c] for c, _ in group], dtype=torch.int64))
+            if normalize:
+                io["normfac"].copy_(file_normfac[chans.to(dev)])
+            call(lib, h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["seeds"]), L.ptr(io["frame0"]), L.ptr(io["normfac"]) if normalize else None,
+                 L.ptr(io["out"]), B, Lrow, ws, use_graph)
+            k = min(B, len(jobs) - g0)
+            row_out[g0:g0 + k].copy_(io["out"][:k])
+        return row_out
+
+    def _long_stitch_rows(self, lib, plan, row_out):
+        """fd_stitch_chunks per channel over the outputs of all jobs -> [C, n]."""
+        dev, rows, R, n, xfade = plan.dev, plan.rows, plan.R, plan.n, plan.xfade
+        x_hat = torch.empty(plan.C, n, dtype=torch.float32, device=dev)
+        starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
+        bounds = torch.tensor([r.xfade_lo for r in rows[1:]], dtype=torch.int32).to(dev) if R > 1 else None
+        weights = torch.from_numpy(longform.stitch_weights(xfade)).to(dev) if R > 1 and xfade > 0 else None
+        for c in range(plan.C):
+            L.check(lib.fd_stitch_chunks(L.ptr(row_out[c * R:(c + 1) * R]), plan.Lrow, L.ptr(starts), L.ptr(bounds), R, L.ptr(weights),
+                                         xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
+        return x_hat
+
 
 # ------------------------------------------------------------------------------------------------
 # FlowModel
@@ -869,17 +1042,18 @@ class FlowModel(_WaveModel):
         """`valid_loss` for lists of pairs of any lengths, bucketed by padded frame count; every pair bit-identical to its one-pair call."""
         return fd_loss.valid_loss_batch(self, "flow", xs, ys, seeds=seeds, noise=noise, t=t, reduce=reduce, return_t=return_t, max_batch=max_batch)
 
-    def _long_buffers(self, B, Lrow, dev):
-        """The device arrays of `enhance_long`'s native calls.  They live as long as the shape does: a captured graph is keyed on their
-        addresses, so every group of rows of every file of that shape replays one graph.  Not an entry of `_io`: a caller that alternates
-        `enhance` and `enhance_long` keeps both shapes, and both graphs, resident."""
-        key = (B, Lrow, str(dev))
-        if getattr(self, "_io_long_key", None) != key:
-            self._io_long = dict(y=torch.zeros(B, Lrow, dtype=torch.float32, device=dev), out=torch.empty(B, Lrow, dtype=torch.float32, device=dev),
-                                 lens=torch.empty(B, dtype=torch.int32, device=dev), seeds=torch.empty(B, dtype=torch.int64, device=dev),
-                                 frame0=torch.empty(B, dtype=torch.int32, device=dev), normfac=torch.empty(B, dtype=torch.float32, device=dev))
-            self._io_long_key = key
-        return self._io_long
+    def _chunks_call(self, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, who: str = "enhance_long", **unknown):
+        """The long-form hook (see _WaveModel._chunks_call): fd_enhance_chunks with a fixed-step solver."""
+        if unknown:
+            raise ValueError(f"{who}: a flow model takes N, solver and sigma_fac (got {sorted(unknown)})")
+        if solver not in L.SOLVERS:
+            raise ValueError(f"{who}: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
+        N, sigma_fac, solver_id = int(N), float(sigma_fac), L.SOLVERS[solver]
+
+        def call(lib, h, y, lens, seeds, frame0, normfac, out, B, Lrow, ws, use_graph):
+            L.check(lib.fd_enhance_chunks(h, y, lens, seeds, frame0, normfac, sigma_fac, N, solver_id, out, B, Lrow, L.ptr(ws), ws.numel(),
+                                          int(use_graph), L.stream()))
+        return call
 
     @torch.no_grad()
     @_serialized
@@ -905,15 +1079,11 @@ class FlowModel(_WaveModel):
         Keyword `normfac` (normalize_mode='noisy' only; added by @_normfac_option) replaces the recording's maximum: a float, or a tensor of one factor per channel; or
         "causal": row j is scaled by fd_normfac(y[0 : start_j + len_j)), the peak of everything up to the row's END -- the one
         normalisation a stream can reproduce (flowdec_amd.stream), as it depends on the samples up to there and on nothing else.
-        Overlapping rows then differ slightly in scale; the cross-fade absorbs the difference.  None: the recording's maximum."""
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
-        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, self._long_normfac)
-        with self._long_stream(plan) as (lib, h, y_dev):
-            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs, N, solver, sigma_fac, rows_per_call, use_graph)
-            x_hat = self._long_stitch_rows(lib, plan, row_out)
-        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
-        return x_hat.reshape(y.shape).to(y.device)
+        Overlapping rows then differ slightly in scale; the cross-fade absorbs the difference.  None: the recording's maximum.
+
+        The machinery is the base class's (`_WaveModel._enhance_long`), shared with the ScoreDec and regression models."""
+        return self._enhance_long(y, self._chunks_call(N, solver, sigma_fac), seed, row_frames, halo_frames, xfade, rows_per_call, use_graph,
+                                  normfac=self._long_normfac)
 
     @torch.no_grad()
     @_serialized
@@ -926,134 +1096,17 @@ class FlowModel(_WaveModel):
         from its row's start on; what lies beyond the row's length is unspecified).  `seed` must be given: the rows of one recording
         share it.  The normalisation is the whole recording's whichever jobs run (a maximum: the same bits in every call); `normfac` as
         in `enhance_long` (with "causal", overlapping rows differ slightly in scale; the cross-fade of the stitch absorbs it)."""
-        if seed is None:
-            raise ValueError("enhance_long_rows: pass the recording's seed (the calls that share a recording must share it)")
-        plan = self._long_plan(y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, self._long_normfac)
-        lo, hi = (0, len(plan.jobs)) if jobs is None else (int(jobs[0]), int(jobs[1]))
-        if not 0 <= lo <= hi <= len(plan.jobs):
-            raise ValueError(f"enhance_long_rows: jobs {(lo, hi)} outside the recording's {len(plan.jobs)} (channel, row) jobs")
-        with self._long_stream(plan) as (lib, h, y_dev):
-            row_out = self._long_run_jobs(lib, h, plan, y_dev, plan.jobs[lo:hi], N, solver, sigma_fac, rows_per_call, use_graph)
-        row_out.record_stream(torch.cuda.current_stream(plan.dev))
-        return row_out
+        return self._enhance_long_rows(y, self._chunks_call(N, solver, sigma_fac), jobs, seed, row_frames, halo_frames, xfade, rows_per_call,
+                                       use_graph, normfac=self._long_normfac)
 
-    @torch.no_grad()
-    @_serialized
     def enhance_long_stitch(self, y, row_out, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None):
         """The second half of `enhance_long`: the recording from the outputs of ALL its jobs (`enhance_long_rows`, in job order).  Only the
         shape, the device and the length of `y` are used."""
-        plan = self._long_plan(y, "euler", 0, row_frames, halo_frames, xfade, 1)
-        if tuple(row_out.shape) != (len(plan.jobs), plan.Lrow) or row_out.dtype != torch.float32:
-            raise ValueError(f"enhance_long_stitch: expected float32 row outputs {(len(plan.jobs), plan.Lrow)} (got {row_out.dtype} {tuple(row_out.shape)})")
-        row_out = row_out.to(plan.dev).contiguous()
-        with self._long_stream(plan, upload=False) as (lib, h, _):
-            x_hat = self._long_stitch_rows(lib, plan, row_out)
-        x_hat.record_stream(torch.cuda.current_stream(plan.dev))
-        return x_hat.reshape(y.shape).to(y.device)
+        return self._enhance_long_stitch(y, row_out, row_frames, halo_frames, xfade)
 
     def enhance_long_jobs(self, y, row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None) -> int:
         """The number of (channel, row) jobs `enhance_long` cuts y into."""
-        return len(self._long_plan(y, "euler", 0, row_frames, halo_frames, xfade, 1).jobs)
-
-    def _long_plan(self, y, solver, seed, row_frames, halo_frames, xfade, rows_per_call, normfac=None):
-        """Argument checks and the host-side geometry of a long-form call: rows, bucket, the (channel, row) job pool, per-channel seeds."""
-        from types import SimpleNamespace
-        if solver not in L.SOLVERS:
-            raise ValueError(f"enhance_long: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
-        if int(rows_per_call) < 1:
-            raise ValueError(f"enhance_long: rows_per_call must be >= 1 (got {rows_per_call})")
-        dev = self._gpu()
-        y3, _ = _to_3d(y, "enhance_long expects", rows="C")
-        lib = L.load()
-        cfg = self.feature_extractor._cfg()
-        hop = cfg["hop"]
-        C_, n = y3.shape[0], y3.shape[-1]
-        rows = longform.plan_rows(n, hop, row_frames, halo_frames, xfade)
-        xfade = 2 * hop if xfade is None else int(xfade)
-        Tp = int(lib.fd_padded_frames(lib.fd_num_frames(rows[0].length, hop)))
-        Lrow = hop * Tp - 1
-        ops.check_ragged_lengths([r.length for r in rows], Lrow, cfg["n_fft"], hop)
-        if n // hop + Tp >= 2 ** 31:
-            raise RuntimeError(f"enhance_long: {n} samples exceed the 2^31 absolute frames of the noise contract")
-        normalize = self.normalize_mode == "noisy"
-        if normfac is not None:
-            if not normalize:
-                raise ValueError("enhance_long: normfac needs normalize_mode='noisy' (a 'none' model does not normalise)")
-            if isinstance(normfac, str):
-                if normfac != "causal":
-                    raise ValueError(f"enhance_long: normfac is None, a float, a per-channel tensor or 'causal' (got {normfac!r})")
-            else:
-                normfac = torch.as_tensor(normfac, dtype=torch.float32).reshape(-1)
-                if normfac.numel() not in (1, C_) or not bool((torch.isfinite(normfac) & (normfac > 0)).all()):
-                    raise ValueError(f"enhance_long: normfac must be one positive finite factor, or one per channel ({C_})")
-                normfac = normfac.expand(C_)
-        jobs = [(c, r) for c in range(C_) for r in rows]          # every channel's rows, one pool: a row's result depends on nothing else
-        return SimpleNamespace(dev=dev, y3=y3, C=C_, n=n, rows=rows, R=len(rows), xfade=xfade, Tp=Tp, Lrow=Lrow, jobs=jobs,
-                               file_seeds=fd_noise.seeds_to_tensor(seed, C_, "cpu").tolist(), normalize=normalize, normfac=normfac)
-
-    @contextlib.contextmanager
-    def _long_stream(self, plan, upload: bool = True):
-        """The long-form native calls run on the side stream, after the upload of the recording.  -> (lib, handle, the recording [C, n] on
-        the device, or None without `upload`)."""
-        lib = L.load()
-        h = self._sync_native()
-        with torch.cuda.device(plan.dev):
-            y_dev = plan.y3.reshape(plan.C, plan.n).to(plan.dev, torch.float32).contiguous() if upload else None
-            with self._on_side_stream(plan.dev):
-                yield lib, h, y_dev
-
-    def _long_run_jobs(self, lib, h, plan, y_dev, jobs, N, solver, sigma_fac, rows_per_call, use_graph):
-        """`jobs` (a slice of plan.jobs) through fd_enhance_chunks in balanced groups of at most `rows_per_call` -> [len(jobs), Lrow]."""
-        dev, Lrow, normalize = plan.dev, plan.Lrow, plan.normalize
-        row_out = torch.empty(len(jobs), Lrow, dtype=torch.float32, device=dev)
-        if not jobs:
-            return row_out
-        n_calls = -(-len(jobs) // int(rows_per_call))
-        B = -(-len(jobs) // n_calls)                              # balanced groups: at most n_calls - 1 filler rows
-        io = self._long_buffers(B, Lrow, dev)
-        file_normfac = row_index = None                           # [C], or [C, R] with normfac="causal"
-        if normalize and plan.normfac is None:                    # the WHOLE recording's factor, whichever of its jobs run here
-            file_normfac = torch.empty(plan.C, dtype=torch.float32, device=dev)
-            L.check(lib.fd_normfac(L.ptr(y_dev), None, plan.C, plan.n, L.ptr(file_normfac), L.stream()))
-        elif normalize and isinstance(plan.normfac, str):         # "causal": the peak of [0, row end) -- one prefix pass per row that runs here
-            file_normfac = torch.ones(plan.C, plan.R, dtype=torch.float32, device=dev)
-            row_index = {r.start: j for j, r in enumerate(plan.rows)}
-            for c, r in sorted(set((c, r) for c, r in jobs)):
-                L.check(lib.fd_normfac(L.ptr(y_dev[c]), None, 1, r.start + r.length, L.ptr(file_normfac[c, row_index[r.start]:]), L.stream()))
-            file_normfac = file_normfac.reshape(-1)
-        elif normalize:
-            file_normfac = plan.normfac.to(dev)
-        ws = self._enhance_workspace(lib, h, B, Lrow, dev)
-        for g0 in range(0, len(jobs), B):
-            group = jobs[g0:g0 + B]
-            group = group + [group[-1]] * (B - len(group))    # filler rows keep (B, T_pad) -- and the graph -- fixed; their output is dropped
-            for b, (c, r) in enumerate(group):
-                io["y"][b, :r.length].copy_(y_dev[c, r.start:r.start + r.length])
-                io["y"][b, r.length:].zero_()
-            chans = torch.tensor([c if row_index is None else c * plan.R + row_index[r.start] for c, r in group], dtype=torch.int64)
-            io["lens"].copy_(torch.tensor([r.length for _, r in group], dtype=torch.int32))
-            io["frame0"].copy_(torch.tensor([r.frame0 for _, r in group], dtype=torch.int32))
-            io["seeds"].copy_(torch.tensor([plan.file_seeds[c] for c, _ in group], dtype=torch.int64))
-            if normalize:
-                io["normfac"].copy_(file_normfac[chans.to(dev)])
-            L.check(lib.fd_enhance_chunks(h, L.ptr(io["y"]), L.ptr(io["lens"]), L.ptr(io["seeds"]), L.ptr(io["frame0"]),
-                                          L.ptr(io["normfac"]) if normalize else None, float(sigma_fac), int(N), L.SOLVERS[solver],
-                                          L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
-            k = min(B, len(jobs) - g0)
-            row_out[g0:g0 + k].copy_(io["out"][:k])
-        return row_out
-
-    def _long_stitch_rows(self, lib, plan, row_out):
-        """fd_stitch_chunks per channel over the outputs of all jobs -> [C, n]."""
-        dev, rows, R, n, xfade = plan.dev, plan.rows, plan.R, plan.n, plan.xfade
-        x_hat = torch.empty(plan.C, n, dtype=torch.float32, device=dev)
-        starts = torch.tensor([r.start for r in rows], dtype=torch.int32).to(dev)
-        bounds = torch.tensor([r.xfade_lo for r in rows[1:]], dtype=torch.int32).to(dev) if R > 1 else None
-        weights = torch.from_numpy(longform.stitch_weights(xfade)).to(dev) if R > 1 and xfade > 0 else None
-        for c in range(plan.C):
-            L.check(lib.fd_stitch_chunks(L.ptr(row_out[c * R:(c + 1) * R]), plan.Lrow, L.ptr(starts), L.ptr(bounds), R, L.ptr(weights),
-                                         xfade if R > 1 else 0, L.ptr(x_hat[c]), n, L.stream()))
-        return x_hat
+        return self._enhance_long_jobs(y, row_frames, halo_frames, xfade)
 
     def _enhance_adaptive(self, lib, h, y_rows, noise, seeds, B, Lw, N, sigma_fac, return_traj, atol, rtol, method, per_clip, lengths=None):
         """solver='dopri5' / 'tsit5' on the staged rows y_rows [B, Lw]: adaptive 5(4) pair over t_span = linspace(0, 1, N+1) (torchdyn
@@ -1220,6 +1273,24 @@ class ScoreModel(_WaveModel):
                                                 L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
         return self._ragged_call(clips, n_draws, noise, generator, seeds, launch)
 
+    def _chunks_call(self, predictor="reverse_diffusion", corrector="ald", N=30, corrector_steps=1, snr=0.5, denoise=True, sampler_type="pc",
+                     eps=None, who: str = "enhance_long", **unknown):
+        """The long-form hook (see _WaveModel._chunks_call): fd_score_enhance_chunks -- the predictor-corrector sampler with every one of its
+        draws taken at the absolute frame.  The ODE sampler is refused: its per-clip step control would give two overlapping rows
+        different step sequences (no common noise-free trajectory to cross-fade), and it is synchronous."""
+        if unknown:
+            raise ValueError(f"{who}: a score model takes the sampler arguments predictor, corrector, N, corrector_steps, snr and denoise "
+                             f"(got {sorted(unknown)}; `solver` and `sigma_fac` belong to the flow model)")
+        if sampler_type != "pc":
+            raise ValueError(f"{who}: sampler_type='pc' only (got {sampler_type!r}); the 'ode' sampler has no long-form: every row would take "
+                             f"its own adaptive steps, and the driver is synchronous")
+        cfg, _ = self._pc_config(predictor, corrector, N, corrector_steps, snr, denoise, eps)
+
+        def call(lib, h, y, lens, seeds, frame0, normfac, out, B, Lrow, ws, use_graph):
+            L.check(lib.fd_score_enhance_chunks(h, y, lens, seeds, frame0, normfac, C.byref(cfg), out, B, Lrow, L.ptr(ws), ws.numel(),
+                                                int(use_graph), L.stream()))
+        return call
+
     def _ode_config(self, N, denoise, eps, rtol, atol, who):
         """-> (fd_score_config of the ODE sampler, rtol, atol); the tolerances are checked here, before the device is touched."""
         rtol, atol = float(rtol), float(atol)
@@ -1348,9 +1419,20 @@ class ScoreModel(_WaveModel):
 class RegressionModel(_WaveModel):
     """Drop-in for flowdec.model.RegressionModel.enhance (model.py:539-578): one backbone call with x_t = Y, t = 0."""
 
+    _draws_noise = False
+
     def __init__(self, *args, loss_type: str = "l2", **kwargs):
         super().__init__(*args, **kwargs)
         self.loss_type = loss_type
+
+    def _chunks_call(self, who: str = "enhance_long", **unknown):
+        """The long-form hook (see _WaveModel._chunks_call): fd_regression_enhance_chunks.  No sampler, no seed: seeds and frame0 are not read."""
+        if unknown:
+            raise ValueError(f"{who}: a regression model makes one network evaluation per row and takes no sampler arguments (got {sorted(unknown)})")
+
+        def call(lib, h, y, lens, seeds, frame0, normfac, out, B, Lrow, ws, use_graph):
+            L.check(lib.fd_regression_enhance_chunks(h, y, lens, normfac, out, B, Lrow, L.ptr(ws), ws.numel(), int(use_graph), L.stream()))
+        return call
 
     def forward(self, xt, y, t):
         if t.ndim == 0:

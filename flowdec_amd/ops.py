@@ -264,11 +264,16 @@ def output_update(pyr, w, coef, base=None, kold=None, dst=None, ksave=None, want
     return dst, ksave
 
 
-def score_update(pyr, w, base, cb, Y, cy, cn, cz, z=None, seeds=None, draw=0, dst=None):
-    """dst = cb base + cy Y + cn output_layer(pyr) + cz z; z = a complex64 plane, or generated from `seeds` (uint64 [B]) and `draw`."""
+def score_update(pyr, w, base, cb, Y, cy, cn, cz, z=None, seeds=None, draw=0, dst=None, frame0=None, at=None):
+    """dst = cb base + cy Y + cn output_layer(pyr) + cz z; z = a complex64 plane, or generated from `seeds` (uint64 [B]) and `draw` -- at the
+    absolute frames frame0[b] + t with `frame0` (int32 [B]; fd_score_update_at, which `at=True` selects with a NULL frame0 too)."""
     B, H, W, c4 = _nhwc(pyr)
     assert c4 == 4
     dst = torch.empty(B, H, W, dtype=torch.complex64, device=pyr.device) if dst is None else dst
+    if frame0 is not None if at is None else at:
+        L.check(L.load().fd_score_update_at(L.ptr(pyr), L.ptr(w), L.ptr(base), cb, L.ptr(Y), cy, cn, L.ptr(z), L.ptr(seeds), L.ptr(frame0), draw, cz,
+                                               L.ptr(dst), B, H, W, _output_ks(w), L.dtype_id(pyr.dtype), L.stream()))
+        return dst
     L.check(L.load().fd_op_score_update(L.ptr(pyr), L.ptr(w), L.ptr(base), cb, L.ptr(Y), cy, cn, L.ptr(z), L.ptr(seeds), draw, cz, L.ptr(dst),
                                         B, H, W, _output_ks(w), L.dtype_id(pyr.dtype), L.stream()))
     return dst
@@ -295,10 +300,14 @@ def init_state(Y, sigma, sigma_fac, noise=None, seeds=None, frame0=None, draw=0,
     return out
 
 
-def caxpy(a, cq, q=None, seeds=None, draw=0, out=None):
-    """a + cq * q; a complex64 [B, F, T]; q = a plane of the same shape, or generated from `seeds` and `draw`."""
+def caxpy(a, cq, q=None, seeds=None, draw=0, out=None, frame0=None, at=None):
+    """a + cq * q; a complex64 [B, F, T]; q = a plane of the same shape, or generated from `seeds` and `draw` -- at the absolute frames
+    frame0[b] + t with `frame0` (int32 [B]; fd_caxpy_at, which `at=True` selects with a NULL frame0 too)."""
     B, F, T = _plane(a).shape
     out = torch.empty_like(a) if out is None else out
+    if frame0 is not None if at is None else at:
+        L.check(L.load().fd_caxpy_at(L.ptr(a), L.ptr(q), L.ptr(seeds), L.ptr(frame0), draw, cq, L.ptr(out), B, F, T, L.stream()))
+        return out
     L.check(L.load().fd_op_caxpy(L.ptr(a), L.ptr(q), L.ptr(seeds), draw, cq, L.ptr(out), B, F, T, L.stream()))
     return out
 

@@ -1,4 +1,5 @@
-"""Streaming enhance: push / flush sessions whose output is, bit for bit, `FlowModel.enhance_long` on the concatenated input.
+"""Streaming enhance: push / flush sessions whose output is, bit for bit, the model's long-form enhance (`FlowModel.enhance_long`; for a
+ScoreModel or a RegressionModel the same machinery, `_WaveModel._enhance_long`) on the concatenated input.
 
 Decoded audio arrives a block at a time and enhanced audio leaves with a bounded delay; several such streams share one model.  A
 session runs the rows `longform.plan_rows` would cut the finished recording into, each as soon as it can run
@@ -6,8 +7,10 @@ session runs the rows `longform.plan_rows` would cut the finished recording into
 stride, so neither the cut of the input into pushes nor the other sessions in a native call leave a trace in the output.
 
 One `StreamPool.step()` is one table upload and three native calls whatever the number of sessions (include/flowdec_hip.h "Streaming"):
-fd_stream_gather (the sessions' rings -> the rows of the call, the causal factors), fd_enhance_chunks, fd_stream_emit (finished samples
-out, cross-faded against the tail each session carries; the next tail stored).
+fd_stream_gather (the sessions' rings -> the rows of the call, the causal factors), the model class's chunks call (fd_enhance_chunks,
+fd_score_enhance_chunks or fd_regression_enhance_chunks: `model._chunks_call`), fd_stream_emit (finished samples out, cross-faded against
+the tail each session carries; the next tail stored).  The regression model makes ONE network evaluation per row: the lowest-latency
+post-filter a stream can have.
 
 Geometry, with h = hop, rf = row_frames, halo = halo_frames, half = xfade / 2:  W = rf * h - 1, S = (rf - 2 * halo - 1) * h.  Worst-case
 algorithmic delay: a sample leaves once (rf - halo) * h + half further samples have arrived (`StreamPool.delay_samples`), plus one
@@ -31,10 +34,8 @@ from . import resample as R
 from .model import _serialized
 
 
-def _check_args(model, solver, normfac, capacity):
-    """The refusals that need no GPU.  -> normfac as None, 'causal' or a positive float."""
-    if solver not in L.SOLVERS:
-        raise ValueError(f"StreamPool: fixed-step solvers only ({sorted(L.SOLVERS)}), got {solver!r}")
+def _check_args(model, normfac, capacity):
+    """The refusals that need no GPU (the sampler's are the model's: `_chunks_call`).  -> normfac as None, 'causal' or a positive float."""
     if int(capacity) < 1:
         raise ValueError(f"StreamPool: capacity must be >= 1 (got {capacity})")
     if model.normalize_mode == "noisy":
@@ -62,7 +63,7 @@ class _Session:
 
 
 class StreamPool:
-    """Up to `capacity` concurrent streaming sessions on one model.
+    """Up to `capacity` concurrent streaming sessions on one model: a FlowModel, a ScoreModel or a RegressionModel.
 
         pool = StreamPool(model, capacity=8, N=6, solver="euler", row_frames=256, halo_frames=64, normfac="causal")
         sid = pool.open(seed=7)
@@ -71,14 +72,21 @@ class StreamPool:
         tail = pool.flush(sid)                # the rest of the stream; closes the session
 
     Concatenated, what `step` and `flush` return for a session equals `model.enhance_long(all its input, seed=seed, normfac=normfac,
-    same geometry)` bit for bit.  Outputs are float32 tensors on the model's device.  `native_calls` counts fd_enhance_chunks calls,
-    `rows_run` the rows they carried.  The buffers of every batch size B live as long as the pool, so each B captures its hipGraph once."""
+    same geometry)` bit for bit.  Outputs are float32 tensors on the model's device.  `native_calls` counts the chunks calls,
+    `rows_run` the rows they carried.  The buffers of every batch size B live as long as the pool, so each B captures its hipGraph once.
 
-    def __init__(self, model, capacity: int = 8, N: int = 50, solver: str = "euler", sigma_fac: float = 1.0, row_frames: int = 3712,
-                 halo_frames: int = 256, xfade: Optional[int] = None, normfac="causal", use_graph: bool = True):
-        self.normfac = _check_args(model, solver, normfac, capacity)
+    All sessions of a pool share ONE sampler configuration.  A flow model takes `N`, `solver`, `sigma_fac` (None: N = 50, 'euler', 1.0);
+    a score model takes `N` (None: 30) and, in place of `solver`, the arguments of its predictor-corrector sampler as keywords --
+    predictor, corrector, corrector_steps, snr, denoise --, and refuses `solver` / `sigma_fac`; a regression model takes none of them, and
+    `open` ignores its seed."""
+
+    def __init__(self, model, capacity: int = 8, N: Optional[int] = None, solver: Optional[str] = None, sigma_fac: Optional[float] = None,
+                 row_frames: int = 3712, halo_frames: int = 256, xfade: Optional[int] = None, normfac="causal", use_graph: bool = True, **sampler):
+        sampler.update({k: v for k, v in dict(N=N, solver=solver, sigma_fac=sigma_fac).items() if v is not None})
+        self._call = model._chunks_call(who="StreamPool", **sampler)      # the sampler's refusals; what a step issues between gather and emit
+        self.normfac = _check_args(model, normfac, capacity)
         self.model, self.backbone = model, model.backbone      # (.backbone: what @_serialized locks)
-        self.capacity, self.N, self.solver, self.sigma_fac, self.use_graph = int(capacity), int(N), solver, float(sigma_fac), bool(use_graph)
+        self.capacity, self.sampler, self.use_graph = int(capacity), sampler, bool(use_graph)
         self.dev = model.device
         if self.dev.type != "cuda":
             raise RuntimeError("flowdec_amd: move the model to the GPU first (`model.cuda()`)")
@@ -104,12 +112,12 @@ class StreamPool:
 
     # -- sessions ------------------------------------------------------------------------------------------------------------
     @_serialized
-    def open(self, seed) -> int:
+    def open(self, seed=None) -> int:
         """A new session.  `seed` as `enhance_long(seed=)` of a one-channel recording: an int s means clip_seed(s, 0); [s] or an int64 /
-        uint64 tensor [1] gives the 64-bit seed directly."""
+        uint64 tensor [1] gives the 64-bit seed directly.  A regression model draws no noise: its sessions need none."""
         if not self._free:
             raise RuntimeError(f"StreamPool: all {self.capacity} sessions are open")
-        seed64 = int(fd_noise.seeds_to_tensor(seed, 1, "cpu")[0])
+        seed64 = int(fd_noise.seeds_to_tensor(seed, 1, "cpu")[0]) if self.model._draws_noise else 0
         slot = self._free.pop()
         sid, self._next_sid = self._next_sid, self._next_sid + 1
         self._sessions[sid] = _Session(sid, slot, seed64, longform.StreamPlanner(self.geom.hop, self.rf, self.halo, self.xfade, t_pad=self.Tp))
@@ -268,7 +276,7 @@ class StreamPool:
         return self._io[key]
 
     def _run(self, ready, Lrow, h):
-        """gather -> fd_enhance_chunks -> emit over `ready` = [(session, StreamRow)] -> {sid: finished samples}.  Inside `_side()`, whose
+        """gather -> the model's chunks call -> emit over `ready` = [(session, StreamRow)] -> {sid: finished samples}.  Inside `_side()`, whose
         model handle is `h`."""
         lib, dev, B, X, half = L.load(), self.dev, len(ready), self.xfade, self.xfade // 2
         io = self._buffers(B, Lrow)
@@ -303,9 +311,8 @@ class StreamPool:
         if need == 0 or need_cap == 0:
             raise RuntimeError("flowdec_hip: " + lib.fd_last_error().decode())
         ws = self.backbone.workspace(("enh", self.capacity, self.W), max(need, need_cap), dev)
-        L.check(lib.fd_enhance_chunks(h, L.ptr(io["y"]), lens, seeds, frame0, L.ptr(io["normfac"]) if self.normfac is not None else None,
-                                      self.sigma_fac, self.N, L.SOLVERS[self.solver], L.ptr(io["out"]), B, Lrow, L.ptr(ws), ws.numel(),
-                                      int(self.use_graph), L.stream()))
+        self._call(lib, h, L.ptr(io["y"]), lens, seeds, frame0, L.ptr(io["normfac"]) if self.normfac is not None else None, L.ptr(io["out"]), B, Lrow,
+                   ws, self.use_graph)
         L.check(lib.fd_stream_emit(table, B, L.ptr(io["out"]), Lrow, L.ptr(self._weights), X, L.stream()))
         self.native_calls += 1
         self.rows_run += B
@@ -319,12 +326,14 @@ class EnhanceStream:
         for block in blocks: out.append(st.push(block))     # whatever became final (often empty)
         out.append(st.flush())                               # torch.cat(out) == model.enhance_long(cat(blocks), seed=7, normfac="causal", ...)
 
+    `model` is any of the three classes; `pool_kwargs` carry its sampler as `StreamPool` takes it (a regression model needs no seed).
+
     `in_rate` / `out_rate` (Hz; None or the model's rate: as above) put a `resample.ResampleStream` in front of the pool and one behind
     it: the concatenated output is then R_out(model.enhance_long(R_in(all input), ...)) bit for bit, R = `resample.resample_device` at
     lowpass_filter_width 64, however the input was cut.  `delays` = (resampler in, pool, resampler out) in samples at the input rate,
     the model's rate and the model's rate; `delay_samples` stays the pool's."""
 
-    def __init__(self, model, seed, in_rate: Optional[int] = None, out_rate: Optional[int] = None, **pool_kwargs):
+    def __init__(self, model, seed=None, in_rate: Optional[int] = None, out_rate: Optional[int] = None, **pool_kwargs):
         self.pool = StreamPool(model, capacity=1, **pool_kwargs)
         self.sid = self.pool.open(seed)
         self.delay_samples = self.pool.delay_samples

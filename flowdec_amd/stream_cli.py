@@ -3,9 +3,13 @@
     python -m flowdec_amd.stream_cli --ckpt C --N 6 --solver euler --seed 7 [--row-frames 256 --halo-frames 64] \\
         --normfac causal|FLOAT --format s16le|f32le [--in - --out -] [--block-samples 4800] [--in-rate R] [--out-rate R]
 
+The checkpoint names the model class (flowdec_amd.checkpoint): a FlowDec checkpoint runs as above; a ScoreDec checkpoint takes --N and, in
+place of --solver, --predictor / --corrector / --corrector-steps / --snr (its predictor-corrector sampler); a regression checkpoint makes one
+network evaluation per row and ignores --N, --solver and --seed (it says so on stderr).  --codes works with all three.
+
 The input is mono PCM, little endian, without a header, at the model's sampling rate unless --in-rate says otherwise.  The output -- same
-format -- is, as float32, `model.enhance_long(input, seed=SEED, normfac=..., row_frames=..., halo_frames=...)` bit for bit
-(flowdec_amd.stream); s16le output is that rounded to 16 bits with clipping.  A sample leaves once (row_frames - halo_frames) * hop +
+format -- is, as float32, the model's long-form enhance of the input (`enhance_long(input, seed=SEED, normfac=..., row_frames=...,
+halo_frames=...)`) bit for bit (flowdec_amd.stream); s16le output is that rounded to 16 bits with clipping.  A sample leaves once (row_frames - halo_frames) * hop +
 xfade / 2 further samples have arrived, plus one row's compute time.
 
 --in-rate / --out-rate (default: the model's rate) resample the stream on the device on its way in and out (flowdec_amd.resample:
@@ -29,6 +33,7 @@ import numpy as np
 import torch
 
 from .checkpoint import load_from_checkpoint
+from .model import RegressionModel, ScoreModel
 from .ndac import DAC
 from .ndac_stream import DecodeStream
 from .stream import EnhanceStream
@@ -49,10 +54,14 @@ def _normfac(s: str):
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Enhance a raw PCM stream with a FlowDec postfilter on MI355X (stdin -> stdout by default)")
+    p = argparse.ArgumentParser(description="Enhance a raw PCM stream with a FlowDec, ScoreDec or regression postfilter on MI355X (stdin -> stdout by default)")
     p.add_argument("--ckpt", type=str, required=True)
     p.add_argument("--N", type=int, required=True)
-    p.add_argument("--solver", type=str, default="euler", choices=["euler", "midpoint", "heun2", "heun2_eulerlast"], help="fixed-step solvers only")
+    p.add_argument("--solver", type=str, default="euler", choices=["euler", "midpoint", "heun2", "heun2_eulerlast"], help="flow checkpoint: fixed-step solvers only")
+    p.add_argument("--predictor", type=str, default="reverse_diffusion", choices=["reverse_diffusion", "euler_maruyama", "none"], help="score checkpoint")
+    p.add_argument("--corrector", type=str, default="ald", choices=["ald", "none"], help="score checkpoint")
+    p.add_argument("--corrector-steps", type=int, default=1, help="score checkpoint")
+    p.add_argument("--snr", type=float, default=0.5, help="score checkpoint: the corrector's target SNR")
     p.add_argument("--seed", type=int, required=True, help="the stream's noise seed, as enhance_long(seed=SEED)")
     p.add_argument("--row-frames", type=int, default=256, help="STFT frames per row (a multiple of 64)")
     p.add_argument("--halo-frames", type=int, default=64)
@@ -81,6 +90,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         p.error("--block-samples must be >= 1")
     if args.N < 1:
         p.error("--N must be >= 1")
+    if args.corrector_steps < 0:
+        p.error("--corrector-steps must be >= 0")
     for name in ("in_rate", "out_rate"):
         if getattr(args, name) is not None and getattr(args, name) < 1:
             p.error(f"--{name.replace('_', '-')} must be >= 1")
@@ -129,10 +140,17 @@ def encode(x: torch.Tensor, fmt: str) -> bytes:
 
 
 def run(argv: Optional[List[str]] = None, model=None) -> int:
-    """-> the number of samples written.  `model`: an already loaded FlowModel (tests)."""
+    """-> the number of samples written.  `model`: an already loaded FlowModel, ScoreModel or RegressionModel (tests)."""
     args = parse_args(argv)
     if model is None:
-        model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision, model="flow")
+        model = load_from_checkpoint(args.ckpt, map_location=args.device, ema=args.ema, precision=args.precision)   # the class the checkpoint names
+    if isinstance(model, RegressionModel):
+        print("stream_cli: a regression checkpoint makes one network evaluation per row: --N, --solver and --seed are ignored", file=sys.stderr)
+        sampler = dict(seed=None)
+    elif isinstance(model, ScoreModel):
+        sampler = dict(seed=args.seed, N=args.N, predictor=args.predictor, corrector=args.corrector, corrector_steps=args.corrector_steps, snr=args.snr)
+    else:
+        sampler = dict(seed=args.seed, N=args.N, solver=args.solver)
     dec = split = None
     if args.codes:
         error = build_parser().error
@@ -146,8 +164,8 @@ def run(argv: Optional[List[str]] = None, model=None) -> int:
             args.in_rate = int(dac.sample_rate)
         dec = DecodeStream(dac, n_quantizers=nq, block_frames=args.decode_block_frames)
         split = CodeFrames(nq, dac.codebook_size, error)
-    st = EnhanceStream(model, seed=args.seed, N=args.N, solver=args.solver, row_frames=args.row_frames, halo_frames=args.halo_frames,
-                       normfac=args.normfac, in_rate=args.in_rate, out_rate=args.out_rate)
+    st = EnhanceStream(model, row_frames=args.row_frames, halo_frames=args.halo_frames, normfac=args.normfac, in_rate=args.in_rate,
+                       out_rate=args.out_rate, **sampler)
     dt = FORMATS[args.format]
     fin = sys.stdin.buffer if args.inp == "-" else open(args.inp, "rb")
     fout = sys.stdout.buffer if args.out == "-" else open(args.out, "wb")

@@ -298,6 +298,11 @@ int fd_op_output_update(const void* pyr, const float* w, const float* base, cons
  * noise" below with F = H, T = W, generated in registers) must be given. */
 int fd_op_score_update(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn, const float* z,
                        const unsigned long long* seeds, int draw, float cz, float* dst, int B, int H, int W, int ks, int dtype, void* stream);
+/* fd_op_score_update with the seeded plane at absolute frames: column t of image b is frame frame0[b] + t (frame0 = DEVICE int32 [B], or
+ * NULL = zeros: fd_op_score_update, bit for bit; frame0 needs seeds).  With cz == 0 neither seeds nor frame0 is read. */
+int fd_score_update_at(const void* pyr, const float* w, const float* base, float cb, const float* Y, float cy, float cn, const float* z,
+                          const unsigned long long* seeds, const int* frame0, int draw, float cz, float* dst, int B, int H, int W, int ks,
+                          int dtype, void* stream);
 /* fd_op_score_update with one time per clip and no noise term (the right-hand side of fd_score_ode_solve under per-clip step control):
  *   dst[b] = fma(cy_b, Y[b], fma(cn_b, v[b], cb_b * base[b])),  (cb_b, cy_b, cn_b) = ctab[b][0..2]   (ctab: DEVICE float [B][3])
  * The Y term of a clip is skipped when its cy_b == 0; cy lives on the device, so Y is always required.  Image b equals
@@ -312,6 +317,10 @@ int fd_op_init_state(const float* Y, const float* noise, const unsigned long lon
 /* dst = fma(cq, q, a): a, dst complex [B][F][T]; exactly one of q (complex [B][F][T]) and seeds (uint64 [B], plane (seeds[b], draw)). */
 int fd_op_caxpy(const float* a, const float* q, const unsigned long long* seeds, int draw, float cq, float* dst, int B, int F, int T,
                 void* stream);
+/* fd_op_caxpy with the seeded plane at the absolute frames frame0[b] + t (frame0 = DEVICE int32 [B], or NULL = zeros: fd_op_caxpy, bit for
+ * bit; frame0 needs seeds). */
+int fd_caxpy_at(const float* a, const float* q, const unsigned long long* seeds, const int* frame0, int draw, float cq, float* dst, int B,
+                   int F, int T, void* stream);
 /* Adaptive solvers.  n = complex elements of the state (fd_op_ode_lincomb, fd_op_ode_scaled_sq) or of ONE clip of a [B][n] state (the
  * *_clips forms, 1 <= B <= 65535: one grid row per clip).
  * dst = fma(cx, x, dt * s),  s = fma(c[m-1], k[m-1], ... fma(c[0], k[0], 0))  over the m terms kept: k, c = HOST arrays of nk <= 7 device
@@ -532,8 +541,9 @@ int fd_enhance_ragged(fd_model* m, const float* y, const int* lengths, const flo
  *     Value 1 is the clip's validation-loss time ("Validation loss" below): counter (0, 0, 0, 1), u = (r0 >> 8) * 2^-24 in [0, 1).
  *     Every other value of word 3 stays unused.
  *   - t is the ABSOLUTE frame: frame0[b] + the local frame (column) of row b, where frame0 (DEVICE int32 [B], fd_noise_fill_at /
- *     fd_enhance_chunks) says where in a longer recording the row starts; 0 <= frame0[b] and frame0[b] + T_pad < 2^31.  Every other
- *     entry point, and a NULL frame0, has frame0 = 0: t is the local frame.
+ *     fd_enhance_chunks / fd_score_enhance_chunks, every draw of the sampler / fd_op_init_state / fd_caxpy_at / fd_score_update_at)
+ *     says where in a longer recording the row starts; 0 <= frame0[b] and frame0[b] + T_pad < 2^31.  Every other entry point, and a NULL
+ *     frame0, has frame0 = 0: t is the local frame.
  *   - an even t uses (ra, rb) = (r0, r1), an odd t (r2, r3).
  *   - u1 = ((ra >> 9) + 0.5) * 2^-23 in (0, 1), u2 = (rb >> 8) * 2^-24 in [0, 1): both exact in float32.
  *   - z = sqrt(-ln u1) * (cos 2 pi u2 + i sin 2 pi u2) in float32 (logf, sqrtf, sincospif(2 u2)): complex normal with
@@ -566,7 +576,10 @@ int fd_enhance_seeded(fd_model* m, const float* y, const int* lengths, const uns
  *   normfac_in float [B]: the recording's normalisation factor (fd_normfac).  The per-row maximum is not taken: the front end divides
  *              by normfac_in[b], the back end multiplies by it; the workspace's normfac slot (fd_enhance_normfac_offset) is not written.
  * Both NULL: fd_enhance_seeded, bit for bit.  Workspace: fd_enhance_workspace_bytes(m, B, L).  A captured graph is keyed on the POINTERS
- * lengths, seeds, frame0 and normfac_in (their contents may change between replays: one graph serves every group of rows of a file). */
+ * lengths, seeds, frame0 and normfac_in (their contents may change between replays: one graph serves every group of rows of a file).
+ * The ScoreDec and regression baselines run the same rows through fd_score_enhance_chunks / fd_regression_enhance_chunks (declared with the
+ * baselines below): the same two arrays with the same meaning, frame0 applied to every draw of the score sampler; the regression model
+ * draws no noise and takes normfac_in only.  fd_normfac and fd_stitch_chunks serve the three classes alike. */
 int fd_enhance_chunks(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, const int* frame0, const float* normfac_in,
                       float sigma_fac, int N, int solver, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
 /* The front end's normalisation rule on its own: normfac_out[b] = max |y[b][0 .. len_b)|, 1 where that is <= 1e-8 (torch.isclose(., 0));
@@ -597,6 +610,8 @@ int fd_stitch_chunks(const float* rows, long long row_stride, const int* starts,
  * cross-fade absorbs it.
  * One step of a pool of sessions = one table upload and three launches whatever the number of sessions:
  *   fd_stream_gather (rings -> y [B][L], lengths' zero tails, causal factors) -> fd_enhance_chunks -> fd_stream_emit (x_hat -> outputs, tails).
+ * gather and emit know nothing of the model: with fd_score_enhance_chunks or fd_regression_enhance_chunks in the middle the same step
+ * serves a ScoreDec or a regression model (all rows of a call share one fd_score_config).
  * Both read ONE DEVICE table, an entry per row of the call (at most one row of a session per call): */
 typedef struct fd_stream_row {
   const float* ring;     /* gather: the session's input ring, ring_cap floats; absolute sample i lives at ring[i % ring_cap] */
@@ -662,6 +677,16 @@ int fd_score_enhance_seeded(fd_model* m, const float* y, const unsigned long lon
  * may change between replays) and on the values of *cfg. */
 int fd_score_enhance_ragged(fd_model* m, const float* y, const int* lengths, const float* noise, const unsigned long long* seeds,
                             const fd_score_config* cfg, float* x_hat, int B, int L, void* ws, size_t ws_bytes, int use_graph, void* stream);
+/* Long-form ("Long-form" above): fd_score_enhance_ragged on seeds (required, as lengths) plus the two optional DEVICE arrays of
+ * fd_enhance_chunks.  frame0 (int32 [B]): EVERY one of the fd_score_num_draws(cfg) planes -- the prior and each predictor / corrector
+ * draw -- is the recording's, z(seeds[b], draw, f, frame0[b] + t), so two overlapping rows see bit-identical noise where they overlap at
+ * every step of the sampler.  normfac_in (float [B]) replaces the per-row maximum in the front and the back end.  Both NULL:
+ * fd_score_enhance_ragged(seeds), bit for bit.  An invalid argument is FD_EINVAL before any launch.  Workspace:
+ * fd_enhance_workspace_bytes(m, B, L).  A captured graph is keyed on the POINTERS lengths, seeds, frame0 and normfac_in (their contents
+ * may change between replays) and on the values of *cfg. */
+int fd_score_enhance_chunks(fd_model* m, const float* y, const int* lengths, const unsigned long long* seeds, const int* frame0,
+                            const float* normfac_in, const fd_score_config* cfg, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
+                            int use_graph, void* stream);
 /* One score-network evaluation in the form the black-box ODE sampler needs (sampling/__init__.py:75-146, which drives
  * scipy.integrate.solve_ivp on the host): x, Y, out = complex64 [B][1][n_freq][T_pad]; workspace fd_model_workspace_bytes.
  *   FD_SCORE_DRIFT_PF : out = theta (Y - x) - 0.5 g(t)^2 score(x, Y, t)     (probability-flow drift, sdes.py:93-109)
@@ -711,6 +736,11 @@ int fd_regression_enhance(fd_model* m, const float* y, float* x_hat, int B, int 
  * of a row of x_hat zero, workspace fd_enhance_workspace_bytes(m, B, L), a captured graph keyed on the POINTER lengths. */
 int fd_regression_enhance_ragged(fd_model* m, const float* y, const int* lengths, float* x_hat, int B, int L, void* ws, size_t ws_bytes,
                                  int use_graph, void* stream);
+/* Long-form ("Long-form" above): fd_regression_enhance_ragged plus normfac_in (DEVICE float [B] or NULL) in place of the per-row maximum,
+ * as in fd_enhance_chunks; the model draws no noise, so there is no frame0.  NULL: fd_regression_enhance_ragged, bit for bit.  A captured
+ * graph is keyed on the POINTERS lengths and normfac_in. */
+int fd_regression_enhance_chunks(fd_model* m, const float* y, const int* lengths, const float* normfac_in, float* x_hat, int B, int L, void* ws,
+                                 size_t ws_bytes, int use_graph, void* stream);
 
 /* Per-launch timing of the dominant kernel (conv MFMA) measured with HIP events on the launch stream;
  * used by bench.py for the roofline object.  enable != 0 starts recording (forces eager launches). */
