@@ -241,6 +241,11 @@ SIGNATURES = {
     "fd_xcorr_frac_workspace_bytes": (c_size_t, [c_int] * 4),
     "fd_xcorr_lags_frac": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "fd_frac_shift": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, _P]),
+    "fd_loudness_tables": (c_int, [_P, _P, _P]),
+    "fd_loudness_workspace_bytes": (c_size_t, [c_int] * 2),
+    "fd_loudness_energies": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "fd_loudness_gate": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
+    "fd_loudness": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "fd_estimate_workspace_bytes": (c_size_t, [c_int] * 4),
     "fd_estimate_pair_stats": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "fd_select_workspace_bytes": (c_size_t, [c_int]),

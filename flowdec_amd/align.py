@@ -26,7 +26,8 @@ Sub-sample delays and polarity (eval_cli --align-frac / --align-polarity; the --
 * align_triple_frac / align_pair_frac: the signals on the intersection of their supports with [0, Lx).  A signal with j = 0 and sign = +1 is
                   cut as a view, as align_triple cuts it, so whole-sample delays give the very samples of the integer path.
 
-What is left out: clock drift (a lag that changes along the file), gain matching, and alignment inside enhance.
+What is left out: clock drift (a lag that changes along the file) and alignment inside enhance; a level difference is
+undone by loudness.py (eval_cli --match-loudness).
 
 Imports `_lib` and `batching` only (no command line).
 """

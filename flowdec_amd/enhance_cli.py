@@ -75,7 +75,9 @@ evaluation scores them (flowdec/eval/metrics.py).  `--eval-estoi` (with --eval) 
 `--eval-spectral` passes `--spectral` on: two last columns, the multi-scale STFT and mel distances; `--eval-align MS` passes `--align MS` on:
 the triples are aligned in time within +-MS milliseconds before they are scored, two last columns `lag_x_hat` and `lag_y`;
 `--eval-align-frac` and `--eval-align-polarity` (with --eval-align MS) pass `--align-frac` and `--align-polarity` on: sub-sample delays,
-and an inverted polarity undone with two further last columns `pol_x_hat` and `pol_y`.
+and an inverted polarity undone with two further last columns `pol_x_hat` and `pol_y`; `--eval-loudness` and `--eval-match-loudness` pass
+`--loudness` and `--match-loudness` on: the integrated loudness (BS.1770) of the three signals in three columns behind the metrics, and
+x_hat and y scaled to x's loudness before they are scored.
 """
 import argparse
 import collections
@@ -181,6 +183,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-align-polarity", action="store_true",
                    help="with --eval-align MS: undo an inverted polarity before scoring (eval_cli --align-polarity), two further last columns "
                         "`pol_x_hat` and `pol_y`")
+    p.add_argument("--eval-loudness", action="store_true",
+                   help="with --eval: also measure the integrated loudness of x_hat, x and y (eval_cli --loudness), three columns `lufs_x_hat`, "
+                        "`lufs_x`, `lufs_y` behind the metrics")
+    p.add_argument("--eval-match-loudness", action="store_true",
+                   help="with --eval: scale x_hat and y to the loudness of x before every metric (eval_cli --match-loudness; implies "
+                        "--eval-loudness)")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -647,7 +655,9 @@ def evaluate_triples(args, suffix: str) -> None:
                      + (["--spectral"] if getattr(args, "eval_spectral", False) else [])
                      + (["--align", repr(float(args.eval_align))] if getattr(args, "eval_align", None) is not None else [])
                      + (["--align-frac"] if getattr(args, "eval_align_frac", False) else [])
-                     + (["--align-polarity"] if getattr(args, "eval_align_polarity", False) else []))
+                     + (["--align-polarity"] if getattr(args, "eval_align_polarity", False) else [])
+                     + (["--loudness"] if getattr(args, "eval_loudness", False) else [])
+                     + (["--match-loudness"] if getattr(args, "eval_match_loudness", False) else []))
 
 
 def run_launcher(args, parser, argv: List[str]) -> RunResult:

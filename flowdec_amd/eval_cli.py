@@ -3,7 +3,7 @@ flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for t
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
                                    [--sr 48000] [--estoi] [--spectral] [--align MS [--align-frac] [--align-polarity] [--align-q 64]
-                                   [--align-taps 32]]
+                                   [--align-taps 32]] [--loudness] [--match-loudness]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -56,7 +56,19 @@ that much later through the same interpolator (align.frac_shift; csrc/fracshift.
 (align.support_frac).  `lag_x_hat` and `lag_y` then print lag_q / Q in full (an exact binary fraction for the default Q).  A signal whose
 delay is a whole number of samples is cut as --align cuts it, so such a triple scores the same bits.  --align-polarity picks the peak of
 |c| and multiplies a signal whose peak is negative by -1 before it is scored: two further last columns `pol_x_hat`, `pol_y` (1 or -1)
-and a summary line with the count of inverted signals.  No drift, no gain matching.
+and a summary line with the count of inverted signals.  No drift.
+
+--loudness and --match-loudness (off by default; without them every byte of the output is what it was, with any of the switches above)
+are for a row that plays at another level: of the seven metrics only the SI-SxR three are scale-invariant.  --loudness measures the
+integrated loudness of ITU-R BS.1770-4 / EBU R 128 (K-weighting, 400 ms blocks, the absolute and the relative gate; mono) of x_hat, x and
+y as they are scored -- after alignment and cropping -- on the GPU for all triples of the run in length-sorted ragged batches
+(csrc/loudness.hip; flowdec_amd/loudness.py loudness_batch, host yardstick integrated_loudness): three CSV columns `lufs_x_hat`, `lufs_x`,
+`lufs_y` after `mel` / `estoi` when those are on and before the `lag_*` / `pol_*` columns, and three summary lines.  A signal shorter
+than 400 ms reads nan, a silent one -inf.  The measure is defined at 48 kHz: at another --sr the signals are resampled to 48 kHz for the
+measurement only.  --match-loudness implies --loudness and then multiplies x_hat and y by the one float32 factor each that brings them
+to x's loudness (loudness.match_loudness) before every metric; the three columns report the loudness before matching.  A signal whose
+loudness, or whose reference's, is nan or -inf is left as it is, with a warning.  The coefficients and the conformance readings of the
+standard pin the host function; parity with the pyloudnorm package is UNPINNED (scripts/pin_loudness.py).
 
 The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
 (DESIGN section 9).
@@ -72,7 +84,7 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import align, metrics, specdist
+from . import align, loudness, metrics, specdist
 from .audio import RESAMPLE_HELP, load_mono, split_pair
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
@@ -81,6 +93,7 @@ ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), the l
 SPECTRAL_NAMES = specdist.NAMES     # the optional metrics of --spectral (msstft, mel), always the last two columns
 LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two (before POL_NAMES)
 POL_NAMES = ("pol_x_hat", "pol_y")  # the optional columns of --align-polarity, always the last two
+LUFS_NAMES = ("lufs_x_hat", "lufs_x", "lufs_y")  # the optional columns of --loudness, behind the metrics and before LAG_NAMES
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -130,7 +143,8 @@ class Scorer:
     batch) -> [n] (optional: only --estoi calls it); spectral(x_hats, xs, sr, batch) -> [n, 2] (msstft, mel) (optional: only --spectral
     calls it); align(as_, bs, max_lag, batch) -> int64 [n], the lag of each b against its a (optional: only --align calls it);
     align_frac(as_, bs, max_lag, Q, W, polarity, batch) -> (lag_q int64 [n], sign int32 [n]) and shift(signals, lag_q, sign, windows, Q, W,
-    batch) -> float32 tensors (optional: only --align-frac / --align-polarity call them)."""
+    batch) -> float32 tensors (optional: only --align-frac / --align-polarity call them); loudness(signals, sr, batch) -> float64 [n] in
+    LUFS (optional: only --loudness / --match-loudness call it)."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
@@ -138,6 +152,7 @@ class Scorer:
     align: Optional[Callable] = None
     align_frac: Optional[Callable] = None
     shift: Optional[Callable] = None
+    loudness: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -172,10 +187,16 @@ def _host_spectral(x_hats, xs, sr, batch):
     return np.array([(specdist.multiscale_stft_distance(h, x), specdist.mel_distance(h, x, sr)) for h, x in zip(x_hats, xs)], np.float64).reshape(-1, 2)
 
 
-# ragged batches on the device (csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/xcorr.hip)
-GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch, align.lags_batch_frac, align.shift_batch)
+def _gpu_loudness(signals, sr, batch):
+    return loudness.loudness_batch(signals, sr=sr, batch=batch)
+
+
+# ragged batches on the device (csrc/loudness.hip, csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/xcorr.hip)
+GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch, align.lags_batch_frac, align.shift_batch,
+                    _gpu_loudness)
 # the host functions of metrics.py, specdist.py and align.py, one triple at a time: the yardstick
-HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags, align.host_lags_frac, align.host_shift)
+HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags, align.host_lags_frac, align.host_shift,
+                     loudness.host_loudness)
 
 
 def metric_columns(estoi: bool = False, spectral: bool = False) -> tuple:
@@ -244,15 +265,16 @@ def _columns_of(values: np.ndarray, columns) -> tuple:
     return tuple(columns)
 
 
-def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None, lag_q=None, Q: int = 1, pols=None) -> None:
+def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None, lag_q=None, Q: int = 1, pols=None, lufs=None) -> None:
     """lags (--align): int [n, 2], written as the two last columns LAG_NAMES.  lag_q (--align-frac) instead: int [n, 2] in units of 1 / Q
-    sample, written as lag_q / Q.  pols (--align-polarity): int [n, 2] of 1 / -1, written behind them as POL_NAMES."""
+    sample, written as lag_q / Q.  pols (--align-polarity): int [n, 2] of 1 / -1, written behind them as POL_NAMES.  lufs
+    (--loudness): float64 [n, 3], written as LUFS_NAMES behind the metrics and before all of those (nan and -inf as `fmt` prints them)."""
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LAG_NAMES if lags is not None or lag_q is not None else ())
+        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LUFS_NAMES if lufs is not None else ()) + (LAG_NAMES if lags is not None or lag_q is not None else ())
                    + (POL_NAMES if pols is not None else ()))
         for i, (t, row) in enumerate(zip(triples, values)):
-            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([str(int(l)) for l in lags[i]] if lags is not None else [])
+            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([fmt(v) for v in lufs[i]] if lufs is not None else []) + ([str(int(l)) for l in lags[i]] if lags is not None else [])
                        + ([align.lag_text(l, Q) for l in lag_q[i]] if lag_q is not None else []) + ([str(int(g)) for g in pols[i]] if pols is not None else []))
 
 
@@ -276,6 +298,7 @@ class EvalResult:
     csv_path: Optional[str] = None
     lags: list = field(default_factory=list)   # --align: [(column, min, max, count of non-zero lags)], empty without it
     inverted: list = field(default_factory=list)   # --align-polarity: [(column, count of inverted signals)], empty without it
+    loudness: list = field(default_factory=list)   # --loudness: [(column, mean over its finite rows, count of finite rows)], empty without it
 
     @property
     def exit_code(self) -> int:
@@ -306,6 +329,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--align-polarity", action="store_true",
                    help="with --align MS: pick the peak of |c| and undo an inverted polarity before scoring: two further last CSV columns "
                         "`pol_x_hat` and `pol_y` (1 or -1)")
+    p.add_argument("--loudness", action="store_true",
+                   help="also measure the integrated loudness (ITU-R BS.1770-4 / EBU R 128, mono; on the GPU) of x_hat, x and y as they are "
+                        "scored: three CSV columns `lufs_x_hat`, `lufs_x`, `lufs_y` behind the metrics and three more means")
+    p.add_argument("--match-loudness", action="store_true",
+                   help="implies --loudness: scale x_hat and y to the loudness of x (one float32 factor each) before every metric; the three "
+                        "columns report the loudness before matching")
     p.add_argument("--align-q", type=int, default=align.FRAC_Q, metavar="Q", help="--align-frac: grid steps per sample (2 to 1024)")
     p.add_argument("--align-taps", type=int, default=align.FRAC_W, metavar="W", help="--align-frac: the interpolator has 2 W taps (W from 1 to 256)")
     return p
@@ -383,6 +412,37 @@ def align_signals_frac(loaded, M: int, batch: int, scorer: Scorer, frac: bool, p
     return [(cut[i], x[..., n0:n1], cut[n + i]) for i, ((_, x, _), (n0, n1)) in enumerate(zip(loaded, windows))], lag_q, sign
 
 
+def measure_loudness(signals, sr: int, batch: int, scorer: Scorer) -> np.ndarray:
+    """signals: one (x_hat, x, y) of 1-D tensors per triple, as they will be scored -> float64 [n, 3] LUFS in LUFS_NAMES order, from ONE
+    call of scorer.loudness."""
+    if scorer.loudness is None:
+        raise ValueError("measure_loudness: --loudness / --match-loudness need a Scorer with a loudness function")
+    loudness.check_rate(sr)
+    n = len(signals)
+    if not n:
+        return np.zeros((0, 3), np.float64)
+    got = np.asarray(scorer.loudness([s[k] for k in range(3) for s in signals], sr, batch), np.float64).reshape(3, n)
+    return np.ascontiguousarray(got.T)
+
+
+def match_signals(signals, lufs: np.ndarray, names: Optional[List[str]] = None):
+    """--match-loudness: x_hat and y of every triple times the float32 factor that brings them to x's loudness (loudness.match_loudness).
+    A signal whose loudness, or whose reference's, is not finite stays as it is, with a warning naming the triple."""
+    out = []
+    for i, (h, x, y) in enumerate(signals):
+        who = names[i] if names else "triple %d" % i
+        scaled = []
+        for sig, k in ((h, 0), (y, 2)):
+            if math.isfinite(lufs[i, k]) and math.isfinite(lufs[i, 1]):
+                scaled.append(loudness.match_loudness(sig, lufs[i, k], lufs[i, 1]))
+            else:
+                print(f"warning: {who}: {LUFS_NAMES[k]} = {fmt(lufs[i, k])}, {LUFS_NAMES[1]} = {fmt(lufs[i, 1])}: no loudness to match "
+                      f"(under 400 ms, silent or not finite); {'x_hat' if k == 0 else 'y'} is scored as it is", file=sys.stderr)
+                scaled.append(sig)
+        out.append((scaled[0], x, scaled[1]))
+    return out
+
+
 def lag_summary_frac(lag_q: np.ndarray, Q: int):
     """lag_summary of lag_q / Q: the minimum and the maximum as the text the CSV holds."""
     return [(name, align.lag_text(lag_q[:, k].min(), Q) if len(lag_q) else "0", align.lag_text(lag_q[:, k].max(), Q) if len(lag_q) else "0",
@@ -405,6 +465,11 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
         except ValueError as err:
             parser.error(str(err))
     check_align_args(parser, args)
+    if args.loudness or args.match_loudness:
+        try:
+            loudness.check_rate(args.sr)
+        except ValueError as err:
+            parser.error(str(err))
     triples = read_triples(args.triples)
     res = EvalResult(n_triples=len(triples), csv_path=args.out)
     kept, signals = [], []
@@ -424,22 +489,30 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
     elif max_lag is not None:
         signals, lags = align_signals(signals, max_lag, args.batch_files, scorer, names=names)
     signals = [crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat) for x_hat, x, y in signals]
+    lufs = None
+    if args.loudness or args.match_loudness:
+        lufs = measure_loudness(signals, args.sr, args.batch_files, scorer)
+        if args.match_loudness:
+            signals = match_signals(signals, lufs, names=names)
     values = score(signals, args.sr, args.batch_files, scorer, names=names, estoi=args.estoi, spectral=args.spectral)
     columns = metric_columns(args.estoi, args.spectral)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if lag_q is not None:
         pols = sign if args.align_polarity else None
-        write_csv(args.out, kept, values, columns=columns, lag_q=lag_q, Q=args.align_q, pols=pols)
+        write_csv(args.out, kept, values, columns=columns, lag_q=lag_q, Q=args.align_q, pols=pols, lufs=lufs)
         res.lags = lag_summary_frac(lag_q, args.align_q)
         res.inverted = [(name, int(np.count_nonzero(sign[:, k] < 0))) for k, name in enumerate(POL_NAMES)] if pols is not None else []
     elif lags is None:
-        write_csv(args.out, kept, values, columns=columns)
+        write_csv(args.out, kept, values, columns=columns, lufs=lufs)
     else:
-        write_csv(args.out, kept, values, columns=columns, lags=lags)
+        write_csv(args.out, kept, values, columns=columns, lags=lags, lufs=lufs)
         res.lags = lag_summary(lags)
     res.n_scored, res.means = len(kept), summary(values, columns=columns)
+    res.loudness = summary(lufs, columns=LUFS_NAMES) if lufs is not None else []
     print(f"eval: {res.n_triples} triples, {res.n_scored} rows in {args.out}, {res.n_unreadable} skipped (unreadable)")
     for name, mean, count in res.means:
+        print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
+    for name, mean, count in res.loudness:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
     for name, lo, hi, nonzero in res.lags:
         print(f"  {name:12s} min = {lo}  max = {hi}  non-zero in {nonzero} of {res.n_scored} rows")

@@ -991,6 +991,39 @@ int fd_xcorr_lags_frac(const float* a, const float* b, const int* lens_a, const 
 int fd_frac_shift(const float* s, const int* lens, int B, int Ls, const int* base, const double* taps, int W, const int* sign, const int* n0,
                   const int* n1, float* out, int Lo, void* stream);
 
+/* Loudness (still "Evaluation metrics": eval_cli --loudness / --match-loudness and loudness.LoudnessMeter; csrc/loudness.hip, host
+ * yardstick and the definition in flowdec_amd/loudness.py).  The integrated loudness of ITU-R BS.1770-4 / EBU R 128 of every clip of a
+ * ragged batch of MONO signals at 48 kHz: the K-weighting (the standard's two biquads at 48 kHz, a recursive filter in float64), the
+ * energies E[j] of the filtered signal over the sub-blocks [4800 j, 4800 (j + 1)), gating blocks of four sub-blocks
+ * (ms_j = (((E[j] + E[j+1]) + E[j+2]) + E[j+3]) / 19200) and the two gates, both taken on the mean squares (no logarithm decides a
+ * comparison): ms_j > 10^((-70 + 0.691) / 10), then ms_j > 0.1 * the mean of the blocks above the first gate.  LUFS = -0.691 +
+ * 10 log10(ms_gated) is formed by the caller.  Only whole sub-blocks are read: the last len mod 4800 samples of a clip, the row behind
+ * it and the next row are never loaded.  The filter runs parallel in time (chunks of 75 samples, 64 to a sub-block, one lane each; the
+ * chunk and sub-block states joined through the tabulated zero-input transitions) in an order of operations that csrc/loudness.hip and
+ * loudness.py state and that depends on the clip's own length only: a clip's E, ms and counts have the SAME BITS alone, in a batch, at
+ * any batch position, and cut at any multiple of 4800 samples into calls that hand the state on.  No atomics, no fused multiply-add.
+ *   x DEVICE float [B][L]; lengths DEVICE int32 [B], clamped to [0, L]; Jmax = L / 4800 (0 is allowed: nothing is filtered).
+ *   fd_loudness_energies: E_out DEVICE double [B][Jmax] (E_out[b][j] = 0.0 for j >= nsub_b; NULL only when Jmax = 0); nsub_out DEVICE
+ *     int32 [B] = len_b / 4800; state DEVICE double [B][4] in/out: the filter state at the clip's sample 0 on entry and after its last
+ *     whole sub-block on return (what a stream hands to its next call), or NULL = the zero state, nothing written back.
+ *   fd_loudness_gate: E DEVICE double [B][Jmax], nsub DEVICE int32 [B] (clamped to [0, Jmax]) -> ms_out DEVICE double [B] (ms_gated) and
+ *     counts_out DEVICE int32 [B][3] = blocks, blocks above the absolute gate, blocks above both.  Fewer than four sub-blocks: NaN and
+ *     0 0 0.  A block that is NaN or Inf (a NaN or Inf sample in a sub-block that was read): NaN and (blocks, 0, 0).  No block above the
+ *     absolute gate: 0.0 (-inf LUFS) and (blocks, 0, 0).
+ *   fd_loudness: the two in one call, E and nsub in the workspace.
+ *   fd_loudness_workspace_bytes(B, L): what both calls need (never 0 for a good shape); 0 for a bad argument.
+ *   fd_loudness_tables: HOST double [16] + [16] + [1]: the two transition matrices (75 and 4800 samples, row-major) and the absolute gate
+ *     as the library holds them (tests compare them with loudness.py's, bit for bit); no device is touched.
+ * All calls are asynchronous on `stream`, allocate nothing and launch nothing when they refuse: FD_EINVAL with a message for a NULL
+ * pointer, B outside [1, 65535], L outside [1, 0x7fffffff - 1024] (Jmax outside [0, (0x7fffffff - 1024) / 4800]) and a workspace that is
+ * not 8-byte aligned; FD_ENOMEM for a workspace that is too small. */
+int fd_loudness_tables(double* chunk16, double* sub16, double* abs_gate);
+size_t fd_loudness_workspace_bytes(int B, int L);
+int fd_loudness_energies(const float* x, const int* lengths, int B, int L, double* state, double* E_out, int* nsub_out, void* ws, size_t ws_bytes,
+                         void* stream);
+int fd_loudness_gate(const double* E, const int* nsub, int B, int Jmax, double* ms_out, int* counts_out, void* stream);
+int fd_loudness(const float* x, const int* lengths, int B, int L, double* ms_out, int* counts_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Parameter estimation: the statistics behind a FlowDec model's beta and sigma_y (the reference's scripts/estimate_flowdec_params.py;
  * flowdec_amd/estimate.py, flowdec_amd/estimate_cli.py).  Both calls are asynchronous on `stream`, allocate nothing, keep no state and
