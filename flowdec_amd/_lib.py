@@ -274,6 +274,11 @@ SIGNATURES = {
     "fd_metrics_specdist_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
     "fd_metrics_specdist": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "fd_metrics_specdist_spectra": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "fd_segsnr_tables": (c_int, [c_int, _P, _P, _P, _P, _P, _P]),
+    "fd_segsnr_plan_create": (c_int, [c_int, C.POINTER(_P)]),
+    "fd_segsnr_plan_destroy": (None, [_P]),
+    "fd_metrics_segsnr_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "fd_metrics_segsnr": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

@@ -9,25 +9,20 @@
 // FPB = max(1, 1024 / N) frame pairs of one clip, TPF = 256 / FPB threads each:
 //   load      the N samples of frame t of x_hat and x straight from the rows with the clip's own reflect indices, times the periodic Hann
 //             window (one rounding), as z = w x_hat + i w x, into LDS at the bit-reversed position
-//   FFT       radix-2 decimation-in-time butterflies u +- W v, two stages per LDS pass (N / 4 four-point groups a pass; one two-point pass
-//             first where log2 N is odd), in place, natural order out.  Twiddles W_N^m = (cos, -sin)(2 pi m / N), m < N / 2, from the plan's
-//             table.  Element i sits at i + i / 32 (one float2 of padding per 32): the early passes, whose threads stand 4 or 16 elements apart,
-//             would otherwise fold onto a quarter or a sixteenth of the banks.
+//   FFT       fft_lds.h (shared with segsnr.hip): radix-2 decimation-in-time butterflies u +- W v, two stages per LDS pass, in place,
+//             natural order out.  Twiddles W_N^m = (cos, -sin)(2 pi m / N), m < N / 2, from the plan's table.
 //   unpack    A_k = (Z_k + conj Z_{N-k}) / 2, R_k = (Z_k - conj Z_{N-k}) / 2i for k = 0..N/2, |.| in float32
 //   epilogue  the STFT terms per bin in float64; P = |.|^2 of both signals into LDS; per mel filter the band's weighted sum in float64 in
 //             ascending bin order, rounded to float32, the mel term in float64; the frame's three sums by a fixed tree over its threads (then its waves in order)
 //   finalise  one workgroup per clip adds the frames' partials scale by scale (thread i: frames i, i + 256, ..; then the tree) and divides
 //
-// x_hat == x gives exactly 0: with equal real and imaginary parts going in, Z_{N-k} is Z_k with its parts exchanged, BIT FOR BIT, at every
-// level of the decimation-in-time recursion (X_k = E_k + W^k O_k, X_{N-k} = E_{N/2-k} - W^{N/2-k} O_{N/2-k}): sums are componentwise, the
-// table has W^{N/2-m} = (-re, im) of W^m exactly, and cmul below forms re = fma(wr, vr, -(wi vi)), im = fma(wr, vi, wi vr), which the
-// exchange maps onto each other.  So A_k and R_k come out equal.  This is why the butterflies are the plain radix-2 ones, fused by two,
-// and why cmul is written with explicit roundings.
+// x_hat == x gives exactly 0: with equal real and imaginary parts going in, A_k and R_k come out equal BIT FOR BIT (fft_lds.h says why).
 #include <math.h>
 
 #include <vector>
 
 #include "common.h"
+#include "fft_lds.h"
 #include "internal.h"
 
 namespace {
@@ -46,21 +41,12 @@ struct fd_specdist_plan {
 
 namespace {
 
+using fft_lds::padi;
+
 template <int LOG2N>
-struct Geo {
-  static constexpr int N = 1 << LOG2N, F = N / 2 + 1, HOP = N / 4;
-  static constexpr int TPF = N / 4 < 256 ? N / 4 : 256;     // threads per frame pair
-  static constexpr int FPB = 256 / TPF;                     // frame pairs per workgroup
-  static constexpr int NP = N + N / 32;                     // padded row
+struct Geo : fft_lds::Geo<LOG2N> {
+  static constexpr int F = fft_lds::Geo<LOG2N>::N / 2 + 1, HOP = fft_lds::Geo<LOG2N>::N / 4;
 };
-
-__device__ __forceinline__ int padi(int i) { return i + (i >> 5); }
-
-__device__ __forceinline__ float2 cmul(float2 w, float2 v) {
-  return make_float2(__fmaf_rn(w.x, v.x, -__fmul_rn(w.y, v.y)), __fmaf_rn(w.x, v.y, __fmul_rn(w.y, v.x)));
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y)); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y)); }
 
 __device__ __forceinline__ float mag_of(float re, float im) { return sqrtf(__fmaf_rn(re, re, __fmul_rn(im, im))); }
 
@@ -106,40 +92,11 @@ __global__ __launch_bounds__(256) void specdist_kernel(const float* __restrict__
       const float w = win[n];
       v = make_float2(__fmul_rn(w, rh[m]), __fmul_rn(w, rx[m]));
     }
-    z[padi((int)(__brev((unsigned)n) >> (32 - LOG2N)))] = v;
+    z[fft_lds::bitrev_slot<LOG2N>(n)] = v;
   }
   __syncthreads();
 
-  if (LOG2N & 1) {                                            // the stage of span 1 alone: W = 1
-    for (int j = lt; j < N / 2; j += TPF) {
-      const int i0 = padi(2 * j), i1 = padi(2 * j + 1);
-      const float2 u = z[i0], v = z[i1];
-      z[i0] = cadd(u, v);
-      z[i1] = csub(u, v);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int lh = LOG2N & 1; lh < LOG2N; lh += 2) {             // the stages of span h and 2 h in one pass
-    const int h = 1 << lh;
-    for (int j = lt; j < N / 4; j += TPF) {
-      const int pos = j & (h - 1);
-      const int base = ((j - pos) << 2) + pos;
-      const int i0 = padi(base), i1 = padi(base + h), i2 = padi(base + 2 * h), i3 = padi(base + 3 * h);
-      const float2 w1 = tw[pos << (LOG2N - 1 - lh)];          // W_{2h}^pos
-      const float2 w2 = tw[pos << (LOG2N - 2 - lh)];          // W_{4h}^pos
-      const float2 w3 = tw[(pos + h) << (LOG2N - 2 - lh)];    // W_{4h}^{pos + h}
-      const float2 x0 = z[i0], x2 = z[i2];
-      const float2 v1 = cmul(w1, z[i1]), v3 = cmul(w1, z[i3]);
-      const float2 s0 = cadd(x0, v1), s1 = csub(x0, v1);
-      const float2 q2 = cmul(w2, cadd(x2, v3)), q3 = cmul(w3, csub(x2, v3));
-      z[i0] = cadd(s0, q2);
-      z[i2] = csub(s0, q2);
-      z[i1] = cadd(s1, q3);
-      z[i3] = csub(s1, q3);
-    }
-    __syncthreads();
-  }
+  fft_lds::passes<LOG2N>(z, tw, lt);
 
   double acc[3] = {0.0, 0.0, 0.0};
   float* __restrict__ ph = pw[0] + fr * F;
@@ -147,8 +104,8 @@ __global__ __launch_bounds__(256) void specdist_kernel(const float* __restrict__
   const size_t row = (size_t)b * T + t;
   for (int k = lt; k <= N / 2; k += TPF) {
     const float2 zk = z[padi(k)], zn = z[padi((N - k) & (N - 1))];
-    const float a = mag_of(0.5f * __fadd_rn(zk.x, zn.x), 0.5f * __fsub_rn(zk.y, zn.y));
-    const float r = mag_of(0.5f * __fadd_rn(zk.y, zn.y), 0.5f * __fsub_rn(zn.x, zk.x));
+    const float2 ak = fft_lds::unpack_re(zk, zn), rk = fft_lds::unpack_im(zk, zn);
+    const float a = mag_of(ak.x, ak.y), r = mag_of(rk.x, rk.y);
     ph[k] = __fmul_rn(a, a);
     px[k] = __fmul_rn(r, r);
     if (stft) {

@@ -77,7 +77,8 @@ the triples are aligned in time within +-MS milliseconds before they are scored,
 `--eval-align-frac` and `--eval-align-polarity` (with --eval-align MS) pass `--align-frac` and `--align-polarity` on: sub-sample delays,
 and an inverted polarity undone with two further last columns `pol_x_hat` and `pol_y`; `--eval-loudness` and `--eval-match-loudness` pass
 `--loudness` and `--match-loudness` on: the integrated loudness (BS.1770) of the three signals in three columns behind the metrics, and
-x_hat and y scaled to x's loudness before they are scored.
+x_hat and y scaled to x's loudness before they are scored; `--eval-ssnr` passes `--ssnr` on: two columns behind the other metrics, the
+reference's `fwSSNR` and `SSNR` (the frequency-weighted segmental SNR and the segmental SNR).
 """
 import argparse
 import collections
@@ -189,6 +190,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-match-loudness", action="store_true",
                    help="with --eval: scale x_hat and y to the loudness of x before every metric (eval_cli --match-loudness; implies "
                         "--eval-loudness)")
+    p.add_argument("--eval-ssnr", action="store_true",
+                   help="with --eval: also score the segmental SNRs (eval_cli --ssnr), two columns `fwSSNR` and `SSNR` behind the other metrics")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -657,7 +660,8 @@ def evaluate_triples(args, suffix: str) -> None:
                      + (["--align-frac"] if getattr(args, "eval_align_frac", False) else [])
                      + (["--align-polarity"] if getattr(args, "eval_align_polarity", False) else [])
                      + (["--loudness"] if getattr(args, "eval_loudness", False) else [])
-                     + (["--match-loudness"] if getattr(args, "eval_match_loudness", False) else []))
+                     + (["--match-loudness"] if getattr(args, "eval_match_loudness", False) else [])
+                     + (["--ssnr"] if getattr(args, "eval_ssnr", False) else []))
 
 
 def run_launcher(args, parser, argv: List[str]) -> RunResult:

@@ -3,7 +3,7 @@ flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for t
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
                                    [--sr 48000] [--estoi] [--spectral] [--align MS [--align-frac] [--align-polarity] [--align-q 64]
-                                   [--align-taps 32]] [--loudness] [--match-loudness]
+                                   [--align-taps 32]] [--loudness] [--match-loudness] [--ssnr]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -70,8 +70,18 @@ to x's loudness (loudness.match_loudness) before every metric; the three columns
 loudness, or whose reference's, is nan or -inf is left as it is, with a warning.  The coefficients and the conformance readings of the
 standard pin the host function; parity with the pyloudnorm package is UNPINNED (scripts/pin_loudness.py).
 
-The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL, the pysepm segmental SNRs) need outside programs or models: out of scope
-(DESIGN section 9).
+--ssnr (off by default; without it every byte of the output is what it was, with any of the switches above) adds two CSV columns,
+`fwSSNR` and `SSNR` -- the reference's names for the frequency-weighted segmental SNR and the segmental SNR it takes from the pysepm package
+(eval/metrics.py:511-547: fwSNRseg and SNRseg with 30 ms frames at 75 % overlap; Hu & Loizou's comp_fwseg.m / comp_snr.m), in the order of
+its default list -- after `estoi` / `msstft` / `mel` when those are on and before the `lufs_*`, `lag_*` and `pol_*` columns, and two
+summary lines.  Scored on the GPU in the same ragged batches (csrc/segsnr.hip: one fused kernel per frame pair, a float32 FFT in LDS and
+float64 band arithmetic; flowdec_amd/segsnr.py segsnr_batch, host yardsticks fw_segmental_snr and segmental_snr), on the signals as every
+other metric that is not scale-invariant sees them: after --align and --match-loudness.  Both drop the last frame, so a triple shorter
+than win + skip = round(0.03 sr) + floor(0.0075 sr) samples has none: NaN in those two columns and a warning.  pysepm is not available to
+the tests: the host functions are pinned against a transcription through scipy.signal.stft and the published algorithm, parity with the
+package is UNPINNED (scripts/pin_segsnr.py prints it where pysepm is importable).
+
+The reference's other metrics (PESQ, DNSMOS, SIGMOS, ViSQOL) need outside programs or models: out of scope.
 """
 import argparse
 import csv
@@ -84,13 +94,14 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import align, loudness, metrics, specdist
+from . import align, loudness, metrics, segsnr, specdist
 from .audio import RESAMPLE_HELP, load_mono, split_pair
 
 METRIC_NAMES = ("sisdr", "sisir", "sisar", "logspec_mse")
 CSV_HEADER = ("name", "x_hat", "x", "y") + METRIC_NAMES
 ESTOI_NAME = "estoi"                # the optional fifth metric (--estoi), the last column without --spectral
 SPECTRAL_NAMES = specdist.NAMES     # the optional metrics of --spectral (msstft, mel), always the last two columns
+SSNR_NAMES = segsnr.NAMES          # the optional metrics of --ssnr (fwSSNR, SSNR), behind every other metric column
 LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two (before POL_NAMES)
 POL_NAMES = ("pol_x_hat", "pol_y")  # the optional columns of --align-polarity, always the last two
 LUFS_NAMES = ("lufs_x_hat", "lufs_x", "lufs_y")  # the optional columns of --loudness, behind the metrics and before LAG_NAMES
@@ -144,7 +155,8 @@ class Scorer:
     calls it); align(as_, bs, max_lag, batch) -> int64 [n], the lag of each b against its a (optional: only --align calls it);
     align_frac(as_, bs, max_lag, Q, W, polarity, batch) -> (lag_q int64 [n], sign int32 [n]) and shift(signals, lag_q, sign, windows, Q, W,
     batch) -> float32 tensors (optional: only --align-frac / --align-polarity call them); loudness(signals, sr, batch) -> float64 [n] in
-    LUFS (optional: only --loudness / --match-loudness call it)."""
+    LUFS (optional: only --loudness / --match-loudness call it); segsnr(x_hats, xs, sr, batch) -> [n, 2] (fwSSNR, SSNR) (optional: only --ssnr
+    calls it)."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
@@ -153,6 +165,7 @@ class Scorer:
     align_frac: Optional[Callable] = None
     shift: Optional[Callable] = None
     loudness: Optional[Callable] = None
+    segsnr: Optional[Callable] = None
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -191,33 +204,45 @@ def _gpu_loudness(signals, sr, batch):
     return loudness.loudness_batch(signals, sr=sr, batch=batch)
 
 
-# ragged batches on the device (csrc/loudness.hip, csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/xcorr.hip)
+def _gpu_segsnr(x_hats, xs, sr, batch):
+    return segsnr.segsnr_batch(x_hats, xs, sr=sr, batch=batch)
+
+
+def _host_segsnr(x_hats, xs, sr, batch):
+    details = [segsnr.segsnr_detail(h, x, sr) for h, x in zip(x_hats, xs)]
+    return np.array([(d["fwssnr"], d["ssnr"]) for d in details], np.float64).reshape(-1, 2)
+
+
+# ragged batches on the device (csrc/loudness.hip, csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/segsnr.hip, csrc/xcorr.hip)
 GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch, align.lags_batch_frac, align.shift_batch,
-                    _gpu_loudness)
-# the host functions of metrics.py, specdist.py and align.py, one triple at a time: the yardstick
+                    _gpu_loudness, _gpu_segsnr)
+# the host functions of metrics.py, specdist.py, segsnr.py and align.py, one triple at a time: the yardstick
 HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags, align.host_lags_frac, align.host_shift,
-                     loudness.host_loudness)
+                     loudness.host_loudness, _host_segsnr)
 
 
-def metric_columns(estoi: bool = False, spectral: bool = False) -> tuple:
-    """The names of the value columns, in order: the four metrics, then estoi, then msstft and mel."""
-    return METRIC_NAMES + ((ESTOI_NAME,) if estoi else ()) + (SPECTRAL_NAMES if spectral else ())
+def metric_columns(estoi: bool = False, spectral: bool = False, ssnr: bool = False) -> tuple:
+    """The names of the value columns, in order: the four metrics, then estoi, then msstft and mel, then fwSSNR and SSNR."""
+    return METRIC_NAMES + ((ESTOI_NAME,) if estoi else ()) + (SPECTRAL_NAMES if spectral else ()) + (SSNR_NAMES if ssnr else ())
 
 
 def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Optional[List[str]] = None, estoi: bool = False,
-          spectral: bool = False) -> np.ndarray:
+          spectral: bool = False, ssnr: bool = False) -> np.ndarray:
     """signals: one (x_hat, x, y) of 1-D tensors per triple, cropped -> [n, 4] float64 in METRIC_NAMES order, row i for triple i whatever
     order the batches ran in.  Unequal lengths: NaN in all four; too short for the transform: NaN in the spectral column.
     estoi=True: [n, 5], the last column ESTOI (1e-5 and a warning under the 30-frame rule; NaN with the others for unequal lengths).
     spectral=True: two more last columns, msstft and mel (metric_columns gives the layout); NaN and a warning for a triple under the
-    2049-sample rule, NaN with the others for unequal lengths."""
+    2049-sample rule, NaN with the others for unequal lengths.
+    ssnr=True: two more last columns, fwSSNR and SSNR; NaN and a warning for a triple shorter than win + skip, NaN with the others for
+    unequal lengths."""
     def warn(i, msg):
         print(f"warning: {names[i] if names else 'triple %d' % i}: {msg}", file=sys.stderr)
 
     def column(idx, k):
         return [signals[i][k] for i in idx]
 
-    out = np.full((len(signals), len(metric_columns(estoi, spectral))), np.nan, np.float64)
+    out = np.full((len(signals), len(metric_columns(estoi, spectral, ssnr))), np.nan, np.float64)
+    n_spec = len(METRIC_NAMES) + (1 if estoi else 0) + (len(SPECTRAL_NAMES) if spectral else 0)     # the columns before fwSSNR
     ok = []
     for i, (h, x, y) in enumerate(signals):
         if not (h.shape[-1] == x.shape[-1] == y.shape[-1]):
@@ -248,7 +273,15 @@ def score(signals, sr: int, batch: int, scorer: Scorer = GPU_SCORER, names: Opti
         for i in sorted(set(ok) - set(long_enough)):
             warn(i, f"{signals[i][1].shape[-1]} samples: {specdist.SHORT_RULE}")
         if long_enough:
-            out[long_enough, -2:] = scorer.spectral(column(long_enough, 0), column(long_enough, 1), sr, batch)
+            out[long_enough, n_spec - 2:n_spec] = scorer.spectral(column(long_enough, 0), column(long_enough, 1), sr, batch)
+    if ssnr:
+        if scorer.segsnr is None:
+            raise ValueError("score: ssnr=True needs a Scorer with a segsnr function")
+        with_frame = [i for i in ok if signals[i][1].shape[-1] >= segsnr.min_samples(sr)]
+        for i in sorted(set(ok) - set(with_frame)):
+            warn(i, f"{signals[i][1].shape[-1]} samples: {segsnr.short_rule(sr)}")
+        if with_frame:
+            out[with_frame, n_spec:] = scorer.segsnr(column(with_frame, 0), column(with_frame, 1), sr, batch)
     return out
 
 
@@ -335,6 +368,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--match-loudness", action="store_true",
                    help="implies --loudness: scale x_hat and y to the loudness of x (one float32 factor each) before every metric; the three "
                         "columns report the loudness before matching")
+    p.add_argument("--ssnr", action="store_true",
+                   help="also score the frequency-weighted segmental SNR and the segmental SNR (pysepm's fwSNRseg / SNRseg restated; on the "
+                        "GPU): two CSV columns `fwSSNR` and `SSNR` behind the other metrics and two more means")
     p.add_argument("--align-q", type=int, default=align.FRAC_Q, metavar="Q", help="--align-frac: grid steps per sample (2 to 1024)")
     p.add_argument("--align-taps", type=int, default=align.FRAC_W, metavar="W", help="--align-frac: the interpolator has 2 W taps (W from 1 to 256)")
     return p
@@ -494,8 +530,8 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
         lufs = measure_loudness(signals, args.sr, args.batch_files, scorer)
         if args.match_loudness:
             signals = match_signals(signals, lufs, names=names)
-    values = score(signals, args.sr, args.batch_files, scorer, names=names, estoi=args.estoi, spectral=args.spectral)
-    columns = metric_columns(args.estoi, args.spectral)
+    values = score(signals, args.sr, args.batch_files, scorer, names=names, estoi=args.estoi, spectral=args.spectral, ssnr=args.ssnr)
+    columns = metric_columns(args.estoi, args.spectral, args.ssnr)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if lag_q is not None:
         pols = sign if args.align_polarity else None

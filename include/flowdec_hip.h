@@ -1253,6 +1253,45 @@ int fd_metrics_specdist(const fd_specdist_plan* plan, const float* x_hat, const 
 int fd_metrics_specdist_spectra(const fd_specdist_plan* plan, int scale, const float* x_hat, const float* x, const int* lengths, int B, int L,
                                 float* mag_hat, float* mag_x, float* mel_hat, float* mel_x, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Segmental SNRs: the segmental SNR (`SSNR`) and the frequency-weighted segmental SNR (`fwSSNR`) of an estimate x_hat against a reference
+ * x -- Hu & Loizou's comp_snr.m / comp_fwseg.m as the pysepm package restates them, which the reference's default metric list calls with
+ * frameLen 0.03 and overlap 0.75 -- over ragged batches (csrc/segsnr.hip; host yardstick and the definitions in full:
+ * flowdec_amd/segsnr.py).  Rows [B][L] float32 on the device; lengths: DEVICE int32 [B]; samples behind a clip's end are never read.  A
+ * clip's results have the SAME BITS alone, in a batch, at any batch position and next to clips of any other lengths: every partition and
+ * order of summation depends on the clip's own length only; no atomics.  Parity with the pysepm package is UNPINNED (the package is not
+ * available to the tests; scripts/pin_segsnr.py prints the comparison where it is).
+ *
+ * With win = round(0.03 sr), skip = floor(0.0075 sr), n_fft = 2^ceil(log2(2 win)), w[n] = 0.5 (1 - cos(2 pi (n + 1) / (win + 1))) and
+ * eps = 2^-52, both metrics use the frames t = 0 .. T_b - 1, T_b = (lengths[b] - win) / skip, frame t = samples [t skip, t skip + win):
+ *     SSNR_t    clip(10 log10(sum (w x)^2 / (sum (w x - w x_hat)^2 + eps) + eps), -10, 35), float64 throughout
+ *     fwSSNR_t  |DFT_n_fft(w (x + eps))| over the bins 0 .. n_fft / 2 - 1, divided by its sum over those bins, likewise for x_hat; the 25
+ *               critical bands (Gaussian filters, centres 50 Hz .. 3597.63 Hz) ce = bank . clean, pe = bank . processed;
+ *               clip(sum ce^0.2 10 log10(ce^2 / max((ce - pe)^2, eps)) / sum ce^0.2, -10, 35).  The transform is a float32 FFT in LDS of
+ *               both signals at once (fft_lds.h), each frame of each signal scaled beforehand by the power of two that brings its peak
+ *               into [1, 2) (the division by the sum cancels it); magnitudes, sums, bands and the logarithms in float64.
+ * out[b] = the means over the clip's frames.  x_hat == x scores exactly 35 in both wherever no frame of x is silent.
+ *
+ * fd_segsnr_tables (HOST memory, no GPU needed): the tables of one rate in double: dims [3] = win, skip, n_fft (may be NULL); window
+ *   [win]; twiddle [n_fft / 2][2] float32 (fd_specdist_tables'); the bank as bands: first[25], count[25] = the bins with a non-zero weight
+ *   (contiguous), weights = their values filter after filter.  Returns the number of weights, or a negative FD_* code.  window .. weights
+ *   all NULL: the count (and dims) only.  FD_EINVAL for a rate whose n_fft falls outside [128, 4096] or at which a band has no bin.
+ * fd_segsnr_plan_create: uploads the tables of one rate synchronously; nothing on the call path allocates.
+ * fd_metrics_segsnr_workspace_bytes(plan, B, L): 0 for a bad plan, B or L (1 <= B <= 65535, L >= 1).
+ * fd_metrics_segsnr: out DEVICE double [B][2] = fwSSNR, SSNR (the reference's order); frames DEVICE double [B][T][2] with
+ *   T = (L - win) / skip (0 below win + skip), may be NULL: the per-frame values, NaN in the frames t >= T_b.  A DEVICE length outside
+ *   [win + skip, L] gives NaN in everything of that clip and no out-of-bounds access.
+ * The calls are asynchronous on `stream`, allocate nothing and launch nothing when they refuse: a NULL pointer, a bad B or L and a
+ * workspace that is too small are FD_EINVAL with a message, the outputs untouched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fd_segsnr_plan fd_segsnr_plan;
+int fd_segsnr_tables(int sr, int* dims, double* window, float* twiddle, int* first, int* count, double* weights);
+int fd_segsnr_plan_create(int sr, fd_segsnr_plan** out);
+void fd_segsnr_plan_destroy(fd_segsnr_plan* plan);
+size_t fd_metrics_segsnr_workspace_bytes(const fd_segsnr_plan* plan, int B, int L);
+int fd_metrics_segsnr(const fd_segsnr_plan* plan, const float* x_hat, const float* x, const int* lengths, int B, int L, double* out,
+                      double* frames, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
