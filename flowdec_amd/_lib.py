@@ -4,6 +4,7 @@ The HIP library is the ONLY compute path of this package: if it is missing, impo
 raises -- there is no CPU / eager-PyTorch fallback.  PyTorch is used for device memory, streams
 and torch.distributed only.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -319,6 +320,45 @@ def ptr(t):
 def stream():
     """Raw hipStream_t of torch's current stream (the launch stream of every op)."""
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def cuda_device(device) -> torch.device:
+    """"cuda", "cuda:1" or a torch.device -> the torch.device with its index filled in (a bare "cuda" is the CURRENT device, now); a
+    device of another type comes back as it is, and torch.cuda is not touched for it."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+class Handle:
+    """A native handle and the name of the function that destroys it: `handle` is filled by the caller's create call and freed with the
+    object; errors at interpreter exit (the library or torch already gone) are swallowed."""
+
+    def __init__(self, destroy: str):
+        self.handle, self._destroy = C.c_void_p(), destroy
+
+    def __del__(self):
+        try:
+            if self.handle:
+                getattr(load(), self._destroy)(self.handle)
+        except Exception:
+            pass
+
+
+_PLANS = {}
+
+
+def cached_plan(device, key, make, enter: bool = True):
+    """One native plan per (device, key), created on first use under that device: make() runs inside torch.cuda.device(the resolved
+    device) -- which refuses a device that is not a GPU -- and its result is kept for the life of the process.  `key` starts with the
+    kind of plan (a string).  enter=False: make() takes care of the device itself (a Resampler does, and it has a meaning for "cpu");
+    no context is entered and torch.cuda is not touched for a device of another type."""
+    dev = cuda_device(device)
+    if (dev, key) not in _PLANS:
+        with torch.cuda.device(dev) if enter else contextlib.nullcontext():
+            _PLANS[dev, key] = make()
+    return _PLANS[dev, key]
 
 
 def dtype_id(dt):

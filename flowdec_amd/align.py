@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .batching import length_sorted_batches, padded_rows
+from .batching import ragged_batches
 
 MAX_LAG_CAP = 1 << 20       # fd_xcorr_lags refuses a larger max_lag
 
@@ -116,6 +116,26 @@ def host_lags(as_, bs, max_lag, batch=None, device=None, return_xcorr: bool = Fa
     return (lags, cs) if return_xcorr else lags
 
 
+def _xcorr_batches(as_, bs, M, batch, device, return_xcorr, outs, native):
+    """What lags_batch and lags_batch_frac share: the pairs (`_pairs`) sorted by the longer signal's length and cut into batches of
+    `batch`, each list staged as zero-padded rows of its own length (batching.ragged_batches, own_rows); native(rows of a and b, their
+    lens, B, La, Lb, c, ws, nws) makes the entry point's call and returns its results, which land in `outs`.  -> the float64
+    [n, 2 M + 1] correlations or None."""
+    lib = L.load()
+    cs = np.zeros((len(as_), 2 * M + 1), np.float64) if return_xcorr else None
+
+    def call(rows, lens, idx, Lrow):
+        B, (La, Lb) = len(idx), Lrow
+        nws = lib.fd_xcorr_workspace_bytes(B, La, Lb, M)       # (fd_xcorr_frac_workspace_bytes is the same number)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        c = torch.empty(B, 2 * M + 1, dtype=torch.float64, device=device) if return_xcorr else None
+        got = native(L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(lens[0]), L.ptr(lens[1]), B, La, Lb, L.ptr(c), L.ptr(ws), nws)
+        return got + ([c.cpu().numpy()] if return_xcorr else [])
+
+    ragged_batches((as_, bs), batch, device, call, outs + ([cs] if return_xcorr else []), own_rows=True)
+    return cs
+
+
 def lags_batch(as_, bs, max_lag, batch: int = 8, device="cuda", return_xcorr: bool = False):
     """best_lag of every (a, b) on the GPU: lists of 1-D signals of any lengths (the two of a pair may differ) -> int64 [n] (with
     return_xcorr also the float64 [n, 2 M + 1] correlations).  Sorted by the longer signal's length and cut into batches of `batch` pairs;
@@ -123,24 +143,14 @@ def lags_batch(as_, bs, max_lag, batch: int = 8, device="cuda", return_xcorr: bo
     lib = L.load()
     M = _max_lag(max_lag)
     as_, bs = _pairs(as_, bs)
-    W = 2 * M + 1
     lags = np.zeros(len(as_), np.int64)
-    cs = np.zeros((len(as_), W), np.float64) if return_xcorr else None
-    la, lb = [int(c.numel()) for c in as_], [int(c.numel()) for c in bs]
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches([max(p, q) for p, q in zip(la, lb)], batch):
-            B, La, Lb = len(idx), max(max(la[i] for i in idx), 1), max(max(lb[i] for i in idx), 1)
-            rows_a, lens_a = padded_rows([as_[i] for i in idx], La, device)
-            rows_b, lens_b = padded_rows([bs[i] for i in idx], Lb, device)
-            nws = lib.fd_xcorr_workspace_bytes(B, La, Lb, M)
-            ws = torch.empty(nws, dtype=torch.uint8, device=device)
-            out = torch.empty(B, dtype=torch.int32, device=device)
-            c = torch.empty(B, W, dtype=torch.float64, device=device) if return_xcorr else None
-            L.check(lib.fd_xcorr_lags(L.ptr(rows_a), L.ptr(rows_b), L.ptr(lens_a), L.ptr(lens_b), B, La, Lb, M, L.ptr(c), L.ptr(out), L.ptr(ws), nws,
-                                      L.stream()))
-            lags[idx] = out.cpu().numpy()
-            if return_xcorr:
-                cs[idx] = c.cpu().numpy()
+
+    def native(a, b, lens_a, lens_b, B, La, Lb, c, ws, nws):
+        out = torch.empty(B, dtype=torch.int32, device=device)
+        L.check(lib.fd_xcorr_lags(a, b, lens_a, lens_b, B, La, Lb, M, c, L.ptr(out), ws, nws, L.stream()))
+        return [out.cpu().numpy()]
+
+    cs = _xcorr_batches(as_, bs, M, batch, device, return_xcorr, [lags], native)
     return (lags, cs) if return_xcorr else lags
 
 
@@ -298,32 +308,23 @@ def lags_batch_frac(as_, bs, max_lag, Q: int = FRAC_Q, W: int = FRAC_W, polarity
     M = _max_lag(max_lag)
     Q, W = _grid(Q, W)
     as_, bs = _pairs(as_, bs)
-    Wc = 2 * M + 1
     lag_q, sign = np.zeros(len(as_), np.int64), np.ones(len(as_), np.int32)
-    cs = np.zeros((len(as_), Wc), np.float64) if return_xcorr else None
-    la, lb = [int(c.numel()) for c in as_], [int(c.numel()) for c in bs]
-    with torch.cuda.device(device):
-        bank = torch.tensor(frac_bank(Q, W)).to(device)
-        for idx in length_sorted_batches([max(p, q) for p, q in zip(la, lb)], batch):
-            B, La, Lb = len(idx), max(max(la[i] for i in idx), 1), max(max(lb[i] for i in idx), 1)
-            rows_a, lens_a = padded_rows([as_[i] for i in idx], La, device)
-            rows_b, lens_b = padded_rows([bs[i] for i in idx], Lb, device)
-            nws = lib.fd_xcorr_frac_workspace_bytes(B, La, Lb, M)
-            ws = torch.empty(nws, dtype=torch.uint8, device=device)
-            out_q = torch.empty(B, dtype=torch.int64, device=device)
-            out_s = torch.empty(B, dtype=torch.int32, device=device)
-            c = torch.empty(B, Wc, dtype=torch.float64, device=device) if return_xcorr else None
-            L.check(lib.fd_xcorr_lags_frac(L.ptr(rows_a), L.ptr(rows_b), L.ptr(lens_a), L.ptr(lens_b), B, La, Lb, M, L.ptr(bank), Q, W, int(bool(polarity)),
-                                           L.ptr(c), L.ptr(out_q), L.ptr(out_s), L.ptr(ws), nws, L.stream()))
-            lag_q[idx], sign[idx] = out_q.cpu().numpy(), out_s.cpu().numpy()
-            if return_xcorr:
-                cs[idx] = c.cpu().numpy()
+    bank = torch.tensor(frac_bank(Q, W)).to(device)
+
+    def native(a, b, lens_a, lens_b, B, La, Lb, c, ws, nws):
+        out_q = torch.empty(B, dtype=torch.int64, device=device)
+        out_s = torch.empty(B, dtype=torch.int32, device=device)
+        L.check(lib.fd_xcorr_lags_frac(a, b, lens_a, lens_b, B, La, Lb, M, L.ptr(bank), Q, W, int(bool(polarity)), c, L.ptr(out_q), L.ptr(out_s), ws, nws,
+                                       L.stream()))
+        return [out_q.cpu().numpy(), out_s.cpu().numpy()]
+
+    cs = _xcorr_batches(as_, bs, M, batch, device, return_xcorr, [lag_q, sign], native)
     return (lag_q, sign, cs) if return_xcorr else (lag_q, sign)
 
 
 def shift_batch(signals, lag_q, sign, windows, Q: int = FRAC_Q, W: int = FRAC_W, batch: int = 8, device="cuda"):
     """frac_shift of every signal over its window (n0, n1) on the GPU (fd_frac_shift) -> float32 tensors on the host, bit for bit the
-    yardstick's.  Sorted by the signal's length and cut into batches of `batch`; staged through batching.padded_rows."""
+    yardstick's.  Sorted by the signal's length and cut into batches of `batch`; staged through batching.ragged_batches."""
     lib = L.load()
     Q, W = _grid(Q, W)
     signals = [torch.as_tensor(s).reshape(-1) for s in signals]
@@ -334,20 +335,19 @@ def shift_batch(signals, lag_q, sign, windows, Q: int = FRAC_Q, W: int = FRAC_W,
     win = [(int(a), max(int(b), int(a))) for a, b in windows]
     if any(abs(v) >= 1 << 31 for bj, w in zip(split, win) for v in (bj[0], w[0], w[1])):
         raise ValueError("align: a lag or a window beyond 32 bits")
-    lens = [int(s.numel()) for s in signals]
     out = [None] * len(signals)
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches(lens, batch):
-            B, Ls, Lo = len(idx), max(max(lens[i] for i in idx), 1), max(max(win[i][1] - win[i][0] for i in idx), 1)
-            rows, dlens = padded_rows([signals[i] for i in idx], Ls, device)
-            ints = torch.tensor([[split[i][0], int(sign[i]), win[i][0], win[i][1]] for i in idx], dtype=torch.int32).t().contiguous().to(device)
-            taps = torch.from_numpy(np.stack([H[split[i][1]] for i in idx])).to(device)
-            res = torch.empty(B, Lo, dtype=torch.float32, device=device)
-            L.check(lib.fd_frac_shift(L.ptr(rows), L.ptr(dlens), B, Ls, L.ptr(ints[0]), L.ptr(taps), W, L.ptr(ints[1]), L.ptr(ints[2]), L.ptr(ints[3]),
-                                      L.ptr(res), Lo, L.stream()))
-            res = res.cpu()
-            for k, i in enumerate(idx):
-                out[i] = res[k, :win[i][1] - win[i][0]].clone()
+
+    def call(rows, lens, idx, Lrow):
+        B, Ls, Lo = len(idx), Lrow[0], max(max(win[i][1] - win[i][0] for i in idx), 1)
+        ints = torch.tensor([[split[i][0], int(sign[i]), win[i][0], win[i][1]] for i in idx], dtype=torch.int32).t().contiguous().to(device)
+        taps = torch.from_numpy(np.stack([H[split[i][1]] for i in idx])).to(device)
+        res = torch.empty(B, Lo, dtype=torch.float32, device=device)
+        L.check(lib.fd_frac_shift(L.ptr(rows[0]), L.ptr(lens[0]), B, Ls, L.ptr(ints[0]), L.ptr(taps), W, L.ptr(ints[1]), L.ptr(ints[2]), L.ptr(ints[3]),
+                                  L.ptr(res), Lo, L.stream()))
+        res = res.cpu()
+        return [[res[k, :win[i][1] - win[i][0]].clone() for k, i in enumerate(idx)]]
+
+    ragged_batches((signals,), batch, device, call, [out], own_rows=True)     # (own_rows: a signal may be empty)
     return out
 
 

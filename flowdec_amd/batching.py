@@ -5,9 +5,12 @@
 * Length-sorted batches (`length_sorted_batches`): the metric and resampler kernels take rows of any lengths, so similar lengths share a
   call and little of a row is padding.
 * `padded_rows`: clips -> zero-padded rows [B, Lrow] on the device with their int32 lengths, for every ragged call.
+* `as_clips`, `ragged_batches`: the ONE loop over length-sorted batches that every measurement (metrics, specdist, segsnr, loudness,
+  align) makes its native calls from.
 
 Imports `_lib` and `ops` only.
 """
+import contextlib
 from typing import List, Sequence, Tuple
 
 import torch
@@ -97,3 +100,40 @@ def padded_rows(clips, Lrow: int, device, out=None):
             block[b, :lens[b]].copy_(c)
         rows = block.to(dev) if out is None else out.copy_(block)
     return rows, torch.tensor(lens, dtype=torch.int32).to(dev)
+
+
+def as_clips(*lists):
+    """The signals of every list as 1-D tensors: one entry per clip in each list, the signals of one clip equally long and not empty."""
+    out = [[torch.as_tensor(c).reshape(-1) for c in l] for l in lists]
+    n = len(out[0])
+    for l in out[1:]:
+        if len(l) != n:
+            raise ValueError("metrics: the lists must have one entry per clip each")
+    for i in range(n):
+        if len({int(l[i].numel()) for l in out}) != 1:
+            raise ValueError(f"metrics: the signals of clip {i} differ in length ({[int(l[i].numel()) for l in out]})")
+        if out[0][i].numel() < 1:
+            raise ValueError(f"metrics: clip {i} is empty")
+    return out
+
+
+def ragged_batches(lists, batch, device, call, outs, own_rows: bool = False, host_call: bool = False):
+    """The loop of every measurement's batch function: the clips of `lists` (one list of 1-D tensors per signal) in length-sorted batches
+    of `batch` as zero-padded rows on `device`; call(rows, lens, idx, Lrow) makes the native call for the clips `idx` and returns one
+    sequence per entry of `outs`, whose k-th item lands in outs[.][idx[k]] (an array or a list).  What belongs to single clips (a lag, a
+    window) `call` builds from `idx`.
+    The signals of a clip are equally long (`as_clips`): rows = one [B, Lrow] tensor per list, lens = their int32 [B] lengths, Lrow = the
+    batch's longest clip.  own_rows: the signals of a clip may differ in length, even be empty; clips are sorted by their longest signal and
+    every list is staged at its OWN row length, at least 1: lens and Lrow are then lists, one entry per list.
+    A device that is not a GPU is refused by torch.cuda.device before anything is staged: `call` hands the rows to a kernel.  host_call:
+    `call` runs on the host (a test's stand-in); device "cpu" then stages on the host and torch.cuda is never touched."""
+    dev = L.cuda_device(device)
+    lengths = [[int(c.numel()) for c in l] for l in lists]
+    with contextlib.nullcontext() if host_call and dev.type != "cuda" else torch.cuda.device(dev):
+        for idx in length_sorted_batches([max(ls) for ls in zip(*lengths)], batch):
+            Lrows = [max(max(ls[i] for i in idx), 1) for ls in lengths]
+            staged = [padded_rows([l[i] for i in idx], Lrow, dev) for l, Lrow in zip(lists, Lrows)]
+            rows, lens = [r for r, _ in staged], [n for _, n in staged]
+            for out, got in zip(outs, call(rows, lens, idx, Lrows) if own_rows else call(rows, lens[0], idx, Lrows[0])):
+                for k, i in enumerate(idx):
+                    out[i] = got[k]

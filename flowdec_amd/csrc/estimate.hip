@@ -17,8 +17,8 @@
 // synchronisation between the passes.  Ranks that still share their prefix share one histogram (`leader`).
 #include <limits.h>
 
-#include "common.h"
 #include "internal.h"
+#include "measure_common.h"
 
 namespace {
 
@@ -118,8 +118,6 @@ pair_layout pair_bytes(int B, int L, int n_fft, int hop) {
   s.total = 2 * s.clip + 3 * s.plane;      // x / normfac, y / normfac; frames, spec_x, spec_y
   return s;
 }
-
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
 
 // ---- radix select ---------------------------------------------------------------------------------------------------------------------
 constexpr int SEL_MAX_R = 8, SEL_PASSES = 4, SEL_BINS = 256;

@@ -10,10 +10,17 @@
 // table has W^{N/2-m} = (-re, im) of W^m exactly, and cmul below forms re = fma(wr, vr, -(wi vi)), im = fma(wr, vi, wi vr), which the
 // exchange maps onto each other.  This is why the butterflies are the plain radix-2 ones, fused by two, and why cmul is written with
 // explicit roundings.
+//
+// Around the transform: the run-time choice of LOG2N (dispatch, both files) and the reduction over the threads of one frame that leaves
+// the result in all of them (frame_all, segsnr.hip).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace fft_lds {
+
+constexpr int MIN_LOG2N = 7, MAX_LOG2N = 12;                // the transform lengths 128 .. 4096 that dispatch() instantiates
 
 template <int LOG2N>
 struct Geo {
@@ -22,6 +29,53 @@ struct Geo {
   static constexpr int FPB = 256 / TPF;                     // frame pairs per workgroup of 256 threads
   static constexpr int NP = N + N / 32;                     // padded row
 };
+
+// f(std::integral_constant<int, LOG2N>()) for the run-time log2n in [MIN_LOG2N, MAX_LOG2N] (host; the callers have checked the range)
+template <typename F>
+inline void dispatch(int log2n, F&& f) {
+  switch (log2n) {
+    case 7: f(std::integral_constant<int, 7>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 9: f(std::integral_constant<int, 9>()); break;
+    case 10: f(std::integral_constant<int, 10>()); break;
+    case 11: f(std::integral_constant<int, 11>()); break;
+    default: f(std::integral_constant<int, 12>()); break;
+  }
+}
+
+// The sums (and the maxima) of one frame over its TPF threads, the result in every thread of the frame: a butterfly over the frame's
+// lanes of a wave (v_i + v_{i ^ o} is the same number on both sides), then the frame's waves in index order through red[wave][q].
+// Every thread of the workgroup calls it.  segsnr_kernel needs the result in every thread (each divides by the frame's sums and scales
+// by its peaks).  specdist_kernel deliberately does not call it: only lane 0 of a frame stores there, so it runs the same order as a
+// one-sided tree without the broadcast.
+template <int TPF, int Q, bool MAX>
+__device__ __forceinline__ void frame_all(double (&v)[Q], double (*red)[4], int fr) {
+  static_assert(Q <= 4, "red holds four quantities a wave");
+  constexpr int W = TPF < 64 ? TPF : 64, WPF = TPF / W;      // lanes of a frame in one wave, waves of a frame
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+      const double u = __shfl_xor(v[q], o, 64);
+      v[q] = MAX ? fmax(v[q], u) : v[q] + u;
+    }
+  }
+  if (WPF > 1) {
+    __syncthreads();                                          // the last readers of red are done
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) red[threadIdx.x >> 6][q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      double r = red[fr * WPF][q];
+#pragma unroll
+      for (int w = 1; w < WPF; ++w) r = MAX ? fmax(r, red[fr * WPF + w][q]) : r + red[fr * WPF + w][q];
+      v[q] = r;
+    }
+  }
+}
 
 __device__ __forceinline__ int padi(int i) { return i + (i >> 5); }
 

@@ -11,8 +11,8 @@
 //                     elements [j SQ_CHUNK, (j + 1) SQ_CHUNK); thread k adds elements k, k + 256, ... in that order, the 256 thread sums
 //                     are added by a fixed LDS tree.  Stage 2: one workgroup per clip adds the partials the same way.  The order depends on
 //                     F T_pad only, there is no floating-point atomic, and a clip's bits do not depend on the batch.
-#include "common.h"
 #include "internal.h"
+#include "measure_common.h"
 #include "noise.h"
 
 namespace {
@@ -191,8 +191,6 @@ __global__ __launch_bounds__(256) void loss_sqerr_finish_kernel(const double* __
 inline bool plane_ok(int B, int F, int T) { return B >= 1 && B <= 65535 && F >= 1 && T >= 1 && (long long)F * T <= (1LL << 30); }
 inline int sq_blocks(int F, int T) { return fd_cdiv((long long)F * T, SQ_CHUNK); }
 inline size_t sq_part_bytes(int B, int F, int T) { return fd_align(8 * (size_t)B * sq_blocks(F, T)); }
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
-
 template <int KIND>
 void launch_state(const state_args& a, bool seeded, int B, hipStream_t st) {
   const int n = a.F * a.T;

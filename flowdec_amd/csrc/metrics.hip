@@ -26,8 +26,8 @@
 
 #include <algorithm>
 
-#include "common.h"
 #include "internal.h"
+#include "measure_common.h"
 
 namespace {
 
@@ -35,29 +35,21 @@ constexpr int PARTS = 128;          // slices per clip of the SI-SxR passes (a 3
 constexpr int Q1 = 7, Q2 = 4;       // quantities of pass 1 / pass 2
 constexpr int LOGSPEC_TILE_T = 8;   // frames per epilogue workgroup
 
-__device__ __forceinline__ int sisxr_len(const int* __restrict__ lens, int b, int L) {
-  const int l = lens[b];
-  return l < 0 ? 0 : (l > L ? L : l);      // clamped into the row: a wrong length gives a wrong number, never an out-of-bounds read
-}
-
-// acc[q] of the 256 threads -> out[q]: wave reduction, then the four waves in index order
+// acc[q] of the 256 threads -> out[q] (fd_block_sums' fixed order)
 template <int Q>
 __device__ __forceinline__ void block_sums(double (&acc)[Q], double* __restrict__ out) {
-  __shared__ double red[4][Q];
+  fd_block_sums<Q>(acc);
+  if (threadIdx.x == 0) {
 #pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    const double v = fd_wave_sum(acc[q]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+    for (int q = 0; q < Q; ++q) out[q] = acc[q];
   }
-  __syncthreads();
-  if (threadIdx.x < Q) out[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
 // part1[b][j][0..6] = x.y, x.x, x_hat.x, x_hat.(y - x), |y - x|^2, x_hat.(y + x), |y + x|^2 over slice j of clip b
 __global__ __launch_bounds__(256) void sisxr_pass1_kernel(const float* __restrict__ xh, const float* __restrict__ x, const float* __restrict__ y,
                                                           const int* __restrict__ lens, int L, double* __restrict__ part1) {
   const int b = blockIdx.y, j = blockIdx.x;
-  const long long n = sisxr_len(lens, b, L);
+  const long long n = fd_clip_len(lens, b, L);
   const long long lo = j * n / PARTS, hi = (j + 1) * n / PARTS;
   const size_t row = (size_t)b * L;
   double acc[Q1] = {0, 0, 0, 0, 0, 0, 0};
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(256) void sisxr_pass2_kernel(const float* __restric
                                                           const int* __restrict__ lens, int L, const double* __restrict__ coef,
                                                           double* __restrict__ part2) {
   const int b = blockIdx.y, j = blockIdx.x;
-  const long long n = sisxr_len(lens, b, L);
+  const long long n = fd_clip_len(lens, b, L);
   const long long lo = j * n / PARTS, hi = (j + 1) * n / PARTS;
   const size_t row = (size_t)b * L;
   const double as = coef[b * 4 + 0], an = coef[b * 4 + 1], sgn = coef[b * 4 + 2];
@@ -171,7 +163,7 @@ __global__ __launch_bounds__(64) void logspec_finalise_kernel(const double* __re
   const int b = blockIdx.x;
   if (threadIdx.x != 0) return;
   const int Tb = logspec_frames(lens, b, L, n_fft, hop);
-  if (Tb == 0) { mse[b] = __longlong_as_double(0x7ff8000000000000LL); return; }
+  if (Tb == 0) { mse[b] = fd_nan(); return; }
   const int nt = (Tb + LOGSPEC_TILE_T - 1) / LOGSPEC_TILE_T;
   double v = 0.0;
   for (int j = 0; j < nt; ++j) v += partial[(size_t)b * tiles + j];
@@ -207,8 +199,6 @@ spec_layout spec_bytes(int B, int L, int n_fft, int hop) {
   s.total = 3 * s.plane + s.partial;
   return s;
 }
-
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
 
 inline bool batch_ok(int B, int L) { return B > 0 && B <= 65535 && L > 0; }
 

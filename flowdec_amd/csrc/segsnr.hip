@@ -33,9 +33,9 @@
 
 #include <vector>
 
-#include "common.h"
 #include "fft_lds.h"
 #include "internal.h"
+#include "measure_common.h"
 
 struct fd_segsnr_plan {
   int sr, win, skip, log2n;
@@ -47,12 +47,12 @@ struct fd_segsnr_plan {
 
 namespace {
 
+using fft_lds::frame_all;
 using fft_lds::padi;
 
-constexpr int MIN_LOG2N = 7, MAX_LOG2N = 12, NBANDS = 25;
+constexpr int NBANDS = 25;
 constexpr double EPS = 2.220446049250313e-16;     // 2^-52
 constexpr double LO = -10.0, HI = 35.0;
-const double PI = 3.14159265358979323846;
 
 const double CENT[NBANDS] = {50.0, 120.0, 190.0, 260.0, 330.0, 400.0, 470.0, 540.0, 617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72,
                              1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63};
@@ -82,37 +82,6 @@ __device__ __forceinline__ double get_double(const float2* __restrict__ z, int s
   return __hiloint2double(__float_as_int(v.y), __float_as_int(v.x));
 }
 
-// The sums (and the maxima) of one frame over its TPF threads, the result in every thread of the frame: a butterfly over the frame's
-// lanes of a wave (v_i + v_{i ^ o} is the same number on both sides), then the frame's waves in index order through red[wave][q].
-// Every thread of the workgroup calls it.
-template <int TPF, int Q, bool MAX>
-__device__ __forceinline__ void frame_all(double (&v)[Q], double (*red)[4], int fr) {
-  constexpr int W = TPF < 64 ? TPF : 64, WPF = TPF / W;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-      const double u = __shfl_xor(v[q], o, 64);
-      v[q] = MAX ? fmax(v[q], u) : v[q] + u;
-    }
-  }
-  if (WPF > 1) {
-    __syncthreads();                                          // the last readers of red are done
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) red[threadIdx.x >> 6][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      double r = red[fr * WPF][q];
-#pragma unroll
-      for (int w = 1; w < WPF; ++w) r = MAX ? fmax(r, red[fr * WPF + w][q]) : r + red[fr * WPF + w][q];
-      v[q] = r;
-    }
-  }
-}
-
 // partial[b][t][0..1] = fwSSNR_t, SSNR_t of the frames t < T_b; frames [B][T][2] (or null): the same, NaN in the frames t >= T_b.
 template <int LOG2N>
 __global__ __launch_bounds__(256) void segsnr_kernel(const float* __restrict__ xh, const float* __restrict__ x, const int* __restrict__ lens, int L, int win,
@@ -128,9 +97,8 @@ __global__ __launch_bounds__(256) void segsnr_kernel(const float* __restrict__ x
   const int fr = threadIdx.x / TPF, lt = threadIdx.x % TPF, t = t0 + fr;
   if (t0 >= Tb) {                                             // (workgroup-uniform)
     if (frames && lt == 0 && t < T) {
-      const double nan = __longlong_as_double(0x7ff8000000000000LL);
-      frames[((size_t)b * T + t) * 2 + 0] = nan;
-      frames[((size_t)b * T + t) * 2 + 1] = nan;
+      frames[((size_t)b * T + t) * 2 + 0] = fd_nan();
+      frames[((size_t)b * T + t) * 2 + 1] = fd_nan();
     }
     return;
   }
@@ -221,9 +189,8 @@ __global__ __launch_bounds__(256) void segsnr_kernel(const float* __restrict__ x
       frames[row * 2 + 1] = ss;
     }
   } else if (lt == 0 && frames && t < T) {
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    frames[((size_t)b * T + t) * 2 + 0] = nan;
-    frames[((size_t)b * T + t) * 2 + 1] = nan;
+    frames[((size_t)b * T + t) * 2 + 0] = fd_nan();
+    frames[((size_t)b * T + t) * 2 + 1] = fd_nan();
   }
 }
 
@@ -231,10 +198,9 @@ __global__ __launch_bounds__(256) void segsnr_kernel(const float* __restrict__ x
 __global__ __launch_bounds__(256) void segsnr_finalise_kernel(const double* __restrict__ partial, const int* __restrict__ lens, int L, int win, int skip, int T,
                                                               double* __restrict__ out) {
   const int b = blockIdx.x;
-  __shared__ double red[4][2];
   const int Tb = frames_of(lens, b, L, win, skip);
   if (Tb == 0) {                                              // (uniform)
-    if (threadIdx.x == 0) out[b * 2 + 0] = out[b * 2 + 1] = __longlong_as_double(0x7ff8000000000000LL);
+    if (threadIdx.x == 0) out[b * 2 + 0] = out[b * 2 + 1] = fd_nan();
     return;
   }
   const double* __restrict__ p = partial + (size_t)b * T * 2;
@@ -243,13 +209,11 @@ __global__ __launch_bounds__(256) void segsnr_finalise_kernel(const double* __re
     acc[0] += p[(size_t)t * 2 + 0];
     acc[1] += p[(size_t)t * 2 + 1];
   }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const double v = fd_wave_sum(acc[q]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
+  fd_block_sums<2>(acc);
+  if (threadIdx.x == 0) {
+    out[b * 2 + 0] = acc[0] / (double)Tb;
+    out[b * 2 + 1] = acc[1] / (double)Tb;
   }
-  __syncthreads();
-  if (threadIdx.x < 2) out[b * 2 + threadIdx.x] = (((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]) / (double)Tb;
 }
 
 // ---- host: the tables ---------------------------------------------------------------------------------------------------------------
@@ -264,7 +228,7 @@ bool dims_of(int sr, dims* d) {
   d->log2n = 0;
   while ((1 << d->log2n) < 2 * d->win) ++d->log2n;
   d->n_fft = 1 << d->log2n;
-  return d->log2n >= MIN_LOG2N && d->log2n <= MAX_LOG2N;
+  return d->log2n >= fft_lds::MIN_LOG2N && d->log2n <= fft_lds::MAX_LOG2N;
 }
 
 struct banded { int first[NBANDS], count[NBANDS], off[NBANDS]; std::vector<double> w; };
@@ -296,14 +260,6 @@ bool bank_of(int sr, int n_fft, banded* out) {
   return true;
 }
 
-template <typename T>
-hipError_t upload(T** dst, const T* src, size_t n) {
-  *dst = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * n);
-  if (e == hipSuccess) e = hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice);
-  return e;
-}
-
 struct layout { int T; size_t total; };
 
 bool layout_of(const fd_segsnr_plan* p, int B, int L, layout* s) {
@@ -311,15 +267,6 @@ bool layout_of(const fd_segsnr_plan* p, int B, int L, layout* s) {
   s->T = L >= p->win + p->skip ? (L - p->win) / p->skip : 0;
   s->total = fd_align(sizeof(double) * (size_t)B * (size_t)(s->T > 0 ? s->T : 1) * 2) + 256;
   return true;
-}
-
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
-
-template <int LOG2N>
-void launch_frames(const fd_segsnr_plan* p, const float* xh, const float* x, const int* lens, int B, int L, int T, double* partial, double* frames,
-                   hipStream_t st) {
-  hipLaunchKernelGGL(segsnr_kernel<LOG2N>, dim3(fd_cdiv(T, fft_lds::Geo<LOG2N>::FPB), B), dim3(256), 0, st, xh, x, lens, L, p->win, p->skip, T, p->window,
-                     p->tw, p->band, p->wgt, partial, frames);
 }
 
 }  // namespace
@@ -394,14 +341,11 @@ extern "C" int fd_metrics_segsnr(const fd_segsnr_plan* plan, const float* x_hat,
   hipStream_t st = fd_stream(stream);
   double* partial = reinterpret_cast<double*>(aligned(ws));
   if (s.T > 0) {
-    switch (plan->log2n) {
-      case 7: launch_frames<7>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-      case 8: launch_frames<8>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-      case 9: launch_frames<9>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-      case 10: launch_frames<10>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-      case 11: launch_frames<11>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-      default: launch_frames<12>(plan, x_hat, x, lengths, B, L, s.T, partial, frames, st); break;
-    }
+    fft_lds::dispatch(plan->log2n, [&](auto k) {
+      using G = fft_lds::Geo<decltype(k)::value>;
+      hipLaunchKernelGGL(segsnr_kernel<decltype(k)::value>, dim3(fd_cdiv(s.T, G::FPB), B), dim3(256), 0, st, x_hat, x, lengths, L, plan->win, plan->skip, s.T,
+                         plan->window, plan->tw, plan->band, plan->wgt, partial, frames);
+    });
   }
   hipLaunchKernelGGL(segsnr_finalise_kernel, dim3(B), dim3(256), 0, st, partial, lengths, L, plan->win, plan->skip, s.T, out);
   FD_LAUNCH_CHECK();

@@ -21,12 +21,12 @@
 
 #include <vector>
 
-#include "common.h"
 #include "fft_lds.h"
 #include "internal.h"
+#include "measure_common.h"
 
 namespace {
-constexpr int MAX_SCALES = 16, MIN_LOG2N = 7, MAX_LOG2N = 12;
+constexpr int MAX_SCALES = 16;
 constexpr double CLAMP = 1e-5;     // clamp_eps of both losses
 }  // namespace
 
@@ -138,7 +138,9 @@ __global__ __launch_bounds__(256) void specdist_kernel(const float* __restrict__
   }
   if (!partial) return;                                       // (uniform)
 
-  // the frame's sums: a tree over its threads within a wave, then the frame's waves in index order
+  // the frame's sums: a tree over its threads within a wave, then the frame's waves in index order.  This is fft_lds::frame_all's order
+  // (lane 0 of the frame gets the same operands at every level) written for lane 0 alone: only lane 0 stores, so the sums need not reach
+  // the frame's other threads, and that saves frame_all's second barrier and its 3 WPF LDS reads a thread.
   constexpr int W = TPF < 64 ? TPF : 64, WPF = TPF / W;      // lanes of a frame in one wave, waves of a frame
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
@@ -173,8 +175,7 @@ struct fin_args {
 __global__ __launch_bounds__(256) void specdist_finalise_kernel(fin_args a, const double* __restrict__ partial, const int* __restrict__ lens, int L,
                                                                 double* __restrict__ out, double* __restrict__ terms) {
   const int b = blockIdx.x;
-  __shared__ double red[4][3];
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = fd_nan();
   double msstft = 0.0, mel = 0.0;
   for (int s = 0; s < a.n_scales; ++s) {
     const int Tb = frames_of(lens, b, L, a.min_len, a.hop[s]);
@@ -192,15 +193,9 @@ __global__ __launch_bounds__(256) void specdist_finalise_kernel(fin_args a, cons
       acc[1] += p[(size_t)t * 3 + 1];
       acc[2] += p[(size_t)t * 3 + 2];
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double v = fd_wave_sum(acc[q]);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = v;
-    }
-    __syncthreads();
+    fd_block_sums<3>(acc);
     if (threadIdx.x == 0) {
-      double m[3];
-      for (int q = 0; q < 3; ++q) m[q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+      double (&m)[3] = acc;
       m[0] = a.stft[s] ? m[0] / ((double)a.F[s] * (double)Tb) : 0.0;
       m[1] = a.stft[s] ? m[1] / ((double)a.F[s] * (double)Tb) : 0.0;
       m[2] = a.n_mels[s] > 0 ? m[2] / ((double)a.n_mels[s] * (double)Tb) : 0.0;
@@ -208,7 +203,7 @@ __global__ __launch_bounds__(256) void specdist_finalise_kernel(fin_args a, cons
       if (a.n_mels[s] > 0) mel += m[2];
       if (terms) for (int q = 0; q < 3; ++q) terms[((size_t)b * a.n_scales + s) * 3 + q] = m[q];
     }
-    __syncthreads();
+    __syncthreads();                                          // the last readers of fd_block_sums' red
   }
   if (threadIdx.x == 0) {
     out[b * 2 + 0] = msstft;
@@ -217,8 +212,6 @@ __global__ __launch_bounds__(256) void specdist_finalise_kernel(fin_args a, cons
 }
 
 // ---- host: the tables ---------------------------------------------------------------------------------------------------------------
-const double PI = 3.14159265358979323846;
-
 // cos and sin of 2 pi m / N for 0 <= m <= N / 2, the phase reduced to the first octant in integers
 void unit(int m, int N, double* c, double* s) {
   const bool mirror = m > N / 4;                  // pi - theta: cos changes sign
@@ -231,7 +224,7 @@ void unit(int m, int N, double* c, double* s) {
   *s = sr;
 }
 
-bool size_ok(int N) { return N >= (1 << MIN_LOG2N) && N <= (1 << MAX_LOG2N) && (N & (N - 1)) == 0; }
+bool size_ok(int N) { return N >= (1 << fft_lds::MIN_LOG2N) && N <= (1 << fft_lds::MAX_LOG2N) && (N & (N - 1)) == 0; }
 
 int log2_of(int N) { int l = 0; while ((1 << l) < N) ++l; return l; }
 
@@ -284,15 +277,6 @@ int tables_check(const char* who, int sr, int N, int n_mels) {
   return FD_OK;
 }
 
-template <typename T>
-hipError_t upload(T** dst, const T* src, size_t n) {
-  *dst = nullptr;
-  if (n == 0) return hipSuccess;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * n);
-  if (e == hipSuccess) e = hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice);
-  return e;
-}
-
 struct layout { long long off[MAX_SCALES]; int T[MAX_SCALES]; size_t total; };
 
 bool layout_of(const fd_specdist_plan* p, int B, int L, layout* s) {
@@ -307,25 +291,13 @@ bool layout_of(const fd_specdist_plan* p, int B, int L, layout* s) {
   return true;
 }
 
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
-
-template <int LOG2N>
-void launch_scale(const fd_specdist_plan* p, int i, const float* xh, const float* x, const int* lens, int B, int L, int T, double* partial,
-                  float* mag_hat, float* mag_x, float* mel_hat, float* mel_x, hipStream_t st) {
-  hipLaunchKernelGGL(specdist_kernel<LOG2N>, dim3(fd_cdiv(T, Geo<LOG2N>::FPB), B), dim3(256), 0, st, xh, x, lens, L, p->max_n / 2, T, p->win[i], p->tw[i],
-                     p->band[i], p->wgt[i], p->n_mels[i], p->stft[i], partial, mag_hat, mag_x, mel_hat, mel_x);
-}
-
 void launch(const fd_specdist_plan* p, int i, const float* xh, const float* x, const int* lens, int B, int L, int T, double* partial, float* mag_hat,
             float* mag_x, float* mel_hat, float* mel_x, hipStream_t st) {
-  switch (p->log2n[i]) {
-    case 7: launch_scale<7>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-    case 8: launch_scale<8>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-    case 9: launch_scale<9>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-    case 10: launch_scale<10>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-    case 11: launch_scale<11>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-    default: launch_scale<12>(p, i, xh, x, lens, B, L, T, partial, mag_hat, mag_x, mel_hat, mel_x, st); break;
-  }
+  fft_lds::dispatch(p->log2n[i], [&](auto k) {
+    constexpr int LOG2N = decltype(k)::value;
+    hipLaunchKernelGGL(specdist_kernel<LOG2N>, dim3(fd_cdiv(T, Geo<LOG2N>::FPB), B), dim3(256), 0, st, xh, x, lens, L, p->max_n / 2, T, p->win[i], p->tw[i],
+                       p->band[i], p->wgt[i], p->n_mels[i], p->stft[i], partial, mag_hat, mag_x, mel_hat, mel_x);
+  });
 }
 
 // the checks the two entry points share

@@ -20,8 +20,8 @@
 
 #include <vector>
 
-#include "common.h"
 #include "internal.h"
+#include "measure_common.h"
 
 struct fd_estoi_plan {
   double* win;     // device [256]: np.hanning(258)[1:-1]
@@ -49,8 +49,7 @@ __host__ __device__ inline int frames_of(long long len) { return len > FRAME ? (
 
 // the clip's own length at 10 kHz (o == 0: the rows are at 10 kHz already); the length is clamped into its row
 __device__ __forceinline__ int clip_len10(const int* __restrict__ lens, int b, int L, int o, int n) {
-  const int l = lens[b];
-  const int c = l < 0 ? 0 : (l > L ? L : l);
+  const int c = fd_clip_len(lens, b, L);
   return o > 0 ? (int)out_length(c, o, n) : c;
 }
 
@@ -300,8 +299,6 @@ bool layout_of(int B, int L, int o, int n, estoi_layout* s) {
   s->total = 2 * s->rows + s->energy + s->kept + s->tob + s->seg + 256;
   return true;
 }
-
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
 
 // the whole chain; kept_out / tob_out: the caller's buffers of the stage call, or null (workspace)
 int run(const char* who, const fd_estoi_plan* plan, const fd_resample_plan* rs, const float* x_hat, const float* x, const int* lengths, int B, int L,

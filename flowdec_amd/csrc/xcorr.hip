@@ -3,7 +3,7 @@
 //
 //   c[b][l + M] = sum_n a_b[n] b_b[n + l],  l in [-M, M],  n over max(0, -l) <= n < min(la, lb - l);  an empty range is exactly 0.0
 //
-// Rows a [B][La], b [B][Lb] float32; clip b = the first lens_a[b] / lens_b[b] samples of its rows (clamped into the row like sisxr_len).
+// Rows a [B][La], b [B][Lb] float32; clip b = the first lens_a[b] / lens_b[b] samples of its rows (clamped into the row by fd_clip_len).
 // The samples are float32, so every product is exact in float64 and only the float64 additions round; a term whose factor is a staged
 // zero adds exactly nothing.  Samples outside [0, len) are zeros BY DEFINITION: they are staged as zeros from the index alone and never
 // loaded, neither from the row's tail nor from the next row.  (Inputs are finite: an infinity inside a clip times such a zero would be a
@@ -37,7 +37,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "measure_common.h"
 
 namespace {
 
@@ -51,11 +51,6 @@ constexpr int MAX_ROW = 0x7fffffff - 1024;
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
-__device__ __forceinline__ int clip_len(const int* __restrict__ lens, int b, int L) {
-  const int l = lens[b];
-  return l < 0 ? 0 : (l > L ? L : l);      // clamped into the row: a wrong length gives a wrong number, never an out-of-bounds read
-}
-
 // a clip of la samples has the steps s = 0 .. la + 14 (offset 15 meets its last sample at s = la + 14)
 __host__ __device__ __forceinline__ int slices_of(long long la) { return (int)((la + 15 + SLICE - 1) / SLICE); }
 
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256) void xcorr_slice_kernel(const float* __restric
   __shared__ float sa[CHUNK + APAD];            // sa[i] = a[n0 - APAD + i]
   __shared__ float sb[CHUNK + LAG_TILE];        // sb[i] = b[n0 + l0 + i]
   const int j = blockIdx.x, tile = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
-  const long long la = clip_len(lens_a, b, La), lb = clip_len(lens_b, b, Lb);
+  const long long la = fd_clip_len(lens_a, b, La), lb = fd_clip_len(lens_b, b, Lb);
   if (j >= slices_of(la)) return;                               // not one of this clip's slices (uniform)
   const long long slice_lo = (long long)j * SLICE;
   const long long W = 2LL * M + 1;
@@ -130,15 +125,16 @@ __device__ __forceinline__ void block_best(double& v, int& l, double* __restrict
   v = sv[0]; l = sl[0];
 }
 
-// the clip's slice partials in index order -> part[b][0][.] (and c); the best of this workgroup's PICK lags -> best_v / best_l [b][blk]
+// the clip's slice partials in index order -> part[b][0][.] (and c); the best of this workgroup's PICK lags -> best_v / best_l [b][blk],
+// picked on |c| when `polarity` is set (fd_xcorr_lags_frac); the finished c is the same either way
 __global__ __launch_bounds__(256) void xcorr_finalise_kernel(double* __restrict__ part, const int* __restrict__ lens_a, int La, int M, int slices, int blocks,
-                                                             double* __restrict__ c, double* __restrict__ best_v, int* __restrict__ best_l) {
+                                                             int polarity, double* __restrict__ c, double* __restrict__ best_v, int* __restrict__ best_l) {
   __shared__ double sv[256];
   __shared__ int sl[256];
   const int b = blockIdx.y, t = threadIdx.x;
   const long long W = 2LL * M + 1;
   const long long idx = (long long)blockIdx.x * PICK + t;
-  const int ns = slices_of(clip_len(lens_a, b, La));
+  const int ns = slices_of(fd_clip_len(lens_a, b, La));
   double v = -HUGE_VAL;
   int l = INT_MAX;                          // loses every tie against a real lag
   if (idx < W) {
@@ -147,7 +143,8 @@ __global__ __launch_bounds__(256) void xcorr_finalise_kernel(double* __restrict_
     for (int j = 0; j < ns; ++j) s += p[(size_t)j * W];
     p[0] = s;
     if (c) c[(size_t)b * W + idx] = s;
-    v = s != s ? -HUGE_VAL : s;
+    const double m = polarity ? fabs(s) : s;
+    v = m != m ? -HUGE_VAL : m;
     l = (int)(idx - M);
   }
   block_best(v, l, sv, sl);
@@ -170,31 +167,6 @@ __global__ __launch_bounds__(256) void xcorr_pick_kernel(const double* __restric
 }
 
 // ---- fd_xcorr_lags_frac: the peak on a grid of 1 / Q samples, with polarity (align.py refine_lag) -----------------------------------------
-// xcorr_finalise_kernel with the best picked on |c| when `polarity` is set; the finished c is the same either way
-__global__ __launch_bounds__(256) void xcorr_finalise_pol_kernel(double* __restrict__ part, const int* __restrict__ lens_a, int La, int M, int slices, int blocks,
-                                                                 int polarity, double* __restrict__ c, double* __restrict__ best_v, int* __restrict__ best_l) {
-  __shared__ double sv[256];
-  __shared__ int sl[256];
-  const int b = blockIdx.y, t = threadIdx.x;
-  const long long W = 2LL * M + 1;
-  const long long idx = (long long)blockIdx.x * PICK + t;
-  const int ns = slices_of(clip_len(lens_a, b, La));
-  double v = -HUGE_VAL;
-  int l = INT_MAX;
-  if (idx < W) {
-    double* __restrict__ p = part + (size_t)b * slices * (size_t)W + idx;
-    double s = 0.0;
-    for (int j = 0; j < ns; ++j) s += p[(size_t)j * W];
-    p[0] = s;
-    if (c) c[(size_t)b * W + idx] = s;
-    const double m = polarity ? fabs(s) : s;
-    v = m != m ? -HUGE_VAL : m;
-    l = (int)(idx - M);
-  }
-  block_best(v, l, sv, sl);
-  if (t == 0) { best_v[(size_t)b * blocks + blockIdx.x] = v; best_l[(size_t)b * blocks + blockIdx.x] = l; }
-}
-
 // One workgroup per clip: l0 from the workgroups' winners (xcorr_pick_kernel's reduction), the sign of c[l0], then the 2 Q - 1 candidates
 // q of refine_lag from the finished c (part[b][0][.]) and the bank [Q][2 taps]: r(q) = sum_k (sign c[l0 + floor(q / Q) + k]) H[q mod Q][k],
 // k ascending, every product and sum rounded on its own (no contraction), indices outside [-M, M] left out, NaN as -inf; the best by
@@ -265,7 +237,34 @@ xcorr_layout layout(int B, int La, int max_lag) {
   return s;
 }
 
-inline char* aligned(void* ws) { return reinterpret_cast<char*>(((uintptr_t)ws + 255) / 256 * 256); }
+struct xcorr_front { xcorr_layout s; hipStream_t st; double* part; double* best_v; int* best_l; };
+
+// What fd_xcorr_lags and fd_xcorr_lags_frac (`who`) share: the checks of the batch (and of grid = {Q, W}, fractional only), the carve-up
+// of the workspace (`ws_fn` sizes it), the slice sums and the finalise kernel.  The entry point adds its own last kernel.
+// The Q / W checks sit here, behind the batch checks and ahead of the workspace check, and not in fd_xcorr_lags_frac ahead of the call:
+// that is the order a caller with several bad arguments has always been answered in.
+int front(const char* who, const char* ws_fn, const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag,
+          const int* grid, int polarity, double* c, void* ws, size_t ws_bytes, void* stream, xcorr_front* f) {
+  FD_REQUIRE(B > 0 && B <= 65535, "%s: bad batch B %d (1 <= B <= 65535)", who, B);
+  FD_REQUIRE(max_lag >= 1 && max_lag <= MAX_LAG_CAP, "%s: bad max_lag %d (1 <= max_lag <= %d)", who, max_lag, MAX_LAG_CAP);
+  FD_REQUIRE(La > 0 && La <= MAX_ROW && Lb > 0 && Lb <= MAX_ROW, "%s: bad row lengths La %d Lb %d (1 <= La, Lb <= %d)", who, La, Lb, MAX_ROW);
+  if (grid) {
+    FD_REQUIRE(grid[0] >= 2 && grid[0] <= 1024, "%s: bad grid Q %d (2 <= Q <= 1024 steps per sample)", who, grid[0]);
+    FD_REQUIRE(grid[1] >= 1 && grid[1] <= 256, "%s: bad half width W %d (1 <= W <= 256: 2 W taps)", who, grid[1]);
+  }
+  f->s = layout(B, La, max_lag);
+  const size_t need = f->s.total + 256;
+  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "%s: workspace %zu < required %zu bytes (%s)", who, ws_bytes, need, ws_fn);
+  f->st = fd_stream(stream);
+  char* base = aligned(ws);
+  f->part = reinterpret_cast<double*>(base);
+  f->best_v = reinterpret_cast<double*>(base + f->s.part);
+  f->best_l = reinterpret_cast<int*>(base + f->s.part + f->s.best_v);
+  hipLaunchKernelGGL(xcorr_slice_kernel, dim3(f->s.slices, f->s.tiles, B), dim3(256), 0, f->st, a, b, lens_a, lens_b, La, Lb, max_lag, f->s.slices, f->part);
+  hipLaunchKernelGGL(xcorr_finalise_kernel, dim3(f->s.blocks, B), dim3(256), 0, f->st, f->part, lens_a, La, max_lag, f->s.slices, f->s.blocks, polarity, c,
+                     f->best_v, f->best_l);
+  return FD_OK;
+}
 
 }  // namespace
 
@@ -277,20 +276,9 @@ extern "C" size_t fd_xcorr_workspace_bytes(int B, int La, int Lb, int max_lag) {
 extern "C" int fd_xcorr_lags(const float* a, const float* b, const int* lens_a, const int* lens_b, int B, int La, int Lb, int max_lag, double* c,
                              int* lags, void* ws, size_t ws_bytes, void* stream) {
   FD_REQUIRE(a && b && lens_a && lens_b && lags && ws, "fd_xcorr_lags: null pointer");
-  FD_REQUIRE(B > 0 && B <= 65535, "fd_xcorr_lags: bad batch B %d (1 <= B <= 65535)", B);
-  FD_REQUIRE(max_lag >= 1 && max_lag <= MAX_LAG_CAP, "fd_xcorr_lags: bad max_lag %d (1 <= max_lag <= %d)", max_lag, MAX_LAG_CAP);
-  FD_REQUIRE(La > 0 && La <= MAX_ROW && Lb > 0 && Lb <= MAX_ROW, "fd_xcorr_lags: bad row lengths La %d Lb %d (1 <= La, Lb <= %d)", La, Lb, MAX_ROW);
-  const xcorr_layout s = layout(B, La, max_lag);
-  const size_t need = s.total + 256;
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_xcorr_lags: workspace %zu < required %zu bytes (fd_xcorr_workspace_bytes)", ws_bytes, need);
-  hipStream_t st = fd_stream(stream);
-  char* base = aligned(ws);
-  double* part = reinterpret_cast<double*>(base);
-  double* best_v = reinterpret_cast<double*>(base + s.part);
-  int* best_l = reinterpret_cast<int*>(base + s.part + s.best_v);
-  hipLaunchKernelGGL(xcorr_slice_kernel, dim3(s.slices, s.tiles, B), dim3(256), 0, st, a, b, lens_a, lens_b, La, Lb, max_lag, s.slices, part);
-  hipLaunchKernelGGL(xcorr_finalise_kernel, dim3(s.blocks, B), dim3(256), 0, st, part, lens_a, La, max_lag, s.slices, s.blocks, c, best_v, best_l);
-  hipLaunchKernelGGL(xcorr_pick_kernel, dim3(B), dim3(256), 0, st, best_v, best_l, s.blocks, lags);
+  xcorr_front f;
+  FD_TRY(front("fd_xcorr_lags", "fd_xcorr_workspace_bytes", a, b, lens_a, lens_b, B, La, Lb, max_lag, nullptr, 0, c, ws, ws_bytes, stream, &f));
+  hipLaunchKernelGGL(xcorr_pick_kernel, dim3(B), dim3(256), 0, f.st, f.best_v, f.best_l, f.s.blocks, lags);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }
@@ -302,23 +290,12 @@ extern "C" int fd_xcorr_lags_frac(const float* a, const float* b, const int* len
                                   void* stream) {
   FD_REQUIRE(a && b && lens_a && lens_b && lag_q && sign && ws, "fd_xcorr_lags_frac: null pointer");
   FD_REQUIRE(bank, "fd_xcorr_lags_frac: null bank (DEVICE double [Q][2 W], align.frac_bank)");
-  FD_REQUIRE(B > 0 && B <= 65535, "fd_xcorr_lags_frac: bad batch B %d (1 <= B <= 65535)", B);
-  FD_REQUIRE(max_lag >= 1 && max_lag <= MAX_LAG_CAP, "fd_xcorr_lags_frac: bad max_lag %d (1 <= max_lag <= %d)", max_lag, MAX_LAG_CAP);
-  FD_REQUIRE(La > 0 && La <= MAX_ROW && Lb > 0 && Lb <= MAX_ROW, "fd_xcorr_lags_frac: bad row lengths La %d Lb %d (1 <= La, Lb <= %d)", La, Lb, MAX_ROW);
-  FD_REQUIRE(Q >= 2 && Q <= 1024, "fd_xcorr_lags_frac: bad grid Q %d (2 <= Q <= 1024 steps per sample)", Q);
-  FD_REQUIRE(W >= 1 && W <= 256, "fd_xcorr_lags_frac: bad half width W %d (1 <= W <= 256: 2 W taps)", W);
-  const xcorr_layout s = layout(B, La, max_lag);
-  const size_t need = s.total + 256;
-  if (ws_bytes < need) return fd_set_error(FD_ENOMEM, "fd_xcorr_lags_frac: workspace %zu < required %zu bytes (fd_xcorr_frac_workspace_bytes)", ws_bytes, need);
-  hipStream_t st = fd_stream(stream);
-  char* base = aligned(ws);
-  double* part = reinterpret_cast<double*>(base);
-  double* best_v = reinterpret_cast<double*>(base + s.part);
-  int* best_l = reinterpret_cast<int*>(base + s.part + s.best_v);
-  hipLaunchKernelGGL(xcorr_slice_kernel, dim3(s.slices, s.tiles, B), dim3(256), 0, st, a, b, lens_a, lens_b, La, Lb, max_lag, s.slices, part);
-  hipLaunchKernelGGL(xcorr_finalise_pol_kernel, dim3(s.blocks, B), dim3(256), 0, st, part, lens_a, La, max_lag, s.slices, s.blocks, polarity ? 1 : 0, c, best_v,
-                     best_l);
-  hipLaunchKernelGGL(xcorr_refine_kernel, dim3(B), dim3(256), 0, st, part, best_v, best_l, s.slices, s.blocks, max_lag, bank, Q, W, polarity ? 1 : 0, lag_q, sign);
+  const int grid[2] = {Q, W};
+  xcorr_front f;
+  FD_TRY(front("fd_xcorr_lags_frac", "fd_xcorr_frac_workspace_bytes", a, b, lens_a, lens_b, B, La, Lb, max_lag, grid, polarity ? 1 : 0, c, ws, ws_bytes, stream,
+               &f));
+  hipLaunchKernelGGL(xcorr_refine_kernel, dim3(B), dim3(256), 0, f.st, f.part, f.best_v, f.best_l, f.s.slices, f.s.blocks, max_lag, bank, Q, W, polarity ? 1 : 0,
+                     lag_q, sign);
   FD_LAUNCH_CHECK();
   return FD_OK;
 }

@@ -42,8 +42,8 @@ import torch
 
 from . import _lib as L
 from . import audio
-from . import metrics
 from . import resample as fd_resample
+from .batching import ragged_batches
 
 SR = 48000
 SUB = 4800                       # samples per sub-block: 100 ms
@@ -318,7 +318,8 @@ def energies_batch(signals, sr: int = SR, batch: int = 8, device="cuda"):
     idx = [i for i, c in enumerate(clips) if c.numel() >= SUB]
     got = np.empty(len(idx), object)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, sel, Lmax):
+        B = len(sel)
         ws, nws = _workspace(lib, B, Lmax, device)
         E = torch.empty(B, Lmax // SUB, dtype=torch.float64, device=device)
         nsub = torch.empty(B, dtype=torch.int32, device=device)
@@ -330,7 +331,7 @@ def energies_batch(signals, sr: int = SR, batch: int = 8, device="cuda"):
         return [res]
 
     if idx:
-        metrics._ragged_batches(([clips[i] for i in idx],), batch, device, call, [got])
+        ragged_batches(([clips[i] for i in idx],), batch, device, call, [got])
     for k, i in enumerate(idx):
         out[i] = got[k]
     return out
@@ -347,7 +348,8 @@ def loudness_ms_batch(signals, sr: int = SR, batch: int = 8, device="cuda"):
     idx = [i for i, c in enumerate(clips) if c.numel() > 0]
     got_ms, got_counts = np.zeros(len(idx), np.float64), np.zeros((len(idx), 3), np.int32)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, sel, Lmax):
+        B = len(sel)
         ws, nws = _workspace(lib, B, Lmax, device)
         m = torch.empty(B, dtype=torch.float64, device=device)
         c = torch.empty(B, 3, dtype=torch.int32, device=device)
@@ -355,7 +357,7 @@ def loudness_ms_batch(signals, sr: int = SR, batch: int = 8, device="cuda"):
         return [m.cpu().numpy(), c.cpu().numpy()]
 
     if idx:
-        metrics._ragged_batches(([clips[i] for i in idx],), batch, device, call, [got_ms, got_counts])
+        ragged_batches(([clips[i] for i in idx],), batch, device, call, [got_ms, got_counts])
         ms[idx], counts[idx] = got_ms, got_counts
     return ms, counts
 
@@ -376,11 +378,9 @@ class LoudnessMeter:
     input, bit for bit, however it was cut into pushes.  Another rate: put a `resample.ResampleStream` in front."""
 
     def __init__(self, device="cuda"):
-        self.dev = torch.device(device)
+        self.dev = L.cuda_device(device)
         if self.dev.type != "cuda":
             raise RuntimeError("flowdec_amd: LoudnessMeter runs on the GPU (HIP is the only compute path)")
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
         self._state = torch.zeros(1, 4, dtype=torch.float64, device=self.dev)
         self._pending = torch.empty(0, dtype=torch.float32, device=self.dev)
         self._E = torch.empty(0, dtype=torch.float64, device=self.dev)

@@ -22,10 +22,10 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .batching import length_sorted_batches, padded_rows  # noqa: F401  (length_sorted_batches: callers take it from here)
+from .batching import as_clips, length_sorted_batches, ragged_batches  # noqa: F401  (length_sorted_batches: callers take it from here)
 
 
-def _flat(a) -> np.ndarray:
+def flat(a) -> np.ndarray:
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
     return np.asarray(a, dtype=np.float64).reshape(-1) if np.asarray(a).dtype == np.float64 else np.asarray(a).reshape(-1)
@@ -40,7 +40,7 @@ def si_sxr_components(s_hat, s, n):
 def si_sxr(x_hat, x, y):
     """-> (si_sdr, si_sir, si_sar) in dB; x = reference signal, y = degraded input (noise n = y - x, or y + x when that has
     less power: the reference's global-phase-flip guard)."""
-    x_hat, x, y = _flat(x_hat), _flat(x), _flat(y)
+    x_hat, x, y = flat(x_hat), flat(x), flat(y)
     n = y - x
     if np.linalg.norm(y + x) < np.linalg.norm(y - x):
         n = y + x
@@ -52,7 +52,7 @@ def si_sxr(x_hat, x, y):
 
 def si_sdr(x_hat, x) -> float:
     """Plain scale-invariant SDR of x_hat against x (no noise decomposition), for build-vs-reference comparisons."""
-    x_hat, x = _flat(x_hat).astype(np.float64), _flat(x).astype(np.float64)
+    x_hat, x = flat(x_hat).astype(np.float64), flat(x).astype(np.float64)
     s_target = (np.dot(x_hat, x) / np.dot(x, x)) * x
     return float(10 * np.log10(np.dot(s_target, s_target) / max(np.dot(x_hat - s_target, x_hat - s_target), 1e-300)))
 
@@ -62,7 +62,7 @@ def logspec_mse(x_hat, x, sr: int = 48000, win_dur: float = 32e-3, hop_dur: floa
     win = torch.signal.windows.hann(n_fft)
 
     def logspec(a):
-        a = torch.as_tensor(np.asarray(_flat(a), dtype=np.float32))
+        a = torch.as_tensor(np.asarray(flat(a), dtype=np.float32))
         S = torch.stft(a, n_fft, hop_length=hop, win_length=n_fft, window=win, center=True, pad_mode="reflect", return_complex=True)
         return 10 * torch.log10(torch.clamp(S.abs() ** 2, min=eps))
     return float(torch.mean(torch.square(logspec(x) - logspec(x_hat))))
@@ -79,47 +79,21 @@ def sisxr_from_sums(sums) -> np.ndarray:
         return np.stack([10 * np.log10(s[:, 4] / s[:, 7]), 10 * np.log10(s[:, 4] / s[:, 5]), 10 * np.log10(s[:, 4] / s[:, 6])], axis=1)
 
 
-def _as_clips(*lists):
-    out = [[torch.as_tensor(c).reshape(-1) for c in l] for l in lists]
-    n = len(out[0])
-    for l in out[1:]:
-        if len(l) != n:
-            raise ValueError("metrics: the lists must have one entry per clip each")
-    for i in range(n):
-        if len({int(l[i].numel()) for l in out}) != 1:
-            raise ValueError(f"metrics: the signals of clip {i} differ in length ({[int(l[i].numel()) for l in out]})")
-        if out[0][i].numel() < 1:
-            raise ValueError(f"metrics: clip {i} is empty")
-    return out
-
-
-def _ragged_batches(lists, batch, device, call, outs):
-    """The loop of the three batch functions: the clips of `lists` (one list per signal, `_as_clips`) in length-sorted batches of `batch`
-    as zero-padded rows; call(rows of every list, lens, B, Lmax) makes the native call and returns one host array per entry of `outs`,
-    which lands in its rows `idx`."""
-    lengths = [int(c.numel()) for c in lists[0]]
-    with torch.cuda.device(device):
-        for idx in length_sorted_batches(lengths, batch):
-            Lmax = max(lengths[i] for i in idx)
-            staged = [padded_rows([l[i] for i in idx], Lmax, device) for l in lists]
-            for out, got in zip(outs, call([rows for rows, _ in staged], staged[0][1], len(idx), Lmax)):
-                out[idx] = got
-
-
 def si_sxr_sums_batch(x_hats, xs, ys, batch: int = 8, device="cuda") -> np.ndarray:
     """The float64 sums of fd_metrics_sisxr per clip, [n, 8] (layout SISXR_SUMS)."""
     lib = L.load()
-    x_hats, xs, ys = _as_clips(x_hats, xs, ys)
+    x_hats, xs, ys = as_clips(x_hats, xs, ys)
     out = np.zeros((len(xs), 8), np.float64)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, idx, Lmax):
+        B = len(idx)
         nws = lib.fd_metrics_workspace_bytes(B, Lmax, 0, 0)
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         sums = torch.empty(B, 8, dtype=torch.float64, device=device)
         L.check(lib.fd_metrics_sisxr(L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(rows[2]), L.ptr(lens), B, Lmax, L.ptr(sums), L.ptr(ws), nws, L.stream()))
         return [sums.cpu().numpy()]
 
-    _ragged_batches((x_hats, xs, ys), batch, device, call, [out])
+    ragged_batches((x_hats, xs, ys), batch, device, call, [out])
     return out
 
 
@@ -135,7 +109,7 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
     n_fft / 2 samples or fewer cannot be reflect-padded (torch.stft raises): ValueError naming the clip."""
     lib = L.load()
     n_fft, hop = int(win_dur * sr), int(hop_dur * sr)
-    x_hats, xs = _as_clips(x_hats, xs)
+    x_hats, xs = as_clips(x_hats, xs)
     lengths = [int(c.numel()) for c in xs]
     for i, l in enumerate(lengths):
         if l <= n_fft // 2:
@@ -143,7 +117,8 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
     out = np.zeros(len(xs), np.float64)
     plan = ops.stft_plan(n_fft, hop, device)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, idx, Lmax):
+        B = len(idx)
         nws = lib.fd_metrics_workspace_bytes(B, Lmax, n_fft, hop)
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         mse = torch.empty(B, dtype=torch.float64, device=device)
@@ -151,7 +126,7 @@ def logspec_mse_batch(x_hats, xs, sr: int = 48000, win_dur: float = 32e-3, hop_d
                                            L.stream()))
         return [mse.cpu().numpy()]
 
-    _ragged_batches((x_hats, xs), batch, device, call, [out])
+    ragged_batches((x_hats, xs), batch, device, call, [out])
     return out
 
 
@@ -255,7 +230,7 @@ def estoi_detail(x_hat, x, sr: int, precision: str = "float64", keep_spectra: bo
     if precision not in ("float64", "float32"):
         raise ValueError(f"estoi: precision is 'float64' or 'float32' (got {precision!r})")
     f32 = precision == "float32"
-    x, y = (np.asarray(_flat(a), dtype=np.float64) for a in (x, x_hat))
+    x, y = (np.asarray(flat(a), dtype=np.float64) for a in (x, x_hat))
     if len(x) != len(y):
         raise ValueError(f"estoi: the signals differ in length (x_hat {len(y)}, x {len(x)})")
     if int(sr) != ESTOI_FS:
@@ -314,53 +289,38 @@ def estoi(x_hat, x, sr: int, precision: str = "float64") -> float:
     return estoi_detail(x_hat, x, sr, precision)["value"]
 
 
-_ESTOI_PLANS = {}
-
-
 class _EstoiPlans:
-    """The device tables of fd_metrics_estoi and the 10 kHz resample plan of one rate (None at 10 kHz), created on first use."""
+    """The device tables of fd_metrics_estoi and the 10 kHz resample plan of one rate (None at 10 kHz)."""
 
     def __init__(self, sr):
         lib = L.load()
-        self.estoi, self.resample, self.o, self.n = C.c_void_p(), None, 1, 1
+        self._estoi, self._resample = L.Handle("fd_estoi_plan_destroy"), None
+        self.estoi, self.resample, self.o, self.n = self._estoi.handle, None, 1, 1
         if int(sr) != ESTOI_FS:
             bank, o, n, width = estoi_bank(sr)
             if n * bank.shape[1] > (1 << 24):
                 raise ValueError(f"estoi: the 10 kHz filter bank of {sr} Hz has {n} x {bank.shape[1]} coefficients, over the device resampler's cap")
-            self.resample, self.o, self.n = C.c_void_p(), o, n
+            self._resample = L.Handle("fd_resample_plan_destroy")
+            self.resample, self.o, self.n = self._resample.handle, o, n
             L.check(lib.fd_resample_plan_create(bank.ctypes.data_as(C.c_void_p), o, n, width, C.byref(self.resample)))
         L.check(lib.fd_estoi_plan_create(C.byref(self.estoi)))
 
-    def __del__(self):
-        try:
-            if getattr(self, "resample", None):
-                L.load().fd_resample_plan_destroy(self.resample)
-            if getattr(self, "estoi", None):
-                L.load().fd_estoi_plan_destroy(self.estoi)
-        except Exception:
-            pass
-
 
 def estoi_plans(sr: int, device="cuda") -> _EstoiPlans:
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (int(sr), str(dev))
-    if key not in _ESTOI_PLANS:
-        with torch.cuda.device(dev):
-            _ESTOI_PLANS[key] = _EstoiPlans(sr)
-    return _ESTOI_PLANS[key]
+    """The plans of one rate on one device, created on first use."""
+    return L.cached_plan(device, ("estoi", int(sr)), lambda: _EstoiPlans(sr))
 
 
 def estoi_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", return_frames: bool = False):
     """estoi of every (x_hat, x) on the GPU -> [n] float64 (with return_frames also [n, 3] int32: frames, kept, spectral frames; fewer than
     30 spectral frames: 1e-5).  Length-sorted ragged batches of `batch` clips; the plans are cached per (sr, device)."""
     lib = L.load()
-    x_hats, xs = _as_clips(x_hats, xs)
+    x_hats, xs = as_clips(x_hats, xs)
     out, frames = np.zeros(len(xs), np.float64), np.zeros((len(xs), 3), np.int32)
     plans = estoi_plans(sr, device)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, idx, Lmax):
+        B = len(idx)
         nws = lib.fd_metrics_estoi_workspace_bytes(B, Lmax, plans.o, plans.n)
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         val = torch.empty(B, dtype=torch.float64, device=device)
@@ -369,5 +329,5 @@ def estoi_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", retu
                                      L.ptr(ws), nws, L.stream()))
         return [val.cpu().numpy(), fr.cpu().numpy()]
 
-    _ragged_batches((x_hats, xs), batch, device, call, [out, frames])
+    ragged_batches((x_hats, xs), batch, device, call, [out, frames])
     return (out, frames) if return_frames else out

@@ -353,31 +353,17 @@ def ode_commit_clips(accept, ckpt, x_new, k6, x, k0, traj=None):
                                             x.numel() // B, L.stream()))
 
 
-class _StftPlan:
-    """Caller-owned fd_stft_plan (device-resident DFT matrices of one (n_fft, hop)); freed with the object."""
-
-    def __init__(self, n_fft, hop):
-        import ctypes as C
-        self.handle = C.c_void_p()
-        L.check(L.load().fd_stft_plan_create(int(n_fft), int(hop), C.byref(self.handle)))
-
-    def __del__(self):
-        try:
-            L.load().fd_stft_plan_destroy(self.handle)
-        except Exception:
-            pass
-
-
-_PLANS = {}
+def _make_stft_plan(n_fft, hop):
+    import ctypes as C
+    plan = L.Handle("fd_stft_plan_destroy")      # device-resident DFT matrices of one (n_fft, hop)
+    L.check(L.load().fd_stft_plan_create(int(n_fft), int(hop), C.byref(plan.handle)))
+    return plan
 
 
 def stft_plan(n_fft, hop, device):
-    """One plan per (device, n_fft, hop), created on first use (allocates and uploads: call it outside graph capture)."""
-    key = (torch.device(device).index, int(n_fft), int(hop))
-    if key not in _PLANS:
-        with torch.cuda.device(device):
-            _PLANS[key] = _StftPlan(n_fft, hop)
-    return _PLANS[key].handle
+    """One plan per (device, n_fft, hop), created on first use (allocates and uploads: call it outside graph capture).  A bare "cuda" is
+    the current device's plan."""
+    return L.cached_plan(device, ("stft", int(n_fft), int(hop)), lambda: _make_stft_plan(n_fft, hop)).handle
 
 
 def check_ragged_lengths(lengths, Ls, n_fft, hop):

@@ -108,8 +108,7 @@ class Resampler:
         self.device = torch.device(device)
         if self.identity:
             return
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = L.cuda_device(self.device)
         if self.device.type != "cuda":
             raise RuntimeError("flowdec_amd: Resampler runs on the GPU (HIP is the only compute path)")
         bank, width, o, n = sinc_resample_kernel(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff)
@@ -195,19 +194,12 @@ class Resampler:
         return y
 
 
-_PLANS = {}
-
-
 def get_resampler(orig_freq: int, new_freq: int, lowpass_filter_width: int = 64, rolloff: float = 0.99, device="cuda") -> Resampler:
     """The cached `Resampler` of (o, n, lowpass_filter_width, rolloff, device)."""
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    o, n, _ = rate_ratio(orig_freq, new_freq, lowpass_filter_width, rolloff)
-    key = (o, n, int(lowpass_filter_width), float(rolloff), str(dev))
-    if key not in _PLANS:
-        _PLANS[key] = Resampler(o, n, lowpass_filter_width, rolloff, dev)     # (o, n): the bank depends on the ratio only
-    return _PLANS[key]
+    dev = L.cuda_device(device)
+    o, n, _ = rate_ratio(orig_freq, new_freq, lowpass_filter_width, rolloff)     # (o, n): the bank depends on the ratio only
+    return L.cached_plan(dev, ("resample", o, n, int(lowpass_filter_width), float(rolloff)), lambda: Resampler(o, n, lowpass_filter_width, rolloff, dev),
+                         enter=False)      # (a Resampler enters its own device; equal rates need none, and "cpu" is allowed for them)
 
 
 def resample_device(y: torch.Tensor, sr: int, target: int, lowpass_filter_width: int = 64, rolloff: float = 0.99) -> torch.Tensor:

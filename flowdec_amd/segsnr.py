@@ -37,7 +37,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import _as_clips, _flat, _ragged_batches
+from .batching import as_clips, ragged_batches
+from .metrics import flat
 
 EPS = 2.0 ** -52
 MIN_SNR, MAX_SNR = -10.0, 35.0
@@ -115,7 +116,7 @@ def band_centres(sr: int, n_fft: int) -> np.ndarray:
 
 
 def _pair(x_hat, x):
-    x_hat, x = (np.asarray(_flat(a), dtype=np.float64) for a in (x_hat, x))
+    x_hat, x = (np.asarray(flat(a), dtype=np.float64) for a in (x_hat, x))
     if len(x_hat) != len(x):
         raise ValueError(f"segsnr: the signals differ in length (x_hat {len(x_hat)}, x {len(x)})")
     return x_hat, x
@@ -176,36 +177,19 @@ def tables(sr: int):
     return (win, skip, n_fft), w, tw, first, count, wgt
 
 
-_PLANS = {}
-
-
-class SegsnrPlan:
+class SegsnrPlan(L.Handle):
     """The device tables of fd_metrics_segsnr for one rate."""
 
     def __init__(self, sr):
-        lib = L.load()
-        self.sr, self.handle = int(sr), C.c_void_p()
+        super().__init__("fd_segsnr_plan_destroy")
+        self.sr = int(sr)
         self.win, self.skip, self.n_fft = frame_params(self.sr)
-        L.check(lib.fd_segsnr_plan_create(self.sr, C.byref(self.handle)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                L.load().fd_segsnr_plan_destroy(self.handle)
-        except Exception:
-            pass
+        L.check(L.load().fd_segsnr_plan_create(self.sr, C.byref(self.handle)))
 
 
 def segsnr_plan(sr: int, device="cuda") -> SegsnrPlan:
     """The plan of one rate on one device, created on first use."""
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (int(sr), str(dev))
-    if key not in _PLANS:
-        with torch.cuda.device(dev):
-            _PLANS[key] = SegsnrPlan(sr)
-    return _PLANS[key]
+    return L.cached_plan(device, ("segsnr", int(sr)), lambda: SegsnrPlan(sr))
 
 
 def segsnr_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", return_frames: bool = False):
@@ -213,11 +197,12 @@ def segsnr_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", ret
     values).  Length-sorted ragged batches of `batch` clips; one cached plan per (sr, device).  A clip shorter than win + skip has no
     frame: NaN in its row."""
     lib = L.load()
-    x_hats, xs = _as_clips(x_hats, xs)
+    x_hats, xs = as_clips(x_hats, xs)
     plan = segsnr_plan(sr, device)
     out = np.zeros((len(xs), 2), np.float64)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, idx, Lmax):
+        B = len(idx)
         T = num_frames(Lmax, sr)
         nws = lib.fd_metrics_segsnr_workspace_bytes(plan.handle, B, Lmax)
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
@@ -238,5 +223,5 @@ def segsnr_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", ret
     if return_frames:
         frames_out = np.empty(len(xs), object)
         outs.append(frames_out)
-    _ragged_batches((x_hats, xs), batch, device, call, outs)
+    ragged_batches((x_hats, xs), batch, device, call, outs)
     return (out, list(frames_out)) if return_frames else out

@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import _as_clips, _flat, _ragged_batches
+from .batching import as_clips, ragged_batches
+from .metrics import flat
 
 CLAMP_EPS = 1e-5
 MSSTFT_SCALES = (4096, 2048, 1024, 512)
@@ -89,7 +90,7 @@ def _log2(v: np.ndarray) -> np.ndarray:
 
 
 def _pair(x_hat, x):
-    x_hat, x = (np.asarray(_flat(a), dtype=np.float64) for a in (x_hat, x))
+    x_hat, x = (np.asarray(flat(a), dtype=np.float64) for a in (x_hat, x))
     if len(x_hat) != len(x):
         raise ValueError(f"specdist: the signals differ in length (x_hat {len(x_hat)}, x {len(x)})")
     return x_hat, x
@@ -150,37 +151,21 @@ def tables(sr: int, n_fft: int, n_mels: int):
     return win, tw, first[:n_mels], count[:n_mels], w[:nw]
 
 
-_PLANS = {}
-
-
-class SpecdistPlan:
+class SpecdistPlan(L.Handle):
     """The device tables of fd_metrics_specdist for one rate and one list of scales (N, n_mels or 0, stft term)."""
 
     def __init__(self, sr, scales=PLAN_SCALES):
+        super().__init__("fd_specdist_plan_destroy")
         lib = L.load()
-        self.sr, self.scales, self.handle = int(sr), tuple((int(n), int(m), bool(s)) for n, m, s in scales), C.c_void_p()
+        self.sr, self.scales = int(sr), tuple((int(n), int(m), bool(s)) for n, m, s in scales)
         k = len(self.scales)
         arr = [(C.c_int * k)(*[int(s[i]) for s in self.scales]) for i in range(3)]
         L.check(lib.fd_specdist_plan_create(self.sr, k, arr[0], arr[1], arr[2], C.byref(self.handle)))
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                L.load().fd_specdist_plan_destroy(self.handle)
-        except Exception:
-            pass
-
 
 def specdist_plan(sr: int, device="cuda") -> SpecdistPlan:
     """The default plan (PLAN_SCALES) of one rate on one device, created on first use."""
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    key = (int(sr), str(dev))
-    if key not in _PLANS:
-        with torch.cuda.device(dev):
-            _PLANS[key] = SpecdistPlan(sr)
-    return _PLANS[key]
+    return L.cached_plan(device, ("specdist", int(sr)), lambda: SpecdistPlan(sr))
 
 
 def spectral_distances_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device="cuda", return_terms: bool = False):
@@ -188,7 +173,7 @@ def spectral_distances_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device
     means of every scale of PLAN_SCALES).  Length-sorted ragged batches of `batch` clips; one cached plan per (sr, device).  A clip of 2048
     samples or fewer cannot be reflect-padded at the largest scale: ValueError naming the clip."""
     lib = L.load()
-    x_hats, xs = _as_clips(x_hats, xs)
+    x_hats, xs = as_clips(x_hats, xs)
     for i, c in enumerate(xs):
         if int(c.numel()) < MIN_SAMPLES:
             raise ValueError(f"specdist: clip {i} has {int(c.numel())} samples, {SHORT_RULE}")
@@ -196,7 +181,8 @@ def spectral_distances_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device
     k = len(plan.scales)
     out, terms = np.zeros((len(xs), 2), np.float64), np.zeros((len(xs), k, 3), np.float64)
 
-    def call(rows, lens, B, Lmax):
+    def call(rows, lens, idx, Lmax):
+        B = len(idx)
         nws = lib.fd_metrics_specdist_workspace_bytes(plan.handle, B, Lmax)
         ws = torch.empty(nws, dtype=torch.uint8, device=device)
         val = torch.empty(B, 2, dtype=torch.float64, device=device)
@@ -205,5 +191,5 @@ def spectral_distances_batch(x_hats, xs, sr: int = 48000, batch: int = 8, device
                                         L.stream()))
         return [val.cpu().numpy(), tm.cpu().numpy()]
 
-    _ragged_batches((x_hats, xs), batch, device, call, [out, terms])
+    ragged_batches((x_hats, xs), batch, device, call, [out, terms])
     return (out, terms) if return_terms else out

@@ -1,7 +1,8 @@
-"""The layering of the package's Python: _lib -> ops, noise, longform, audio, batching -> resample, metrics, estimate, loss -> model ->
-checkpoint, dist, stream -> the five *_cli.  No library module imports a command line, the function-local intra-package imports
-that remain are listed here with their reasons, and the two pieces the layers share -- `batching.padded_rows` (clips -> zero-padded rows)
-and `batching.plan_clip_batches` (the T_pad bucket plan) -- are each one function."""
+"""The layering of the package's Python: _lib -> ops, noise, longform, audio, batching -> resample, metrics, align, estimate, loss ->
+specdist, segsnr, loudness -> model -> checkpoint, dist, stream -> the five *_cli.  No library module imports a command line, the
+function-local intra-package imports that remain are listed here with their reasons, the measurement modules take nothing private from a
+sibling, and the pieces the layers share -- `batching.padded_rows` (clips -> zero-padded rows), `batching.plan_clip_batches` (the T_pad
+bucket plan) and `batching.ragged_batches` (the loop over length-sorted batches) -- are each one function."""
 import ast
 import glob
 import os
@@ -13,7 +14,9 @@ import torch
 
 from conftest import ROOT
 
-LIBRARY_MODULES = ("audio", "batching", "checkpoint", "resample", "metrics", "estimate", "loss", "dist", "stream", "longform", "noise", "ops", "model")
+LIBRARY_MODULES = ("audio", "batching", "checkpoint", "resample", "metrics", "estimate", "loss", "dist", "stream", "longform", "noise", "ops", "model",
+                   "align", "specdist", "segsnr", "loudness")
+MEASUREMENT_MODULES = ("metrics", "align", "specdist", "segsnr", "loudness")
 
 # (file, imported module) -> why the import stays inside a function
 LAZY_IMPORTS = {
@@ -50,6 +53,36 @@ def test_lazy_intra_package_imports_are_the_listed_ones():
                         found.add((os.path.basename(path), target.split(".")[0]))
     assert len(LAZY_IMPORTS) <= 4 and all(isinstance(why, str) and why for why in LAZY_IMPORTS.values())
     assert found <= set(LAZY_IMPORTS), f"function-local intra-package imports outside the allow-list: {sorted(found - set(LAZY_IMPORTS))}"
+
+
+def test_measurement_modules_take_nothing_private_from_a_sibling():
+    """None of MEASUREMENT_MODULES imports an underscore-prefixed name from another module of the package or reads one through a module
+    alias (`metrics._x`); `_lib` itself, the lowest layer, is the one module they may name.  And the loop over length-sorted batches
+    exists once in the package."""
+    siblings = {os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(ROOT, "flowdec_amd", "*.py"))}
+    found, loops = [], []
+    for path in sorted(glob.glob(os.path.join(ROOT, "flowdec_amd", "*.py"))):
+        name = os.path.splitext(os.path.basename(path))[0]
+        with open(path, "r") as f:
+            src = f.read()
+        loops += [name] * src.count("for idx in length_sorted_batches")
+        if name not in MEASUREMENT_MODULES:
+            continue
+        tree = ast.parse(src, path)
+        aliases = {}                                            # local name -> sibling module it stands for
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.level >= 1:
+                for a in node.names:
+                    if node.module is None and a.name in siblings:
+                        aliases[a.asname or a.name] = a.name    # from . import metrics [as m]
+                    if node.module is not None and a.name.startswith("_"):
+                        found.append(f"{name}: from .{node.module} import {a.name}")
+        for node in ast.walk(tree):
+            if (isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in aliases
+                    and aliases[node.value.id] != "_lib" and node.attr.startswith("_")):
+                found.append(f"{name}: {node.value.id}.{node.attr}")
+    assert not found, found
+    assert loops == ["batching"], loops
 
 
 def _clips(lengths):
