@@ -247,6 +247,11 @@ SIGNATURES = {
     "fd_loudness_energies": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "fd_loudness_gate": (c_int, [_P, _P, c_int, c_int, _P, _P, _P]),
     "fd_loudness": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "fd_true_peak_tile": (c_int, []),
+    "fd_true_peak_workspace_bytes": (c_size_t, [c_int] * 2),
+    "fd_true_peak": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
+    "fd_loudness_range_workspace_bytes": (c_size_t, [c_int] * 2),
+    "fd_loudness_range": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "fd_estimate_workspace_bytes": (c_size_t, [c_int] * 4),
     "fd_estimate_pair_stats": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "fd_select_workspace_bytes": (c_size_t, [c_int]),

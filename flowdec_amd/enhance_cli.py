@@ -78,7 +78,24 @@ the triples are aligned in time within +-MS milliseconds before they are scored,
 and an inverted polarity undone with two further last columns `pol_x_hat` and `pol_y`; `--eval-loudness` and `--eval-match-loudness` pass
 `--loudness` and `--match-loudness` on: the integrated loudness (BS.1770) of the three signals in three columns behind the metrics, and
 x_hat and y scaled to x's loudness before they are scored; `--eval-ssnr` passes `--ssnr` on: two columns behind the other metrics, the
-reference's `fwSSNR` and `SSNR` (the frequency-weighted segmental SNR and the segmental SNR).
+reference's `fwSSNR` and `SSNR` (the frequency-weighted segmental SNR and the segmental SNR); `--eval-loudness-range` and
+`--eval-true-peak` pass `--loudness-range` and `--true-peak` on: the loudness range (EBU Tech 3342) and the true peak (BS.1770-4 Annex 2)
+of the three signals, three columns each behind the `lufs_*` columns.
+
+Level of the written files: `--target-lufs VALUE|input` and `--peak-ceiling DBTP` (default off; without them nothing changes and nothing is
+measured).  A post-filter should not change the level of what it filters, and a delivery specification caps the true peak (EBU R 128: -23
+LUFS and -1 dBTP; the codec package this project restates normalises to -16 LUFS in front of its file path).  The finished output of every
+file -- the stitched output of a --chunk-seconds file included -- is measured on the GPU after, and outside, the region --rtf times: its
+integrated loudness and its true peak (loudness.file_level_batch; the level of a file is one number: where a waveform has several channels
+their K-weighted energies are added with unit weights and gated once, and the true peak is the largest of theirs -- the models here take
+one channel, so today every file has one).  ONE gain per file follows (loudness.output_gain):
+target - lufs, where the target is VALUE or, with `input`, the loudness of the file's own input measured the same way, capped so that
+dbtp + gain does not exceed the ceiling (default -1.0 with --target-lufs) -- a gain cap, not a limiter.  --peak-ceiling alone asks for 0
+dB: a file over the ceiling is turned down to it, the others stay.  Every sample gets ONE float32 multiply before the file is written.  A
+file without a finite level (under 400 ms, silent) is written as it is, with a warning.  `loudness{suffix}.csv` beside `rtfs{suffix}.csv`
+holds name, lufs, dbtp (both of the output BEFORE the gain), gain_db (nan: none) and limited (1: the ceiling capped the gain) for every
+file written in this run, in plan order; a --gpus N run merges its workers' parts into the same bytes.  A measurement is the same bits in
+any batch and on any rank, so the outputs are those of a one-process run.
 """
 import argparse
 import collections
@@ -96,7 +113,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import eval_cli, longform
+from . import eval_cli, longform, loudness
 from .audio import (load_wav, read_list, resample, resample_to, resampled_length, save_wav, sinc_resample_kernel,  # noqa: F401
                     wav_info)
 from .batching import padded_frames_of, plan_clip_batches
@@ -119,6 +136,19 @@ PRECISION_NOTE = {   # printed at start-up so that a log says which arithmetic p
 # ------------------------------------------------------------------------------------------------
 # main loop
 # ------------------------------------------------------------------------------------------------
+def target_lufs_arg(text: str):
+    """--target-lufs: `input` or a finite number of LUFS."""
+    if text.strip().lower() == "input":
+        return "input"
+    try:
+        value = float(text)
+    except ValueError:
+        value = float("nan")
+    if value != value or value in (float("inf"), float("-inf")):
+        raise argparse.ArgumentTypeError(f"{text!r} is neither a finite number of LUFS nor `input`")
+    return value
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Enhance wav files with a FlowDec postfilter (or its ScoreDec / regression baselines) on MI355X")
     p.add_argument("--ckpt", type=str, required=True)
@@ -192,6 +222,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "--eval-loudness)")
     p.add_argument("--eval-ssnr", action="store_true",
                    help="with --eval: also score the segmental SNRs (eval_cli --ssnr), two columns `fwSSNR` and `SSNR` behind the other metrics")
+    p.add_argument("--eval-loudness-range", action="store_true",
+                   help="with --eval: also measure the loudness range of x_hat, x and y (eval_cli --loudness-range), three columns `lra_*`")
+    p.add_argument("--eval-true-peak", action="store_true",
+                   help="with --eval: also measure the true peak of x_hat, x and y (eval_cli --true-peak), three columns `dbtp_*`")
+    p.add_argument("--target-lufs", type=target_lufs_arg, default=None, metavar="VALUE|input",
+                   help="bring every written file to VALUE LUFS (integrated loudness, ITU-R BS.1770-4 / EBU R 128; R 128 asks for -23, the codec "
+                        "package this project restates for -16), or with `input` to the integrated loudness of its own input file: ONE gain per "
+                        "file, measured on the finished output, applied before it is written and outside the region --rtf times; "
+                        "`loudness{suffix}.csv` (name, lufs, dbtp, gain_db, limited) records every file (default: off, the files are written "
+                        "as the model gives them)")
+    p.add_argument("--peak-ceiling", type=float, default=None, metavar="DBTP",
+                   help="cap the gain of --target-lufs so that no written file's true peak (BS.1770-4 Annex 2) exceeds DBTP (a gain cap, not a "
+                        "limiter; default -1.0 with --target-lufs, as R 128 asks).  Given alone: files over the ceiling are turned down to it, "
+                        "the others are left as they are")
     p.add_argument("--share-gpu", action="store_true", help="with --gpus N: all N <= %d workers on cuda:0 (a test aid for one-GPU boxes)" % SHARE_GPU_MAX_RANKS)
     p.add_argument("--worker-rank", type=int, default=None, help=argparse.SUPPRESS)        # set by the launcher of a --gpus N run
     p.add_argument("--worker-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -275,6 +319,13 @@ def rtf_part_name(suffix: str, rank: int) -> str:
     return f"rtfs{suffix}.rank{rank}.csv"
 
 
+LEVEL_HEADER = "name,lufs,dbtp,gain_db,limited"
+
+
+def level_part_name(suffix: str, rank: int) -> str:
+    return f"loudness{suffix}.rank{rank}.csv"
+
+
 def result_part_name(suffix: str, rank: int) -> str:
     return f"result{suffix}.rank{rank}.json"
 
@@ -288,13 +339,16 @@ class RunLog:
     path,runtime,filetime,rtf (--rtf) and `triples_list{suffix}.txt` with `clean ---> noisy ---> enhanced` lines (pair lists).
     The files are opened on __enter__ (a failing second open closes the first)."""
 
-    def __init__(self, outdir: str, suffix: str, want_rtf: bool, want_triples: bool, part: Optional[int] = None):
+    def __init__(self, outdir: str, suffix: str, want_rtf: bool, want_triples: bool, part: Optional[int] = None, want_level: bool = False):
         """part = r: the log of worker r of a --gpus N run -- `rtfs{suffix}.rank{r}.csv` with the plan position (`self.position`, set by
-        the caller before each batch) as an extra first column, and no triples list (the launcher writes that one)."""
+        the caller before each batch) as an extra first column, and no triples list (the launcher writes that one).  want_level
+        (--target-lufs / --peak-ceiling): also `loudness{suffix}.csv` (LEVEL_HEADER), as a part `loudness{suffix}.rank{r}.csv` with the
+        position column for a worker."""
         self._paths = (os.path.join(outdir, f"rtfs{suffix}.csv" if part is None else rtf_part_name(suffix, part)) if want_rtf else None,
-                       os.path.join(outdir, f"triples_list{suffix}.txt") if want_triples and part is None else None)
+                       os.path.join(outdir, f"triples_list{suffix}.txt") if want_triples and part is None else None,
+                       os.path.join(outdir, f"loudness{suffix}.csv" if part is None else level_part_name(suffix, part)) if want_level else None)
         self._stack = contextlib.ExitStack()
-        self._rtf = self._tri = None
+        self._rtf = self._tri = self._level = None
         self._part, self.position = part, 0
         self.runtime = self.filetime = 0.0
 
@@ -302,10 +356,20 @@ class RunLog:
         with contextlib.ExitStack() as guard:
             self._rtf = guard.enter_context(open(self._paths[0], "w")) if self._paths[0] else None
             self._tri = guard.enter_context(open(self._paths[1], "w")) if self._paths[1] else None
+            self._level = guard.enter_context(open(self._paths[2], "w")) if self._paths[2] else None
             self._stack = guard.pop_all()
         if self._rtf:
             print(RTF_HEADER if self._part is None else "position," + RTF_HEADER, file=self._rtf)
+        if self._level:
+            print(LEVEL_HEADER if self._part is None else "position," + LEVEL_HEADER, file=self._level)
         return self
+
+    def level(self, dst: str, lufs: float, dbtp: float, gain_db: Optional[float], limited: bool):
+        """One row of loudness{suffix}.csv: the file's name, its level as the model gave it, the gain applied (nan: none) and whether the
+        ceiling capped it."""
+        if self._level:
+            row = [os.path.basename(dst), eval_cli.fmt(lufs), eval_cli.fmt(dbtp), eval_cli.fmt(float("nan") if gain_db is None else gain_db), str(int(limited))]
+            print(("" if self._part is None else f"{self.position},") + ",".join(row), file=self._level)
 
     def __exit__(self, *exc):
         return self._stack.__exit__(*exc)
@@ -423,6 +487,42 @@ def skip_over_memory(job: FileJob, res: RunResult, err: Exception) -> None:
     print(f"Skipping file: {err}:", job.src)
 
 
+def level_wanted(args) -> bool:
+    return getattr(args, "target_lufs", None) is not None or getattr(args, "peak_ceiling", None) is not None
+
+
+def _file_level(w: torch.Tensor, sr: int, args, peak: bool = True):
+    """(lufs, dbtp) of the FILE w [C, L] (or [L]): its channels' energies added and gated once, the largest true peak
+    (loudness.file_level_batch, on the GPU, one staging).  peak=False: the loudness alone, dbtp NaN."""
+    chans = list(w.detach().reshape(-1, w.shape[-1]).to(torch.float32))
+    with torch.cuda.device(args.device):
+        lufs, dbtp = loudness.file_level_batch([chans], sr, batch=max(len(chans), 1), device=args.device, peak=peak)
+    return float(lufs[0]), float(dbtp[0])
+
+
+def control_level(x_hat: torch.Tensor, y: torch.Tensor, job: FileJob, args, log: RunLog, sr: int) -> torch.Tensor:
+    """--target-lufs / --peak-ceiling: the finished output x_hat of the input y (both at rate sr) -> what is written.  The level of the file
+    is measured once (the channels of a file count as one programme), ONE gain follows from it (loudness.output_gain) and every sample gets
+    ONE float32 multiply (loudness.normalize_loudness); a row goes to loudness{suffix}.csv.  A file with no finite level (under 400 ms,
+    silent, a sample that is not finite) is written as it is, with a warning.  Without the switches: x_hat itself, nothing measured."""
+    if not level_wanted(args):
+        return x_hat
+    lufs, dbtp = _file_level(x_hat, sr, args)
+    ceiling = args.peak_ceiling
+    if args.target_lufs is None:          # --peak-ceiling alone: 0 dB, capped
+        gain, limited = loudness.output_gain(0.0, dbtp, 0.0, ceiling)
+    else:
+        ceiling = -1.0 if ceiling is None else ceiling
+        target = _file_level(y, sr, args, peak=False)[0] if args.target_lufs == "input" else float(args.target_lufs)
+        gain, limited = loudness.output_gain(lufs, dbtp, target, ceiling) if target == target and abs(target) != float("inf") else (None, False)
+    log.level(job.dst, lufs, dbtp, gain, limited)
+    if gain is None:
+        print(f"warning: {job.dst}: lufs = {eval_cli.fmt(lufs)}, dbtp = {eval_cli.fmt(dbtp)}: no level to set (under 400 ms, silent or not finite); "
+              f"the file is written as it is", file=sys.stderr)
+        return x_hat
+    return loudness.match_loudness(x_hat.to(torch.float32), 0.0, gain)
+
+
 def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResult, max_seconds: float, y=None) -> None:
     """One file per native call (the reference's loop): load -> enhance (timed under --rtf) -> save.  Updates `res`.  `y`: the file's
     waveform when the caller has already loaded (and resampled) it."""
@@ -446,7 +546,7 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
             return
         if timer.seconds is not None:
             log.rtf(job.dst, timer.seconds, y.shape[-1] / sr)
-        save_wav(job.dst, x_hat.cpu(), sr)
+        save_wav(job.dst, control_level(x_hat, y, job, args, log, sr).cpu(), sr)
         res.n_done += 1
         return
     # use_graph=False: every file has its own length, and a replay would not be faster anyway -- a one-clip solve is bound by the GPU,
@@ -462,7 +562,7 @@ def enhance_file(model: FlowModel, job: FileJob, args, log: RunLog, res: RunResu
         return
     if timer.seconds is not None:
         log.rtf(job.dst, timer.seconds, y.shape[-1] / sr)
-    save_wav(job.dst, x_hat.cpu(), sr)
+    save_wav(job.dst, control_level(x_hat, y, job, args, log, sr).cpu(), sr)
     res.n_done += 1
 
 
@@ -509,7 +609,7 @@ def enhance_batch_files(model: FlowModel, batch: List[FileJob], args, log: RunLo
     for (job, y), x_hat in zip(loaded, outs):
         if timer.seconds is not None:   # the batch's time, split in proportion to the files' durations
             log.rtf(job.dst, timer.seconds * (y.shape[-1] / sr) / total, y.shape[-1] / sr)
-        save_wav(job.dst, x_hat.cpu(), sr)
+        save_wav(job.dst, control_level(x_hat, y, job, args, log, sr).cpu(), sr)
         res.n_done += 1
 
 
@@ -562,11 +662,12 @@ def visible_gpus() -> int:
         raise RuntimeError("could not read the number of visible GPUs: " + (r.stdout + r.stderr)[-500:])
 
 
-def merge_parts(outdir: str, suffix: str, world: int, jobs: List[FileJob], want_rtf: bool, want_triples: bool) -> RunResult:
+def merge_parts(outdir: str, suffix: str, world: int, jobs: List[FileJob], want_rtf: bool, want_triples: bool, want_level: bool = False) -> RunResult:
     """The launcher's last step: the workers' `rtfs{suffix}.rank{r}.csv` rows sorted by plan position (rows of one position keep their
     order; the position column is dropped) -> `rtfs{suffix}.csv`, the rows and order of a one-process run; `triples_list{suffix}.txt` from
-    the work list; the workers' RunResults summed.  Removes the part files it read."""
-    res, rows, used = RunResult(), [], []
+    the work list; the workers' RunResults summed.  want_level: `loudness{suffix}.csv` from the `loudness{suffix}.rank{r}.csv` parts in
+    the same way.  Removes the part files it read."""
+    res, rows, used, level_rows = RunResult(), [], [], []
     for r in range(world):
         path = os.path.join(outdir, result_part_name(suffix, r))
         with open(path, "r") as f:
@@ -583,6 +684,17 @@ def merge_parts(outdir: str, suffix: str, world: int, jobs: List[FileJob], want_
                 if line.strip():
                     pos, row = line.split(",", 1)
                     rows.append((int(pos), r, k, row))
+        if want_level:
+            path = os.path.join(outdir, level_part_name(suffix, r))
+            with open(path, "r") as f:
+                lines = f.read().splitlines()
+            used.append(path)
+            level_rows += [(int(line.split(",", 1)[0]), r, k, line.split(",", 1)[1]) for k, line in enumerate(lines[1:]) if line.strip()]
+    if want_level:
+        with open(os.path.join(outdir, f"loudness{suffix}.csv"), "w") as f:
+            print(LEVEL_HEADER, file=f)
+            for _, _, _, row in sorted(level_rows):
+                print(row, file=f)
     if want_rtf:
         with open(os.path.join(outdir, f"rtfs{suffix}.csv"), "w") as f:
             print(RTF_HEADER, file=f)
@@ -661,6 +773,8 @@ def evaluate_triples(args, suffix: str) -> None:
                      + (["--align-polarity"] if getattr(args, "eval_align_polarity", False) else [])
                      + (["--loudness"] if getattr(args, "eval_loudness", False) else [])
                      + (["--match-loudness"] if getattr(args, "eval_match_loudness", False) else [])
+                     + (["--loudness-range"] if getattr(args, "eval_loudness_range", False) else [])
+                     + (["--true-peak"] if getattr(args, "eval_true_peak", False) else [])
                      + (["--ssnr"] if getattr(args, "eval_ssnr", False) else []))
 
 
@@ -677,7 +791,7 @@ def run_launcher(args, parser, argv: List[str]) -> RunResult:
     jobs = list(plan_jobs(noisy, clean, args.outdir, args.i_min, args.i_max, args.skip_existing, args.exclude_files_matching))
     manifest = os.path.join(args.outdir, manifest_name(suffix))
     for stale in glob.glob(os.path.join(glob.escape(args.outdir), f"*{suffix}.rank*.*")):      # parts a failed earlier run left for diagnosis
-        if re.fullmatch(r"(rtfs|result)%s\.rank\d+\.(csv|json)" % re.escape(suffix), os.path.basename(stale)):
+        if re.fullmatch(r"(rtfs|result|loudness)%s\.rank\d+\.(csv|json)" % re.escape(suffix), os.path.basename(stale)):
             os.remove(stale)
     write_manifest(manifest, jobs)
     worker_argv = list(argv) + (["--seed", str(args.seed)] if args.seed is not None else [])
@@ -690,7 +804,7 @@ def run_launcher(args, parser, argv: List[str]) -> RunResult:
         raise WorkerFailed("\n".join(f"rank {r} ended with status {rc}; its last lines:\n" + "\n".join(tail) for r, rc, tail in failed)
                            + f"\n{len(failed)} of {args.gpus} workers failed; the others finished.  The part files stay in {args.outdir}; a rerun with "
                              f"--skip-existing completes what is missing.")
-    res = merge_parts(args.outdir, suffix, args.gpus, jobs, want_rtf=args.rtf, want_triples=clean is not None)
+    res = merge_parts(args.outdir, suffix, args.gpus, jobs, want_rtf=args.rtf, want_triples=clean is not None, want_level=level_wanted(args))
     os.remove(manifest)
     if args.rtf and res.gpu_seconds > 0:
         print(f"total: {res.audio_seconds:.2f} s of audio in {res.gpu_seconds:.3f} s of GPU time -> rtf = {res.gpu_seconds / res.audio_seconds:.5f} "
@@ -783,7 +897,12 @@ def run(argv=None, model: Optional[FlowModel] = None) -> RunResult:
     if worker:      # the plan is the one-process plan; this rank runs its share of it, in plan order
         mine = balance([batch_cost(model, batch, args) for batch in plan], args.worker_world)[args.worker_rank]
         print(f"flowdec_amd: worker {args.worker_rank} of {args.worker_world} on {args.device}: {len(mine)} of {len(plan)} batches")
-    with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None, part=args.worker_rank) as log:
+    if level_wanted(args):
+        try:
+            loudness.check_rate(model.sampling_rate)
+        except ValueError as err:
+            parser.error(f"--target-lufs / --peak-ceiling: {err}")
+    with RunLog(args.outdir, suffix, want_rtf=args.rtf, want_triples=clean is not None, part=args.worker_rank, want_level=level_wanted(args)) as log:
         for position in mine:
             batch = plan[position]
             log.position = position

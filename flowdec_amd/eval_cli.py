@@ -3,7 +3,7 @@ flowdec/eval/metrics.py get_metrics_df / get_metrics_df_parallel reads it) for t
 
     python -m flowdec_amd.eval_cli --triples out/triples_list.txt --out out/metrics.csv [--batch-files 8] [--crop-to-x] [--crop-to-x-hat]
                                    [--sr 48000] [--estoi] [--spectral] [--align MS [--align-frac] [--align-polarity] [--align-q 64]
-                                   [--align-taps 32]] [--loudness] [--match-loudness] [--ssnr]
+                                   [--align-taps 32]] [--loudness] [--match-loudness] [--loudness-range] [--true-peak] [--ssnr]
 
 Input: lines `clean ---> noisy ---> enhanced` (x, y, x_hat), split like enhance_cli's lists (audio.split_pair) (a comma inside an arrow line is part of the
 path).  Every file is loaded like the reference's load48000 (util/other.py:137-): mean of the channels, resampled to --sr with
@@ -70,6 +70,16 @@ to x's loudness (loudness.match_loudness) before every metric; the three columns
 loudness, or whose reference's, is nan or -inf is left as it is, with a warning.  The coefficients and the conformance readings of the
 standard pin the host function; parity with the pyloudnorm package is UNPINNED (scripts/pin_loudness.py).
 
+--loudness-range and --true-peak (off by default; without them every byte of the output is what it was, with any of the switches above)
+complete the level report after EBU R 128: did the enhancer flatten or inflate the dynamics, and do the files overshoot between samples.
+--loudness-range adds three columns `lra_x_hat`, `lra_x`, `lra_y` (loudness range after EBU Tech 3342, in LU: the spread between the 10th
+and the 95th percentile of the gated 3 s loudness; nan under 3 s), --true-peak three columns `dbtp_x_hat`, `dbtp_x`, `dbtp_y` (the true
+peak of BS.1770-4 Annex 2 in dBTP, read through the project's own 4x Hann-windowed-sinc interpolator of 24 taps per phase, not the
+standard's example filter).  Both stand behind the `lufs_*` columns (when those are on) and before the `lag_*` / `pol_*` columns, each
+with three summary lines, and both measure the signals as they are scored -- after --align and the crops -- and before --match-loudness
+scales, as `lufs_*` does (csrc/loudness_range.hip; loudness.py loudness_range_batch and true_peak_batch, host yardsticks loudness_range
+and true_peak).
+
 --ssnr (off by default; without it every byte of the output is what it was, with any of the switches above) adds two CSV columns,
 `fwSSNR` and `SSNR` -- the reference's names for the frequency-weighted segmental SNR and the segmental SNR it takes from the pysepm package
 (eval/metrics.py:511-547: fwSNRseg and SNRseg with 30 ms frames at 75 % overlap; Hu & Loizou's comp_fwseg.m / comp_snr.m), in the order of
@@ -88,7 +98,7 @@ import csv
 import math
 import os
 import sys
-from dataclasses import dataclass, field
+from dataclasses import InitVar, dataclass, field, fields
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -105,6 +115,8 @@ SSNR_NAMES = segsnr.NAMES          # the optional metrics of --ssnr (fwSSNR, SSN
 LAG_NAMES = ("lag_x_hat", "lag_y")  # the optional columns of --align, always the last two (before POL_NAMES)
 POL_NAMES = ("pol_x_hat", "pol_y")  # the optional columns of --align-polarity, always the last two
 LUFS_NAMES = ("lufs_x_hat", "lufs_x", "lufs_y")  # the optional columns of --loudness, behind the metrics and before LAG_NAMES
+LRA_NAMES = ("lra_x_hat", "lra_x", "lra_y")     # the optional columns of --loudness-range, behind LUFS_NAMES and before LAG_NAMES
+DBTP_NAMES = ("dbtp_x_hat", "dbtp_x", "dbtp_y")  # the optional columns of --true-peak, behind LRA_NAMES and before LAG_NAMES
 WIN_DUR, HOP_DUR = 32e-3, 8e-3      # LogSpecMSE (eval/metrics.py:333-372)
 
 
@@ -156,7 +168,11 @@ class Scorer:
     align_frac(as_, bs, max_lag, Q, W, polarity, batch) -> (lag_q int64 [n], sign int32 [n]) and shift(signals, lag_q, sign, windows, Q, W,
     batch) -> float32 tensors (optional: only --align-frac / --align-polarity call them); loudness(signals, sr, batch) -> float64 [n] in
     LUFS (optional: only --loudness / --match-loudness call it); segsnr(x_hats, xs, sr, batch) -> [n, 2] (fwSSNR, SSNR) (optional: only --ssnr
-    calls it)."""
+    calls it); loudness_range(signals, sr, batch) -> float64 [n] in LU (optional: only --loudness-range calls it); true_peak(signals, sr,
+    batch) -> float64 [n] in dBTP (optional: only --true-peak calls it).
+    The last two are constructor arguments and attributes like the others but NOT dataclass fields: `dataclasses.fields(Scorer)` stays the
+    list it was, ending with segsnr.  Equality, the hash's consistency with it and the repr take them in through the methods below;
+    `dataclasses.replace` does not know them and would hand back a Scorer without them: use `Scorer.replace`, which carries them over."""
     si_sxr: Callable
     logspec: Callable
     estoi: Optional[Callable] = None
@@ -166,6 +182,32 @@ class Scorer:
     shift: Optional[Callable] = None
     loudness: Optional[Callable] = None
     segsnr: Optional[Callable] = None
+    # the two functions of the level report: constructor arguments (appended, default None) and attributes like the others, but not
+    # dataclass fields -- dataclasses.fields(Scorer) stays the list of the scoring functions it was, ending with segsnr
+    loudness_range: InitVar[Optional[Callable]] = None
+    true_peak: InitVar[Optional[Callable]] = None
+
+    def __post_init__(self, loudness_range, true_peak):
+        object.__setattr__(self, "loudness_range", loudness_range)
+        object.__setattr__(self, "true_peak", true_peak)
+
+    def _all(self) -> tuple:
+        return tuple(getattr(self, f.name) for f in fields(self)) + (self.loudness_range, self.true_peak)
+
+    def replace(self, **changes) -> "Scorer":
+        """A copy with the named functions changed, the two level functions included."""
+        names = [f.name for f in fields(self)] + ["loudness_range", "true_peak"]
+        return Scorer(**{**dict(zip(names, self._all())), **changes})
+
+    def __eq__(self, other):
+        return self._all() == other._all() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._all())
+
+    def __repr__(self):
+        names = [f.name for f in fields(self)] + ["loudness_range", "true_peak"]
+        return "Scorer(" + ", ".join(f"{n}={v!r}" for n, v in zip(names, self._all())) + ")"
 
 
 def _gpu_si_sxr(x_hats, xs, ys, batch):
@@ -204,6 +246,14 @@ def _gpu_loudness(signals, sr, batch):
     return loudness.loudness_batch(signals, sr=sr, batch=batch)
 
 
+def _gpu_loudness_range(signals, sr, batch):
+    return loudness.loudness_range_batch(signals, sr=sr, batch=batch)
+
+
+def _gpu_true_peak(signals, sr, batch):
+    return loudness.true_peak_batch(signals, sr=sr, batch=batch)
+
+
 def _gpu_segsnr(x_hats, xs, sr, batch):
     return segsnr.segsnr_batch(x_hats, xs, sr=sr, batch=batch)
 
@@ -215,10 +265,10 @@ def _host_segsnr(x_hats, xs, sr, batch):
 
 # ragged batches on the device (csrc/loudness.hip, csrc/metrics.hip, csrc/stoi.hip, csrc/specdist.hip, csrc/segsnr.hip, csrc/xcorr.hip)
 GPU_SCORER = Scorer(_gpu_si_sxr, _gpu_logspec, _gpu_estoi, _gpu_spectral, align.lags_batch, align.lags_batch_frac, align.shift_batch,
-                    _gpu_loudness, _gpu_segsnr)
+                    _gpu_loudness, _gpu_segsnr, _gpu_loudness_range, _gpu_true_peak)
 # the host functions of metrics.py, specdist.py, segsnr.py and align.py, one triple at a time: the yardstick
 HOST_SCORER = Scorer(_host_si_sxr, _host_logspec, _host_estoi, _host_spectral, align.host_lags, align.host_lags_frac, align.host_shift,
-                     loudness.host_loudness, _host_segsnr)
+                     loudness.host_loudness, _host_segsnr, loudness.host_loudness_range, loudness.host_true_peak)
 
 
 def metric_columns(estoi: bool = False, spectral: bool = False, ssnr: bool = False) -> tuple:
@@ -298,16 +348,19 @@ def _columns_of(values: np.ndarray, columns) -> tuple:
     return tuple(columns)
 
 
-def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None, lag_q=None, Q: int = 1, pols=None, lufs=None) -> None:
+def write_csv(path: str, triples: List[Triple], values: np.ndarray, columns=None, lags=None, lag_q=None, Q: int = 1, pols=None, lufs=None, lra=None,
+              dbtp=None) -> None:
     """lags (--align): int [n, 2], written as the two last columns LAG_NAMES.  lag_q (--align-frac) instead: int [n, 2] in units of 1 / Q
     sample, written as lag_q / Q.  pols (--align-polarity): int [n, 2] of 1 / -1, written behind them as POL_NAMES.  lufs
-    (--loudness): float64 [n, 3], written as LUFS_NAMES behind the metrics and before all of those (nan and -inf as `fmt` prints them)."""
+    (--loudness): float64 [n, 3], written as LUFS_NAMES behind the metrics and before all of those (nan and -inf as `fmt` prints them);
+    lra (--loudness-range) and dbtp (--true-peak): float64 [n, 3] each, written as LRA_NAMES and DBTP_NAMES behind LUFS_NAMES."""
+    level = [(names, v) for names, v in ((LUFS_NAMES, lufs), (LRA_NAMES, lra), (DBTP_NAMES, dbtp)) if v is not None]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + (LUFS_NAMES if lufs is not None else ()) + (LAG_NAMES if lags is not None or lag_q is not None else ())
+        w.writerow(CSV_HEADER[:4] + _columns_of(values, columns) + tuple(c for names, _ in level for c in names) + (LAG_NAMES if lags is not None or lag_q is not None else ())
                    + (POL_NAMES if pols is not None else ()))
         for i, (t, row) in enumerate(zip(triples, values)):
-            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + ([fmt(v) for v in lufs[i]] if lufs is not None else []) + ([str(int(l)) for l in lags[i]] if lags is not None else [])
+            w.writerow([t.name, t.x_hat, t.x, t.y] + [fmt(v) for v in row] + [fmt(v) for _, lv in level for v in lv[i]] + ([str(int(l)) for l in lags[i]] if lags is not None else [])
                        + ([align.lag_text(l, Q) for l in lag_q[i]] if lag_q is not None else []) + ([str(int(g)) for g in pols[i]] if pols is not None else []))
 
 
@@ -332,6 +385,8 @@ class EvalResult:
     lags: list = field(default_factory=list)   # --align: [(column, min, max, count of non-zero lags)], empty without it
     inverted: list = field(default_factory=list)   # --align-polarity: [(column, count of inverted signals)], empty without it
     loudness: list = field(default_factory=list)   # --loudness: [(column, mean over its finite rows, count of finite rows)], empty without it
+    loudness_range: list = field(default_factory=list)   # --loudness-range: the same for LRA_NAMES
+    true_peak: list = field(default_factory=list)        # --true-peak: the same for DBTP_NAMES
 
     @property
     def exit_code(self) -> int:
@@ -368,6 +423,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--match-loudness", action="store_true",
                    help="implies --loudness: scale x_hat and y to the loudness of x (one float32 factor each) before every metric; the three "
                         "columns report the loudness before matching")
+    p.add_argument("--loudness-range", action="store_true",
+                   help="also measure the loudness range (EBU Tech 3342; on the GPU) of x_hat, x and y as they are scored, before "
+                        "--match-loudness scales: three CSV columns `lra_x_hat`, `lra_x`, `lra_y` behind the `lufs_*` columns and three more "
+                        "means (nan under 3 s)")
+    p.add_argument("--true-peak", action="store_true",
+                   help="also measure the true peak (ITU-R BS.1770-4 Annex 2 with the project's 4x windowed-sinc interpolator; on the GPU) of "
+                        "x_hat, x and y as they are scored, before --match-loudness scales: three CSV columns `dbtp_x_hat`, `dbtp_x`, "
+                        "`dbtp_y` behind the `lufs_*` / `lra_*` columns and three more means")
     p.add_argument("--ssnr", action="store_true",
                    help="also score the frequency-weighted segmental SNR and the segmental SNR (pysepm's fwSNRseg / SNRseg restated; on the "
                         "GPU): two CSV columns `fwSSNR` and `SSNR` behind the other metrics and two more means")
@@ -448,17 +511,35 @@ def align_signals_frac(loaded, M: int, batch: int, scorer: Scorer, frac: bool, p
     return [(cut[i], x[..., n0:n1], cut[n + i]) for i, ((_, x, _), (n0, n1)) in enumerate(zip(loaded, windows))], lag_q, sign
 
 
+def _measure_level(fn, signals, sr: int, batch: int) -> np.ndarray:
+    loudness.check_rate(sr)
+    n = len(signals)
+    if not n:
+        return np.zeros((0, 3), np.float64)
+    got = np.asarray(fn([s[k] for k in range(3) for s in signals], sr, batch), np.float64).reshape(3, n)
+    return np.ascontiguousarray(got.T)
+
+
 def measure_loudness(signals, sr: int, batch: int, scorer: Scorer) -> np.ndarray:
     """signals: one (x_hat, x, y) of 1-D tensors per triple, as they will be scored -> float64 [n, 3] LUFS in LUFS_NAMES order, from ONE
     call of scorer.loudness."""
     if scorer.loudness is None:
         raise ValueError("measure_loudness: --loudness / --match-loudness need a Scorer with a loudness function")
-    loudness.check_rate(sr)
-    n = len(signals)
-    if not n:
-        return np.zeros((0, 3), np.float64)
-    got = np.asarray(scorer.loudness([s[k] for k in range(3) for s in signals], sr, batch), np.float64).reshape(3, n)
-    return np.ascontiguousarray(got.T)
+    return _measure_level(scorer.loudness, signals, sr, batch)
+
+
+def measure_loudness_range(signals, sr: int, batch: int, scorer: Scorer) -> np.ndarray:
+    """measure_loudness for --loudness-range: float64 [n, 3] LU in LRA_NAMES order, from ONE call of scorer.loudness_range."""
+    if scorer.loudness_range is None:
+        raise ValueError("measure_loudness_range: --loudness-range needs a Scorer with a loudness_range function")
+    return _measure_level(scorer.loudness_range, signals, sr, batch)
+
+
+def measure_true_peak(signals, sr: int, batch: int, scorer: Scorer) -> np.ndarray:
+    """measure_loudness for --true-peak: float64 [n, 3] dBTP in DBTP_NAMES order, from ONE call of scorer.true_peak."""
+    if scorer.true_peak is None:
+        raise ValueError("measure_true_peak: --true-peak needs a Scorer with a true_peak function")
+    return _measure_level(scorer.true_peak, signals, sr, batch)
 
 
 def match_signals(signals, lufs: np.ndarray, names: Optional[List[str]] = None):
@@ -501,7 +582,7 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
         except ValueError as err:
             parser.error(str(err))
     check_align_args(parser, args)
-    if args.loudness or args.match_loudness:
+    if args.loudness or args.match_loudness or args.loudness_range or args.true_peak:
         try:
             loudness.check_rate(args.sr)
         except ValueError as err:
@@ -525,7 +606,11 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
     elif max_lag is not None:
         signals, lags = align_signals(signals, max_lag, args.batch_files, scorer, names=names)
     signals = [crop(x_hat, x, y, args.crop_to_x, args.crop_to_x_hat) for x_hat, x, y in signals]
-    lufs = None
+    lufs, lra, dbtp = None, None, None
+    if args.loudness_range:
+        lra = measure_loudness_range(signals, args.sr, args.batch_files, scorer)
+    if args.true_peak:
+        dbtp = measure_true_peak(signals, args.sr, args.batch_files, scorer)
     if args.loudness or args.match_loudness:
         lufs = measure_loudness(signals, args.sr, args.batch_files, scorer)
         if args.match_loudness:
@@ -535,20 +620,22 @@ def run(argv=None, scorer: Scorer = GPU_SCORER) -> EvalResult:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if lag_q is not None:
         pols = sign if args.align_polarity else None
-        write_csv(args.out, kept, values, columns=columns, lag_q=lag_q, Q=args.align_q, pols=pols, lufs=lufs)
+        write_csv(args.out, kept, values, columns=columns, lag_q=lag_q, Q=args.align_q, pols=pols, lufs=lufs, lra=lra, dbtp=dbtp)
         res.lags = lag_summary_frac(lag_q, args.align_q)
         res.inverted = [(name, int(np.count_nonzero(sign[:, k] < 0))) for k, name in enumerate(POL_NAMES)] if pols is not None else []
     elif lags is None:
-        write_csv(args.out, kept, values, columns=columns, lufs=lufs)
+        write_csv(args.out, kept, values, columns=columns, lufs=lufs, lra=lra, dbtp=dbtp)
     else:
-        write_csv(args.out, kept, values, columns=columns, lags=lags, lufs=lufs)
+        write_csv(args.out, kept, values, columns=columns, lags=lags, lufs=lufs, lra=lra, dbtp=dbtp)
         res.lags = lag_summary(lags)
     res.n_scored, res.means = len(kept), summary(values, columns=columns)
     res.loudness = summary(lufs, columns=LUFS_NAMES) if lufs is not None else []
+    res.loudness_range = summary(lra, columns=LRA_NAMES) if lra is not None else []
+    res.true_peak = summary(dbtp, columns=DBTP_NAMES) if dbtp is not None else []
     print(f"eval: {res.n_triples} triples, {res.n_scored} rows in {args.out}, {res.n_unreadable} skipped (unreadable)")
     for name, mean, count in res.means:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
-    for name, mean, count in res.loudness:
+    for name, mean, count in res.loudness + res.loudness_range + res.true_peak:
         print(f"  {name:12s} mean = {mean:.6g}  over {count} finite rows")
     for name, lo, hi, nonzero in res.lags:
         print(f"  {name:12s} min = {lo}  max = {hi}  non-zero in {nonzero} of {res.n_scored} rows")

@@ -54,7 +54,9 @@ def _normfac(s: str):
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Enhance a raw PCM stream with a FlowDec, ScoreDec or regression postfilter on MI355X (stdin -> stdout by default)")
+    p = argparse.ArgumentParser(description="Enhance a raw PCM stream with a FlowDec, ScoreDec or regression postfilter on MI355X (stdin -> stdout by default).  The output is "
+                                            "not loudness-normalised: a stream has no integrated loudness until it ends (enhance_cli --target-lufs "
+                                            "sets the level of files)")
     p.add_argument("--ckpt", type=str, required=True)
     p.add_argument("--N", type=int, required=True)
     p.add_argument("--solver", type=str, default="euler", choices=["euler", "midpoint", "heun2", "heun2_eulerlast"], help="flow checkpoint: fixed-step solvers only")

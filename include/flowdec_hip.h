@@ -1024,6 +1024,39 @@ int fd_loudness_energies(const float* x, const int* lengths, int B, int L, doubl
 int fd_loudness_gate(const double* E, const int* nsub, int B, int Jmax, double* ms_out, int* counts_out, void* stream);
 int fd_loudness(const float* x, const int* lengths, int B, int L, double* ms_out, int* counts_out, void* ws, size_t ws_bytes, void* stream);
 
+/* True peak (ITU-R BS.1770-4 Annex 2) and loudness range (EBU Tech 3342): csrc/loudness_range.hip; the host yardsticks and the definitions
+ * are loudness.py true_peak_lin and range_of.  eval_cli --true-peak / --loudness-range, loudness.loudness_report_batch and
+ * loudness.LoudnessMeter run on them.  Both calls are asynchronous on `stream`, allocate nothing, use no floating-point atomics and no
+ * fused multiply-add; a clip's results have the SAME BITS alone, in a batch and at any batch position; nothing is launched on a refusal:
+ * FD_EINVAL with a message for a NULL pointer, B outside [1, 65535], L outside [1, 0x7fffffff - 1024], Jmax outside [0, (0x7fffffff -
+ * 1024) / 4800] and W outside [1, 256]; FD_ENOMEM for a workspace smaller than the *_workspace_bytes function gives (0 for a bad argument).
+ *
+ * fd_true_peak: x DEVICE float [B][L] at 48 kHz, lengths DEVICE int32 [B] (clamped to [0, L]); lo, hi DEVICE int32 [B]: the positions
+ *   [lo_b, hi_b) of clip b (clamped into [0, len_b]), or both NULL: every position; taps DEVICE double [4][2 W]: the host's table of a 4x
+ *   oversampling interpolator (align.frac_bank(4, W): row j, column t is the tap k = t - W + 1 of the delay j / 4; row 0 the unit
+ *   impulse, so the sample peak is included) -- the device only reads it and evaluates no transcendental.
+ *       p_out[b] = max over n in [lo_b, hi_b), j in 0..3 of | sum_{t = 0 .. 2W-1} f64(x_b[n + t - W + 1]) * taps[j][t] |
+ *   p_out DEVICE double [B]; t ascending, every product and sum rounded to float64 on its own; samples outside [0, len_b) are zeros and
+ *   are never loaded, every index is clamped: a wrong table or window gives a wrong number, never an access outside a row.  A sum that
+ *   is not finite (a NaN or Inf sample among those the window reads): NaN.  An empty clip: NaN.  An empty window of a clip that is not
+ *   empty: 0.0.  dBTP = 20 log10(p) is formed by the caller.  fd_true_peak_tile(): the positions one workgroup owns (tests put lengths
+ *   and windows around its multiples).
+ * fd_loudness_range: E DEVICE double [B][Jmax] and nsub DEVICE int32 [B] (clamped to [0, Jmax]) as fd_loudness_gate takes them.  Short-
+ *   term windows st_j = (((E[j] + E[j+1]) + ...) + E[j+29]) / 144000 for j = 0 .. nsub - 30 (kept in the workspace); the absolute gate
+ *   st_j > 10^((-70 + 0.691) / 10); the relative gate st_j > 0.01 * the mean of the windows above the first (the sum in fd_loudness_gate's
+ *   order: 64 lane sums, added in ascending lane order); with m windows above both and s their ascending order,
+ *       st_out[b] = (s[((m - 1) * 10 + 50) / 100], s[((m - 1) * 95 + 50) / 100])     (DEVICE double [B][2], exact order statistics by a
+ *   radix select on the 64-bit patterns, linear in the number of windows); counts_out DEVICE int32 [B][3] = windows, windows above the
+ *   absolute gate, windows above both.  LRA = 10 log10(st_hi) - 10 log10(st_lo) is formed by the caller.  Fewer than 30 sub-blocks: NaN
+ *   NaN and 0 0 0.  A window that is NaN or Inf: NaN NaN and (windows, 0, 0).  No window above the absolute gate: 0.0 0.0 (0 LU by
+ *   definition) and (windows, 0, 0). */
+int fd_true_peak_tile(void);
+size_t fd_true_peak_workspace_bytes(int B, int L);
+int fd_true_peak(const float* x, const int* lengths, int B, int L, const int* lo, const int* hi, const double* taps, int W, double* p_out,
+                 void* ws, size_t ws_bytes, void* stream);
+size_t fd_loudness_range_workspace_bytes(int B, int Jmax);
+int fd_loudness_range(const double* E, const int* nsub, int B, int Jmax, double* st_out, int* counts_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Parameter estimation: the statistics behind a FlowDec model's beta and sigma_y (the reference's scripts/estimate_flowdec_params.py;
  * flowdec_amd/estimate.py, flowdec_amd/estimate_cli.py).  Both calls are asynchronous on `stream`, allocate nothing, keep no state and
